@@ -5,7 +5,13 @@ M = 26 (53 Laplace samples), tanh-sinh k = 6 / R = 4, 10 J0 intervals x 48 Gauss
 nodes => 543 abscissae, 28 779 Laplace-Hankel samples per point, fp64 throughout.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--workload c2|c2pp|c3|c4|c5]
-                  [--mode fast|faithful]
+                  [--mode fast|faithful] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the JSON line (with --dump-outputs DIR it first writes h and dh
+of the last timed step, [nt][nr][nz] over the whole sweep, as DIR/h.npy and DIR/dh.npy).  Everything the headline
+figure does not need -- the other scaling mode, the measured fp64 FMA peak, the CPU baseline and the accuracy against
+it, the host-array entry, the other workloads -- is measured only with --full.  So the second half of the metric
+("max |rel err| vs CPU ref", accuracy_vs_cpu_ref below) is in a --full line only.
 
 One "step" = one pass of the hot path over the whole synthetic sweep that is resident in HBM
 (times tD[nt] with their split index, radii rD[nr] in; h and dh per point out).
@@ -20,8 +26,8 @@ environment) this file is a rank; started plainly with --gpus N it launches its 
                               blocks of time rows (ucf_shard_rows: the reference's i loop, driver.f90:100); every
                               rank computes its rows in place in the full-size result arrays and one in-place
                               all-gather per array completes them on every rank (the reference's single output).
-No data-path collective in either; the final gather is inside the timed step.  The other mode is measured after the
-line of the timed region is complete and reported under "other_scaling" (under a time limit: the line is never lost to it).
+No data-path collective in either; the final gather is inside the timed step.  With --full the other mode is measured after
+the line of the timed region is complete and reported under "other_scaling" (under a time limit: the line is never lost to it).
 
 The JSON line carries
   roofline      : bound = fp64 VALU (this path is neither HBM- nor MFMA-bound).  `achieved` = fp64 flop the
@@ -33,9 +39,9 @@ The JSON line carries
                   MI355X_MICROARCH.md).  `kernels` = the same for every kernel of the step.  The SURVEY 8(d)
                   convention figure (flop of the REFERENCE formulation / kernel time) is kept apart as
                   `time_to_solution_vs_reference_formulation`: it is not a utilisation.
-  cpu_baseline  : the reference binary itself (oracle/_ref/O2/unconfined, flang -O2, OpenMP) when it was shipped with
-                  the repo, else the C oracle; timed on a bounded sample of the same workload, rank 0, N = 1.
-  accuracy_vs_cpu_ref : the second half of the metric, both flavours, on that sample (outside the timed region).
+  cpu_baseline  : (--full) the reference binary itself (oracle/_ref/O2/unconfined, flang -O2, OpenMP) when it was
+                  built with the repo, else the C oracle; timed on a bounded sample of the same workload, rank 0, N = 1.
+  accuracy_vs_cpu_ref : (--full) the second half of the metric, both flavours, on that sample (outside the timed region).
 """
 import argparse
 import json
@@ -154,10 +160,34 @@ def parse_args(argv=None):
     ap.add_argument("--nt", type=int, default=0)
     ap.add_argument("--nr", type=int, default=0)
     ap.add_argument("--layout", default="auto", choices=["auto", "sample"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the other scaling mode (N > 1), the measured fp64 FMA "
+                         "peak, the CPU baseline with the accuracy against it, the host-array entry and the other workloads")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write h and dh of the last timed step as DIR/<name>.npy (float64; a fixed, seeded sample above 60 MB)")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-other-scaling", action="store_true")
     ap.add_argument("--no-other-workloads", action="store_true")
     return ap.parse_args(argv)
+
+
+DUMP_BYTES = 60_000_000
+
+
+def dump_outputs(out_dir, h, dh):
+    """h and dh as a caller of the timed path receives them ([nt][nr][nz], float64); above DUMP_BYTES a fixed, seeded
+    sample of the flattened points instead, with the flat index of every sampled point (sample_index.npy)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    h = np.ascontiguousarray(h, np.float64)
+    dh = np.ascontiguousarray(dh, np.float64)
+    if h.nbytes + dh.nbytes > DUMP_BYTES:
+        k = DUMP_BYTES // (3 * 8)
+        idx = np.sort(np.random.default_rng(12345).choice(h.size, size=k, replace=False))
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+        h, dh = h.ravel()[idx], dh.ravel()[idx]
+    np.save(os.path.join(out_dir, "h.npy"), h)
+    np.save(os.path.join(out_dir, "dh.npy"), dh)
 
 
 def self_launch(args):
@@ -427,6 +457,22 @@ def worker(args):
         if world > 1:
             ok = ok and bool(torch.equal(d_all[2 * rank:2 * rank + 2], d_out))
     main_gather = gather_via if args.scaling == "strong" else ("torch.distributed all_gather_into_tensor" if world > 1 else "none")
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left in the result arrays, as [nt][nr][nz] over the whole sweep
+        if args.scaling == "strong":
+            h_all = d_full[0][: nt * row].view(nt, nr, nz).cpu().numpy()
+            dh_all = d_full[1][: nt * row].view(nt, nr, nz).cpu().numpy()
+        elif world == 1:
+            h_all = d_out[0].view(nt, nr, nz).cpu().numpy()
+            dh_all = d_out[1].view(nt, nr, nz).cpu().numpy()
+        else:                                      # rank q holds every world-th radius from the q-th on
+            g = d_all.view(world, 2, nt, nr, nz).cpu().numpy()
+            h_all = np.empty((nt, nr * world, nz))
+            dh_all = np.empty((nt, nr * world, nz))
+            for q in range(world):
+                h_all[:, q::world] = g[q, 0]
+                dh_all[:, q::world] = g[q, 1]
+        dump_outputs(args.dump_outputs, h_all, dh_all)
 
     def other_scaling(line):
         """The other scaling mode, AFTER the line of the timed region is complete (rank 0 holds it): if this second
@@ -469,7 +515,7 @@ def worker(args):
             engine.comm_destroy(lib_comm)
         return other
 
-    want_other = world > 1 and not args.no_other_scaling
+    want_other = args.full and world > 1 and not args.no_other_scaling
     if rank != 0:
         if want_other:
             other_scaling(None)
@@ -486,10 +532,12 @@ def worker(args):
     if dk.model == 6 and dk.MNtype == 2:
         per_sample += dk.order * 68.0            # n*(1 cdiv + 3 cmul + 2 cadd)*2 passes
     flop_per_pt = per_sample * D.nabs * D.np + 0.35 * per_sample * D.nabs * D.np * (nz - 1) + FLOP_TAIL_PER_POINT * nz
-    try:
-        fma_peak = engine.fp64_fma_peak()
-    except Exception:
-        fma_peak = None
+    fma_peak = None
+    if args.full:                                # a microbenchmark launch of its own
+        try:
+            fma_peak = engine.fp64_fma_peak()
+        except Exception:
+            fma_peak = None
     build_id = engine.build_id()
     prof, prof_src = load_profile(build_id, args.workload, args.mode)
     dom = max(kernels, key=lambda kv: kv[1] * kv[2]) if kernels else ("all kernels of a step", elapsed / args.steps * 1e3, 1)
@@ -553,7 +601,7 @@ def worker(args):
     elif lib_comm:
         torch.cuda.synchronize()
         engine.comm_destroy(lib_comm)
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         # the box shows every hardware thread of the host but a 1-GPU job owns a 16-core share; the
         # reference's OpenMP regions are 48-63 iterations long, so more threads only add overhead
         navail = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -602,7 +650,7 @@ def worker(args):
         except Exception as exc:
             line["host_entry_pcie_inclusive"] = {"error": str(exc)}
         line["gpu_over_cpu"] = value / cb["value"] if args.workload == "c2" else None
-    if world == 1 and not args.no_other_workloads and not args.no_cpu and args.workload == "c2" and not args.nt and not args.nr:
+    if args.full and world == 1 and not args.no_other_workloads and not args.no_cpu and args.workload == "c2" and not args.nt and not args.nr:
         # the other BASELINE.json configurations (and the models outside them) at FULL size on this GPU, after the timed
         # region: the same step (resident inputs, the grid entry on the current stream), 1 warm-up + 2 timed steps each,
         # per-kernel times from the library's event brackets
@@ -655,6 +703,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return self_launch(args)
     return worker(args)

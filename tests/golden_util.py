@@ -10,6 +10,7 @@ from unconfined_amd.deck import Deck, TimeSpec
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 DECKS = os.path.join(GOLD, "decks")
+REFOUT = os.path.join(GOLD, "refout")
 
 
 def deck_names():
@@ -30,6 +31,12 @@ def load_stages(name):
     with open(os.path.join(GOLD, f"stages_{name}.json")) as f:
         meta = json.load(f)
     return meta, np.load(os.path.join(GOLD, f"stages_{name}.npz"))
+
+
+def ref_out_lines(name):
+    """the lines of the file the reference binary (flang -O2) writes for deck `name` (tests/golden/refout/, oracle/gen_refout.py)"""
+    with open(os.path.join(REFOUT, f"{name}.out"), errors="replace") as f:
+        return f.read().split("\n")
 
 
 def load_e2e(name):

@@ -1,5 +1,6 @@
-"""`python -m unconfined_amd deck` against `./unconfined deck` (the reference binary shipped under
-oracle/_ref): identical header bytes, identical time/space columns, values within the end-to-end gate."""
+"""`python -m unconfined_amd deck` against `./unconfined deck` (what the reference binary writes, stored under
+tests/golden/refout/ by oracle/gen_refout.py): identical header bytes, identical time/space columns, values within
+the end-to-end gate."""
 import os
 import shutil
 import subprocess
@@ -8,12 +9,10 @@ import sys
 import numpy as np
 import pytest
 
-from golden_util import DECKS, e2e_gate_bounds, load_e2e, rel_err
-from unconfined_amd.deck import Deck, SpaceSpec, TimeSpec
+from golden_util import DECKS, REFOUT, e2e_gate_bounds, load_e2e, ref_out_lines, rel_err
+from unconfined_amd.deck import Deck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref", "O2", "unconfined")
-REF_ALT = os.path.join(ROOT, "oracle", "_ref", "O3native", "unconfined")
 
 pytestmark = pytest.mark.gpu
 
@@ -32,10 +31,7 @@ def _cli(tmp_path, name, mode="faithful"):
 @pytest.mark.parametrize("name", ["neuman74_partpen", "c3_moench"])
 def test_cli_time_series_file(tmp_path, oracle, name):
     dk, ours = _cli(tmp_path, name)
-    if not os.path.exists(REF):
-        pytest.skip("reference binary not shipped")
-    subprocess.run([REF, f"{name}.in"], cwd=tmp_path, env=dict(os.environ, OMP_NUM_THREADS="8"), check=True, capture_output=True)
-    ref = [ln for ln in open(tmp_path / dk.outFileName, errors="replace").read().split("\n") if ln]
+    ref = [ln for ln in ref_out_lines(name) if ln]
     assert len(ours) == len(ref)
     assert [a for a in ours if a.startswith("#")] == [b for b in ref if b.startswith("#")]
     va = np.array([[float(x) for x in a.split()] for a in ours if not a.startswith("#")])
@@ -44,7 +40,7 @@ def test_cli_time_series_file(tmp_path, oracle, name):
     e2e = load_e2e(name)
     ir = int(np.argmin(np.abs(e2e["radii"] - dk.rval)))
     fix, bh, bd = e2e_gate_bounds(oracle, name, ir)          # the gate of tests/test_gpu_parity.py, per row
-    assert np.array_equal(fix, vb)                            # the binary run here writes what the fixture holds
+    assert np.array_equal(fix, vb)                            # the stored file holds what the e2e fixture holds
     assert (rel_err(va[:, 1], vb[:, 1], 1e-3) <= bh).all()
     assert (rel_err(va[:, 2], vb[:, 2], 1e-3) <= bd).all()
 
@@ -53,33 +49,22 @@ def test_cli_contour_file_every_radius(tmp_path):
     """contour mode: header bytes and (z, r) columns against the reference's contour run; VALUES at every (r, z)
     against one reference TIME-SERIES run per point -- the reference's own contour values are wrong for every radius
     after the first (it keeps the first radius' tanh-sinh abscissae), its single-point runs are
-    not.  Gate: max(1e-10, 20 x the reference's -O2 / -O3-native spread at that point)."""
+    not.  Gate: max(1e-10, 20 x the reference's -O2 / -O3-native spread at that point).  The reference's runs are
+    stored: tests/golden/refout/contour_neuman.out and contour_points.npz (oracle/gen_refout.py)."""
     name = "contour_neuman"
     dk, ours = _cli(tmp_path, name)
-    if not (os.path.exists(REF) and os.path.exists(REF_ALT)):
-        pytest.skip("reference binaries not shipped")
-    env = dict(os.environ, OMP_NUM_THREADS="8")
-    subprocess.run([REF, f"{name}.in"], cwd=tmp_path, env=env, check=True, capture_output=True)
-    ref = [ln for ln in open(tmp_path / dk.outFileName, errors="replace").read().split("\n") if ln]
+    ref = [ln for ln in ref_out_lines(name) if ln]
     assert len(ours) == len(ref)
     assert [a for a in ours if a.startswith("#")] == [b for b in ref if b.startswith("#")]
     va = np.array([[float(x) for x in a.split()] for a in ours if not a.startswith("#")])
     vb = np.array([[float(x) for x in b.split()] for b in ref if not b.startswith("#")])
     assert np.array_equal(va[:, :2], vb[:, :2])
-    TimeSpec(False, 0, 1, 1, times=[dk.tval]).write(tmp_path / "one_time.dat")
+    pts = np.load(os.path.join(REFOUT, "contour_points.npz"))
+    assert np.array_equal(pts["zr"], vb[:, :2])              # one stored point run per (z, r) of the contour, in its order
     wrong_in_reference = 0
-    for row_ours, row_contour in zip(va, vb):
+    for row_ours, row_contour, p0, p1 in zip(va, vb, pts["O2"], pts["O3native"]):
         z, r = row_ours[0], row_ours[1]
-        d = dk.replace(timeseries=True, piezometer=True, rval=float(r), zTop=float(z), zBot=float(z), timeFileName="one_time.dat",
-                       outFileName="pt.out")
-        d.write(tmp_path / "pt.in")
-        vals = []
-        for exe in (REF, REF_ALT):
-            subprocess.run([exe, "pt.in"], cwd=tmp_path, env=env, check=True, capture_output=True)
-            rows = [ln for ln in open(tmp_path / "pt.out", errors="replace").read().split("\n") if ln and not ln.startswith("#")]
-            assert len(rows) == 1
-            vals.append([float(x) for x in rows[0].split()])
-        (t0, h0, d0), (_, h1, d1) = vals
+        (t0, h0, d0), (_, h1, d1) = p0, p1
         assert t0 == dk.tval
         bh = max(1e-10, 20.0 * float(rel_err(h1, h0, 1e-3)))
         bd = max(1e-10, 20.0 * float(rel_err(d1, d0, 1e-3)))

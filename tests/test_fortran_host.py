@@ -7,13 +7,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from golden_util import DECKS, e2e_gate_bounds, load_deck, load_e2e, rel_err
+from golden_util import DECKS, e2e_gate_bounds, load_deck, load_e2e, ref_out_lines, rel_err
 from unconfined_amd import output
 from unconfined_amd.deck import Deck, SpaceSpec
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "unconfined_amd", "fortran", "build", "ucf_host")
-REF = os.path.join(ROOT, "oracle", "_ref", "O2", "unconfined")
 
 
 def _have_host():
@@ -44,8 +43,8 @@ def test_fortran_host_fails_loudly_without_gpu(tmp_path):
                                   "hstorage_partpen_lay2", "c1_theis", "malama_partpen_b1", "contour_neuman"])
 def test_fortran_host_header_is_the_reference_header(tmp_path, oracle, name):
     """the '#' parameter echo written by ucf_output.f90 equals unconfined_amd/output.py's line for line -- and that one is
-    pinned byte for byte to files written by the reference binary (tests/test_output_format.py); where the reference
-    binary travels with the repo its own header is compared too.  No GPU needed ("header" mode)."""
+    pinned byte for byte to files written by the reference binary (tests/test_output_format.py) -- and to the header of
+    the reference binary's own file for this deck (tests/golden/refout/).  No GPU needed ("header" mode)."""
     if not _have_host():
         pytest.skip("flang not available")
     res, dk = _run(tmp_path, name, mode="header")
@@ -62,11 +61,7 @@ def test_fortran_host_header_is_the_reference_header(tmp_path, oracle, name):
         want = output.contour_header(dk, D, oracle.linspace(sp.min_r, sp.max_r, sp.n_r), oracle.linspace(sp.min_z, sp.max_z, sp.n_z),
                                      dk.tval, dk.tval / D.Tc)
     assert mine == want
-    if os.path.exists(REF):
-        os.rename(tmp_path / dk.outFileName, tmp_path / "ours.out")
-        subprocess.run([REF, f"{name}.in"], cwd=tmp_path, env=dict(os.environ, OMP_NUM_THREADS="4"), check=True, capture_output=True)
-        ref = [ln for ln in open(tmp_path / dk.outFileName, errors="replace").read().split("\n") if ln.startswith("#")]
-        assert mine == ref
+    assert mine == [ln for ln in ref_out_lines(name) if ln.startswith("#")]
 
 
 @pytest.mark.gpu

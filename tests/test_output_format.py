@@ -1,31 +1,20 @@
 """Byte-level check of unconfined_amd/output.py against files written by the reference binary
-(oracle/_ref/O2/unconfined, built by `make -C oracle ref`; the binary travels with the repo, its
-sources do not).  Numbers are taken from the reference file itself, so this tests formatting only."""
+(oracle/_ref/O2/unconfined, stored under tests/golden/refout/ by oracle/gen_refout.py).  Numbers are
+taken from the reference file itself, so this tests formatting only."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
-from golden_util import DECKS, load_deck
+from golden_util import DECKS, load_deck, ref_out_lines
 from unconfined_amd import output
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.path.join(ROOT, "oracle", "_ref", "O2", "unconfined")
 
 
 @pytest.mark.parametrize("name", ["neuman74_partpen", "c3_moench", "mishra_fd30", "hantush_lay2", "theis_pulse",
                                   "mishra_malama", "hstorage_partpen_lay2"])
-def test_timeseries_file_matches_reference_bytes(tmp_path, oracle, name):
-    if not os.path.exists(REF):
-        pytest.skip("reference binary not built (oracle/_ref)")
+def test_timeseries_file_matches_reference_bytes(oracle, name):
     dk, ts, P = load_deck(name)
-    for fn in (f"{name}.in", dk.timeFileName):
-        shutil.copy(os.path.join(DECKS, fn), tmp_path)
-    env = dict(os.environ, OMP_NUM_THREADS="4")
-    subprocess.run([REF, f"{name}.in"], cwd=tmp_path, env=env, check=True, capture_output=True)
-    ref_lines = open(tmp_path / dk.outFileName, errors="replace").read().split("\n")
+    ref_lines = ref_out_lines(name)
     rows_ref = [ln for ln in ref_lines if ln and not ln.startswith("#")]
     vals = np.array([[float(x) for x in ln.split()] for ln in rows_ref])
     D = oracle.nondim(P)
@@ -48,19 +37,14 @@ def test_es_edit_descriptors():
     assert output.hfmt(float("nan")).strip() == "NaN"
 
 
-def test_contour_file_matches_reference_bytes(tmp_path, oracle):
+def test_contour_file_matches_reference_bytes(oracle):
     """contour mode (timeseries = F): header of driver_io.f90:760-845 and rows of driver.f90:259-271.
     (Values of the reference are only trustworthy for its first radius, SURVEY.md quirk Q1 -- this test
     re-formats the reference's own numbers.)"""
-    if not os.path.exists(REF):
-        pytest.skip("reference binary not built (oracle/_ref)")
     from unconfined_amd.deck import Deck, SpaceSpec
     name = "contour_neuman"
     dk = Deck.read(os.path.join(DECKS, f"{name}.in"))
-    for fn in (f"{name}.in", dk.spaceFileName):
-        shutil.copy(os.path.join(DECKS, fn), tmp_path)
-    subprocess.run([REF, f"{name}.in"], cwd=tmp_path, env=dict(os.environ, OMP_NUM_THREADS="4"), check=True, capture_output=True)
-    ref_lines = [ln for ln in open(tmp_path / dk.outFileName, errors="replace").read().split("\n") if ln != ""]
+    ref_lines = [ln for ln in ref_out_lines(name) if ln != ""]
     vals = np.array([[float(x) for x in ln.split()] for ln in ref_lines if not ln.startswith("#")])
     from unconfined_amd.abi import params_from_deck
     D = oracle.nondim(params_from_deck(dk))

@@ -6,16 +6,20 @@ through the shipped ISO_C_BINDING module, and the loop nest of driver.f90:100-23
     for bit, for every model; times, radii, depths, layers and split indices that the call receives == the product's
     own deck path (unconfined_amd.engine.grids_from_deck);
   * GPU: the file the binding driver writes (header by the reference's own writer) against the reference binary's.
+The reference's side of both is also stored (tests/golden/refout/, oracle/gen_refout.py): the nondim listing's reference
+column, checked against the library's own mapping of the deck wherever the driver is absent too, and the header lines.
 The driver links the reference's modules from oracle/_ref/O2 (built where /root/reference exists; the binaries travel to
 the GPU box).  Nothing here is product code."""
+import ctypes as C
 import os
 import shutil
+import struct
 import subprocess
 
 import numpy as np
 import pytest
 
-from golden_util import DECKS, e2e_gate_bounds, load_deck, load_e2e, rel_err, unhx
+from golden_util import DECKS, REFOUT, e2e_gate_bounds, load_deck, load_e2e, ref_out_lines, rel_err, unhx
 from unconfined_amd.deck import Deck
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,13 +41,56 @@ def _need_driver():
         pytest.skip("oracle/_ref/O2/ref_binding_driver not built (needs /root/reference + flang: __graft_entry__.build())")
 
 
+def _stored_nondim(name):
+    """the reference's column of `ref_binding_driver <deck>.in nondim` (tests/golden/refout/<deck>.nondim)"""
+    with open(os.path.join(REFOUT, f"{name}.nondim")) as f:
+        return [ln.split() for ln in f if ln.strip()]
+
+
+def _reference_side(rows):
+    return [r[:4] if r[0] == "sizes" else r[:3] if r[0] in ("tD", "rD", "zD") else r[:2] for r in rows]
+
+
+def _hx(x):
+    return "%016X" % struct.unpack("<Q", struct.pack("<d", float(x)))[0]
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_mapped_params_reproduce_read_input(tmp_path, oracle, name):
     _need_driver()
-    from unconfined_amd import engine
     res, dk = _run(tmp_path, name, "nondim")
     assert res.returncode == 0, res.stdout + res.stderr
     rows = [ln.split() for ln in res.stdout.split("\n") if ln.strip()]
+    assert _reference_side(rows) == _stored_nondim(name)        # the stored reference column is this driver's
+    _check_nondim_rows(oracle, name, dk, rows)
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_stored_read_input_matches_library_nondim(oracle, name):
+    """the same checks on the stored reference column (no driver needed): the library's side here is
+    ucf_nondimensionalise of the product's own mapping of the deck (unconfined_amd.abi.params_from_deck), not the
+    Fortran binding -- that one is test_mapped_params_reproduce_read_input's"""
+    from unconfined_amd import lib as ucflib
+    from unconfined_amd.abi import UcfDerived, params_from_deck
+    dk = Deck.read(os.path.join(DECKS, f"{name}.in"))
+    D = UcfDerived()
+    ucflib.check(ucflib.load().ucf_nondimensionalise(C.byref(params_from_deck(dk)), C.byref(D)))
+    rows, m = [], 0
+    for r in _stored_nondim(name):
+        if r[0] == "sizes":
+            rows.append(r + [str(D.nj0z)])
+        elif r[0] in ("tD", "rD", "zD"):
+            rows.append(r)
+        elif r[0] == "MoenchGamma":
+            rows.append(r + [_hx(D.MoenchGamma[m])])
+            m += 1
+        else:
+            rows.append(r + [_hx(getattr(D, r[0]))])
+    _check_nondim_rows(oracle, name, dk, rows)
+
+
+def _check_nondim_rows(oracle, name, dk, rows):
+    from unconfined_amd import engine
     pairs = [(r[0], r[1], r[2]) for r in rows if r[0] not in ("sizes", "tD", "rD", "zD")]
     assert len(pairs) >= 10
     for nm, ref_bits, lib_bits in pairs:
@@ -99,9 +146,5 @@ def test_binding_driver_file_matches_reference(tmp_path, oracle, name, mode):
     assert np.array_equal(rows[:, 0], ref[:, 0])
     assert (rel_err(rows[:, 1], ref[:, 1], 1e-3) <= bh).all()
     assert (rel_err(rows[:, 2], ref[:, 2], 1e-3) <= bd).all()
-    refbin = os.path.join(ROOT, "oracle", "_ref", "O2", "unconfined")
-    if os.path.exists(refbin):
-        os.rename(tmp_path / dk.outFileName, tmp_path / "ours.out")
-        subprocess.run([refbin, f"{name}.in"], cwd=tmp_path, env=dict(os.environ, OMP_NUM_THREADS="4"), check=True, capture_output=True)
-        theirs = [ln for ln in open(tmp_path / dk.outFileName, errors="replace").read().split("\n") if ln.startswith("#")]
-        assert [ln for ln in lines if ln.startswith("#")] == theirs
+    theirs = [ln for ln in ref_out_lines(name) if ln.startswith("#")]     # the reference binary's file, stored
+    assert [ln for ln in lines if ln.startswith("#")] == theirs

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Copy the evidence of tools/gpu_final.sh from gpurun_out/ (scratch) into profiles/ (tracked):
+"""Copy the evidence of tools/gpu_final.sh from its log folder (tools_out/ or $UCF_TOOLS_OUT, scratch) into profiles/ (tracked):
   profiles/<tag>_<workload>_kernel_stats.csv   rocprofv3 --kernel-trace --stats summary
   profiles/<tag>_bench_<...>.json              bench lines
   profiles/pmc_r03.json                        per workload and kernel: counters per launch, executed fp64 flop, VALU-busy,
@@ -9,7 +9,7 @@ usage: tools/collect_profiles.py [tag]"""
 import collections, csv, glob, json, os, re, shutil, sys
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
-G, P = os.path.join(R, "gpurun_out"), os.path.join(R, "profiles")
+G, P = os.path.join(R, os.environ.get("UCF_TOOLS_OUT", "tools_out")), os.path.join(R, "profiles")
 WORKLOADS = ("c2", "c2pp", "c3", "c4", "c5", "c1", "hstorage", "mnm")
 
 
