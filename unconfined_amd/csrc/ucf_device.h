@@ -1494,6 +1494,7 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
     //  work item, its abscissa row and the row's entries live in VGPRs and are fetched by vector loads)
     const int lane = threadIdx.x & (UCF_WAVE - 1), wv = __builtin_amdgcn_readfirstlane(threadIdx.x / UCF_WAVE);
     constexpr int EF = (FAMILY == 5) ? 1 : FAMILY;      // the evaluator: model 2 runs family 1's with its own lane constant
+    constexpr bool ZPAIR = FOLD && EF == 2 && NZC == 1;      // shared seeds: fast_eta's rsq_pair, prim_pair in fast_common_terms
     const int nz = NZC ? NZC : P0.nz, R = P0.R, nacc = P0.nacc, N = P0.N, ngl = P0.ngl;
     __builtin_assume(nz >= 1 && R >= 1 && nacc >= 1 && ngl >= 1);     // (the launcher's business: no loop guards in the kernel)
     const int nabs = N + nacc * ngl;
@@ -1586,15 +1587,15 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
             const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
             const bool ts = n < N;
             F.sc.salt = n;
-            if (!fast_eta_wave<EF>(P, LC, aa.x, F)) break;                                       // (every lane is live here)
-            fast_common_terms<EF, FOLD, LAY3, LAY1, NOFOLD>(P, LC, aa.x, need_lay1, F, need_lay3, need_lay12);
+            if (!fast_eta_wave<EF, ZPAIR>(P, LC, aa.x, F)) break;                                       // (every lane is live here)
+            fast_common_terms<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, LC, aa.x, need_lay1, F, need_lay3, need_lay12);
             const int n1 = n + 1;
             int tz = __builtin_ctz(n1);
             if (tz > R - 1) tz = R - 1;
             for (int z = 0; z < nz; z++) {
                 // val = a*J0(a rD) * f(a,p,z) [* lapTime(p): at the end]                         (lhs.f90:118)
                 // (Gauss-Lobatto part: aa.y carries the node's weight, abscissa_kernel)
-                const cplx fz = fast_sample_z<EF, FOLD, LAY3, LAY1, NOFOLD>(P, F, z);
+                const cplx fz = fast_sample_z<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, F, z);
                 if (ts) {
                     const cplx val = rscale(aa.y, fz);
                     // tanh-sinh on [0, arg]: abscissa n+1 belongs to level j when 2^(R-j) divides it  (driver.f90:129-157)

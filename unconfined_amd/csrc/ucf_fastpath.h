@@ -32,15 +32,12 @@ struct fprim {
     double ch, sh, ei, sn, cs;    // cosh(x), sinh(x), exp(-|x|), sin(y), cos(y)
 };
 
-// POS: the caller knows x >= 0 (Re eta > 0 times a non-negative factor): no sign to put back on sinh
-template <bool POS = false>
-UCF_DEV fprim prim(double x, double y, const sc_ctx& sc)
+// (the part of prim after e = exp(ax) and ei = 1/e)
+template <bool POS>
+UCF_DEV fprim prim_from_e(double x, double ax, double e, double ei, double y, const sc_ctx& sc)
 {
     const int salt = sc.salt;
     fprim f;
-    const double ax = POS ? x : fabs(x);          // (POS: the absolute value would be two VALU instructions in front of the inline asm)
-    const double e = exp_tab_(ax, sc);
-    const double ei = fast_rcp(e);
     f.ei = ei;
     const double he = 0.5 * e;
     f.ch = __builtin_fma(0.5, ei, he);
@@ -59,6 +56,27 @@ UCF_DEV fprim prim(double x, double y, const sc_ctx& sc)
     f.sh = POS ? s : copysign(s, x);
     sincos_tab_(y, sc, &f.sn, &f.cs);     // |y| < 1e6: fast_eta() vouches for it
     return f;
+}
+// POS: the caller knows x >= 0 (Re eta > 0 times a non-negative factor): no sign to put back on sinh
+template <bool POS = false>
+UCF_DEV fprim prim(double x, double y, const sc_ctx& sc)
+{
+    const double ax = POS ? x : fabs(x);          // (POS: the absolute value would be two VALU instructions in front of the inline asm)
+    const double e = exp_tab_(ax, sc);
+    return prim_from_e<POS>(x, ax, e, fast_rcp(e), y, sc);
+}
+// the primitives of eta = (x, y) and eta zD, 0 <= zD <= 1, with ONE reciprocal for both real exponentials (batch inversion:
+// 1/E = E_z / (E E_z), 1/E_z = E / (E E_z); a rounding of the product and of each quotient more than two fast_rcp).  Only
+// lanes with x < xcap read the results: x is clamped there, so that E E_z <= e^{xcap (1 + zD)} (e^24 for the water-table
+// closure's xcap = maxexp) cannot overflow in the lanes that do not
+UCF_DEV void prim_pair(double x, double y, double zD, double xcap, const sc_ctx& sc, fprim* f, fprim* fz)
+{
+    const double xc = fmin(x, xcap);
+    const double xz = xc * zD;
+    const double e = exp_tab_(xc, sc), ez = exp_tab_(xz, sc);
+    const double r = fast_rcp(e * ez);
+    *f = prim_from_e<true>(xc, xc, e, r * ez, y, sc);
+    *fz = prim_from_e<true>(xz, xz, ez, r * e, y * zD, sc);
 }
 // primitive of x1 - x2, y1 - y2 from the primitives of (x1, y1) and (x2, y2), 0 <= x2 <= x1: the real
 // exponentials divide, the angles subtract (no cancellation in either; sinh of a small difference loses
@@ -150,6 +168,7 @@ UCF_DEV lane_consts make_lane_consts(const ucf_dev_params& P, cplx p, cplx lt)
 struct fast_common {
     sc_ctx sc;           // sin/cos table in LDS + constants (sincos_tab_), set once per kernel; sc.salt = the loop counter
     cplx th, eta, ff1, ff2, inv_she, she, che, top, g3, inv_den, ex1;   // ex1 = exp(-eta)
+    cplx chz0;           // ZPAIR: cosh(eta zD) of the launch's one depth (valid when any_small)
     fprim p1;            // primitive of eta itself (valid when have_p1)
     int have_p1;         // (wave-uniform flags are ints: a uniform bool that crosses a join is rebuilt through VALU selects)
     cplx mn_uod;         // MN-Malama: u / Delta_0                                                     (:437-439)
@@ -179,7 +198,9 @@ UCF_DEV double fast_scale(const ucf_dev_params& P)
 // theta and eta of this abscissa.  Returns false (for this lane) if the fast evaluation is not applicable:
 // a cosh/sinh could overflow, or the argument of a sin/cos (|Im eta| times a factor <= 1) leaves the range of
 // the two-stage Cody-Waite reduction.
-template <int FAMILY>
+// PAIR: |q| and 1/|q|^2 from one seed (rsq_pair; the ZPAIR kernel only -- the roundings it moves took the worst-conditioned
+// point of the c4_malama_partpen fixture past its parity gate, 1.23e-10 against 1.02e-10)
+template <int FAMILY, bool PAIR = false>
 UCF_DEV bool fast_eta(const ucf_dev_params& P, const lane_consts& L, double a, fast_common& S)
 {
     const double a2 = a * a;
@@ -187,15 +208,22 @@ UCF_DEV bool fast_eta(const ucf_dev_params& P, const lane_consts& L, double a, f
 #ifdef UCF_SINGLE_RCP
     S.q = q;
 #endif
-    {
-        const double r = fast_rcp(q.re * q.re + q.im * q.im);
+    // PAIR: |q| and 1/|q|^2 from one seed (rsq_pair): |q|^2 is normal wherever the separate reciprocal of it was, and above
+    // 4e307 (|q| > 6e153) eta = sqrt(q/kappa) passes the wave's test only for kappa > 1e148
+    double mq = 0.0;
+    if (PAIR && FAMILY != 0) {
+        double r;
+        rsq_pair(q.re * q.re + q.im * q.im, &mq, &r);
         S.th = cmake(q.re * r, -(q.im * r));                      // HALF of theis = 2/q (:122-131): see fast_scale()
+    } else {
+        const double r = fast_rcp(q.re * q.re + q.im * q.im);
+        S.th = cmake(q.re * r, -(q.im * r));
     }
     if (FAMILY == 0) return q.re > 0.0;                           // Theis is that reciprocal and nothing else
     {   // eta = sqrt(q/kappa), Re q > 0                                                         (:69,172)
         const double qr = q.re * P.inv_kappa, qi = q.im * P.inv_kappa;
         double r, hr;
-        const double d = sqrt_only(__builtin_fma(qr, qr, qi * qi));
+        const double d = PAIR ? mq * P.inv_kappa : sqrt_only(__builtin_fma(qr, qr, qi * qi));   // |q/kappa|
         sqrt_hrsqrt(0.5 * (d + qr), &r, &hr);
         S.eta = cmake(r, qi * hr);
     }
@@ -205,10 +233,10 @@ UCF_DEV bool fast_eta(const ucf_dev_params& P, const lane_consts& L, double a, f
 // the same for a whole wave: true if EVERY lane may take the fast evaluation.  One ballot per compare and the scalar unit's OR
 // (the ballot of the combined per-lane flag came back as flag -> 0 / 1 in a VGPR -> compare again: two VALU instructions per
 // abscissa for nothing)
-template <int FAMILY>
+template <int FAMILY, bool PAIR = false>
 UCF_DEV bool fast_eta_wave(const ucf_dev_params& P, const lane_consts& L, double a, fast_common& S)
 {
-    (void)fast_eta<FAMILY>(P, L, a, S);
+    (void)fast_eta<FAMILY, PAIR>(P, L, a, S);
     const cplx q = caddr(L.p, a * a);
     unsigned long long bad = __builtin_amdgcn_ballot_w64(!(q.re > 0.0));
     if (FAMILY != 0) {
@@ -231,10 +259,13 @@ UCF_DEV bool fast_eta_wave(const ucf_dev_params& P, const lane_consts& L, double
 // LAY3 = false: the launcher knows that no depth of the call lies above the screen top; LAY1 = false: none below its bottom
 // (the usual piezometer beside the screen: the terms of the layer below -- exp(-eta), g3 -- are then not even allocated:
 //  18 -> 14 spilled VGPRs in the partially penetrating water-table kernel, C2pp 87.9 -> 85.7 ms, C4 236.2 -> 230.3)
-template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false>
+// ZPAIR (FOLD, water-table family, one depth per launch): the primitive of eta zD, the only other one such a sample takes, is
+// formed here together with that of eta, from one reciprocal (prim_pair), and fast_sample_z reads its cosh from S.chz0
+template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false, bool ZPAIR = false>
 UCF_DEV void fast_common_terms(const ucf_dev_params& P, const lane_consts& L, double a, bool need_lay1_in, fast_common& S,
                                bool need_lay3_in = false, bool need_lay12 = true)
 {
+    static_assert(!ZPAIR || (FOLD && FAMILY == 2), "ZPAIR: folded water-table kernels only");
     const double a2 = a * a;
     if (FAMILY == 0) return;
     if (FAMILY == 3) {
@@ -263,7 +294,14 @@ UCF_DEV void fast_common_terms(const ucf_dev_params& P, const lane_consts& L, do
     const bool need_p1 = (hantush && (!(z1 && z2) || need_lay1)) || FAMILY == 4 || (FAMILY == 2 && S.any_small);
     S.have_p1 = (need_p1 && !z2) ? 1 : 0;      // kept only where fast_hantush_z derives the primitive of eta (1 - zD) from it
     fprim p1;
-    if (need_p1) {
+    if (ZPAIR && need_p1) {             // (FOLD: need_p1 = any_small, and neither S.p1 nor ex1 is wanted)
+        fprim pz;
+        prim_pair(S.eta.re, S.eta.im, P.zD[0], P.maxexp, S.sc, &p1, &pz);
+        S.chz0 = pcosh(pz);
+        S.che = pcosh(p1);
+        S.she = psinh(p1);
+        S.ex1 = cmake(0.0, 0.0);
+    } else if (need_p1) {
         p1 = prim<true>(S.eta.re, S.eta.im, S.sc);
         if (!z2) S.p1 = p1;
         S.che = pcosh(p1);
@@ -391,7 +429,7 @@ UCF_DEV bool fast_prepare(const ucf_dev_params& P, const lane_consts& L, double 
 }
 
 // Hantush factor at depth zD (:133-202); chz = cosh(eta*zD) is returned for the closure
-template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false>
+template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false, bool ZPAIR = false>
 UCF_DEV cplx fast_hantush_z(const ucf_dev_params& P, const fast_common& S, double zD, int lay_in, cplx* chz_out,
                             cplx* exz_out)
 {
@@ -400,7 +438,8 @@ UCF_DEV cplx fast_hantush_z(const ucf_dev_params& P, const fast_common& S, doubl
     const bool need_chz = (lay == 1) || !z1 || (FAMILY == 2 && S.any_small) || FAMILY == 4;
     cplx chz = cmake(1.0, 0.0);
     fprim pz;
-    if (need_chz) { pz = prim<true>(S.eta.re * zD, S.eta.im * zD, S.sc); chz = pcosh(pz); }      // (0 <= zD <= 1 on this path)
+    if (ZPAIR) { if (need_chz) chz = S.chz0; }                   // (FOLD: pz has no other use)
+    else if (need_chz) { pz = prim<true>(S.eta.re * zD, S.eta.im * zD, S.sc); chz = pcosh(pz); }  // (0 <= zD <= 1 on this path)
     *chz_out = chz;
     cplx udp;
     if (lay == 1) {
@@ -447,7 +486,7 @@ UCF_DEV cplx fast_hantush_z(const ucf_dev_params& P, const fast_common& S, doubl
     return res;
 }
 
-template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false>
+template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false, bool ZPAIR = false>
 UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz)
 {
     const double zD = P.zD[iz];
@@ -467,10 +506,10 @@ UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz
     cplx u;
     if (!NOFOLD && P.model == 4) {
         u = S.th;
-        if (S.any_small) chz = pcosh(prim(S.eta.re * zD, S.eta.im * zD, S.sc));
+        if (S.any_small) chz = ZPAIR ? S.chz0 : pcosh(prim(S.eta.re * zD, S.eta.im * zD, S.sc));
         if (S.any_large) { const double c = 1.0 - zD; exz = expneg_direct(S.eta.re * c, S.eta.im * c, S.sc); }
     } else {
-        u = fast_hantush_z<2, FOLD, LAY3, LAY1, NOFOLD>(P, S, zD, lay, &chz, &exz);
+        u = fast_hantush_z<2, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, S, zD, lay, &chz, &exz);
         if (LAY1 && S.any_large && lay == 1) { const double c = 1.0 - zD; exz = expneg_direct(S.eta.re * c, S.eta.im * c, S.sc); }
     }
 #ifdef UCF_SINGLE_RCP
