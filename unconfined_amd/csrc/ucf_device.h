@@ -1566,6 +1566,12 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
         const double2 ltv = ltab[(size_t)(W.mlap < P0.np ? W.mlap : P0.np - 1) * nrows + W.it];
         const cplx lt = cmake(ltv.x, ltv.y);
         const lane_consts LC = make_lane_consts(P, p, lt);
+        auto lt_again = [&]() {
+            int it = W.it;
+            asm volatile("" : "+v"(it));
+            const double2 v = ltab[(size_t)(W.mlap < P0.np ? W.mlap : P0.np - 1) * nrows + it];
+            return cmake(v.x, v.y);
+        };
         double2* __restrict__ sti = state + (size_t)pt * state_slots(P0) * UCF_WAVE;
         double2* __restrict__ areas = sti + (size_t)(R + 1) * nz * UCF_WAVE;
         for (int s = 0; s < lslots; s++) lds_st(wlds, s, lane, cmake(0.0, 0.0));
@@ -1583,19 +1589,65 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
         double2 aa = row[n0 < nabs ? n0 : 0];
         int m = 0, jj = n0 > N ? (n0 - N) / ngl : 0;   // Gauss-Lobatto node and J0 interval of abscissa n >= N
         cplx acc0 = cmake(0.0, 0.0), acc1 = cmake(0.0, 0.0);      // running area of the interval: registers when nz = 1 (or
+        if constexpr (ZPAIR) {
+            // The folded water-table kernel with one depth walks the two parts in loops of their own: the tanh-sinh loop
+            // knows the level sums and P.ts_w, the Gauss-Lobatto loop the running area -- which then stays in its registers
+            // (in the one loop the two arms met in copies: two v_mov_b64 per abscissa) -- and neither tests `ts`.  The
+            // sample is fast_sample_zpair (ucf_fastpath.h).  Same operations in the same order: same bits.
+            // lapTime(p) is wanted when an interval is complete and after the loops, not in between: it is read again there
+            // (ltab, as above) instead of being held in four registers across the loops -- the index is laundered so that the
+            // load stays where it is written
+            int stopped = 0;
+            const int nts = nlim < N ? nlim : N;
+            for (; n < nts; n++) {
+                const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
+                F.sc.salt = n;
+                if (!fast_eta_wave<EF, true>(P, LC, aa.x, F)) { stopped = 1; break; }
+                const cplx val = rscale(aa.y, fast_sample_zpair<!MULTI>(P, LC, F));
+                const int n1 = n + 1;
+                int tz = __builtin_ctz(n1);
+                if (tz > R - 1) tz = R - 1;
+                for (int sh = 0; sh <= tz; sh++) {                                               // (driver.f90:129-157)
+                    const int j = R - sh;
+                    const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
+                    lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
+                }
+                aa = nxt;
+            }
+            if (!stopped) for (; n < nlim; n++) {
+                const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
+                F.sc.salt = n;
+                if (!fast_eta_wave<EF, true>(P, LC, aa.x, F)) break;
+                const cplx fz = fast_sample_zpair<!MULTI>(P, LC, F);
+                acc0 = cmake(__builtin_fma(fz.re, aa.y, acc0.re), __builtin_fma(fz.im, aa.y, acc0.im));           // :201-202
+                if (++m == ngl) {                                                                // (driver.f90:187-203)
+                    const double lob = P.j0z[sv + jj - 1] / rD;
+                    const double hib = P.j0z[sv + jj] / rD;
+                    const double hw = (hib - lob) / 2.0;
+                    const cplx ar = cmul(rscale(hw, acc0), lt_again());
+                    areas[(size_t)jj * UCF_WAVE + lane] = make_double2(ar.re, ar.im);
+                    acc0 = cmake(0.0, 0.0);
+                    m = 0;
+                    jj++;
+                }
+                aa = nxt;
+            }
+        } else
         for (; n < nlim; n++) {                   // NZC = 2: two depths known at compile time), else accCur[z] in LDS
             const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
             const bool ts = n < N;
             F.sc.salt = n;
             if (!fast_eta_wave<EF, ZPAIR>(P, LC, aa.x, F)) break;                                       // (every lane is live here)
-            fast_common_terms<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, LC, aa.x, need_lay1, F, need_lay3, need_lay12);
+            if constexpr (!ZPAIR) fast_common_terms<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, LC, aa.x, need_lay1, F, need_lay3, need_lay12);
             const int n1 = n + 1;
             int tz = __builtin_ctz(n1);
             if (tz > R - 1) tz = R - 1;
             for (int z = 0; z < nz; z++) {
                 // val = a*J0(a rD) * f(a,p,z) [* lapTime(p): at the end]                         (lhs.f90:118)
                 // (Gauss-Lobatto part: aa.y carries the node's weight, abscissa_kernel)
-                const cplx fz = fast_sample_z<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, F, z);
+                cplx fz;
+                if constexpr (ZPAIR) fz = fast_sample_zpair<!MULTI>(P, LC, F);
+                else fz = fast_sample_z<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, F, z);
                 if (ts) {
                     const cplx val = rscale(aa.y, fz);
                     // tanh-sinh on [0, arg]: abscissa n+1 belongs to level j when 2^(R-j) divides it  (driver.f90:129-157)
@@ -1637,8 +1689,9 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
         // travels and the parts of an item need not agree on one.  ndone[pt] was set to nabs by the launcher; the smallest
         // hand-over point of the item's parts counts, the part that lowers it first lists the item.
         if (sub == 0) {
+            const cplx lte = ZPAIR ? lt_again() : lt;
             for (int s = 0; s < R * nz; s++) {
-                const cplx v = cmul(lds_ld(wlds, s, lane), lt);
+                const cplx v = cmul(lds_ld(wlds, s, lane), lte);
                 sti[(size_t)s * UCF_WAVE + lane] = make_double2(v.re, v.im);
             }
             // (the slots of the running areas: nothing travels in them, point_kernel starts its interval afresh)

@@ -78,6 +78,22 @@ UCF_DEV void prim_pair(double x, double y, double zD, double xcap, const sc_ctx&
     *f = prim_from_e<true>(xc, xc, e, r * ez, y, sc);
     *fz = prim_from_e<true>(xz, xz, ez, r * e, y * zD, sc);
 }
+// the same for the folded water-table kernel's own sample (fast_sample_zpair).  fmin() comes back as three instructions: the
+// compiler first canonicalises both operands (v_max_f64 of a value with itself, for the sake of signalling NaNs), one of
+// them the loop-invariant cap.  x has passed fast_eta_wave's range test, so it is a number, and v_min_f64 alone returns the
+// same bits.  UNI: xcap is wave-uniform (one plan per launch) and is read from its SGPR pair; a parameter batch keeps fmin
+template <bool UNI>
+UCF_DEV void prim_pair_min(double x, double y, double zD, double xcap, const sc_ctx& sc, fprim* f, fprim* fz)
+{
+    double xc;
+    if constexpr (UNI) asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(xcap));
+    else xc = fmin(x, xcap);
+    const double xz = xc * zD;
+    const double e = exp_tab_(xc, sc), ez = exp_tab_(xz, sc);
+    const double r = fast_rcp(e * ez);
+    *f = prim_from_e<true>(xc, xc, e, r * ez, y, sc);
+    *fz = prim_from_e<true>(xz, xz, ez, r * e, y * zD, sc);
+}
 // primitive of x1 - x2, y1 - y2 from the primitives of (x1, y1) and (x2, y2), 0 <= x2 <= x1: the real
 // exponentials divide, the angles subtract (no cancellation in either; sinh of a small difference loses
 // relative, not absolute, accuracy, which is all cosh/sinh products of complex arguments need)
@@ -527,5 +543,63 @@ UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz
     }
     return cfnma(cmul(top, g), S.inv_den, u);
 }
+
+// The whole sample of the folded water-table kernel with one depth per launch (ZPAIR: FOLD, family 2, NZC = 1), after
+// fast_eta_wave said yes: what fast_common_terms and fast_sample_z compute for it, operation for operation (same bits), laid
+// out by what a WAVE needs.  A fully penetrating screen leaves u = top = 1/q (S.th), so the sample is
+//   th - th g / den,  g = cosh(eta zD), den = (1 + beta eta xi) cosh(eta) + xi sinh(eta)     where Re eta < maxexp   (:86-87)
+//                     g = exp(eta (zD - 1)), den = 1 + beta eta xi + xi                      beyond                 (:90-91)
+// Nearly every wave is on one form only (Re eta grows with the abscissa, and the lanes of a wave share it): such a wave takes
+// a branch of its own that holds that form and nothing else.  In the general code the arm of the other form was still
+// issued with an empty EXEC mask (the compiler leaves out the skip around a short block), the values its lanes would have
+// read were set to zero, the per-lane select of g was guarded by a flag that travelled through a VGPR, and the copies where
+// the arms joined were made in every wave: 10 to 14 VALU slots per abscissa, none of them arithmetic.  A wave with lanes on
+// both forms does what it did before.
+template <bool UNI>
+UCF_DEV cplx fast_sample_zpair(const ucf_dev_params& P, const lane_consts& L, const fast_common& S)
+{
+    const double zD = P.zD[0];
+    const bool small_eta = S.eta.re < P.maxexp;                                                 // :84
+    const bool any_small = __builtin_amdgcn_ballot_w64(small_eta) != 0, any_large = __builtin_amdgcn_ballot_w64(!small_eta) != 0;
+    // (xi = eta alphaD / p ... (:70-75) is formed in each arm AFTER the primitives: four registers less while they are evaluated;
+    //  |den| needs no exponent scaling: fast_common_terms)
+    cplx den, g;
+    if (!any_large) {
+        fprim p1, pz;
+        prim_pair_min<UNI>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
+        g = pcosh(pz);
+        const cplx che = pcosh(p1), she = psinh(p1);
+        const cplx xi = cmul(S.eta, L.xifac);
+        if (P.beta != 0.0) den = cfma(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), che, cmul(xi, she));
+        else den = cfma(xi, she, che);                           // beta = 0 (wave-uniform): no product with (1, 0)
+        UCF_UNIFORM_BLOCK();
+    } else if (!any_small) {
+        const double c = 1.0 - zD;
+        g = expneg_direct(S.eta.re * c, S.eta.im * c, S.sc);
+        const cplx xi = cmul(S.eta, L.xifac);
+        if (P.beta != 0.0) den = cadd(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), xi);
+        else den = radd(1.0, xi);
+        UCF_UNIFORM_BLOCK();
+    } else {
+        fprim p1, pz;
+        prim_pair_min<UNI>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
+        const cplx chz = pcosh(pz), che = pcosh(p1), she = psinh(p1);
+        const cplx xi = cmul(S.eta, L.xifac);
+        if (P.beta != 0.0) {
+            const cplx one_bex = radd(1.0, cmul(rscale(P.beta, S.eta), xi));
+            den = small_eta ? cfma(one_bex, che, cmul(xi, she)) : cadd(one_bex, xi);
+        } else {
+            den = small_eta ? cfma(xi, she, che) : radd(1.0, xi);
+        }
+        const double c = 1.0 - zD;
+        const cplx exz = expneg_direct(S.eta.re * c, S.eta.im * c, S.sc);
+        g = small_eta ? chz : exz;
+        UCF_UNIFORM_BLOCK();
+    }
+    const double r = fast_rcp(__builtin_fma(den.im, den.im, den.re * den.re));                  // cinv_plain, its contraction pinned
+    const cplx inv_den = cmake(den.re * r, -(den.im * r));
+    return cfnma(cmul(S.th, g), inv_den, S.th);
+}
+
 
 }  // namespace UCF_NS
