@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Where the (wave, abscissa) pairs of the folded one-depth water-table kernel lie for a grid, from a binary64 CPU evaluation
+of eta = sqrt((p + a^2) / kappa): the form the wave is on (cosh/sinh below Re eta = maxexp in every lane, exponential above,
+both), whether the wave is on the short sin/cos form there (sincos_small_: every lane's argument below UCF_SC_SMALL at an
+abscissa where the kernel may set the bit, and from then on), and the transitions along an item.
+No GPU: the oracle's J0 zeros, tanh-sinh and Gauss-Lobatto nodes, split vector and de Hoog p-values.  A wave is 64
+consecutive times of one split index, one radius and one Laplace index; whole items (the kernel cuts them into parts).
+usage: tools/folded_loop_phase_shares.py            the grids of tests/test_gpu_folded_loop_phases.py, one line per depth
+       tools/folded_loop_phase_shares.py bench      the C2 sweep of bench.py (1024 times x 256 radii, every 8th radius)"""
+import os, sys
+import numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+from golden_util import load_deck
+from oracle_lib import Oracle
+import test_gpu_folded_loop_phases as T
+
+SMALL, FAST_ETA_MAX, FAST_IM_MAX = 0.012, 700.0, 1.0e6
+O = Oracle()
+dk, ts, P = load_deck(T.DECK)
+D = O.nondim(P)
+M, N, nacc, ngl = P.M, D.N, P.nacc, P.ord - 2
+maxexp = -np.log(np.finfo(float).eps) / 3.0
+j0z = O.j0_zeros(D.nj0z)
+_, tsx = O.tanh_sinh(P.k, 0.0)
+glx, _ = O.gauss_lobatto(P.ord)
+
+
+def row(rD, sv):
+    a = np.empty(N + nacc * ngl)
+    a[:N] = O.tanh_sinh(P.k, j0z[sv - 1] / rD)[1]
+    for jj in range(nacc):
+        lob, hib = j0z[sv + jj - 1] / rD, j0z[sv + jj] / rD
+        a[N + jj * ngl:N + (jj + 1) * ngl] = ((hib - lob) * glx + (hib + lob)) / 2.0
+    return a
+
+
+# where the kernel may set a bit: any tanh-sinh node, the last (smallest) Gauss-Lobatto node of a J0 interval
+MAY = np.zeros(N + nacc * ngl, bool)
+MAY[:N] = True
+MAY[N + ngl - 1::ngl] = True
+
+
+def first(mask):
+    i = np.flatnonzero(mask)
+    return i[0] if i.size else mask.size
+
+
+def shares(tD, radii, zD):
+    sv = O.split_vector(P.j0s, tD)
+    cnt = dict(cs_tab=0, cs_short=0, mixed=0, ex_tab=0, ex_short=0, out=0)
+    tr = dict(waves=0, to_exp=0, cs_to_short=0, ex_to_short=0, short_at_start=0, could=0)
+    nabs = N + nacc * ngl
+    for s in np.unique(sv):
+        idx = np.flatnonzero(sv == s)
+        for w0 in range(0, len(idx), 64):
+            t = tD[idx[w0:w0 + 64]]
+            pv = np.stack([O.pvalues(2.0 * x, M, P.alpha, P.tol) for x in t])      # [lane][m][re, im]
+            p = pv[..., 0] + 1j * pv[..., 1]
+            for rD in radii:
+                a = row(rD, int(s))
+                for m in range(2 * M + 1):
+                    eta = np.sqrt((p[:, m, None] + a[None, :] ** 2) / P.kappa)      # [lane][abscissa]
+                    ok = (eta.real <= FAST_ETA_MAX).all(0) & (np.abs(eta.imag) < FAST_IM_MAX).all(0) & ((p[:, m].real > 0).all())
+                    ok = np.cumprod(ok).astype(bool)                                 # the fast evaluators are left for good
+                    small = eta.real < maxexp
+                    f0, f2 = ok & small.all(0), ok & (~small).all(0)
+                    ys = (np.abs(eta.imag) < SMALL).all(0)
+                    yl = (np.abs(eta.imag) * (1.0 - zD) < SMALL).all(0)
+                    i_ys = first(MAY & f0 & ys)
+                    i_yl = min(i_ys, first(MAY & f2 & yl))
+                    pos = np.arange(nabs)
+                    cs_short, ex_short = f0 & (pos >= i_ys), f2 & (pos >= i_yl)
+                    cnt["out"] += int((~ok).sum())
+                    cnt["cs_short"] += int(cs_short.sum()); cnt["cs_tab"] += int((f0 & ~cs_short).sum())
+                    cnt["ex_short"] += int(ex_short.sum()); cnt["ex_tab"] += int((f2 & ~ex_short).sum())
+                    cnt["mixed"] += int((ok & ~f0 & ~f2).sum())
+                    tr["could"] += int((f0 & ys).sum() + (f2 & yl).sum())
+                    tr["waves"] += 1
+                    tr["to_exp"] += int(f0.any() and f2.any())
+                    tr["cs_to_short"] += int(cs_short.any() and (f0 & ~cs_short).any())
+                    tr["ex_to_short"] += int(ex_short.any() and (f2 & ~ex_short).any())
+                    tr["short_at_start"] += int(cs_short[0] or ex_short[0])
+    return cnt, tr
+
+
+def line(tag, cnt, tr):
+    n = sum(cnt.values())
+    pc = {k: 100.0 * v / n for k, v in cnt.items()}
+    print(f"{tag:14s} pairs {n:9d}  cosh/sinh table {pc['cs_tab']:5.1f} % short {pc['cs_short']:5.1f} %  both {pc['mixed']:4.1f} %  "
+          f"exponential table {pc['ex_tab']:5.1f} % short {pc['ex_short']:5.1f} %  out of the fast range {pc['out']:4.1f} %")
+    w = tr["waves"]
+    print(f"{'':14s} items {w}: cosh/sinh -> exponential {100.0 * tr['to_exp'] / w:.1f} %, table -> short on cosh/sinh {100.0 * tr['cs_to_short'] / w:.1f} %, "
+          f"on exponential {100.0 * tr['ex_to_short'] / w:.1f} %, short from the first abscissa {100.0 * tr['short_at_start'] / w:.1f} %; "
+          f"pairs with every argument below {SMALL}: {100.0 * tr['could'] / n:.1f} %")
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "bench":
+    tD = O.logspace(-1, 8, 1024) / D.Tc
+    rD = np.logspace(-1, 1, 256)[::8]      # (bench.py's radii span rD = 0.1 ... 10)
+    line("bench C2", *shares(tD, rD, 145.7 / D.Lc))
+else:
+    tD = np.concatenate([np.logspace(c, c + 0.5, 64) for c in T.TD_CLUSTERS])
+    for zD in sorted({c[2] for c in T.CALLS}, reverse=True):
+        line(f"zD = {zD}", *shares(tD, np.array(T.RD), zD))

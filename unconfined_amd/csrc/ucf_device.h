@@ -1582,13 +1582,15 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
         const bool lane_ok = FAMILY != 2 || (fabs(LC.xifac.re) + fabs(LC.xifac.im) < 1.0e90);
         const int nlim = (__builtin_amdgcn_ballot_w64(!lane_ok) == 0) ? n1 : n0;
 
-        // abscissae increase monotonically (tanh-sinh on [0,arg], then the J0 intervals), so does Re(eta):
+        // abscissae increase (tanh-sinh on [0,arg], then the J0 intervals one after the other; the Gauss-Lobatto nodes WITHIN an
+        // interval descend), so does Re(eta):
         // the fast evaluation is valid for a leading run of abscissae; point_kernel finishes the rest.
         // The row entry of the next abscissa is requested one iteration ahead (scalar loads).
         int n = n0;
         double2 aa = row[n0 < nabs ? n0 : 0];
         int m = 0, jj = n0 > N ? (n0 - N) / ngl : 0;   // Gauss-Lobatto node and J0 interval of abscissa n >= N
         cplx acc0 = cmake(0.0, 0.0), acc1 = cmake(0.0, 0.0);      // running area of the interval: registers when nz = 1 (or
+        int zph = 0;                                              // ZPAIR: what the wave knows about the rest of the part
         if constexpr (ZPAIR) {
             // The folded water-table kernel with one depth walks the two parts in loops of their own: the tanh-sinh loop
             // knows the level sums and P.ts_w, the Gauss-Lobatto loop the running area -- which then stays in its registers
@@ -1597,13 +1599,23 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
             // lapTime(p) is wanted when an interval is complete and after the loops, not in between: it is read again there
             // (ltab, as above) instead of being held in four registers across the loops -- the index is laundered so that the
             // load stays where it is written
+            // What the wave has established for the rest of this part (UCF_PH_*, ucf_fastpath.h) travels in `zph` through
+            // both loops: tests that can only turn one way along increasing abscissae are not issued again, and a wave whose
+            // sin/cos arguments have all fallen below UCF_SC_SMALL takes them without the table.  A bit may be set at any
+            // tanh-sinh node (they ascend, below the first J0 zero) and at the LAST Gauss-Lobatto node of a J0 interval (the
+            // nodes of an interval descend, the intervals ascend): no later abscissa of the part lies below those.  Every part
+            // starts from what its own range of abscissae allows (the upper end of its last interval bounds Re eta) and
+            // nothing else.
             int stopped = 0;
+            zph = 0;
+            if (!MULTI && nlim > n0)      // (a parameter batch: no bit is ever set)
+                zph = zpair_part_phase(P, LC, P.j0z[sv - 1 + (nlim > N ? (nlim - N + ngl - 1) / ngl : 0)] / rD);
             const int nts = nlim < N ? nlim : N;
             for (; n < nts; n++) {
                 const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
                 F.sc.salt = n;
-                if (!fast_eta_wave<EF, true>(P, LC, aa.x, F)) { stopped = 1; break; }
-                const cplx val = rscale(aa.y, fast_sample_zpair<!MULTI>(P, LC, F));
+                if (!fast_eta_wave_zpair<!MULTI>(P, LC, aa.x, F, zph, 1)) { stopped = 1; break; }
+                const cplx val = rscale(aa.y, fast_sample_zpair<!MULTI>(P, LC, F, zph, 1));
                 const int n1 = n + 1;
                 int tz = __builtin_ctz(n1);
                 if (tz > R - 1) tz = R - 1;
@@ -1617,8 +1629,9 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
             if (!stopped) for (; n < nlim; n++) {
                 const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
                 F.sc.salt = n;
-                if (!fast_eta_wave<EF, true>(P, LC, aa.x, F)) break;
-                const cplx fz = fast_sample_zpair<!MULTI>(P, LC, F);
+                const int last = m == ngl - 1;
+                if (!fast_eta_wave_zpair<!MULTI>(P, LC, aa.x, F, zph, last)) break;
+                const cplx fz = fast_sample_zpair<!MULTI>(P, LC, F, zph, last);
                 acc0 = cmake(__builtin_fma(fz.re, aa.y, acc0.re), __builtin_fma(fz.im, aa.y, acc0.im));           // :201-202
                 if (++m == ngl) {                                                                // (driver.f90:187-203)
                     const double lob = P.j0z[sv + jj - 1] / rD;
@@ -1646,7 +1659,7 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                 // val = a*J0(a rD) * f(a,p,z) [* lapTime(p): at the end]                         (lhs.f90:118)
                 // (Gauss-Lobatto part: aa.y carries the node's weight, abscissa_kernel)
                 cplx fz;
-                if constexpr (ZPAIR) fz = fast_sample_zpair<!MULTI>(P, LC, F);
+                if constexpr (ZPAIR) fz = fast_sample_zpair<!MULTI>(P, LC, F, zph, 0);
                 else fz = fast_sample_z<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, F, z);
                 if (ts) {
                     const cplx val = rscale(aa.y, fz);

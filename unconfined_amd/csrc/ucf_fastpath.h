@@ -33,7 +33,8 @@ struct fprim {
 };
 
 // (the part of prim after e = exp(ax) and ei = 1/e)
-template <bool POS>
+// SMALLY: the caller knows 0 <= y < UCF_SC_SMALL (sincos_small_)
+template <bool POS, bool SMALLY = false>
 UCF_DEV fprim prim_from_e(double x, double ax, double e, double ei, double y, const sc_ctx& sc)
 {
     const int salt = sc.salt;
@@ -54,7 +55,8 @@ UCF_DEV fprim prim_from_e(double x, double ax, double e, double ei, double y, co
         s = __builtin_fma(-0.5, ei, he);
     }
     f.sh = POS ? s : copysign(s, x);
-    sincos_tab_(y, sc, &f.sn, &f.cs);     // |y| < 1e6: fast_eta() vouches for it
+    if (SMALLY) sincos_small_(y, sc, &f.sn, &f.cs);
+    else sincos_tab_(y, sc, &f.sn, &f.cs);     // |y| < 1e6: fast_eta() vouches for it
     return f;
 }
 // POS: the caller knows x >= 0 (Re eta > 0 times a non-negative factor): no sign to put back on sinh
@@ -121,6 +123,27 @@ UCF_DEV cplx expneg_direct(double x, double y, const sc_ctx& sc)
     double sn, cs;
     sincos_tab_(y, sc, &sn, &cs);
     return cmake(ei * cs, -(ei * sn));
+}
+
+// expneg_direct for 0 <= y < UCF_SC_SMALL (sincos_small_: the same bits)
+UCF_DEV cplx expneg_small(double x, double y, const sc_ctx& sc)
+{
+    const double ei = exp_tab_(-x, sc);
+    double sn, cs;
+    sincos_small_(y, sc, &sn, &cs);
+    return cmake(ei * cs, -(ei * sn));
+}
+// prim_pair_min<true> for 0 <= y < UCF_SC_SMALL (and so 0 <= y zD < UCF_SC_SMALL): prim_from_e<true> with both sin/cos in
+// the short form, operation for operation
+UCF_DEV void prim_pair_small(double x, double y, double zD, double xcap, const sc_ctx& sc, fprim* f, fprim* fz)
+{
+    double xc;
+    asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(xcap));
+    const double xz = xc * zD;
+    const double e = exp_tab_(xc, sc), ez = exp_tab_(xz, sc);
+    const double r = fast_rcp(e * ez);
+    *f = prim_from_e<true, true>(xc, xc, e, r * ez, y, sc);
+    *fz = prim_from_e<true, true>(xz, xz, ez, r * e, y * zD, sc);
 }
 
 // a b + c in four FMAs (one rounding less per component than product, then sum)
@@ -258,6 +281,63 @@ UCF_DEV bool fast_eta_wave(const ucf_dev_params& P, const lane_consts& L, double
     if (FAMILY != 0) {
         bad |= __builtin_amdgcn_ballot_w64(!(S.eta.re <= P.fast_eta_max));
         bad |= __builtin_amdgcn_ballot_w64(!(fabs(S.eta.im) < P.fast_im_max));
+    }
+    return bad == 0;
+}
+
+// What a wave of the folded water-table kernel with one depth per launch (ZPAIR) knows about the REST of its part of a work
+// item, carried across the abscissae as bits of one wave-uniform int (an int: a uniform bool that crosses a join is rebuilt
+// through VALU selects).  Each lane's p is fixed, so Re q = Re p + a^2 and Re eta = Re sqrt(q / kappa) grow with the
+// abscissa a and |Im eta| = |Im q| / (2 kappa Re eta) falls: a test that can only turn one way is not issued again once it
+// has turned at an abscissa that no later one of the part lies below (each v_cmp is a VALU slot, the kernel's bottleneck).
+// Which abscissae those are (`may_set`, the loop's business): the tanh-sinh nodes ascend and end below the first J0 zero,
+// so any of them; the Gauss-Lobatto nodes of a J0 interval DESCEND (cos(pi i / N), integration.f90:70-120) while the
+// intervals ascend, so the last node of an interval only.  The computed eta follows the true one to a few ulp, not
+// monotonically to the last bit (the nodes of tanh-sinh cluster at both ends of its interval: neighbours may differ by an ulp
+// of q), so a bit is only set by a compare with a margin no rounding can bridge, next to the compare that decides this
+// abscissa as before.  A NaN sets nothing.  All bits are cleared at the start of a part.
+// UCF_ZPAIR_PHASES (investigation builds: the two halves measured on their own): bit 0 = the short
+// sin/cos form, bit 1 = the range and form tests carried across abscissae.
+#ifndef UCF_ZPAIR_PHASES
+#define UCF_ZPAIR_PHASES 3
+#endif
+enum {
+    UCF_PH_RANGE = 1,    // Re q > 0 and Re eta <= fast_eta_max in every lane up to the part's last abscissa (zpair_part_phase)
+    UCF_PH_IM = 2,       // |Im eta| < fast_im_max / 2 in every lane: in range from here on
+    UCF_PH_LARGE = 4,    // Re eta > maxexp (1 + 2^-20) in every lane: no lane returns to the cosh/sinh form
+    UCF_PH_YS = 8,       // |Im eta| < UCF_SC_SMALL in every lane: both sin/cos of the cosh/sinh form take sincos_small_
+    UCF_PH_YL = 16       // |Im eta| (1 - zD) < UCF_SC_SMALL in every lane: so does the one of the exponential form
+};
+// The bits known before the first abscissa of a part none of whose abscissae exceeds a_max (wave-uniform: the upper end of
+// the part's last quadrature interval): Re p > 0 gives Re q >= Re p > 0 whatever a; Re eta <= sqrt(|q| / kappa) <=
+// sqrt((a^2 + |Re p| + |Im p|) / kappa), held 1 % below the limit at a_max.  (a limit <= 0 switches the fast evaluators
+// off: no bit)
+UCF_DEV int zpair_part_phase(const ucf_dev_params& P, const lane_consts& L, double a_max)
+{
+    if (!(UCF_ZPAIR_PHASES & 2)) return 0;
+    const double lim = 0.99 * P.fast_eta_max;
+    const bool ok = (L.p.re > 0.0) & (lim > 0.0) & ((__builtin_fma(a_max, a_max, fabs(L.p.re) + fabs(L.p.im)) * P.inv_kappa) < lim * lim);
+    return __builtin_amdgcn_ballot_w64(!ok) == 0 ? UCF_PH_RANGE : 0;
+}
+// fast_eta_wave<2, true> that does not repeat what `ph` already answers.  UNI = false (a parameter batch: the plan's limits
+// differ by lane): exactly fast_eta_wave
+template <bool UNI>
+UCF_DEV bool fast_eta_wave_zpair(const ucf_dev_params& P, const lane_consts& L, double a, fast_common& S, int& ph, int may_set)
+{
+    if constexpr (!UNI) return fast_eta_wave<2, true>(P, L, a, S);
+    (void)fast_eta<2, true>(P, L, a, S);
+    unsigned long long bad = 0;
+    if (!(ph & UCF_PH_RANGE)) {
+        const cplx q = caddr(L.p, a * a);
+        bad |= __builtin_amdgcn_ballot_w64(!(q.re > 0.0));
+        bad |= __builtin_amdgcn_ballot_w64(!(S.eta.re <= P.fast_eta_max));
+        UCF_UNIFORM_BLOCK();
+    }
+    if (!(ph & UCF_PH_IM)) {
+        const double ai = fabs(S.eta.im);
+        bad |= __builtin_amdgcn_ballot_w64(!(ai < P.fast_im_max));
+        if ((UCF_ZPAIR_PHASES & 2) && may_set && __builtin_amdgcn_ballot_w64(!(ai < 0.5 * P.fast_im_max)) == 0) ph |= UCF_PH_IM;
+        UCF_UNIFORM_BLOCK();
     }
     return bad == 0;
 }
@@ -555,32 +635,77 @@ UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz
 // read were set to zero, the per-lane select of g was guarded by a flag that travelled through a VGPR, and the copies where
 // the arms joined were made in every wave: 10 to 14 VALU slots per abscissa, none of them arithmetic.  A wave with lanes on
 // both forms does what it did before.
-template <bool UNI>
-UCF_DEV cplx fast_sample_zpair(const ucf_dev_params& P, const lane_consts& L, const fast_common& S)
+// A wave on one form whose sin/cos arguments have all fallen below UCF_SC_SMALL (they fall with the abscissa like |Im eta|,
+// which bounds them: zD and 1 - zD are in [0, 1]) takes them from sincos_small_: the same bits without the table look-up and
+// the angle addition (SMALLY; a branch of its own per form, so that nothing joins inside an arm).  Im p >= 0
+// (invlap.f90:168, m >= 0), so Im eta and every argument is >= +0, as sincos_small_ wants.  `ph` (UCF_PH_*) is what the
+// wave has established for the rest of its part: the argument test is made (where a bit may be set: `may_set`, above)
+// until it first holds, the form test until every lane is past maxexp by a margin.  A wave with lanes on both forms, and a parameter batch (UNI = false), do what they did.
+template <bool UNI, bool SMALLY>
+UCF_DEV void zpair_arm_small(const ucf_dev_params& P, const lane_consts& L, const fast_common& S, double zD, cplx* g, cplx* den)
 {
+    fprim p1, pz;
+    if (SMALLY) prim_pair_small(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
+    else prim_pair_min<UNI>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
+    *g = pcosh(pz);
+    const cplx che = pcosh(p1), she = psinh(p1);
+    const cplx xi = cmul(S.eta, L.xifac);
+    if (P.beta != 0.0) *den = cfma(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), che, cmul(xi, she));
+    else *den = cfma(xi, she, che);                           // beta = 0 (wave-uniform): no product with (1, 0)
+}
+template <bool SMALLY>
+UCF_DEV void zpair_arm_large(const ucf_dev_params& P, const lane_consts& L, const fast_common& S, double x, double y, cplx* g, cplx* den)
+{
+    *g = SMALLY ? expneg_small(x, y, S.sc) : expneg_direct(x, y, S.sc);
+    const cplx xi = cmul(S.eta, L.xifac);
+    if (P.beta != 0.0) *den = cadd(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), xi);
+    else *den = radd(1.0, xi);
+}
+template <bool UNI>
+UCF_DEV cplx fast_sample_zpair(const ucf_dev_params& P, const lane_consts& L, const fast_common& S, int& ph, int may_set)
+{
+    constexpr bool SHORT = UNI && (UCF_ZPAIR_PHASES & 1);
     const double zD = P.zD[0];
-    const bool small_eta = S.eta.re < P.maxexp;                                                 // :84
-    const bool any_small = __builtin_amdgcn_ballot_w64(small_eta) != 0, any_large = __builtin_amdgcn_ballot_w64(!small_eta) != 0;
+    // the form the wave is on: 0 = cosh/sinh in every lane, 1 = lanes on both, 2 = exponential in every lane
+    int form = 2;
+    if (!UNI || !(ph & UCF_PH_LARGE)) {
+        const bool small_eta = S.eta.re < P.maxexp;                                             // :84
+        const bool any_small = __builtin_amdgcn_ballot_w64(small_eta) != 0, any_large = __builtin_amdgcn_ballot_w64(!small_eta) != 0;
+        form = !any_large ? 0 : (any_small ? 1 : 2);
+        if (UNI && (UCF_ZPAIR_PHASES & 2) && may_set && form == 2 && __builtin_amdgcn_ballot_w64(!(S.eta.re > P.maxexp * (1.0 + 0x1p-20))) == 0) ph |= UCF_PH_LARGE;
+        UCF_UNIFORM_BLOCK();
+    }
     // (xi = eta alphaD / p ... (:70-75) is formed in each arm AFTER the primitives: four registers less while they are evaluated;
     //  |den| needs no exponent scaling: fast_common_terms)
     cplx den, g;
-    if (!any_large) {
-        fprim p1, pz;
-        prim_pair_min<UNI>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
-        g = pcosh(pz);
-        const cplx che = pcosh(p1), she = psinh(p1);
-        const cplx xi = cmul(S.eta, L.xifac);
-        if (P.beta != 0.0) den = cfma(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), che, cmul(xi, she));
-        else den = cfma(xi, she, che);                           // beta = 0 (wave-uniform): no product with (1, 0)
-        UCF_UNIFORM_BLOCK();
-    } else if (!any_small) {
+    if (form == 0) {
+        if (SHORT && may_set && !(ph & UCF_PH_YS)) {
+            if (__builtin_amdgcn_ballot_w64(!(fabs(S.eta.im) < UCF_SC_SMALL)) == 0) ph |= UCF_PH_YS | UCF_PH_YL;
+            UCF_UNIFORM_BLOCK();
+        }
+        if (SHORT && (ph & UCF_PH_YS)) {
+            zpair_arm_small<UNI, true>(P, L, S, zD, &g, &den);
+            UCF_UNIFORM_BLOCK();
+        } else {
+            zpair_arm_small<UNI, false>(P, L, S, zD, &g, &den);
+            UCF_UNIFORM_BLOCK();
+        }
+    } else if (form == 2) {
         const double c = 1.0 - zD;
-        g = expneg_direct(S.eta.re * c, S.eta.im * c, S.sc);
-        const cplx xi = cmul(S.eta, L.xifac);
-        if (P.beta != 0.0) den = cadd(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), xi);
-        else den = radd(1.0, xi);
-        UCF_UNIFORM_BLOCK();
+        const double x = S.eta.re * c, y = S.eta.im * c;
+        if (SHORT && may_set && !(ph & UCF_PH_YL)) {
+            if (__builtin_amdgcn_ballot_w64(!(fabs(y) < UCF_SC_SMALL)) == 0) ph |= UCF_PH_YL;
+            UCF_UNIFORM_BLOCK();
+        }
+        if (SHORT && (ph & UCF_PH_YL)) {
+            zpair_arm_large<true>(P, L, S, x, y, &g, &den);
+            UCF_UNIFORM_BLOCK();
+        } else {
+            zpair_arm_large<false>(P, L, S, x, y, &g, &den);
+            UCF_UNIFORM_BLOCK();
+        }
     } else {
+        const bool small_eta = S.eta.re < P.maxexp;
         fprim p1, pz;
         prim_pair_min<UNI>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
         const cplx chz = pcosh(pz), che = pcosh(p1), she = psinh(p1);

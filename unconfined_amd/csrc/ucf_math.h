@@ -322,6 +322,27 @@ UCF_DEV double fma_vsv(double a, double c, double b)
 // first Horner step z * a + b of two constants
 #define UCF_SC_LEAD(z, av, a, b, C, salt) (((C).kv >= 4) ? fmak(z, av, UCF_KHERE(b, salt)) : addk(mulk(z, UCF_KHERE(a, salt)), UCF_KHERE(b, salt)))
 
+// sincos_tab_ (below) for 0 <= x < UCF_SC_SMALL, the same bits without the table: there x (128/pi) < 0.4889 rounds to k = 0,
+// both reduction FMAs return x itself (fn = +0) and the table entry is (0, 1) exactly (tests/test_constants.py), so that
+// S + (C sin y + S (cos y - 1)) is 0 + (sy + 0) = sy and C + (C (cos y - 1) - S sin y) is 1 + (cm1 - 0) = 1 + cm1.  The same
+// two polynomials in the same forms; what goes is the magic-number addition and its subtraction, the address, the two
+// reduction FMAs, the ds_read_b128 and five of the six closing operations.  x >= +0 is the caller's business (the table
+// form turns a sine of -0 into +0); the bound leaves 2 % to pi/256 = 0.01227 for the rounding of the product with 128/pi.
+#define UCF_SC_SMALL 0.012
+UCF_DEV void sincos_small_(double y, const sc_ctx& C, double* sn, double* cs)
+{
+    const int salt = C.salt;
+#define K(c) UCF_KHERE(c, salt)
+    const double z = y * y;
+    const double ps = fmak(z, UCF_SC_LEAD(z, C.s7, -1.98412698412698412698e-04, 8.33333333333333333333e-03, C, salt), K(-1.66666666666666666667e-01));
+    const double pc = fmak(z, UCF_SC_LEAD(z, C.c6, -1.38888888888888888889e-03, 4.16666666666666666667e-02, C, salt), K(-0.5));
+#undef K
+    double cm1 = z * pc;
+    asm("" : "+v"(cm1));      // (a product of its own, as in sincos_tab_: 1 + z pc must not contract into one fma)
+    *sn = __builtin_fma(y * z, ps, y);
+    *cs = 1.0 + cm1;
+}
+
 UCF_DEV void sincos_tab_(double x, const sc_ctx& C, double* sn, double* cs)
 {
     const int salt = C.salt;
