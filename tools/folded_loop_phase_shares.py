@@ -6,7 +6,11 @@ abscissa where the kernel may set the bit, and from then on), and the transition
 No GPU: the oracle's J0 zeros, tanh-sinh and Gauss-Lobatto nodes, split vector and de Hoog p-values.  A wave is 64
 consecutive times of one split index, one radius and one Laplace index; whole items (the kernel cuts them into parts).
 usage: tools/folded_loop_phase_shares.py            the grids of tests/test_gpu_folded_loop_phases.py, one line per depth
-       tools/folded_loop_phase_shares.py bench      the C2 sweep of bench.py (1024 times x 256 radii, every 8th radius)"""
+       tools/folded_loop_phase_shares.py bench      the C2 sweep of bench.py (1024 times x 256 radii, every 8th radius)
+       tools/folded_loop_phase_shares.py intervals [bench]
+            the Gauss-Lobatto pairs by the class that eta at the two ends of their J0 interval proves for the whole interval
+            (zpair_interval_class, ucf_fastpath.h; interval_class() below is its restatement): the grids of
+            tests/test_gpu_folded_loop_intervals.py, or the bench sweep"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,11 +99,87 @@ def line(tag, cnt, tr):
           f"pairs with every argument below {SMALL}: {100.0 * tr['could'] / n:.1f} %")
 
 
-if len(sys.argv) > 1 and sys.argv[1] == "bench":
-    tD = O.logspace(-1, 8, 1024) / D.Tc
-    rD = np.logspace(-1, 1, 256)[::8]      # (bench.py's radii span rD = 0.1 ... 10)
-    line("bench C2", *shares(tD, rD, 145.7 / D.Lc))
-else:
-    tD = np.concatenate([np.logspace(c, c + 0.5, 64) for c in T.TD_CLUSTERS])
-    for zD in sorted({c[2] for c in T.CALLS}, reverse=True):
-        line(f"zD = {zD}", *shares(tD, np.array(T.RD), zD))
+# ---- whole J0 intervals (zpair_interval_class, ucf_fastpath.h): what eta at an interval's two ends proves for all of its nodes
+CLASSES = ("cs_tab", "cs_short", "ex_tab", "ex_short", "unproven")
+
+
+def interval_class(p, lob, hib, zD, kappa=None):
+    """the kernel's classifier for one wave (p: the lanes' Laplace parameters) and one J0 interval [lob, hib], restated in
+    binary64 with its margins; returns one of CLASSES"""
+    kappa = P.kappa if kappa is None else kappa
+    with np.errstate(all="ignore"):
+        eta_hi, eta_lo = np.sqrt((p + hib * hib) / kappa), np.sqrt((p + lob * lob) / kappa)
+    re_hi, re_lo, im_lo = eta_hi.real, eta_lo.real, np.abs(eta_lo.imag)
+    if not np.all((p.real > 0.0) & (re_hi * 1.01 <= FAST_ETA_MAX) & (im_lo * 2.0 < FAST_IM_MAX)):
+        return "unproven"
+    ys = bool(np.all(im_lo < SMALL))
+    yl = ys or bool(np.all(im_lo * (1.0 - zD) < SMALL))
+    if np.all(re_hi * (1.0 + 2.0 ** -20) < maxexp):
+        return "cs_short" if ys else "cs_tab"
+    if np.all(re_lo * (1.0 - 2.0 ** -20) > maxexp):
+        return "ex_short" if yl else "ex_tab"
+    return "unproven"
+
+
+def waves(tD):
+    """(split index, the lanes' p [lane][m]) of every wave of a lane = time grid"""
+    sv = O.split_vector(P.j0s, tD)
+    for s in np.unique(sv):
+        idx = np.flatnonzero(sv == s)
+        for w0 in range(0, len(idx), 64):
+            pv = np.stack([O.pvalues(2.0 * x, M, P.alpha, P.tol) for x in tD[idx[w0:w0 + 64]]])
+            yield int(s), pv[..., 0] + 1j * pv[..., 1]
+
+
+def interval_shares(tD, radii, zD):
+    """Gauss-Lobatto (wave, abscissa) pairs by the class of their J0 interval, and the transitions along an item"""
+    cnt = dict.fromkeys(CLASSES, 0)
+    tr = dict(items=0, straddle=0, cs_to_short=0, ex_to_short=0, after_proven=0)
+    for s, p in waves(tD):
+        for rD in radii:
+            for m in range(2 * M + 1):
+                seq = [interval_class(p[:, m], j0z[s + jj - 1] / rD, j0z[s + jj] / rD, zD) for jj in range(nacc)]
+                for c in seq:
+                    cnt[c] += ngl
+                tr["items"] += 1
+                pairs = list(zip(seq, seq[1:]))
+                tr["straddle"] += int(any(a.startswith("cs") and b == "unproven" and c.startswith("ex") for a, b, c in zip(seq, seq[1:], seq[2:])))
+                tr["cs_to_short"] += int(("cs_tab", "cs_short") in pairs)
+                tr["ex_to_short"] += int(("ex_tab", "ex_short") in pairs)
+                tr["after_proven"] += int(seq[-1] == "unproven" and any(c != "unproven" for c in seq))
+    return cnt, tr
+
+
+def interval_line(tag, cnt, tr):
+    n = sum(cnt.values())
+    pc = {k: 100.0 * v / n for k, v in cnt.items()}
+    print(f"{tag:14s} Gauss-Lobatto pairs {n:9d}  cosh/sinh table {pc['cs_tab']:5.1f} % short {pc['cs_short']:5.1f} %  "
+          f"exponential table {pc['ex_tab']:5.1f} % short {pc['ex_short']:5.1f} %  unproven {pc['unproven']:5.1f} %  (proven {100.0 - pc['unproven']:.1f} %)")
+    w = tr["items"]
+    print(f"{'':14s} items {w}: cosh/sinh -> unproven -> exponential {100.0 * tr['straddle'] / w:.1f} %, table -> short at an interval boundary on "
+          f"cosh/sinh {100.0 * tr['cs_to_short'] / w:.1f} %, on exponential {100.0 * tr['ex_to_short'] / w:.1f} %, "
+          f"unproven last interval after proven ones {100.0 * tr['after_proven'] / w:.1f} %")
+
+
+def bench_grid():
+    return O.logspace(-1, 8, 1024) / D.Tc, np.logspace(-1, 1, 256)[::8], 145.7 / D.Lc      # (bench.py's radii span rD = 0.1 ... 10)
+
+
+if __name__ == "__main__":
+    args = sys.argv[1:]
+    if args[:1] == ["intervals"]:
+        if args[1:2] == ["bench"]:
+            tD, rD, zD = bench_grid()
+            interval_line("bench C2", *interval_shares(tD, rD, zD))
+        else:
+            import test_gpu_folded_loop_intervals as TI
+            tD = np.concatenate([np.logspace(c, c + 0.5, 64) for c in TI.TD_CLUSTERS])
+            for zD in sorted({c[2] for c in TI.CALLS}, reverse=True):
+                interval_line(f"zD = {zD}", *interval_shares(tD, np.array(TI.RD), zD))
+    elif args[:1] == ["bench"]:
+        tD, rD, zD = bench_grid()
+        line("bench C2", *shares(tD, rD, zD))
+    else:
+        tD = np.concatenate([np.logspace(c, c + 0.5, 64) for c in T.TD_CLUSTERS])
+        for zD in sorted({c[2] for c in T.CALLS}, reverse=True):
+            line(f"zD = {zD}", *shares(tD, np.array(T.RD), zD))

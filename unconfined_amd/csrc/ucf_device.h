@@ -22,6 +22,7 @@
 #include "ucf_math.h"
 #include "ucf_plan.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace UCF_NS {
 
@@ -1582,8 +1583,8 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
         const bool lane_ok = FAMILY != 2 || (fabs(LC.xifac.re) + fabs(LC.xifac.im) < 1.0e90);
         const int nlim = (__builtin_amdgcn_ballot_w64(!lane_ok) == 0) ? n1 : n0;
 
-        // abscissae increase (tanh-sinh on [0,arg], then the J0 intervals one after the other; the Gauss-Lobatto nodes WITHIN an
-        // interval descend), so does Re(eta):
+        // the quadrature units ascend (tanh-sinh on [0,arg], its nodes ascending, then the J0 intervals one after the other),
+        // and Re(eta) with them; the Gauss-Lobatto nodes WITHIN an interval descend:
         // the fast evaluation is valid for a leading run of abscissae; point_kernel finishes the rest.
         // The row entry of the next abscissa is requested one iteration ahead (scalar loads).
         int n = n0;
@@ -1626,6 +1627,63 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                 }
                 aa = nxt;
             }
+#if UCF_ZPAIR_INTERVALS
+            // The Gauss-Lobatto part, one J0 interval at a time (a part holds whole intervals).  What eta at the interval's two
+            // ends settles for all of its nodes in every lane (zpair_interval_class, ucf_fastpath.h) is decided before its first
+            // node: a proven interval runs exactly ngl iterations of the one arm of its class -- no test, no ballot, no `zph`:
+            // it cannot leave the fast evaluators, so no hand-over starts inside it -- any other interval the loop with the
+            // bits, as it was.  The bits a proven interval establishes for the rest of the part are set, none is cleared.  A
+            // parameter batch keeps the loop with the tests.  (The tanh-sinh part, 63 abscissae of 543, keeps its loop too.)
+            auto proven_interval = [&](auto cls, auto beta) {
+                for (int i = 0; i < ngl; i++, n++) {
+                    const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
+                    F.sc.salt = n;
+                    (void)fast_eta<2, true>(P, LC, aa.x, F);
+                    const cplx fz = fast_sample_zpair_proven<decltype(cls)::value, decltype(beta)::value>(P, LC, F);
+                    acc0 = cmake(__builtin_fma(fz.re, aa.y, acc0.re), __builtin_fma(fz.im, aa.y, acc0.im));           // :201-202
+                    aa = nxt;
+                }
+            };
+            auto proven_class = [&](auto cls) {
+                if (P.beta != 0.0) proven_interval(cls, std::true_type());
+                else proven_interval(cls, std::false_type());
+            };
+            if (!stopped) while (n < nlim) {
+                const double lob = P.j0z[sv + jj - 1] / rD;
+                const double hib = P.j0z[sv + jj] / rD;
+                int cls = UCF_IV_UNPROVEN;
+                if constexpr (!MULTI) {
+                    int known;
+                    cls = zpair_interval_class(P, LC, lob, hib, P.zD[0], &known);
+                    zph |= known;
+                }
+                if (cls == UCF_IV_CS_TAB) proven_class(std::integral_constant<int, UCF_IV_CS_TAB>());
+                else if (cls == UCF_IV_CS_SHORT) proven_class(std::integral_constant<int, UCF_IV_CS_SHORT>());
+                else if (cls == UCF_IV_EX_TAB) proven_class(std::integral_constant<int, UCF_IV_EX_TAB>());
+                else if (cls == UCF_IV_EX_SHORT) proven_class(std::integral_constant<int, UCF_IV_EX_SHORT>());
+                else {
+                    for (m = 0; m < ngl; m++, n++) {
+                        const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
+                        F.sc.salt = n;
+                        const int last = m == ngl - 1;
+                        if (!fast_eta_wave_zpair<!MULTI>(P, LC, aa.x, F, zph, last)) { stopped = 1; break; }
+                        const cplx fz = fast_sample_zpair<!MULTI>(P, LC, F, zph, last);
+                        acc0 = cmake(__builtin_fma(fz.re, aa.y, acc0.re), __builtin_fma(fz.im, aa.y, acc0.im));       // :201-202
+                        aa = nxt;
+                    }
+                    if (stopped) break;                          // (n - m: the start of this interval, below)
+                }
+                UCF_UNIFORM_BLOCK();
+                {                                                                                // (driver.f90:187-203)
+                    const double hw = (hib - lob) / 2.0;
+                    const cplx ar = cmul(rscale(hw, acc0), lt_again());
+                    areas[(size_t)jj * UCF_WAVE + lane] = make_double2(ar.re, ar.im);
+                    acc0 = cmake(0.0, 0.0);
+                    m = 0;
+                    jj++;
+                }
+            }
+#else
             if (!stopped) for (; n < nlim; n++) {
                 const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
                 F.sc.salt = n;
@@ -1645,6 +1703,7 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                 }
                 aa = nxt;
             }
+#endif
         } else
         for (; n < nlim; n++) {                   // NZC = 2: two depths known at compile time), else accCur[z] in LDS
             const double2 nxt = row[n + 1 < nabs ? n + 1 : n];

@@ -301,6 +301,11 @@ UCF_DEV bool fast_eta_wave(const ucf_dev_params& P, const lane_consts& L, double
 #ifndef UCF_ZPAIR_PHASES
 #define UCF_ZPAIR_PHASES 3
 #endif
+// UCF_ZPAIR_INTERVALS=0 (A/B builds): no J0 interval is decided as a whole (zpair_interval_class, below), every one runs the
+// loop with these bits
+#ifndef UCF_ZPAIR_INTERVALS
+#define UCF_ZPAIR_INTERVALS 1
+#endif
 enum {
     UCF_PH_RANGE = 1,    // Re q > 0 and Re eta <= fast_eta_max in every lane up to the part's last abscissa (zpair_part_phase)
     UCF_PH_IM = 2,       // |Im eta| < fast_im_max / 2 in every lane: in range from here on
@@ -641,7 +646,8 @@ UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz
 // (invlap.f90:168, m >= 0), so Im eta and every argument is >= +0, as sincos_small_ wants.  `ph` (UCF_PH_*) is what the
 // wave has established for the rest of its part: the argument test is made (where a bit may be set: `may_set`, above)
 // until it first holds, the form test until every lane is past maxexp by a margin.  A wave with lanes on both forms, and a parameter batch (UNI = false), do what they did.
-template <bool UNI, bool SMALLY>
+// KB: what the caller knows of beta (wave-uniform): -1 nothing (tested here), 0 beta = 0, 1 beta != 0
+template <bool UNI, bool SMALLY, int KB = -1>
 UCF_DEV void zpair_arm_small(const ucf_dev_params& P, const lane_consts& L, const fast_common& S, double zD, cplx* g, cplx* den)
 {
     fprim p1, pz;
@@ -650,15 +656,15 @@ UCF_DEV void zpair_arm_small(const ucf_dev_params& P, const lane_consts& L, cons
     *g = pcosh(pz);
     const cplx che = pcosh(p1), she = psinh(p1);
     const cplx xi = cmul(S.eta, L.xifac);
-    if (P.beta != 0.0) *den = cfma(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), che, cmul(xi, she));
+    if (KB < 0 ? P.beta != 0.0 : KB != 0) *den = cfma(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), che, cmul(xi, she));
     else *den = cfma(xi, she, che);                           // beta = 0 (wave-uniform): no product with (1, 0)
 }
-template <bool SMALLY>
+template <bool SMALLY, int KB = -1>
 UCF_DEV void zpair_arm_large(const ucf_dev_params& P, const lane_consts& L, const fast_common& S, double x, double y, cplx* g, cplx* den)
 {
     *g = SMALLY ? expneg_small(x, y, S.sc) : expneg_direct(x, y, S.sc);
     const cplx xi = cmul(S.eta, L.xifac);
-    if (P.beta != 0.0) *den = cadd(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), xi);
+    if (KB < 0 ? P.beta != 0.0 : KB != 0) *den = cadd(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), xi);
     else *den = radd(1.0, xi);
 }
 template <bool UNI>
@@ -672,7 +678,11 @@ UCF_DEV cplx fast_sample_zpair(const ucf_dev_params& P, const lane_consts& L, co
         const bool small_eta = S.eta.re < P.maxexp;                                             // :84
         const bool any_small = __builtin_amdgcn_ballot_w64(small_eta) != 0, any_large = __builtin_amdgcn_ballot_w64(!small_eta) != 0;
         form = !any_large ? 0 : (any_small ? 1 : 2);
-        if (UNI && (UCF_ZPAIR_PHASES & 2) && may_set && form == 2 && __builtin_amdgcn_ballot_w64(!(S.eta.re > P.maxexp * (1.0 + 0x1p-20))) == 0) ph |= UCF_PH_LARGE;
+        // (with the interval loops the limit is formed where it is wanted, once per J0 interval at most: hoisted out of the
+        //  item loop it was the one value the abscissa loop read back from scratch)
+        double mx = P.maxexp;
+        if (UCF_ZPAIR_INTERVALS) asm volatile("" : "+s"(mx));
+        if (UNI && (UCF_ZPAIR_PHASES & 2) && may_set && form == 2 && __builtin_amdgcn_ballot_w64(!(S.eta.re > mx * (1.0 + 0x1p-20))) == 0) ph |= UCF_PH_LARGE;
         UCF_UNIFORM_BLOCK();
     }
     // (xi = eta alphaD / p ... (:70-75) is formed in each arm AFTER the primitives: four registers less while they are evaluated;
@@ -722,6 +732,66 @@ UCF_DEV cplx fast_sample_zpair(const ucf_dev_params& P, const lane_consts& L, co
         UCF_UNIFORM_BLOCK();
     }
     const double r = fast_rcp(__builtin_fma(den.im, den.im, den.re * den.re));                  // cinv_plain, its contraction pinned
+    const cplx inv_den = cmake(den.re * r, -(den.im * r));
+    return cfnma(cmul(S.th, g), inv_den, S.th);
+}
+
+// Whole J0 intervals of that kernel, decided ONCE.  Re eta grows with the abscissa and |Im eta| falls
+// (above UCF_PH_*), so eta at the two ends of a J0 interval -- wave-uniform abscissae, known before its first node; the
+// Gauss-Lobatto nodes lie strictly between them -- bounds both for all of its nodes in every lane.  What one evaluation at
+// each end settles: the range tests, the form the wave is on, and whether every sin/cos argument of that form is below
+// UCF_SC_SMALL.  A proven interval runs a loop of its own that holds the one arm and no test (integrate_kernel); any other
+// runs the loop with the UCF_PH_* bits.  Margins as the bits have them, none of which a rounding of the computed eta
+// bridges (it follows the true one to a few ulp): 1 % on fast_eta_max, a factor 2 on fast_im_max, 2^-20 on maxexp;
+// UCF_SC_SMALL carries its own 2 % (ucf_math.h).  A NaN proves nothing.
+enum {
+    UCF_IV_UNPROVEN = 0,
+    UCF_IV_CS_TAB = 1,       // cosh/sinh form in every lane at every node, sin/cos from the table
+    UCF_IV_CS_SHORT = 2,     // ... both sin/cos from sincos_small_
+    UCF_IV_EX_TAB = 3,       // exponential form in every lane at every node, sin/cos from the table
+    UCF_IV_EX_SHORT = 4      // ... from sincos_small_
+};
+// lob < hib: the interval's ends.  *ph_proven: the UCF_PH_* bits that hold from lob on (every later abscissa of the part
+// lies above it), whatever the class
+UCF_DEV int zpair_interval_class(const ucf_dev_params& P, const lane_consts& L, double lob, double hib, double zD, int* ph_proven)
+{
+    *ph_proven = 0;
+    fast_common T;                                   // (eta only: nothing else of it is read)
+    (void)fast_eta<2, true>(P, L, hib, T);
+    const double re_hi = T.eta.re;
+    (void)fast_eta<2, true>(P, L, lob, T);
+    const double re_lo = T.eta.re, im_lo = fabs(T.eta.im);
+    // Re p > 0: Re q = Re p + a^2 > 0 at every abscissa.  (The margins multiply the lane's value, not the plan's limit: a
+    // product of two wave-uniform numbers is hoisted out of the item loop into a VGPR pair, and this kernel has none to spare)
+    const bool in_range = (L.p.re > 0.0) & (re_hi * 1.01 <= P.fast_eta_max) & (im_lo * 2.0 < P.fast_im_max);
+    if (__builtin_amdgcn_ballot_w64(!in_range) != 0) return UCF_IV_UNPROVEN;
+    *ph_proven = UCF_PH_IM;
+    const bool ys = __builtin_amdgcn_ballot_w64(!(im_lo < UCF_SC_SMALL)) == 0;
+    const bool yl = ys || __builtin_amdgcn_ballot_w64(!(im_lo * (1.0 - zD) < UCF_SC_SMALL)) == 0;
+    if (ys) *ph_proven |= UCF_PH_YS;
+    if (yl) *ph_proven |= UCF_PH_YL;
+    if (__builtin_amdgcn_ballot_w64(!(re_hi * (1.0 + 0x1p-20) < P.maxexp)) == 0) return ys ? UCF_IV_CS_SHORT : UCF_IV_CS_TAB;
+    if (__builtin_amdgcn_ballot_w64(!(re_lo * (1.0 - 0x1p-20) > P.maxexp)) == 0) {
+        *ph_proven |= UCF_PH_LARGE;
+        return yl ? UCF_IV_EX_SHORT : UCF_IV_EX_TAB;
+    }
+    return UCF_IV_UNPROVEN;
+}
+// The sample at a node of a proven interval: fast_sample_zpair's arm of that class and its tail, nothing else.
+// CLS: UCF_IV_*; BETA: the launch's beta != 0 (wave-uniform, one plan per launch), known to the loop
+template <int CLS, bool BETA>
+UCF_DEV cplx fast_sample_zpair_proven(const ucf_dev_params& P, const lane_consts& L, const fast_common& S)
+{
+    const double zD = P.zD[0];
+    cplx den, g;
+    if (CLS == UCF_IV_CS_TAB || CLS == UCF_IV_CS_SHORT) {
+        zpair_arm_small<true, CLS == UCF_IV_CS_SHORT, BETA ? 1 : 0>(P, L, S, zD, &g, &den);
+    } else {
+        const double c = 1.0 - zD;
+        const double x = S.eta.re * c, y = S.eta.im * c;
+        zpair_arm_large<CLS == UCF_IV_EX_SHORT, BETA ? 1 : 0>(P, L, S, x, y, &g, &den);
+    }
+    const double r = fast_rcp(__builtin_fma(den.im, den.im, den.re * den.re));                  // (fast_sample_zpair's tail)
     const cplx inv_den = cmake(den.re * r, -(den.im * r));
     return cfnma(cmul(S.th, g), inv_den, S.th);
 }
