@@ -63,7 +63,8 @@ typedef enum ucf_status {
     UCF_ERR_NO_DEVICE = -12,
     UCF_ERR_HIP = -13,
     UCF_ERR_NOMEM = -14,
-    UCF_ERR_OBSERVATION = -15       /* driver_io.f90:352-383 */
+    UCF_ERR_OBSERVATION = -15,      /* driver_io.f90:352-383 */
+    UCF_ERR_SINGULAR = -16          /* ucf_fit_solve_step: the damped normal matrix is not positive definite */
 } ucf_status;
 
 /*
@@ -279,6 +280,73 @@ int ucf_drawdown_batch_multi(ucf_plan* const* plans, int ngpu, int npts, const d
  * h, dh: [nplans][npts][nz]; dimensional (x Hc of each plan) unless dimensionless != 0. */
 int ucf_drawdown_multi(ucf_plan* const* plans, int nplans, int npts, const double* t, const double* r,
                        int nz, const double* z, int dimensionless, double* h, double* dh);
+
+/* ---- parameter fitting: what the batched evaluation above is for (reference README.md:45-56, PEST).  A fit object owns the
+ * observations on the device, evaluates base and perturbed parameter sets through the launch sequence of ucf_drawdown_multi
+ * (same kernels; the plans come from a pool that the fit makes once and refreshes with ucf_plan_update; h stays in device
+ * memory, nothing but kilobytes of sums crosses the bus) and forms residuals, objective, Jacobian and normal equations in
+ * one small kernel of its own (fit_reduce_kernel, one workgroup per parameter set, sums in a fixed order: a call repeated
+ * gives the same bits).
+ *   parameters   all positive, fitted in ln(theta); theta arrays hold the parameters themselves, in the order of `ids`;
+ *   observation  a DIMENSIONAL drawdown (h x Hc: what a deck with dimensionless = F prints) at dimensional time t[i], radius
+ *                r[i] and depth z[iz[i]], z up from the aquifer base as in ucf_drawdown_multi.
+ *   cost         ALL nz depths are evaluated at every observation point and iz selects one: an observation network with
+ *                per-well depths pays nz evaluations per point (per-well depth sets inside one launch are not built).
+ *   sim_i(theta) the fast-flavour result of the plan made from ucf_fit_perturb(base, theta);   r_i = obs_i - sim_i;
+ *   J[i][j]      (sim_i(theta e^{+dlog e_j}) - sim_i(theta e^{-dlog e_j})) / (2 dlog): the derivative in ln(theta_j);
+ *   phi = sum w_i^2 r_i^2,  g = J' W^2 r,  A = J' W^2 J (full symmetric [npar][npar]).
+ *   An observation whose base value or any perturbed value is not finite (the in-band rules of the overflow regime produce
+ *   such values) is left out of that set's sums and counted in nbad[set]; its rows of J / sim_all hold what was computed.
+ * A fit is used by one host thread at a time; every plan of a fit lives on the fit's device. */
+#define UCF_FIT_MAX_PAR 8
+enum { UCF_PAR_KR, UCF_PAR_KAPPA, UCF_PAR_SS, UCF_PAR_SY, UCF_PAR_AC, UCF_PAR_AK, UCF_PAR_USL,
+       UCF_PAR_MOENCH_ALPHA0 /* + i, i < MoenchM */ };
+/* ucf_fit_lm, per start */
+enum { UCF_FIT_CONVERGED = 0, UCF_FIT_MAX_ITER = 1, UCF_FIT_SINGULAR = 2 /* A + lambda diag A not positive definite */,
+       UCF_FIT_NONFINITE_START = 3 /* nbad > 0 or phi not finite at theta0 */ };
+typedef struct ucf_fit ucf_fit;
+typedef struct ucf_fit_options { int max_iter; double dlog, lambda0, lambda_up, lambda_down, tol_step, tol_phi; } ucf_fit_options;
+/* max_iter 50, dlog 1e-3 (the end-to-end noise floor is 1e-10 relative; its cube root, 5e-4, is where the
+ * truncation and the rounding error of a central difference balance, and within a factor 2 of it they still do), lambda0 1e-2,
+ * lambda_up 10, lambda_down 0.1, tol_step 1e-6 (max |step| in ln theta), tol_phi 1e-9 (relative decrease of phi) */
+int ucf_fit_default_options(ucf_fit_options* opt);
+
+/* host arithmetic only, no GPU: */
+/* *out = *base with the fields named by ids[0..npar) set to theta[0..npar) and no other byte changed.  UCF_ERR_BAD_ARGUMENT:
+ * npar outside 1..UCF_FIT_MAX_PAR, a duplicate id, an id that base->model does not read (kappa for Theis; Sy for models 0..2;
+ * ak outside model 6; ac, usL outside model 6 / MNtype 2; a Moench alpha outside model 3 or beyond MoenchM) */
+int ucf_fit_perturb(const ucf_params* base, int npar, const int* ids, const double* theta, ucf_params* out);
+/* (A + lambda diag A) step = g by a Cholesky factorisation, A [npar][npar] symmetric; UCF_ERR_SINGULAR (step = 0, never a
+ * NaN) where the matrix is not positive definite */
+int ucf_fit_solve_step(int npar, const double* A, const double* g, double lambda, double* step);
+
+/* Validation comes first and needs no GPU -- UCF_ERR_BAD_ARGUMENT, ucf_last_error names the offender: the checks of
+ * ucf_fit_perturb, nobs < npar, iz outside 0..nz-1, a negative or non-finite weight, a non-finite obs, t, r or z, t or r <= 0;
+ * base itself is checked as by ucf_plan_create (with its statuses).  Then UCF_ERR_NO_DEVICE as for every compute entry. */
+int ucf_fit_create(const ucf_params* base, int npar, const int* ids,
+                   int nobs, const double* t, const double* r, const int* iz, int nz, const double* z,
+                   const double* obs, const double* weight, int device, ucf_fit** out);
+void ucf_fit_destroy(ucf_fit* fit);
+/* nsets parameter sets theta[nsets][npar] at once: nsets (1 + 2 npar) plans in one launch sequence (plan by plan on a pool of
+ * streams for the models that have no shared launch, see ucf_drawdown_multi).  phi[nsets], g[nsets][npar],
+ * A[nsets][npar][npar], nbad[nsets]; J [nsets][nobs][npar] and sim_all [nsets][1 + 2 npar][nobs] (row 0 the base values, row
+ * 1 + 2j parameter j up, row 2 + 2j parameter j down) only when asked for; any output may be NULL.
+ * A theta that is not positive and finite: UCF_ERR_BAD_ARGUMENT; a parameter set that fails the checks of ucf_plan_update:
+ * that status, with the set and the parameter in ucf_last_error. */
+int ucf_fit_evaluate(ucf_fit* fit, int nsets, const double* theta /*[nsets][npar]*/, double dlog,
+                     double* phi, double* g, double* A, int* nbad,
+                     double* J /*NULL ok, [nsets][nobs][npar]*/, double* sim_all /*NULL ok, [nsets][1+2npar][nobs]*/);
+/* Levenberg-Marquardt from nstarts starting points theta0[nstarts][npar], all advancing together: per iteration one
+ * ucf_fit_evaluate over the starts that moved and one base-values-only evaluation of the trial points.  Per start: step from
+ * ucf_fit_solve_step with Marquardt's damping, accepted if the trial has nbad = 0 and phi did not grow (lambda x
+ * lambda_down), rejected otherwise (lambda x lambda_up); converged when max |step| <= tol_step or an accepted step lowers
+ * phi by no more than tol_phi x phi; starts that are finished drop out of the batch.  theta[nstarts][npar], phi[nstarts],
+ * iters[nstarts], status[nstarts] (UCF_FIT_*); cov [nstarts][npar][npar] = phi / (nobs - npar) A^-1 at the final point, in
+ * ln theta (NaN where it does not exist), costs one more evaluation. */
+int ucf_fit_lm(ucf_fit* fit, int nstarts, const double* theta0, const ucf_fit_options* opt /*NULL = defaults*/,
+               double* theta, double* phi, int* iters, int* status, double* cov /*NULL ok*/);
+/* device allocations made so far by the fit and its plans (a repeated call of the same size makes none) */
+long long ucf_fit_alloc_count(const ucf_fit* fit);
 
 /* driver.f90:234-243 (quirk Q2: not a textbook trapezoid) */
 int ucf_screen_average(int npts, int zOrd, const double* h, double* havg);

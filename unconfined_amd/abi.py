@@ -8,6 +8,13 @@ UCF_MAX_MOENCH = 16
 UCF_MAX_NZ = 32
 UCF_MAX_LAP_M = 127
 UCF_MAX_SCHEDULE = 100
+UCF_FIT_MAX_PAR = 8
+# parameter ids of a fit (enum UCF_PAR_* of include/ucf.h); a Moench alpha is PAR_MOENCH_ALPHA0 + i
+PAR_KR, PAR_KAPPA, PAR_SS, PAR_SY, PAR_AC, PAR_AK, PAR_USL, PAR_MOENCH_ALPHA0 = range(8)
+PAR_IDS = {"Kr": PAR_KR, "kappa": PAR_KAPPA, "Ss": PAR_SS, "Sy": PAR_SY, "ac": PAR_AC, "ak": PAR_AK, "usL": PAR_USL}
+# status of a start of ucf_fit_lm (enum UCF_FIT_*)
+FIT_CONVERGED, FIT_MAX_ITER, FIT_SINGULAR, FIT_NONFINITE_START = range(4)
+UCF_ERR_BAD_ARGUMENT, UCF_ERR_NO_DEVICE, UCF_ERR_SINGULAR = -11, -12, -16
 
 
 class UcfParams(C.Structure):
@@ -44,6 +51,11 @@ class UcfDerived(C.Structure):
 class UcfStats(C.Structure):
     _fields_ = [(n, C.c_longlong) for n in
                 ("nan_scrubbed", "zero_vectors", "wynn_truncated", "wynn_sentinel", "wynn_early_exit", "wynn_all_zero")]
+
+
+class UcfFitOptions(C.Structure):
+    _fields_ = [("max_iter", C.c_int), ("dlog", C.c_double), ("lambda0", C.c_double), ("lambda_up", C.c_double),
+                ("lambda_down", C.c_double), ("tol_step", C.c_double), ("tol_phi", C.c_double)]
 
 
 def params_from_deck(dk) -> UcfParams:

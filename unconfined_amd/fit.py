@@ -1,0 +1,137 @@
+"""Parameter fitting over the C ABI (ucf_fit_* of include/ucf.h): the observations live on the GPU, base and perturbed
+parameter sets run through the launch sequence of ``ucf_drawdown_multi``, and residuals, objective, Jacobian and normal
+equations are formed on the device; this module only marshals arrays.
+
+    fit = Fit(params, free=["Kr", "kappa", "Ss", "Sy"], t=t, r=r, z=z, iz=iz, obs=obs)
+    out = fit.evaluate(theta, dlog=1e-3)          # phi, g, A, nbad (J, sim_all on request) for many parameter sets
+    res = fit.lm(theta0, max_iter=40)             # Levenberg-Marquardt from many starting points at once
+
+Parameters are positive and fitted in their logarithm; ``theta`` arrays hold the parameters themselves.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Sequence, Union
+
+import numpy as np
+
+from . import lib as _libmod
+from .abi import PAR_IDS, PAR_MOENCH_ALPHA0, UcfFitOptions, UcfParams
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def par_id(name: Union[str, int]) -> int:
+    """'Kr', 'kappa', 'Ss', 'Sy', 'ac', 'ak', 'usL', 'MoenchAlpha[i]' (or the id itself) -> UCF_PAR_*"""
+    if isinstance(name, (int, np.integer)):
+        return int(name)
+    if name in PAR_IDS:
+        return PAR_IDS[name]
+    if name.startswith("MoenchAlpha[") and name.endswith("]"):
+        return PAR_MOENCH_ALPHA0 + int(name[len("MoenchAlpha["):-1])
+    raise ValueError(f"unknown parameter {name!r}")
+
+
+def perturb(params: UcfParams, free: Sequence[Union[str, int]], theta) -> UcfParams:
+    """the parameter set ``params`` with the free parameters set to ``theta`` (ucf_fit_perturb; no GPU)"""
+    lib = _libmod.load()
+    ids = _i32([par_id(n) for n in free])
+    out = UcfParams()
+    _libmod.check(lib.ucf_fit_perturb(C.byref(params), len(ids), ids, _f64(theta), C.byref(out)))
+    return out
+
+
+def solve_step(A, g, lam: float) -> np.ndarray:
+    """(A + lam diag A) step = g (ucf_fit_solve_step; no GPU); raises UcfError (UCF_ERR_SINGULAR) if not positive definite"""
+    lib = _libmod.load()
+    A = _f64(A)
+    g = _f64(g)
+    step = np.zeros(len(g))
+    _libmod.check(lib.ucf_fit_solve_step(len(g), A, g, float(lam), step))
+    return step
+
+
+def default_options() -> UcfFitOptions:
+    opt = UcfFitOptions()
+    _libmod.check(_libmod.load().ucf_fit_default_options(C.byref(opt)))
+    return opt
+
+
+class Fit:
+    """observations (dimensional drawdown at time t[i], radius r[i], depth z[iz[i]], z up from the aquifer base) of one
+    parameter set ``params`` whose ``free`` parameters are to be estimated.  All depths of ``z`` are evaluated at every
+    point and ``iz`` selects one."""
+
+    def __init__(self, params: UcfParams, free, t, r, z, iz, obs, weight=None, device: int = 0):
+        self._lib = _libmod.load()
+        self._h = C.c_void_p()
+        self.params = params
+        self.free = list(free)
+        self.ids = _i32([par_id(n) for n in free])
+        self.npar = len(self.ids)
+        t, r, z, obs = _f64(t), _f64(r), _f64(z), _f64(obs)
+        iz = _i32(iz)
+        weight = np.ones(len(obs)) if weight is None else _f64(weight)
+        if not (len(t) == len(r) == len(iz) == len(obs) == len(weight)):
+            raise ValueError("t, r, iz, obs and weight must have one entry per observation")
+        self.nobs = len(obs)
+        _libmod.check(self._lib.ucf_fit_create(C.byref(params), self.npar, self.ids, self.nobs, t, r, iz, len(z), z, obs, weight,
+                                               int(device), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.ucf_fit_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def alloc_count(self) -> int:
+        """device allocations made so far by the fit and its plans"""
+        return int(self._lib.ucf_fit_alloc_count(self._h))
+
+    def evaluate(self, theta, dlog: float, jacobian: bool = False, sim_all: bool = False) -> dict:
+        """theta [nsets][npar] -> phi [nsets], g [nsets][npar], A [nsets][npar][npar], nbad [nsets]; on request J
+        [nsets][nobs][npar] and sim_all [nsets][1 + 2 npar][nobs] (row 0 base, 1 + 2j parameter j up, 2 + 2j down)"""
+        theta = np.atleast_2d(_f64(theta))
+        n, P = theta.shape
+        if P != self.npar:
+            raise ValueError(f"theta has {P} columns, the fit has {self.npar} free parameters")
+        out = {"phi": np.zeros(n), "g": np.zeros((n, P)), "A": np.zeros((n, P, P)), "nbad": np.zeros(n, np.int32)}
+        if jacobian:
+            out["J"] = np.zeros((n, self.nobs, P))
+        if sim_all:
+            out["sim_all"] = np.zeros((n, 1 + 2 * P, self.nobs))
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        _libmod.check(self._lib.ucf_fit_evaluate(self._h, n, np.ascontiguousarray(theta), float(dlog), ptr("phi"), ptr("g"), ptr("A"),
+                                                 ptr("nbad"), ptr("J"), ptr("sim_all")))
+        return out
+
+    def lm(self, theta0, cov: bool = True, **opt) -> dict:
+        """Levenberg-Marquardt from the starting points theta0 [nstarts][npar], all in one call; options as the fields of
+        ucf_fit_options (max_iter, dlog, lambda0, lambda_up, lambda_down, tol_step, tol_phi).  Returns theta, phi, iters,
+        status (abi.FIT_*) per start and, unless cov=False, the covariance in ln(theta)."""
+        theta0 = np.atleast_2d(_f64(theta0))
+        n, P = theta0.shape
+        if P != self.npar:
+            raise ValueError(f"theta0 has {P} columns, the fit has {self.npar} free parameters")
+        o = default_options()
+        for k, v in opt.items():
+            if not hasattr(o, k):
+                raise TypeError(f"unknown option {k!r}")
+            setattr(o, k, v)
+        out = {"theta": np.zeros((n, P)), "phi": np.zeros(n), "iters": np.zeros(n, np.int32), "status": np.zeros(n, np.int32)}
+        if cov:
+            out["cov"] = np.zeros((n, P, P))
+        _libmod.check(self._lib.ucf_fit_lm(self._h, n, np.ascontiguousarray(theta0), C.byref(o), out["theta"], out["phi"], out["iters"],
+                                           out["status"], out["cov"].ctypes.data if cov else None))
+        return out

@@ -12,7 +12,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import UcfDerived, UcfParams, UcfStats
+from .abi import UcfDerived, UcfFitOptions, UcfParams, UcfStats
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # UCF_LIB_PATH: an experimental build of the SAME library (tools/ubench/build_variant.sh) for A/B timing; the product
@@ -35,6 +35,8 @@ EXPORTS = [
     "ucf_eval_samples", "ucf_pvalues", "ucf_dehoog", "ucf_wynn_epsilon", "ucf_extraptozero", "ucf_bessel_k01",
     "ucf_debug_stages", "ucf_debug_wynn", "ucf_debug_dehoog_tiles",
     "ucf_fp64_fma_peak", "ucf_sincos_table", "ucf_exp2_table",
+    "ucf_fit_perturb", "ucf_fit_solve_step", "ucf_fit_default_options", "ucf_fit_create", "ucf_fit_destroy", "ucf_fit_evaluate",
+    "ucf_fit_lm", "ucf_fit_alloc_count",
 ]
 
 
@@ -122,6 +124,16 @@ def load() -> C.CDLL:
     lib.ucf_fp64_fma_peak.argtypes = [C.POINTER(C.c_double)]
     lib.ucf_sincos_table.argtypes = [C.POINTER(C.c_double)]
     lib.ucf_exp2_table.argtypes = [C.POINTER(C.c_double)]
+    lib.ucf_fit_perturb.argtypes = [C.POINTER(UcfParams), C.c_int, _ip, _dp, C.POINTER(UcfParams)]
+    lib.ucf_fit_solve_step.argtypes = [C.c_int, _dp, _dp, C.c_double, _dp]
+    lib.ucf_fit_default_options.argtypes = [C.POINTER(UcfFitOptions)]
+    lib.ucf_fit_create.argtypes = [C.POINTER(UcfParams), C.c_int, _ip, C.c_int, _dp, _dp, _ip, C.c_int, _dp, _dp, _dp, C.c_int, C.POINTER(vp)]
+    lib.ucf_fit_destroy.argtypes = [vp]
+    lib.ucf_fit_destroy.restype = None
+    lib.ucf_fit_evaluate.argtypes = [vp, C.c_int, _dp, C.c_double, vp, vp, vp, vp, vp, vp]
+    lib.ucf_fit_lm.argtypes = [vp, C.c_int, _dp, C.POINTER(UcfFitOptions), _dp, _dp, _ip, _ip, vp]
+    lib.ucf_fit_alloc_count.argtypes = [vp]
+    lib.ucf_fit_alloc_count.restype = C.c_longlong
     _lib = lib
     return lib
 
