@@ -290,8 +290,9 @@ int ucf_drawdown_multi(ucf_plan* const* plans, int nplans, int npts, const doubl
  *   parameters   all positive, fitted in ln(theta); theta arrays hold the parameters themselves, in the order of `ids`;
  *   observation  a DIMENSIONAL drawdown (h x Hc: what a deck with dimensionless = F prints) at dimensional time t[i], radius
  *                r[i] and depth z[iz[i]], z up from the aquifer base as in ucf_drawdown_multi.
- *   cost         ALL nz depths are evaluated at every observation point and iz selects one: an observation network with
- *                per-well depths pays nz evaluations per point (per-well depth sets inside one launch are not built).
+ *   cost         ucf_fit_create: ALL nz depths are evaluated at every observation point and iz selects one.  An observation
+ *                network with per-well depths and screened wells is made by ucf_fit_create_network (below): there a point is
+ *                evaluated at the depths of its own well only, and the screen average is formed on the device.
  *   sim_i(theta) the fast-flavour result of the plan made from ucf_fit_perturb(base, theta);   r_i = obs_i - sim_i;
  *   J[i][j]      (sim_i(theta e^{+dlog e_j}) - sim_i(theta e^{-dlog e_j})) / (2 dlog): the derivative in ln(theta_j);
  *   phi = sum w_i^2 r_i^2,  g = J' W^2 r,  A = J' W^2 J (full symmetric [npar][npar]).
@@ -347,6 +348,43 @@ int ucf_fit_lm(ucf_fit* fit, int nstarts, const double* theta0, const ucf_fit_op
                double* theta, double* phi, int* iters, int* status, double* cov /*NULL ok*/);
 /* device allocations made so far by the fit and its plans (a repeated call of the same size makes none) */
 long long ucf_fit_alloc_count(const ucf_fit* fit);
+
+/* An observation network: nwell wells, well w at radius well_r[w] with well_nz[w] depths (1..UCF_MAX_NZ) stored
+ * consecutively in well_z (z up from the aquifer base, dimensional).  Observation i: time t[i] at well well[i];
+ * iz[i] >= 0 selects depth iz[i] OF THAT WELL, iz[i] == UCF_FIT_SCREEN (-1) is the screen average of all of the
+ * well's depths by the rule of ucf_screen_average.  Only the depths of its own well are evaluated at a point.
+ *   launch       wells are grouped by their number of depths, one launch sequence of ucf_drawdown_multi per distinct number.
+ *                Inside a group the distinct times of every (parameter set, well) are cut into blocks of 64 points (the last
+ *                block of a well repeats its last time; those results are never read), wells in order of radius, and every
+ *                block carries the parameter block of its plan with the depths of its well: the kernels are those of
+ *                ucf_drawdown_multi, unchanged.  Models without a shared launch run plan by plan and well by well through
+ *                ucf_drawdown_batch_device on the stream pool.  Each plan's split vector is taken over all the launched times
+ *                of the network, so a value does not depend on how the wells fall into groups.
+ *   reduction    fit_network_reduce_kernel: as fit_reduce_kernel, but an observation finds its value through (offset, count):
+ *                count 1 reads one double per plan; count n > 1 forms s = v[1]; s = s + v[j], j = 2..n-1;
+ *                ((v[0] + 2 s) + v[n-1]) / (2 n) on the dimensionless h, then x Hc -- the operations of ucf_screen_average.
+ * A well that no observation names is never launched; observations that share a (well, time) share one evaluation.  J and
+ * sim_all come back in the caller's observation order.  ucf_fit_evaluate, ucf_fit_lm, ucf_fit_destroy and
+ * ucf_fit_alloc_count work on the object as on one made by ucf_fit_create.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything ucf_fit_create
+ * checks, nwell < 1, well_nz outside 1..UCF_MAX_NZ, well[i] outside 0..nwell-1, iz[i] outside -1..well_nz[w]-1, a well_r that
+ * is not finite and positive, a well_z that is not finite. */
+#define UCF_FIT_SCREEN (-1)
+int ucf_fit_create_network(const ucf_params* base, int npar, const int* ids,
+                           int nwell, const double* well_r, const int* well_nz, const double* well_z,
+                           int nobs, const double* t, const int* well, const int* iz,
+                           const double* obs, const double* weight, int device, ucf_fit** out);
+/* (point, depth) evaluations per parameter set that this fit launches (padding included) and that the dense form
+ * -- every depth of the network at every (well, time) -- would launch.  Host arithmetic, no launch.  For a fit made by
+ * ucf_fit_create launched == dense. */
+int ucf_fit_eval_counts(const ucf_fit* fit, long long* launched, long long* dense);
+/* the same two numbers from the network alone (no fit object, no GPU); checks well_nz, well[i] and t[i] as above */
+int ucf_fit_network_eval_counts(int nwell, const int* well_nz, int nobs, const double* t, const int* well,
+                                long long* launched, long long* dense);
+/* diagnostic: the dimensionless h behind observation i under plan `plan` (set * (1 + 2 npar) + row) as the LAST
+ * ucf_fit_evaluate left it in device memory: n = 1 value for a point observation, the n depths of the well for a screen
+ * average (what its average was formed from).  cap < n: UCF_ERR_BAD_ARGUMENT. */
+int ucf_fit_debug_h(ucf_fit* fit, int plan, int i, int cap, double* h, int* n);
 
 /* driver.f90:234-243 (quirk Q2: not a textbook trapezoid) */
 int ucf_screen_average(int npts, int zOrd, const double* h, double* havg);

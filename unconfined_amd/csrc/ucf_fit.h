@@ -12,3 +12,18 @@ static inline int ucf_fit_nsums(int npar) { return 1 + npar + npar * (npar + 1) 
 int ucf_fit_launch_reduce(int npar, int nsets, int nobs, size_t plan_stride, double two_dlog, const double* d_h, const double* d_Hc,
                           const int* d_slot, const double* d_obs, const double* d_w, double* d_sums, int* d_nbad, double* d_J,
                           double* d_sim, void* stream);
+
+// Where an observation of a network fit (ucf_fit_create_network) finds its simulated value.  The h of a network is ragged:
+// one region per group of wells with the same number of depths, group g at nplans * prefix_g doubles, plan k of it at
+// k * stride_g (stride_g = points per plan x depths of the group, prefix_g = sum of the strides before it).  The
+// observation reads `count` consecutive doubles at  prefix * nplans + plan * stride + at:  1 = that depth of its point,
+// n > 1 = all n depths of its well, averaged by the rule of ucf_screen_average.
+struct ucf_fit_obs_ref {
+    long long prefix, stride;
+    int at, count;
+};
+
+// as ucf_fit_launch_reduce (same sums, same order), observation i found through d_ref[i]; nplans = nsets * (1 + 2 npar)
+int ucf_fit_launch_network_reduce(int npar, int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_Hc,
+                                  const ucf_fit_obs_ref* d_ref, const double* d_obs, const double* d_w, double* d_sums, int* d_nbad,
+                                  double* d_J, double* d_sim, void* stream);

@@ -1,5 +1,7 @@
 // ucf_fit.hip -- residuals, objective, central-difference Jacobian and normal equations of a least-squares fit, from the
-// drawdowns that the evaluators left in device memory (ucf_fit_evaluate, include/ucf.h).
+// drawdowns that the evaluators left in device memory (ucf_fit_evaluate, include/ucf.h).  Two kernels over one body:
+// fit_reduce_kernel (ucf_fit_create: one double per observation and plan) and fit_network_reduce_kernel
+// (ucf_fit_create_network: ragged per-group h, point observations and screen averages).
 //
 // Tiny and HBM-bound: (1 + 2 NPAR) x nobs doubles per parameter set are read once.  Built with -ffp-contract=off: every
 // product and sum below is rounded on its own, so that the result is the arithmetic written here.  The sums are reduced in
@@ -20,12 +22,12 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
-template <int NPAR>
-__global__ void __launch_bounds__(FIT_THREADS) fit_reduce_kernel(int nobs, size_t plan_stride, double two_dlog, const double* __restrict__ h,
-                                                                 const double* __restrict__ Hc, const int* __restrict__ slot,
-                                                                 const double* __restrict__ obs, const double* __restrict__ w,
-                                                                 double* __restrict__ sums, int* __restrict__ nbad, double* __restrict__ J,
-                                                                 double* __restrict__ sim)
+// Everything after the simulated values: value(i, plan) is the dimensional simulated value of observation i under plan
+// `plan`; the two kernels below differ only in it.
+template <int NPAR, class VALUE>
+__device__ __forceinline__ void fit_reduce_body(int nobs, double two_dlog, const VALUE& value, const double* __restrict__ obs,
+                                                const double* __restrict__ w, double* __restrict__ sums, int* __restrict__ nbad,
+                                                double* __restrict__ J, double* __restrict__ sim)
 {
     constexpr int NP = NPAR > 0 ? NPAR : 1;                  // array extents (NPAR = 0: objective only)
     constexpr int NPLANS = 1 + 2 * NPAR;
@@ -41,12 +43,11 @@ __global__ void __launch_bounds__(FIT_THREADS) fit_reduce_kernel(int nobs, size_
     for (int j = 0; j < NP * (NP + 1) / 2; j++) A[j] = 0.0;
     int bad = 0;
     for (int i = lane; i < nobs; i += FIT_THREADS) {
-        const int at = slot[i];
         double s[NPLANS];
         bool ok = true;
 #pragma unroll
         for (int k = 0; k < NPLANS; k++) {
-            s[k] = h[(plan0 + k) * plan_stride + at] * Hc[plan0 + k];      // dimensional, as ucf_drawdown_multi scales it
+            s[k] = value(i, plan0 + k);
             ok = ok && isfinite(s[k]);
         }
         if (sim) {
@@ -103,6 +104,68 @@ __global__ void __launch_bounds__(FIT_THREADS) fit_reduce_kernel(int nobs, size_
     }
 }
 
+// observation i = one double per plan, at slot[i] of the plan's block
+struct slot_value {
+    const double* __restrict__ h;
+    const double* __restrict__ Hc;
+    const int* __restrict__ slot;
+    size_t plan_stride;
+    __device__ __forceinline__ double operator()(int i, size_t plan) const
+    {
+        return h[plan * plan_stride + slot[i]] * Hc[plan];      // dimensional, as ucf_drawdown_multi scales it
+    }
+};
+
+// observation i of a network = ref[i].count consecutive depths of one point in the ragged per-group h: one value, or the
+// screen average over the well's depths in the operation order of ucf_screen_average (driver.f90:234-243, quirk Q2), formed
+// on the dimensionless h and then scaled
+struct network_value {
+    const double* __restrict__ h;
+    const double* __restrict__ Hc;
+    const ucf_fit_obs_ref* __restrict__ ref;
+    size_t nplans;
+    __device__ __forceinline__ double operator()(int i, size_t plan) const
+    {
+        const ucf_fit_obs_ref o = ref[i];
+        const double* v = h + ((size_t)o.prefix * nplans + plan * (size_t)o.stride + (size_t)o.at);
+        const int n = o.count;
+        if (n == 1) return v[0] * Hc[plan];
+        double s = v[1];
+        for (int j = 2; j < n; j++) s = s + v[j];
+        return (((v[0] + 2.0 * s) + v[n - 1]) / (2 * n)) * Hc[plan];
+    }
+};
+
+template <int NPAR>
+__global__ void __launch_bounds__(FIT_THREADS) fit_reduce_kernel(int nobs, size_t plan_stride, double two_dlog, const double* __restrict__ h,
+                                                                 const double* __restrict__ Hc, const int* __restrict__ slot,
+                                                                 const double* __restrict__ obs, const double* __restrict__ w,
+                                                                 double* __restrict__ sums, int* __restrict__ nbad, double* __restrict__ J,
+                                                                 double* __restrict__ sim)
+{
+    fit_reduce_body<NPAR>(nobs, two_dlog, slot_value{h, Hc, slot, plan_stride}, obs, w, sums, nbad, J, sim);
+}
+
+template <int NPAR>
+__global__ void __launch_bounds__(FIT_THREADS) fit_network_reduce_kernel(int nobs, size_t nplans, double two_dlog, const double* __restrict__ h,
+                                                                         const double* __restrict__ Hc,
+                                                                         const ucf_fit_obs_ref* __restrict__ ref,
+                                                                         const double* __restrict__ obs, const double* __restrict__ w,
+                                                                         double* __restrict__ sums, int* __restrict__ nbad,
+                                                                         double* __restrict__ J, double* __restrict__ sim)
+{
+    fit_reduce_body<NPAR>(nobs, two_dlog, network_value{h, Hc, ref, nplans}, obs, w, sums, nbad, J, sim);
+}
+
+template <int NPAR>
+int launch_network(int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_Hc, const ucf_fit_obs_ref* d_ref,
+                   const double* d_obs, const double* d_w, double* d_sums, int* d_nbad, double* d_J, double* d_sim, hipStream_t stream)
+{
+    hipLaunchKernelGGL(fit_network_reduce_kernel<NPAR>, dim3(nsets), dim3(FIT_THREADS), 0, stream, nobs, nplans, two_dlog, d_h, d_Hc, d_ref,
+                       d_obs, d_w, d_sums, d_nbad, d_J, d_sim);
+    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
+}
+
 template <int NPAR>
 int launch(int nsets, int nobs, size_t plan_stride, double two_dlog, const double* d_h, const double* d_Hc, const int* d_slot,
            const double* d_obs, const double* d_w, double* d_sums, int* d_nbad, double* d_J, double* d_sim, hipStream_t stream)
@@ -120,6 +183,21 @@ int ucf_fit_launch_reduce(int npar, int nsets, int nobs, size_t plan_stride, dou
     if (nsets < 1 || nobs < 1) return UCF_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
 #define UCF_FIT_CASE(N) case N: return launch<N>(nsets, nobs, plan_stride, two_dlog, d_h, d_Hc, d_slot, d_obs, d_w, d_sums, d_nbad, d_J, d_sim, s)
+    switch (npar) {
+        UCF_FIT_CASE(0); UCF_FIT_CASE(1); UCF_FIT_CASE(2); UCF_FIT_CASE(3); UCF_FIT_CASE(4);
+        UCF_FIT_CASE(5); UCF_FIT_CASE(6); UCF_FIT_CASE(7); UCF_FIT_CASE(8);
+    default: return UCF_ERR_BAD_ARGUMENT;
+    }
+#undef UCF_FIT_CASE
+}
+
+int ucf_fit_launch_network_reduce(int npar, int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_Hc,
+                                  const ucf_fit_obs_ref* d_ref, const double* d_obs, const double* d_w, double* d_sums, int* d_nbad,
+                                  double* d_J, double* d_sim, void* stream)
+{
+    if (nsets < 1 || nobs < 1) return UCF_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+#define UCF_FIT_CASE(N) case N: return launch_network<N>(nsets, nobs, nplans, two_dlog, d_h, d_Hc, d_ref, d_obs, d_w, d_sums, d_nbad, d_J, d_sim, s)
     switch (npar) {
         UCF_FIT_CASE(0); UCF_FIT_CASE(1); UCF_FIT_CASE(2); UCF_FIT_CASE(3); UCF_FIT_CASE(4);
         UCF_FIT_CASE(5); UCF_FIT_CASE(6); UCF_FIT_CASE(7); UCF_FIT_CASE(8);

@@ -5,6 +5,8 @@ equations are formed on the device; this module only marshals arrays.
     fit = Fit(params, free=["Kr", "kappa", "Ss", "Sy"], t=t, r=r, z=z, iz=iz, obs=obs)
     out = fit.evaluate(theta, dlog=1e-3)          # phi, g, A, nbad (J, sim_all on request) for many parameter sets
     res = fit.lm(theta0, max_iter=40)             # Levenberg-Marquardt from many starting points at once
+    net = Fit.network(params, free, wells=[(r0, [z0]), (r1, [za, zb, zc])], t=t, well=well, iz=iz, obs=obs)
+                                                  # an observation network: per-well radius and depths, iz = -1: screen average
 
 Parameters are positive and fitted in their logarithm; ``theta`` arrays hold the parameters themselves.
 """
@@ -16,7 +18,7 @@ from typing import Sequence, Union
 import numpy as np
 
 from . import lib as _libmod
-from .abi import PAR_IDS, PAR_MOENCH_ALPHA0, UcfFitOptions, UcfParams
+from .abi import FIT_SCREEN, PAR_IDS, PAR_MOENCH_ALPHA0, UcfFitOptions, UcfParams
 
 
 def _f64(a):
@@ -63,6 +65,26 @@ def default_options() -> UcfFitOptions:
     return opt
 
 
+def pack_wells(wells):
+    """a sequence of (r, z_array) -> the arrays of ucf_fit_create_network: well_r [nwell], well_nz [nwell] and well_z, the
+    depths of all wells one after the other"""
+    wells = list(wells)
+    well_r = _f64([float(r) for r, _ in wells])
+    zs = [np.atleast_1d(_f64(z)).ravel() for _, z in wells]
+    well_nz = _i32([len(z) for z in zs])
+    well_z = _f64(np.concatenate(zs)) if zs else np.zeros(0)
+    return well_r, well_nz, well_z
+
+
+def network_eval_counts(wells, t, well) -> tuple:
+    """(launched, dense) of the network fit over these observations (ucf_fit_network_eval_counts; no GPU)"""
+    _, well_nz, _ = pack_wells(wells)
+    t, well = _f64(t), _i32(well)
+    a, b = C.c_longlong(), C.c_longlong()
+    _libmod.check(_libmod.load().ucf_fit_network_eval_counts(len(well_nz), well_nz, len(t), t, well, C.byref(a), C.byref(b)))
+    return int(a.value), int(b.value)
+
+
 class Fit:
     """observations (dimensional drawdown at time t[i], radius r[i], depth z[iz[i]], z up from the aquifer base) of one
     parameter set ``params`` whose ``free`` parameters are to be estimated.  All depths of ``z`` are evaluated at every
@@ -83,6 +105,43 @@ class Fit:
         self.nobs = len(obs)
         _libmod.check(self._lib.ucf_fit_create(C.byref(params), self.npar, self.ids, self.nobs, t, r, iz, len(z), z, obs, weight,
                                                int(device), C.byref(self._h)))
+
+    @classmethod
+    def network(cls, params: UcfParams, free, wells, t, well, iz, obs, weight=None, device: int = 0) -> "Fit":
+        """an observation network (ucf_fit_create_network): ``wells`` is a sequence of (r, z_array), observation i is the
+        drawdown at time t[i] in well well[i], at depth iz[i] of that well or, with iz[i] = -1 (``abi.FIT_SCREEN``), the
+        screen average over all depths of that well.  A point is evaluated at the depths of its own well only."""
+        self = cls.__new__(cls)
+        self._lib = _libmod.load()
+        self._h = C.c_void_p()
+        self.params = params
+        self.free = list(free)
+        self.ids = _i32([par_id(n) for n in free])
+        self.npar = len(self.ids)
+        well_r, well_nz, well_z = pack_wells(wells)
+        t, obs = _f64(t), _f64(obs)
+        well, iz = _i32(well), _i32(iz)
+        weight = np.ones(len(obs)) if weight is None else _f64(weight)
+        if not (len(t) == len(well) == len(iz) == len(obs) == len(weight)):
+            raise ValueError("t, well, iz, obs and weight must have one entry per observation")
+        self.nobs = len(obs)
+        _libmod.check(self._lib.ucf_fit_create_network(C.byref(params), self.npar, self.ids, len(well_r), well_r, well_nz, well_z,
+                                                       self.nobs, t, well, iz, obs, weight, int(device), C.byref(self._h)))
+        return self
+
+    def eval_counts(self) -> tuple:
+        """(launched, dense): (point, depth) evaluations per parameter set that this fit launches, padding included, and
+        that every depth of the network at every (well, time) would take"""
+        a, b = C.c_longlong(), C.c_longlong()
+        _libmod.check(self._lib.ucf_fit_eval_counts(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def debug_h(self, plan: int, i: int) -> np.ndarray:
+        """diagnostic (ucf_fit_debug_h): the dimensionless h behind observation i under plan ``plan`` of the last evaluate"""
+        h = np.zeros(64)
+        n = C.c_int()
+        _libmod.check(self._lib.ucf_fit_debug_h(self._h, int(plan), int(i), len(h), h, C.byref(n)))
+        return h[:n.value].copy()
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:

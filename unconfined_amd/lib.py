@@ -37,6 +37,7 @@ EXPORTS = [
     "ucf_fp64_fma_peak", "ucf_sincos_table", "ucf_exp2_table",
     "ucf_fit_perturb", "ucf_fit_solve_step", "ucf_fit_default_options", "ucf_fit_create", "ucf_fit_destroy", "ucf_fit_evaluate",
     "ucf_fit_lm", "ucf_fit_alloc_count",
+    "ucf_fit_create_network", "ucf_fit_eval_counts", "ucf_fit_network_eval_counts", "ucf_fit_debug_h",
 ]
 
 
@@ -134,6 +135,11 @@ def load() -> C.CDLL:
     lib.ucf_fit_lm.argtypes = [vp, C.c_int, _dp, C.POINTER(UcfFitOptions), _dp, _dp, _ip, _ip, vp]
     lib.ucf_fit_alloc_count.argtypes = [vp]
     lib.ucf_fit_alloc_count.restype = C.c_longlong
+    lib.ucf_fit_create_network.argtypes = [C.POINTER(UcfParams), C.c_int, _ip, C.c_int, _dp, _ip, _dp, C.c_int, _dp, _ip, _ip, _dp, _dp, C.c_int,
+                                           C.POINTER(vp)]
+    lib.ucf_fit_eval_counts.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.ucf_fit_network_eval_counts.argtypes = [C.c_int, _ip, C.c_int, _dp, _ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    lib.ucf_fit_debug_h.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]
     _lib = lib
     return lib
 
