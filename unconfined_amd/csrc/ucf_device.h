@@ -669,7 +669,8 @@ UCF_DEV cplx qd_quotient(cplx qn, cplx enn, cplx enew, bool valid)
 // The continued-fraction coefficients go straight to column `dcol` of an LDS tile (d(k) in row k, `pitch` apart): lane 0,
 // which holds q(0,r) and e(0,r), stores d(2r-1) and d(2r) as they appear -- no broadcast, no per-lane selects.  e(i+1,r)
 // of one step is the shifted e of the next: one shift less per step.
-UCF_DEV void dehoog_qd_wave(cplx f, int M, int lane, ucf_stats* st, bool* zero, lds_c* dcol, int pitch)
+// qd_start: the tests of a vector (zero vector, NaN scrub, statistics), d(0) and the first column q(i,1); false: a zero vector
+UCF_DEV bool qd_start(cplx f, int M, int lane, ucf_stats* st, lds_c* dcol, cplx* q1)
 {
     const int n2 = 2 * M;
     const bool act = lane <= n2;
@@ -683,10 +684,9 @@ UCF_DEV void dehoog_qd_wave(cplx f, int M, int lane, ucf_stats* st, bool* zero, 
         if (d_isnan(mag)) mag = 0.0;
         mx = wave_max(mag);
     }
-    *zero = !(mx > UCF_DBL_MIN);
-    if (*zero) {
+    if (!(mx > UCF_DBL_MIN)) {
         if (st) stat_add(&st->zero_vectors, lane == 0);
-        return;
+        return false;
     }
     const bool nanp = act && (d_isnan(f.re) || d_isnan(f.im));
     if (st) stat_add(&st->nan_scrubbed, nanp);
@@ -695,13 +695,20 @@ UCF_DEV void dehoog_qd_wave(cplx f, int M, int lane, ucf_stats* st, bool* zero, 
     const cplx d0 = cdivr(ff0, 2.0);                                                            // :98
     if (lane == 0) dcol[0] = make_double2(d0.re, d0.im);
     cplx fnext = shfl_down1(ff);
-    cplx q = (lane == 0) ? cdiv(fnext, d0) : cdiv(fnext, ff);                                   // :81-82  q(i,1)
+    *q1 = (lane == 0) ? cdiv(fnext, d0) : cdiv(fnext, ff);                                      // :81-82  q(i,1)
+    return true;
+}
+UCF_DEV void dehoog_qd_wave(cplx f, int M, int lane, ucf_stats* st, bool* zero, lds_c* dcol, int pitch)
+{
+    cplx q;
+    *zero = !qd_start(f, M, lane, st, dcol, &q);
+    if (*zero) return;
     cplx en = cmake(0.0, 0.0);                                                                  // :80     e(i+1,0)
     // Lanes outside the rhombus -- i > 2(M - r) for e(.,r), i > 2(M - r) - 1 for q(.,r+1) -- hold whatever the shifts bring
     // and no entry inside ever reads them.  The fast flavour leaves them alone (8 selects per step less); the faithful one
     // keeps them at 1 so that its scaled division never takes the out-of-line Annex-G recovery for a lane nobody reads.
 #if !UCF_FAST
-    if (lane > n2 - 1) q = cmake(1.0, 0.0);
+    if (lane > 2 * M - 1) q = cmake(1.0, 0.0);
 #endif
     for (int r = 1; r <= M; r++) {                                                              // :85-95
         const cplx qn = shfl_down1(q);
@@ -723,6 +730,108 @@ UCF_DEV void dehoog_qd_wave(cplx f, int M, int lane, ucf_stats* st, bool* zero, 
         }
     }
 }
+
+// Packed rhombus (fast flavour, -DUCF_DH_PACK=0: one vector per pass as above).  Step r of a vector needs q(i,r) of the
+// lanes i <= 2(M - r) + 1 only, so from r = M - 15 on a vector fits a group of 32 lanes and from r = M - 7 on a group of 16:
+// two, then four vectors share every instruction of a step.  No entry inside a rhombus reads a lane outside it (the one-lane
+// shift brings a group's last lane its neighbour's lane 0: that lane is outside), so per lane the arithmetic is the solo
+// arithmetic.  The one thing the lanes of a wave decide together, the form of the quotient, is decided per group.
+#ifndef UCF_DH_PACK
+#define UCF_DH_PACK 1
+#endif
+#if UCF_FAST && UCF_DH_PACK
+UCF_DEV cplx lane_gather(cplx v, int src) { return cmake(__shfl(v.re, src, 64), __shfl(v.im, src, 64)); }
+// qd_quotient for groups of W lanes: each group takes the form it would take alone in the wave (a group of the pass may need
+// cdiv while its neighbours keep the unscaled quotient: both forms then, chosen by group)
+template <int W>
+UCF_DEV cplx qd_quotient_groups(cplx qn, cplx enn, cplx enew, bool valid, int lane)
+{
+    const double m = fmax(fabs(enew.re), fabs(enew.im));
+    const unsigned long long bal = __builtin_amdgcn_ballot_w64(valid && !(m < 1.0e150 && m > 1.0e-150));
+    const double r = fast_rcp(__builtin_fma(enew.re, enew.re, enew.im * enew.im));
+    const cplx num = cmul(qn, enn);
+    cplx res = cmake((num.re * enew.re + num.im * enew.im) * r, (num.im * enew.re - num.re * enew.im) * r);
+    if (__builtin_expect(bal != 0, 0)) {
+        const bool mine = ((bal >> (lane & ~(W - 1))) & ((1ull << W) - 1)) != 0;
+        const cplx scaled = cdiv(cmul(qn, enn), enew);
+        if (mine) res = scaled;
+    }
+    return res;
+}
+// step r of the rhombus in every group of W lanes: `lane` in the wave, `occ` this lane's group holds a vector, `dcol` the LDS
+// column of this lane's vector (read by the group's lane 0)
+template <int W>
+UCF_DEV void qd_step(cplx& q, cplx& en, int r, int M, int lane, bool occ, lds_c* dcol, int pitch)
+{
+    const int l = lane & (W - 1);
+    const cplx qn = shfl_down1(q);
+    const cplx enew = cadd(csub(qn, q), en);
+    if (l == 0 && occ) {
+        dcol[(size_t)(2 * r - 1) * pitch] = make_double2(-q.re, -q.im);                         // d(2r-1) = -q(0,r)   :100
+        dcol[(size_t)(2 * r) * pitch] = make_double2(-enew.re, -enew.im);                       // d(2r)   = -e(0,r)   :101
+    }
+    if (r < M) {
+        const cplx enn = shfl_down1(enew);
+        const bool valid = occ && l <= 2 * (M - r - 1) + 1;
+        if constexpr (W == UCF_WAVE) q = qd_quotient(qn, enn, enew, valid);                     // :93
+        else q = qd_quotient_groups<W>(qn, enn, enew, valid, lane);
+        en = enn;
+    }
+}
+// The rhombi of a tile of ncur <= UCF_DH_TILE times, two times = four vectors (h, dh, h, dh) at a go: each vector starts
+// alone at full width (qd_start) and runs alone while it is wider than half a wave, moves into its half of a pair (h in
+// lanes 0..31, dh in 32..63) for the steps up to r16, and the pair into two quarters of the quad.  A zero vector and a time
+// past ncur leave their group empty (bit of `present` clear: no store, no say in the ballot).  Live: the quad, the pair and
+// the vector in progress, 8 registers each.
+UCF_DEV void dehoog_qd_tile(const ucf_dev_params& P, int lane, int ncur, const double* __restrict__ tD4, lds_c* lds, lds_c* tileB,
+                            int pitch, int* zflag, ucf_stats* st)
+{
+    const int M = P.M, np = P.np;
+    const int r32 = (M - 15 > 1) ? M - 15 : 1, r16 = (M - 7 > 1) ? M - 7 : 1;       // first step in groups of 32 / of 16 lanes
+    const cplx c0 = cmake(0.0, 0.0);
+    for (int tq = 0; tq < ncur; tq += 2) {
+        cplx Qq = c0, Qe = c0;
+        int present = 0;                                       // bit g: quarter g of the quad holds a vector
+        for (int hf = 0; hf < 2 && tq + hf < ncur; hf++) {
+            const int tt = tq + hf;
+            const double tee = 2.0 * tD4[tt];
+            const double sigma = P.alpha - P.logtol / (2.0 * tee);
+            cplx tl = c0;
+            if (lane < np) { const lds_c v = lds[lane * pitch + tt]; tl = cmake(v.x, v.y); }
+            const cplx p = cmake(sigma, UCF_PI * lane / tee);
+            cplx Pq = c0, Pe = c0;
+            for (int which = 0; which < 2; which++) {
+                lds_c* col = (which ? tileB : lds) + tt;       // (column tt of the tile is in `tl` by now)
+                cplx q;
+                const bool some = qd_start(which ? cmul(tl, p) : tl, M, lane, st, col, &q);
+                const bool live = __builtin_amdgcn_ballot_w64(some) != 0;                       // (the same in every lane)
+                if (lane == 0) zflag[2 * tt + which] = !live;
+                if (!live) continue;
+                cplx en = c0;                                                                   // :80     e(i+1,0)
+                for (int r = 1; r < r32; r++) qd_step<UCF_WAVE>(q, en, r, M, lane, true, col, pitch);
+                present |= 1 << (2 * hf + which);
+                const cplx gq = lane_gather(q, lane & 31), ge = lane_gather(en, lane & 31);
+                if ((lane >> 5) == which) { Pq = gq; Pe = ge; }
+            }
+            if (((present >> (2 * hf)) & 3) == 0) continue;
+            {
+                const int g = lane >> 5;
+                const bool occ = (present >> (2 * hf + g)) & 1;
+                lds_c* col = (g ? tileB : lds) + tt;
+                for (int r = r32; r < r16; r++) qd_step<32>(Pq, Pe, r, M, lane, occ, col, pitch);
+                const int src = ((lane >> 4) & 1) * 32 + (lane & 15);
+                const cplx gq = lane_gather(Pq, src), ge = lane_gather(Pe, src);
+                if ((lane >> 5) == hf) { Qq = gq; Qe = ge; }
+            }
+        }
+        if (present == 0) continue;
+        const int g = lane >> 4;
+        const bool occ = (present >> g) & 1;
+        lds_c* col = ((g & 1) ? tileB : lds) + tq + (g >> 1);
+        for (int r = r16; r <= M; r++) qd_step<16>(Qq, Qe, r, M, lane, occ, col, pitch);
+    }
+}
+#endif
 
 UCF_DEV double dehoog_cf_lane(const lds_c* dcol, int pitch, int M, double alpha, double logtol, double t, double tee)
 {
@@ -1938,6 +2047,9 @@ dehoog_tiles_kernel(const ucf_dev_params P, int nt, int nr, int ir0, int nrc, co
             }
             __syncthreads();
             if constexpr (!BIG) {
+#if UCF_FAST && UCF_DH_PACK
+                dehoog_qd_tile(P, lane, ncur, tDv + it0, lds, tileB, pitch, zflag, st);
+#else
                 for (int tt = 0; tt < ncur; tt++) {
                     const double tD = tDv[it0 + tt];
                     const double tee = 2.0 * tD;
@@ -1950,6 +2062,7 @@ dehoog_tiles_kernel(const ucf_dev_params P, int nt, int nr, int ir0, int nrc, co
                     dehoog_qd_wave(cmul(tl, p), P.M, lane, st, &z1, tileB + tt, pitch);
                     if (lane == 0) { zflag[2 * tt] = z0; zflag[2 * tt + 1] = z1; }
                 }
+#endif
                 __syncthreads();
                 if (lane < 2 * ncur) {
                     const int tt = lane >> 1, which = lane & 1;
