@@ -623,6 +623,24 @@ np.savez(sys.argv[2], **out)
 """
 
 
+# 2M+1 = 65 samples > 64 lanes: (point, 64-sample chunk) work items, launch_points_chunked.  8 points, one depth: two items
+# of (R + 1 + nacc) x 1 KiB = 15 KiB of state per point, so a 64 KiB state budget cuts the list into launches of 2 points
+_CHUNKED_SCRIPT = r"""
+import sys, numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+from golden_util import load_deck
+from unconfined_amd import engine
+dk, ts, P = load_deck("c2_neuman74_fullpen")
+Pm = type(P).from_buffer_copy(P); Pm.M = 32
+out = {}
+for mode in ("fast", "faithful"):
+    plan = engine.Plan(Pm, mode=mode)
+    zD = np.array([0.91]); tD = 10.0 ** np.linspace(-2, 3, 8); rD = np.array([0.02, 0.1, 0.5, 3.0] * 2)
+    out[mode + "_h"], out[mode + "_dh"] = plan.drawdown(tD, rD, plan.split_vector(tD), zD, plan.zlay(zD))
+np.savez(sys.argv[2], **out)
+"""
+
+
 def test_pipeline_knobs_do_not_change_results(tmp_path):
     """the fast flavour's kernel pipeline (integrate -> finish -> resume of unfinished items): cutting the work
     into small state-budget chunks and every scratch-part width of finish_kernel give the same bits"""
@@ -636,6 +654,15 @@ def test_pipeline_knobs_do_not_change_results(tmp_path):
         e = dict(os.environ); e.update(env)
         subprocess.run([sys.executable, "-c", _PIPE_SCRIPT, root, out], check=True, env=e, timeout=600)
         res[tag] = np.load(out)
+    ck = {}
+    for tag, env in (("default", {}), ("chunks", {"UCF_STATE_BYTES": str(64 << 10)})):
+        out = str(tmp_path / f"chunked_{tag}.npz")
+        e = dict(os.environ); e.update(env)
+        subprocess.run([sys.executable, "-c", _CHUNKED_SCRIPT, root, out], check=True, env=e, timeout=600)
+        ck[tag] = np.load(out)
+    for k in ck["default"].files:
+        assert np.isfinite(ck["default"][k]).any(), k
+        assert np.array_equal(ck["default"][k], ck["chunks"][k], equal_nan=True), ("chunked layout", k)
     ref = res["default"]
     for tag in ("chunks", "part16", "part32", "tables"):
         for k in ref.files:

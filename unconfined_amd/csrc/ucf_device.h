@@ -21,7 +21,6 @@
 
 #include "ucf_math.h"
 #include "ucf_plan.h"
-#include <cstdlib>
 #include <type_traits>
 
 namespace UCF_NS {
@@ -2453,13 +2452,22 @@ size_t lt_table_bytes(const ucf_dev_params& dp, size_t rows)
 
 // The transform stage for `nwork` work items of lane layout LAYOUT: [integrate kernel -> finish_kernel ->] point_kernel.
 // tm (optional): every kernel of the stage is bracketed by HIP events on the launch stream (ucf_timers).
+// (L.npts is not read here: nwork, from the layout launcher, says how much there is to do)
 template <int LAYOUT, bool MULTI>
-static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point, int nr, int nsv, int svmin, const double* d_tD,
-                            const double* d_rD, const int* d_sv, const double* d_tab, double* d_h, double* d_dh,
-                            ucf_stats* d_stats, int nt, int ir0, int nrc, double* d_totlap, double* d_glscr,
-                            double* d_state, int* d_ndone, void* stream, ucf_timers* tm,
-                            const ucf_dev_params* d_params, int ppp, int pbase)
+static int launch_transform_(const ucf_launch& L, int nwork)
 {
+    const ucf_env& env = ucf_env_get();
+    const ucf_dev_params& dp = *L.dp;
+    const int per_point = L.per_point, nr = L.nr, nsv = L.nsv, svmin = L.svmin, nt = L.nt, ir0 = L.ir0, nrc = L.nrc;
+    const double *d_tD = L.tD, *d_rD = L.rD, *d_tab = L.tab;
+    const int* d_sv = L.sv;
+    double *d_h = L.h, *d_dh = L.dh, *d_totlap = L.totlap, *d_glscr = L.glscr, *d_state = L.state;
+    int* d_ndone = L.ndone;
+    ucf_stats* const d_stats = L.stats;
+    ucf_timers* const tm = L.tm;
+    // only a parameter batch reads these
+    const ucf_dev_params* d_params = MULTI ? L.params : nullptr;
+    const int ppp = MULTI ? L.ppp : 1, pbase = MULTI ? L.pbase : 0;
     char kname[96];
     int* d_todo = d_ndone ? d_ndone + nwork : nullptr;     // [count | items]: the caller sizes d_ndone for 2 nwork + 1 ints
     const int fam = family_of(dp);
@@ -2469,11 +2477,11 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
     if (split && (!d_state || !d_ndone)) return UCF_ERR_BAD_ARGUMENT;
     const size_t lds = point_lds_bytes(dp, split);
     if (lds > 160 * 1024) return UCF_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
+    hipStream_t s = (hipStream_t)L.stream;
     const bool al = areas_in_lds(dp) || split;
     if (al) d_glscr = nullptr;
     if (!split) { d_state = nullptr; d_ndone = nullptr; d_todo = nullptr; }
-    dim3 grid((unsigned)((al || nwork < UCF_GRID_SLOTS) ? nwork : UCF_GRID_SLOTS)), block(UCF_WAVE);
+    dim3 grid((unsigned)((al || nwork < env.grid_slots) ? nwork : env.grid_slots)), block(UCF_WAVE);
     if (split) {
         (void)hipMemsetAsync(d_todo, 0, sizeof(int), s);
     }
@@ -2484,7 +2492,7 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
         // parts per item: launches of fewer than ~8 rounds of resident waves (256 CUs x 4 SIMDs x <= 6 waves) run two parts
         // per item -- measured on the 1/8 shard of C2 (27 136 items, tools/gpu_shard.sh): 5.37 / 5.26 / 5.35 / 5.58 ms with
         // 1 / 2 / 4 / 8 parts (every part pays the item's set-up again).  UCF_NSPLIT (diagnostic): force 1, 2, 4 or 8 parts.
-        static const int force_split = [] { const char* e = std::getenv("UCF_NSPLIT"); return e ? std::atoi(e) : 0; }();
+        const int force_split = env.nsplit;
         int lsplit = 0;
         while (lsplit < 1 && ((long long)nwork << lsplit) < 8LL * 256 * 4 * 6) lsplit++;
         if (force_split > 0) { lsplit = 0; while ((1 << (lsplit + 1)) <= force_split && lsplit < 3) lsplit++; }
@@ -2495,8 +2503,7 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
         // items (2 or 4 parts, or 10 240 items: the same within 0.2 %) -- a small gain: a wave on an emptying SIMD does
         // speed up enough to hide most of the quantisation of a launch into rounds.  Bit-neutral like every cut
         // (test_results_do_not_depend_on_how_work_items_are_cut).
-        static const int tail_ls_env = [] { const char* e = std::getenv("UCF_TAIL_LSPLIT"); return e ? std::atoi(e) : -1; }();
-        static const int tail_items_env = [] { const char* e = std::getenv("UCF_TAIL_ITEMS"); return e ? std::atoi(e) : -1; }();
+        const int tail_ls_env = env.tail_lsplit, tail_items_env = env.tail_items;
         int ltail = tail_ls_env >= 0 ? tail_ls_env : UCF_TAIL_LSPLIT_DEFAULT;
         if (ltail > 3) ltail = 3;
         while (ltail > 0 && (1 << ltail) > dp.nacc + 1) ltail--;
@@ -2512,7 +2519,7 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
         // persistent grid: at most 8 workgroups per CU (more than any register / LDS budget admits; the ones that do not fit
         // start when others have finished and find the counter exhausted).  UCF_PERSIST=0 (diagnostic): one workgroup per
         // UCF_IWPB work units, as before round 3's last pass
-        static const bool persist = [] { const char* e = std::getenv("UCF_PERSIST"); return !e || *e != '0'; }();
+        const bool persist = env.persist;
         const long long nwg = (nworkw + UCF_IWPB - 1) / UCF_IWPB;
         const dim3 igrid((unsigned)((persist && nwg > 256 * 8) ? 256 * 8 : nwg)), iblock(UCF_WAVE * UCF_IWPB);
         int* const d_wcount = d_ndone + 2 * (size_t)nwork + 2 + (size_t)nwork * dp.nz;      // behind the deferred list (finish_kernel)
@@ -2539,7 +2546,7 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
             }
 #undef UCF_LAUNCH_LT
         }
-        static const bool nzc2_on = [] { const char* e = std::getenv("UCF_NZC2"); return !e || *e != '0'; }();      // diagnostic: 0 = off
+        const bool nzc2_on = env.nzc2;      // diagnostic: 0 = off
 #define UCF_LAUNCH_I4(F, W, FO, L3, NZC, L1, NF)                                                                     \
     do {                                                                                                       \
         const size_t ilds = ((size_t)((NZC) ? dp.R : dp.R + 1) * dp.nz * UCF_WAVE * sizeof(lds_c)) * UCF_IWPB + UCF_SC_ENTRIES * sizeof(lds_c); \
@@ -2580,8 +2587,7 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
         // neither screen term folds (d > 0 and l < b: the usual partially penetrating well) -- known at compile time in an
         // instantiation of its own (NOFOLD, ucf_fastpath.h); a plan that folds exactly one term, and a parameter batch with
         // such a plan or a fully penetrating one in it, run the general one.  UCF_NOFOLD=0 (diagnostic): always the general one
-        static const bool nofold_on = [] { const char* e = std::getenv("UCF_NOFOLD"); return !e || *e != '0'; }();
-        const bool nofold = nofold_on && !dp.any_fold;
+        const bool nofold = env.nofold && !dp.any_fold;
 #define UCF_LAUNCH_UNF_(F, W, NF)                                                                              \
     do {                                                                                                       \
         if (lay3) UCF_LAUNCH_I3(F, W, false, true, true, NF);                                                  \
@@ -2615,7 +2621,7 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
                 // footprint admits them.  Round 3, C2: 35.8 / 34.8 / 34.8 ms at 4 / 5 / 6 waves -- the sixth wave buys nothing
                 // any more and costs 16 more spilled registers per item (2 GB of scratch traffic per sweep); the 1/8 shard
                 // runs 5.29 against 5.33 ms.  UCF_FOLD_WAVES_RT (diagnostic): force 4, 5 or 6.
-                static const int force_w = [] { const char* e = std::getenv("UCF_FOLD_WAVES_RT"); return e ? std::atoi(e) : 0; }();
+                const int force_w = env.fold_waves_rt;
                 if (force_w == 4) UCF_LAUNCH_FOLD(2, 4);
                 else if (force_w == 6 && wlds_eff * 24 <= 160 * 1024) UCF_LAUNCH_FOLD(2, 6);
                 else if (w5) UCF_LAUNCH_FOLD(2, UCF_FOLD_WAVES);
@@ -2624,7 +2630,7 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
             // the screen terms need the registers: 4 waves/SIMD (128 VGPRs, ~60 spilled; 5 waves: -31 %); with two or more
             // depths per launch 3 waves/SIMD and no spills are 3 % faster (C3), with one depth 5 % slower (C2pp)
             else {
-                static const int unf_w = [] { const char* e = std::getenv("UCF_UNFOLD_WAVES_RT"); return e ? std::atoi(e) : 0; }();   // diagnostic: 3 or 4
+                const int unf_w = env.unfold_waves_rt;      // diagnostic: 3 or 4
                 if (unf_w == 3 || (unf_w != 4 && dp.nz >= 2 && !nzc2)) UCF_LAUNCH_UNF(2, 3);
                 else UCF_LAUNCH_UNF(2, UCF_UNFOLD_WAVES);
             }
@@ -2670,10 +2676,10 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
         // tails of the completed items.  nacc <= UCF_WYNN_REGS: epsilon table in registers, LDS only for the level sums
         // and the Neville column; else the widest scratch part that still leaves 4 waves per CU (measured on C2:
         // 4.8 / 3.6 / 3.1 ms for parts of 16 / 32 / 64 lanes)
-        const bool wreg = dp.nacc <= UCF_WYNN_REGS && !ucf_finish_part;
+        const bool wreg = dp.nacc <= UCF_WYNN_REGS && !env.finish_part;
         const size_t scols = wreg ? (size_t)dp.R : (size_t)(2 * dp.nacc > dp.R ? 2 * dp.nacc : dp.R);
         auto flds = [&](int part) { return ((size_t)dp.R * dp.nz * UCF_WAVE + scols * part) * sizeof(lds_c); };
-        int part = ucf_finish_part;
+        int part = env.finish_part;
         if (part != 16 && part != 32 && part != 64) part = (flds(64) <= 40 * 1024) ? 64 : (flds(32) <= 40 * 1024) ? 32 : 16;
         const size_t fl = flds(part);
         if (fl > 160 * 1024) return UCF_ERR_UNSUPPORTED;
@@ -2735,58 +2741,48 @@ static int launch_transform_(const ucf_dev_params& dp, int nwork, int per_point,
     return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
 }
 
-// d_params != NULL: parameter-batched launch (per-point layouts of the fast flavour only), plan k owns points
-// [k ppp, (k+1) ppp) and reads d_params[k]; dp is plan 0's block
+// L.params != NULL: parameter-batched launch (per-point layouts of the fast flavour only), plan k owns points
+// [k ppp, (k+1) ppp) and reads L.params[k]; L.dp is plan 0's block
 template <int LAYOUT>
-static int launch_transform(const ucf_dev_params& dp, int nwork, int per_point, int nr, int nsv, int svmin, const double* d_tD,
-                            const double* d_rD, const int* d_sv, const double* d_tab, double* d_h, double* d_dh,
-                            ucf_stats* d_stats, int nt, int ir0, int nrc, double* d_totlap, double* d_glscr,
-                            double* d_state, int* d_ndone, void* stream, ucf_timers* tm,
-                            const ucf_dev_params* d_params = nullptr, int ppp = 1, int pbase = 0)
+static int launch_transform(const ucf_launch& L, int nwork)
 {
 #if UCF_FAST
-    if (d_params) {
+    if (L.params) {
         // parameter batches run in the per-point layouts 0, 2, 3 (the lane = time translation unit instantiates none of it)
         if constexpr (LAYOUT == 1) return UCF_ERR_BAD_ARGUMENT;
-        else {
-            if (!per_point) return UCF_ERR_BAD_ARGUMENT;
-            return launch_transform_<LAYOUT, true>(dp, nwork, per_point, nr, nsv, svmin, d_tD, d_rD, d_sv, d_tab, d_h, d_dh, d_stats, nt,
-                                                   ir0, nrc, d_totlap, d_glscr, d_state, d_ndone, stream, tm, d_params, ppp, pbase);
-        }
+        else return L.per_point ? launch_transform_<LAYOUT, true>(L, nwork) : UCF_ERR_BAD_ARGUMENT;
     }
 #else
-    if (d_params) return UCF_ERR_UNSUPPORTED;
+    if (L.params) return UCF_ERR_UNSUPPORTED;
 #endif
-    return launch_transform_<LAYOUT, false>(dp, nwork, per_point, nr, nsv, svmin, d_tD, d_rD, d_sv, d_tab, d_h, d_dh, d_stats, nt, ir0, nrc,
-                                            d_totlap, d_glscr, d_state, d_ndone, stream, tm, nullptr, 1, 0);
+    return launch_transform_<LAYOUT, false>(L, nwork);
 }
 
 #if UCF_TU_HAS(0)
 // LAYOUT 0 (lane = Laplace sample, de Hoog in the same wave)
-int launch_points(const ucf_dev_params& dp, int npts, int per_point, int nr, int nsv, int svmin, const double* d_tD,
-                  const double* d_rD, const int* d_sv, const double* d_tab, double* d_h, double* d_dh,
-                  ucf_stats* d_stats, void* stream, double* d_glscr, double* d_state, int* d_ndone,
-                  const ucf_dev_params* d_params, int ppp, int pbase, double* d_dbg_totlap)
+int launch_points(const ucf_launch& L)
 {
-    return launch_transform<0>(dp, npts, per_point, nr, nsv, svmin, d_tD, d_rD, d_sv, d_tab, d_h, d_dh, d_stats, 0, 0, 0,
-                               d_dbg_totlap, d_glscr, d_state, d_ndone, stream, nullptr, d_params, ppp, pbase);
+    ucf_launch T = L;
+    T.nt = T.ir0 = T.nrc = 0; T.tm = nullptr;      // a point list has neither
+    return launch_transform<0>(T, L.npts);
 }
 
 #endif
 
 #if UCF_TU_HAS(1)
 // LAYOUT 1 (lane = time): transform kernel(s) over (radius chunk x time tiles x Laplace index), then de Hoog
-int launch_grid_transposed(const ucf_dev_params& dp, int nt, int nr, int ir0, int nrc, int svmin, const double* d_tD,
-                           const double* d_rD, const double* d_tab, double* d_totlap, double* d_h, double* d_dh,
-                           ucf_stats* d_stats, void* stream, ucf_timers* tm, double* d_glscr, double* d_state,
-                           int* d_ndone)
+int launch_grid_transposed(const ucf_launch& L)
 {
-    hipStream_t s = (hipStream_t)stream;
+    const ucf_dev_params& dp = *L.dp;
+    const int nt = L.nt, nr = L.nr, ir0 = L.ir0, nrc = L.nrc;
+    ucf_timers* tm = L.tm;
+    hipStream_t s = (hipStream_t)L.stream;
     const int ntiles = (nt + UCF_WAVE - 1) / UCF_WAVE;
     const long long nwork = (long long)nrc * ntiles * dp.np;
     if (nwork > 0x7fffffffLL) return UCF_ERR_BAD_ARGUMENT;
-    int rc = launch_transform<1>(dp, (int)nwork, 0, nr, 1, svmin, d_tD, d_rD, nullptr, d_tab, d_h, d_dh, d_stats, nt, ir0, nrc,
-                                 d_totlap, d_glscr, d_state, d_ndone, stream, tm);
+    ucf_launch T = L;         // one split index for all times, no parameter batch
+    T.per_point = 0; T.nsv = 1; T.sv = nullptr; T.params = nullptr;
+    int rc = launch_transform<1>(T, (int)nwork);
     if (rc) return rc;
     const long long ntl = (long long)nrc * ((nt + UCF_DH_TILE - 1) / UCF_DH_TILE);
     const size_t dlds = 2 * (size_t)dp.np * (UCF_DH_TILE + 1) * sizeof(lds_c) + 2 * UCF_DH_TILE * sizeof(int);
@@ -2795,10 +2791,10 @@ int launch_grid_transposed(const ucf_dev_params& dp, int nt, int nr, int ir0, in
     const dim3 dgrid((unsigned)(ntl > 0x7fffffffLL ? 0x7fffffff : ntl));
     if (dp.np <= UCF_WAVE) {
         ucf_tm_mark(tm, UCF_STR(UCF_NS) "::dehoog_tiles_kernel<1, false>", s);
-        hipLaunchKernelGGL((dehoog_tiles_kernel<1, false>), dgrid, dim3(UCF_WAVE), dlds, s, dp, nt, nr, ir0, nrc, d_tD, (const double2*)d_totlap, d_h, d_dh, d_stats);
+        hipLaunchKernelGGL((dehoog_tiles_kernel<1, false>), dgrid, dim3(UCF_WAVE), dlds, s, dp, nt, nr, ir0, nrc, L.tD, (const double2*)L.totlap, L.h, L.dh, L.stats);
     } else {
         ucf_tm_mark(tm, UCF_STR(UCF_NS) "::dehoog_tiles_kernel<1, true>", s);
-        hipLaunchKernelGGL((dehoog_tiles_kernel<1, true>), dgrid, dim3(UCF_WAVE), dlds, s, dp, nt, nr, ir0, nrc, d_tD, (const double2*)d_totlap, d_h, d_dh, d_stats);
+        hipLaunchKernelGGL((dehoog_tiles_kernel<1, true>), dgrid, dim3(UCF_WAVE), dlds, s, dp, nt, nr, ir0, nrc, L.tD, (const double2*)L.totlap, L.h, L.dh, L.stats);
     }
     ucf_tm_close(tm, s);
     return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
@@ -2809,25 +2805,27 @@ int launch_grid_transposed(const ucf_dev_params& dp, int nt, int nr, int ir0, in
 #if UCF_TU_HAS(3)
 // LAYOUT 3 (lane = point of an arbitrary list, 2M+1 <= 64): npts points, ppp of them per plan (npts for one plan);
 // transform over (64-point tiles x Laplace index), then the tiled de Hoog with the points in the place of the times
-int launch_points_lanes(const ucf_dev_params& dp, int npts, int ppp, const double* d_tD, const double* d_rD, const int* d_sv,
-                        const double* d_tab, double* d_totlap, double* d_h, double* d_dh, ucf_stats* d_stats, void* stream,
-                        double* d_state, int* d_ndone, const ucf_dev_params* d_params, int pbase)
+int launch_points_lanes(const ucf_launch& L)
 {
-    hipStream_t s = (hipStream_t)stream;
+    const ucf_dev_params& dp = *L.dp;
+    const int npts = L.npts, ppp = L.params ? L.ppp : npts;
+    hipStream_t s = (hipStream_t)L.stream;
     if (ppp < 1 || npts % ppp != 0 || dp.np > UCF_WAVE) return UCF_ERR_BAD_ARGUMENT;
     const long long nwork = (long long)(npts / ppp) * ((ppp + UCF_WAVE - 1) / UCF_WAVE) * dp.np;
     if (nwork > 0x7fffffffLL) return UCF_ERR_BAD_ARGUMENT;
-    int rc = launch_transform<3>(dp, (int)nwork, 1, ppp, 1, 0, d_tD, d_rD, d_sv, d_tab, d_h, d_dh, d_stats, npts, 0, 0, d_totlap, nullptr,
-                                 d_state, d_ndone, stream, nullptr, d_params, ppp, pbase);
+    ucf_launch T = L;         // the transform sees a plan's points as the radii of one row, the launch's points as its times
+    T.per_point = 1; T.nr = ppp; T.ppp = ppp; T.nsv = 1; T.svmin = 0; T.nt = npts; T.ir0 = T.nrc = 0;
+    T.glscr = nullptr; T.tm = nullptr;
+    int rc = launch_transform<3>(T, (int)nwork);
     if (rc) return rc;
     const long long ntl = (npts + UCF_DH_TILE - 1) / UCF_DH_TILE;
     const size_t dlds = 2 * (size_t)dp.np * (UCF_DH_TILE + 1) * sizeof(lds_c) + 2 * UCF_DH_TILE * sizeof(int);
     if (dp.np <= UCF_WAVE)
-        hipLaunchKernelGGL((dehoog_tiles_kernel<3, false>), dim3((unsigned)ntl), dim3(UCF_WAVE), dlds, s, dp, npts, 1, 0, 1, d_tD,
-                           (const double2*)d_totlap, d_h, d_dh, d_stats);
+        hipLaunchKernelGGL((dehoog_tiles_kernel<3, false>), dim3((unsigned)ntl), dim3(UCF_WAVE), dlds, s, dp, npts, 1, 0, 1, L.tD,
+                           (const double2*)L.totlap, L.h, L.dh, L.stats);
     else
-        hipLaunchKernelGGL((dehoog_tiles_kernel<3, true>), dim3((unsigned)ntl), dim3(UCF_WAVE), dlds, s, dp, npts, 1, 0, 1, d_tD,
-                           (const double2*)d_totlap, d_h, d_dh, d_stats);
+        hipLaunchKernelGGL((dehoog_tiles_kernel<3, true>), dim3((unsigned)ntl), dim3(UCF_WAVE), dlds, s, dp, npts, 1, 0, 1, L.tD,
+                           (const double2*)L.totlap, L.h, L.dh, L.stats);
     return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
 }
 #endif
@@ -2835,20 +2833,20 @@ int launch_points_lanes(const ucf_dev_params& dp, int npts, int ppp, const doubl
 #if UCF_TU_HAS(2)
 // LAYOUT 2 (2M+1 > 64): (point, 64-sample chunk) work items write the transform, dehoog_points_kernel inverts.
 // Same addressing as launch_points; d_h/d_dh/d_totlap point at this chunk of points.
-int launch_points_chunked(const ucf_dev_params& dp, int npts, int per_point, int nr, int nsv, int svmin, const double* d_tD,
-                          const double* d_rD, const int* d_sv, const double* d_tab, double* d_totlap, double* d_h,
-                          double* d_dh, ucf_stats* d_stats, void* stream, double* d_glscr, double* d_state, int* d_ndone,
-                          const ucf_dev_params* d_params, int ppp, int pbase)
+int launch_points_chunked(const ucf_launch& L)
 {
-    hipStream_t s = (hipStream_t)stream;
+    const ucf_dev_params& dp = *L.dp;
+    const int npts = L.npts;
+    hipStream_t s = (hipStream_t)L.stream;
     const int nchunk = (dp.np + UCF_WAVE - 1) / UCF_WAVE;
     const long long nwork = (long long)npts * nchunk;
     if (nwork > 0x7fffffffLL) return UCF_ERR_BAD_ARGUMENT;
-    int rc = launch_transform<2>(dp, (int)nwork, per_point, nr, nsv, svmin, d_tD, d_rD, d_sv, d_tab, d_h, d_dh, d_stats, 0, 0, 0,
-                                 d_totlap, d_glscr, d_state, d_ndone, stream, nullptr, d_params, ppp, pbase);
+    ucf_launch T = L;
+    T.nt = T.ir0 = T.nrc = 0; T.tm = nullptr;      // a point list has neither
+    int rc = launch_transform<2>(T, (int)nwork);
     if (rc) return rc;
-    hipLaunchKernelGGL(dehoog_points_kernel, dim3((unsigned)npts), dim3(UCF_WAVE), 0, s, dp, (long long)npts, 1, per_point, nr, 0, 0, d_tD,
-                       (const double2*)d_totlap, d_h, d_dh, d_stats);
+    hipLaunchKernelGGL(dehoog_points_kernel, dim3((unsigned)npts), dim3(UCF_WAVE), 0, s, dp, (long long)npts, 1, L.per_point, L.nr, 0, 0, L.tD,
+                       (const double2*)L.totlap, L.h, L.dh, L.stats);
     return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
 }
 

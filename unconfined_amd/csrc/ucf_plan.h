@@ -1,16 +1,13 @@
 // ucf_plan.h -- internal structures shared by the host API and the kernels.
 #pragma once
 #include "../../include/ucf.h"
+#include "ucf_env.h"
 #include <cstdio>
-#include <cstdlib>
 #include <mutex>
 #include <vector>
 
 #define UCF_WAVE 64
 #define UCF_MAX_R 16
-extern int ucf_grid_slots;     /* workgroups per launch (grid-stride over the work items); each owns a scratch slot */
-extern int ucf_finish_part;   /* diagnostic: lanes per scratch part in finish_kernel (16/32/64; 0 = choose from the LDS footprint) */
-#define UCF_GRID_SLOTS ucf_grid_slots
 
 // Everything a kernel needs, passed by value as one kernel argument (lives in
 // SGPRs / the scalar cache: it is wave-uniform).  Table pointers are device
@@ -75,8 +72,7 @@ static inline void ucf_tm_mark(ucf_timers* tm, const char* name, void* stream)
 {
     // UCF_TRACE_LAUNCHES=1 (diagnostic): wait for everything launched so far and name the kernel that comes next on stderr,
     // so that the last line before a device fault names the kernel that faulted
-    static const bool trace = [] { const char* e = std::getenv("UCF_TRACE_LAUNCHES"); return e && *e && *e != '0'; }();
-    if (trace) {
+    if (ucf_env_get().trace_launches) {
         const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
         std::fprintf(stderr, "[ucf] stream %s; next: %s\n", e == hipSuccess ? "clean" : hipGetErrorString(e), name);
         std::fflush(stderr);
@@ -156,60 +152,63 @@ struct ucf_plan {
     void* own_stream = nullptr;
 };
 
-// launchers implemented in ucf_kernels.hip (one set per build flavour)
+// One launch sequence: everything the layout launchers and launch_transform_ (ucf_device.h) read and write.  A caller
+// fills one and, inside its chunk loops, moves only the bases and counts.
+struct ucf_launch {
+    const ucf_dev_params* dp = nullptr;    // the parameter block (plan 0's in a parameter batch)
+    // a point list has npts points (per_point = 1: tD, rD, sv per point; 0: point = it * nr + ir of a grid walked point by
+    // point); the lane = time layout has nt times x radii [ir0, ir0 + nrc) of nr
+    int npts = 0, per_point = 0, nt = 0, nr = 0, ir0 = 0, nrc = 0;
+    int nsv = 1, svmin = 0;                // rows of the abscissa table: row = radius * nsv + (sv - svmin)
+    const double *tD = nullptr, *rD = nullptr, *tab = nullptr;      // tab: the abscissa table
+    const int* sv = nullptr;
+    double *h = nullptr, *dh = nullptr;
+    ucf_stats* stats = nullptr;
+    // workspace.  totlap: the accelerated transform (lane layout 0 keeps none: NULL, or the buffer ucf_debug_stages lends)
+    double *totlap = nullptr, *glscr = nullptr, *state = nullptr;
+    int* ndone = nullptr;
+    void* stream = nullptr;
+    ucf_timers* tm = nullptr;              // (lane = time only) brackets the kernels with events
+    // parameter batch (fast flavour, per-point layouts): point q of the launch reads params[(pbase + q) / ppp]
+    const ucf_dev_params* params = nullptr;
+    int ppp = 1, pbase = 0;
+};
+
+// launchers implemented in ucf_kernels_*.hip (one set per build flavour)
 namespace ucf_faithful {
 // abscissa tables (shared by both flavours): tab[row][nabs] of (a, a*J0(a*rD))
 int launch_abscissae(const ucf_dev_params& dp, int nrows, int per_point, int nsv, int svmin, const double* d_rD,
                      const int* d_sv, double* d_tab, void* stream);
 int launch_expand_grid(int nt, int nr, const double* d_tD, const int* d_sv, const double* d_rD, double* d_tDp, double* d_rDp,
                        int* d_svp, void* stream);
-int launch_points(const ucf_dev_params& dp, int npts, int per_point, int nr, int nsv, int svmin, const double* d_tD,
-                  const double* d_rD, const int* d_sv, const double* d_tab, double* d_h, double* d_dh,
-                  ucf_stats* d_stats, void* stream, double* d_glscr, double* d_state, int* d_ndone,
-                  const ucf_dev_params* d_params = nullptr, int ppp = 1, int pbase = 0, double* d_dbg_totlap = nullptr);
-int launch_points_chunked(const ucf_dev_params& dp, int npts, int per_point, int nr, int nsv, int svmin, const double* d_tD,
-                          const double* d_rD, const int* d_sv, const double* d_tab, double* d_totlap, double* d_h,
-                          double* d_dh, ucf_stats* d_stats, void* stream, double* d_glscr, double* d_state, int* d_ndone,
-                  const ucf_dev_params* d_params = nullptr, int ppp = 1, int pbase = 0);
-int launch_grid_transposed(const ucf_dev_params& dp, int nt, int nr, int ir0, int nrc, int svmin, const double* d_tD,
-                           const double* d_rD, const double* d_tab, double* d_totlap, double* d_h, double* d_dh,
-                           ucf_stats* d_stats, void* stream, ucf_timers* tm, double* d_glscr, double* d_state, int* d_ndone);
-int launch_points_lanes(const ucf_dev_params& dp, int npts, int ppp, const double* d_tD, const double* d_rD, const int* d_sv,
-                        const double* d_tab, double* d_totlap, double* d_h, double* d_dh, ucf_stats* d_stats, void* stream,
-                        double* d_state, int* d_ndone, const ucf_dev_params* d_params = nullptr, int pbase = 0);
-int launch_samples(const ucf_dev_params& dp, int n_a, const double* d_a, double rD, const double* d_p, double* d_fp,
-                   void* stream);
 int launch_bessel(int n, const double* d_z, double* d_k, int* d_ierr, void* stream);
-size_t state_bytes_per_item(const ucf_dev_params& dp);
 int launch_dehoog(int n, int M, double alpha, double logtol, const double* d_t, const double* d_tee,
                   const double* d_fp, double* d_ft, void* stream);
 int launch_wynn(int n, int nterms, const double* d_series, double* d_acc, int* d_status, void* stream);
 int launch_extrap(int n, int R, const double* d_x, const double* d_y, double* d_out, void* stream);
 int launch_debug_gather(const ucf_dev_params& dp, int layout, int nwork, int per_point, int nr, int nt, int ir0, const double* d_state,
                         const int* d_ndone, double* d_out_state, int* d_out_ndone, void* stream);
+}
+// what both flavours define, entry by entry the ucf_flavour table of ucf_api.cpp.  state_bytes_per_item: bytes of integrate
+// kernel -> finish / point kernel state per work item (0: the model has no integrate kernel)
+namespace ucf_faithful {
+int launch_points(const ucf_launch& L);             // lane layout 0
+int launch_grid_transposed(const ucf_launch& L);    // 1
+int launch_points_chunked(const ucf_launch& L);     // 2
+int launch_points_lanes(const ucf_launch& L);       // 3
+int launch_samples(const ucf_dev_params& dp, int n_a, const double* d_a, double rD, const double* d_p, double* d_fp, void* stream);
+size_t state_bytes_per_item(const ucf_dev_params& dp);
 int launch_wynn_regs(int n, int nterms, const double* d_series, double* d_acc, int* d_status, void* stream);
 int launch_dehoog_tiles_hook(const ucf_dev_params& dp, int n, const double* d_tD, const double* d_totlap, double* d_h, double* d_dh, void* stream);
 }
 namespace ucf_fast {
-int launch_points_chunked(const ucf_dev_params& dp, int npts, int per_point, int nr, int nsv, int svmin, const double* d_tD,
-                          const double* d_rD, const int* d_sv, const double* d_tab, double* d_totlap, double* d_h,
-                          double* d_dh, ucf_stats* d_stats, void* stream, double* d_glscr, double* d_state, int* d_ndone,
-                  const ucf_dev_params* d_params = nullptr, int ppp = 1, int pbase = 0);
-int launch_grid_transposed(const ucf_dev_params& dp, int nt, int nr, int ir0, int nrc, int svmin, const double* d_tD,
-                           const double* d_rD, const double* d_tab, double* d_totlap, double* d_h, double* d_dh,
-                           ucf_stats* d_stats, void* stream, ucf_timers* tm, double* d_glscr, double* d_state, int* d_ndone);
-int launch_points(const ucf_dev_params& dp, int npts, int per_point, int nr, int nsv, int svmin, const double* d_tD,
-                  const double* d_rD, const int* d_sv, const double* d_tab, double* d_h, double* d_dh,
-                  ucf_stats* d_stats, void* stream, double* d_glscr, double* d_state, int* d_ndone,
-                  const ucf_dev_params* d_params = nullptr, int ppp = 1, int pbase = 0, double* d_dbg_totlap = nullptr);
-int launch_points_lanes(const ucf_dev_params& dp, int npts, int ppp, const double* d_tD, const double* d_rD, const int* d_sv,
-                        const double* d_tab, double* d_totlap, double* d_h, double* d_dh, ucf_stats* d_stats, void* stream,
-                        double* d_state, int* d_ndone, const ucf_dev_params* d_params = nullptr, int pbase = 0);
-int launch_samples(const ucf_dev_params& dp, int n_a, const double* d_a, double rD, const double* d_p, double* d_fp,
-                   void* stream);
-// bytes of integrate_kernel -> point_kernel state per work item (0 where the flavour / model has no integrate_kernel)
+int launch_points(const ucf_launch& L);             // lane layout 0
+int launch_grid_transposed(const ucf_launch& L);    // 1
+int launch_points_chunked(const ucf_launch& L);     // 2
+int launch_points_lanes(const ucf_launch& L);       // 3
+int launch_samples(const ucf_dev_params& dp, int n_a, const double* d_a, double rD, const double* d_p, double* d_fp, void* stream);
 size_t state_bytes_per_item(const ucf_dev_params& dp);
-size_t lt_table_bytes(const ucf_dev_params& dp, size_t rows);
 int launch_wynn_regs(int n, int nterms, const double* d_series, double* d_acc, int* d_status, void* stream);
 int launch_dehoog_tiles_hook(const ucf_dev_params& dp, int n, const double* d_tD, const double* d_totlap, double* d_h, double* d_dh, void* stream);
+size_t lt_table_bytes(const ucf_dev_params& dp, size_t rows);      // the lapTime table behind the state (laptime_kernel)
 }
