@@ -386,6 +386,63 @@ int ucf_fit_network_eval_counts(int nwell, const int* well_nz, int nobs, const d
  * average (what its average was formed from).  cap < n: UCF_ERR_BAD_ARGUMENT. */
 int ucf_fit_debug_h(ucf_fit* fit, int plan, int i, int cap, double* h, int* n);
 
+/* ---- well fields: the drawdown of several pumping wells -- wells that start at different times, image wells for a river or an
+ * outcrop -- is the sum over wells of q_j h(t - t0_j, |x - x_j|, z).  All wells share the plan's aquifer, well geometry and
+ * time behaviour; they differ in position (xw, yw), rate factor qw (times the plan's Q; negative: injection or a constant-head
+ * image; never 0) and start time t0w >= 0.  A map of a field is a product grid per group of wells that share a start time:
+ * times after the start x distinct distances, which is what ucf_drawdown_grid_device is built for.  A field object owns the
+ * geometry and the device buffers; h and dh of the groups stay in device memory, one small kernel forms the sums, and only the
+ * superposed s, ds cross the bus.  All inputs are dimensional as for ucf_drawdown_multi, z up from the aquifer base.
+ *   groups       wells with bitwise-equal t0w form a group; groups in ascending t0, wells inside a group in the caller's order.
+ *   launch       per group g ONE call of the grid path in the plan's current flavour with exactly the arrays that
+ *                ucf_field_group states:  k0 = first k with t[k] > t0_g, nt_g = nt - k0;  tD[i] = (t[k0+i] - t0_g) / Tc;
+ *                sv = ucf_split_vector(tD), checked as ucf_drawdown_grid checks it;  rD = the distinct values (bitwise) of
+ *                sqrt(dx dx + dy dy) / Lc over (location, well of g), ascending;  col[i][j] = index into rD (-1: well j is not
+ *                in g);  tfac[i] = t[k0+i] / (t[k0+i] - t0_g).  Host code is compiled without FMA contraction: every
+ *                operation above is rounded on its own.
+ *   superposition field_superpose_kernel, one thread per output (k, i, z), z fastest; acc = +0.0, then for j = 0..nwell-1 in the
+ *                caller's order, skipping wells whose group has k < k0:
+ *                    s :  acc = acc + qw[j] * h_g[k-k0][col][z]        ds :  acc = acc + qw[j] * (tfac[k-k0] * dh_g[k-k0][col][z])
+ *                (the library's dh is t dh/dt in the well's OWN time, so the second sum is t ds/dt), both times Hc at the end
+ *                unless dimensionless != 0.  No scrubbing: non-finite values and the Wynn sentinel propagate as the plan
+ *                produced them.  No atomics, fixed order: a call repeated gives the same bits.
+ * A field is used by one host thread at a time; its buffers live on the device of the plan of its first ucf_field_drawdown. */
+typedef struct ucf_field ucf_field;
+/* Host arithmetic, no GPU.  UCF_ERR_BAD_ARGUMENT (ucf_last_error names the offender): a size < 1, a NULL array, a number that is
+ * not finite, t not strictly increasing or not > 0, t0w < 0, qw == 0. */
+int ucf_field_create(int nwell, const double* xw, const double* yw, const double* qw, const double* t0w,
+                     int nloc, const double* x, const double* y, int nt, const double* t, ucf_field** out);
+void ucf_field_destroy(ucf_field* field);
+int ucf_field_group_count(const ucf_field* field, int* ngroups);
+/* Host only: what group g launches under `plan` (arrays sized for the worst case; any output may be NULL).  nt_g may be 0
+ * (no time of the field lies after the group's start: nothing is launched, nr_g, rD and col are still stated).
+ * UCF_ERR_BAD_ARGUMENT: g outside 0..ngroups-1; a distance below the plan's rw -- the location is inside a well bore --
+ * naming the (location, well) pair; nt_g * nr_g > 2^31 - 1; a split index the grid entry would refuse. */
+int ucf_field_group(const ucf_field* field, const ucf_plan* plan, int g, int* k0, int* nt_g, double* tD /*[nt]*/, int* sv /*[nt]*/,
+                    int* nr_g, double* rD /*[nloc*nwell]*/, int* col /*[nloc][nwell], -1 = well not in g*/,
+                    double* tfac /*[nt]*/);
+/* the same from a parameter set alone (no plan, no GPU): P is checked and non-dimensionalised as by ucf_nondimensionalise,
+ * with its statuses; a plan made from P states the same arrays bit for bit */
+int ucf_field_group_from_params(const ucf_field* field, const ucf_params* P, int g, int* k0, int* nt_g, double* tD, int* sv,
+                                int* nr_g, double* rD, int* col, double* tfac);
+/* s, ds [nt][nloc][nz]: drawdown and its logarithmic time derivative t ds/dt, dimensional (x Hc) unless dimensionless != 0;
+ * an output at a time that no well's start precedes is +0.0.  zD = z / Lc and zLay are formed as in ucf_drawdown_multi.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT: NULL field, s, ds or z, nz < 1, a z that is not finite, what
+ * ucf_field_group refuses for any group), then UCF_ERR_NO_DEVICE as for every compute entry.  h_g, dh_g [nt_g][nr_g][nz] of
+ * every group live in buffers of the field that grow when needed and are kept: a repeated call of the same size allocates
+ * nothing.  stats: summed over the groups. */
+int ucf_field_drawdown(ucf_field* field, ucf_plan* plan, int nz, const double* z, int dimensionless,
+                       double* s, double* ds /*[nt][nloc][nz]*/, ucf_stats* stats /*NULL ok*/);
+/* device allocations made so far by the field (the plan's own workspaces count in ucf_plan_alloc_count) */
+long long ucf_field_alloc_count(const ucf_field* field);
+/* Host only: the nwell real wells followed by their mirror images in the straight line a x + b y = c (xo, yo, qo, t0o
+ * [2 nwell]).  An image has q = +q for a no-flow boundary (kind 0), -q for a constant-head boundary (kind 1), and the t0 of its
+ * real well.  One boundary only (two parallel boundaries need an infinite image series).  UCF_ERR_BAD_ARGUMENT: a = b = 0, a
+ * number that is not finite, kind outside 0..1, a well on the line. */
+int ucf_field_images(int nwell, const double* xw, const double* yw, const double* qw, const double* t0w,
+                     double a, double b, double c, int kind /*0 no-flow, 1 constant head*/,
+                     double* xo, double* yo, double* qo, double* t0o /*[2*nwell]*/);
+
 /* driver.f90:234-243 (quirk Q2: not a textbook trapezoid) */
 int ucf_screen_average(int npts, int zOrd, const double* h, double* havg);
 

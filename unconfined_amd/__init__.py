@@ -1,0 +1,1 @@
+from .field import WellField, images  # noqa: F401

@@ -1,0 +1,113 @@
+"""Well fields over the C ABI (ucf_field_* of include/ucf.h): the drawdown of several pumping wells -- wells that start at
+different times, image wells for a river or an outcrop -- as the sum over wells of q_j h(t - t0_j, |x - x_j|, z).  Per group
+of wells that share a start time the library runs ONE product grid (times after the start x distinct distances) through
+``ucf_drawdown_grid_device``, keeps h and dh on the GPU and forms the sums there; this module only marshals arrays.
+
+    wells = images([(0.0, 0.0, 1.0, 0.0)], line=(1.0, 0.0, 40.0), kind="constant_head")      # (x, y, q, t0) per well
+    field = WellField(wells, locations=[(10.0, 0.0), (40.0, 5.0)], times=[1.0, 10.0, 100.0])
+    s, ds = field.drawdown(plan, z=[145.7, 100.0])                                            # [nt, nloc, nz] each
+
+All wells share the plan's aquifer, well geometry and time behaviour; q multiplies the plan's Q (negative: injection).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import lib as _libmod
+from .abi import UcfParams, UcfStats
+
+KINDS = {"no_flow": 0, "constant_head": 1, 0: 0, 1: 1}
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _wells(wells):
+    w = np.atleast_2d(_f64(wells))
+    if w.ndim != 2 or w.shape[1] != 4:
+        raise ValueError("wells: one (x, y, q, t0) per well")
+    return w
+
+
+def images(wells, line, kind):
+    """the wells (x, y, q, t0) followed by their mirror images in the line a x + b y = c (``line`` = (a, b, c)); an image has
+    q = +q for ``kind`` 'no_flow' and -q for 'constant_head' and the t0 of its real well (ucf_field_images; no GPU).
+    Returns an array [2 nwell, 4]."""
+    w = _wells(wells)
+    n = len(w)
+    a, b, c = (float(v) for v in line)
+    out = [np.zeros(2 * n) for _ in range(4)]
+    _libmod.check(_libmod.load().ucf_field_images(n, _f64(w[:, 0]), _f64(w[:, 1]), _f64(w[:, 2]), _f64(w[:, 3]), a, b, c, KINDS[kind],
+                                                  *out))
+    return np.stack(out, axis=1)
+
+
+class WellField:
+    """wells (x, y, q, t0), locations (x, y) and strictly increasing times, all dimensional"""
+
+    def __init__(self, wells, locations, times):
+        self._lib = _libmod.load()
+        self._h = C.c_void_p()
+        w = _wells(wells)
+        loc = np.atleast_2d(_f64(locations))
+        if loc.ndim != 2 or loc.shape[1] != 2:
+            raise ValueError("locations: one (x, y) per location")
+        t = np.atleast_1d(_f64(times))
+        self.nwell, self.nloc, self.nt = len(w), len(loc), len(t)
+        _libmod.check(self._lib.ucf_field_create(self.nwell, _f64(w[:, 0]), _f64(w[:, 1]), _f64(w[:, 2]), _f64(w[:, 3]), self.nloc,
+                                                 _f64(loc[:, 0]), _f64(loc[:, 1]), self.nt, t, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._lib.ucf_field_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def group_count(self) -> int:
+        n = C.c_int()
+        _libmod.check(self._lib.ucf_field_group_count(self._h, C.byref(n)))
+        return n.value
+
+    def groups(self, plan) -> list:
+        """what every group launches under ``plan`` (ucf_field_group; host arithmetic, no launch): a list of dicts with k0, tD,
+        sv, rD, col [nloc, nwell] (-1: the well is not in the group) and tfac.  ``plan`` may also be a parameter set
+        (``UcfParams``): the same arrays without a plan or a GPU (ucf_field_group_from_params)."""
+        out = []
+        for g in range(self.group_count()):
+            k0, nt_g, nr_g = C.c_int(), C.c_int(), C.c_int()
+            tD, tfac, sv = np.zeros(self.nt), np.zeros(self.nt), np.zeros(self.nt, np.int32)
+            rD, col = np.zeros(self.nloc * self.nwell), np.zeros((self.nloc, self.nwell), np.int32)
+            args = (g, C.byref(k0), C.byref(nt_g), tD, sv, C.byref(nr_g), rD, col, tfac)
+            if isinstance(plan, UcfParams):
+                _libmod.check(self._lib.ucf_field_group_from_params(self._h, C.byref(plan), *args))
+            else:
+                _libmod.check(self._lib.ucf_field_group(self._h, plan._h, *args))
+            n = nt_g.value
+            out.append({"k0": k0.value, "tD": tD[:n].copy(), "sv": sv[:n].copy(), "rD": rD[:nr_g.value].copy(), "col": col,
+                        "tfac": tfac[:n].copy()})
+        return out
+
+    def drawdown(self, plan, z, dimensionless: bool = False, with_stats: bool = False):
+        """s, ds of shape [nt, nloc, nz]: superposed drawdown and its logarithmic time derivative t ds/dt at the depths z (up
+        from the aquifer base), dimensional unless ``dimensionless``; in the plan's current flavour"""
+        z = np.atleast_1d(_f64(z))
+        s = np.zeros((self.nt, self.nloc, len(z)))
+        ds = np.zeros_like(s)
+        st = UcfStats()
+        _libmod.check(self._lib.ucf_field_drawdown(self._h, plan._h, len(z), z, 1 if dimensionless else 0, s, ds,
+                                                   C.byref(st) if with_stats else None))
+        if with_stats:
+            return s, ds, {k: getattr(st, k) for k, _ in UcfStats._fields_}
+        return s, ds
+
+    def alloc_count(self) -> int:
+        """device allocations made so far by the field"""
+        return int(self._lib.ucf_field_alloc_count(self._h))

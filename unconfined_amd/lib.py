@@ -38,6 +38,8 @@ EXPORTS = [
     "ucf_fit_perturb", "ucf_fit_solve_step", "ucf_fit_default_options", "ucf_fit_create", "ucf_fit_destroy", "ucf_fit_evaluate",
     "ucf_fit_lm", "ucf_fit_alloc_count",
     "ucf_fit_create_network", "ucf_fit_eval_counts", "ucf_fit_network_eval_counts", "ucf_fit_debug_h",
+    "ucf_field_create", "ucf_field_destroy", "ucf_field_group_count", "ucf_field_group", "ucf_field_group_from_params",
+    "ucf_field_drawdown", "ucf_field_alloc_count", "ucf_field_images",
 ]
 
 
@@ -140,6 +142,17 @@ def load() -> C.CDLL:
     lib.ucf_fit_eval_counts.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.ucf_fit_network_eval_counts.argtypes = [C.c_int, _ip, C.c_int, _dp, _ip, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
     lib.ucf_fit_debug_h.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]
+    lib.ucf_field_create.argtypes = [C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, C.POINTER(vp)]
+    lib.ucf_field_destroy.argtypes = [vp]
+    lib.ucf_field_destroy.restype = None
+    lib.ucf_field_group_count.argtypes = [vp, C.POINTER(C.c_int)]
+    _group_out = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _ip, C.POINTER(C.c_int), _dp, _ip, _dp]
+    lib.ucf_field_group.argtypes = [vp, vp] + _group_out
+    lib.ucf_field_group_from_params.argtypes = [vp, C.POINTER(UcfParams)] + _group_out
+    lib.ucf_field_drawdown.argtypes = [vp, vp, C.c_int, _dp, C.c_int, _dp, _dp, C.POINTER(UcfStats)]
+    lib.ucf_field_alloc_count.argtypes = [vp]
+    lib.ucf_field_alloc_count.restype = C.c_longlong
+    lib.ucf_field_images.argtypes = [C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp]
     _lib = lib
     return lib
 
