@@ -38,6 +38,15 @@ def test_library_exports_every_declared_symbol(so):
     assert so.ucf_version() == 100
 
 
+def test_library_keeps_its_host_helpers_to_itself(so):
+    # what the host sources share (namespace ucf_host, ucf_host.h) links between the objects and is not exported
+    out = subprocess.run(["nm", "-D", "--defined-only", "-C", ucflib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    names = [line.split(None, 2)[2] for line in out.splitlines() if len(line.split(None, 2)) == 3]
+    assert "ucf_version" in names and "ucf_drawdown_grid" in names, "nm lists no dynamic symbols"
+    leaked = [n for n in names if "ucf_host::" in n]
+    assert not leaked, leaked
+
+
 def test_struct_layouts_match_header():
     src = r'''
     #include <stdio.h>

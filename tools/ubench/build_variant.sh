@@ -15,5 +15,5 @@ for l in 0 1 2 3; do
   esac
 done
 wait
-hipcc --offload-arch=gfx950 -shared -fPIC -o $here/libucf_$tag.so $src/build/kernels_faithful.o $objs $src/build/peak.o $src/build/api.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o $here/libucf_$tag.so $src/build/kernels_faithful.o $objs $src/build/peak.o $src/build/fit.o $src/build/field.o $src/build/host_*.o
 echo "built $here/libucf_$tag.so"

@@ -21,7 +21,7 @@ struct ucf_env {
     // launch_transform_, finish_kernel and point_kernel
     int finish_part;       // UCF_FINISH_PART (0 = from the LDS footprint): 16 / 32 / 64 lanes per scratch part, epsilon table in LDS.  kernel
     int grid_slots;        // UCF_GRID_SLOTS (8192; <= 0 = default): workgroups per launch when the interval areas live in global scratch.  cut
-    // host side (ucf_api.cpp)
+    // host side (ucf_plan.cpp, ucf_drawdown.cpp, ucf_multi.cpp, ucf_debug.cpp)
     int z_chunk;           // UCF_Z_CHUNK (0 = from the LDS budget): depths per launch; the depth count selects NZC.  cut (kernel through nz)
     double fast_eta_max;   // UCF_FAST_ETA_MAX (0 = none): cap of the fast evaluators' range, the rest goes to the generic one.  cut of the abscissae
     bool guard;            // UCF_GUARD (off; on when set, non-empty and not starting with '0'): buffers end at a page end.  allocation only
@@ -65,5 +65,5 @@ inline ucf_env ucf_env_read(const char* (*get)(const char*))
     return v;
 }
 
-// the process environment, read on first use (defined in ucf_api.cpp; internal to the library, not an exported symbol)
+// the process environment, read on first use (defined in ucf_api.cpp, the one place that reads it; internal to the library, not an exported symbol)
 __attribute__((visibility("hidden"))) const ucf_env& ucf_env_get();

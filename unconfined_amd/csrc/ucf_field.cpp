@@ -1,0 +1,314 @@
+// ucf_field.cpp -- well fields (include/ucf.h): the superposed drawdown of several pumping and image wells through the grid path
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "ucf_host.h"
+#include "ucf_field.h"
+
+using namespace ucf_host;
+
+struct field_group {
+    double t0 = 0.0;
+    std::vector<int> wells;                // in the caller's order
+};
+
+struct ucf_field {
+    int nwell = 0, nloc = 0, nt = 0;
+    std::vector<double> xw, yw, qw, t0w, x, y, t;
+    std::vector<field_group> groups;       // ascending t0
+    std::vector<int> well_group;
+    int device = -1;                       // where the buffers live: the device of the plan of the first ucf_field_drawdown
+    ucf_buffer b_tD, b_sv, b_rD, b_tfac, b_col, b_wells, b_h, b_dh, b_s, b_ds, b_stats;      // grown on demand, kept
+    long long n_alloc = 0;
+    // every device buffer above: the one list (ucf_field_destroy frees through it)
+    std::array<ucf_buffer*, 11> buffers()
+    {
+        return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats}};
+    }
+};
+
+namespace {
+// what group g launches: the arrays of ucf_field_group
+struct field_launch {
+    int k0 = 0, nt = 0, nr = 0;
+    std::vector<double> tD, rD, tfac;
+    std::vector<int> sv, col;              // col [nloc][nwell], -1 = well not in g
+};
+
+int field_group_core(const ucf_field* f, const ucf_params& P, const ucf_derived& D, int g, field_launch& A)
+{
+    const field_group& G = f->groups[g];
+    int k0 = 0;
+    while (k0 < f->nt && !(f->t[k0] > G.t0)) k0++;
+    A.k0 = k0;
+    A.nt = f->nt - k0;
+    A.tD.resize(A.nt); A.tfac.resize(A.nt); A.sv.assign(A.nt, 0);
+    for (int i = 0; i < A.nt; i++) {
+        const double dt = f->t[k0 + i] - G.t0;
+        A.tD[i] = dt / D.Tc;
+        A.tfac[i] = f->t[k0 + i] / dt;
+    }
+    const size_t nw = G.wells.size();
+    std::vector<double> r((size_t)f->nloc * nw);
+    for (int i = 0; i < f->nloc; i++)
+        for (size_t a = 0; a < nw; a++) {
+            const int j = G.wells[a];
+            const double dx = f->x[i] - f->xw[j], dy = f->y[i] - f->yw[j];
+            const double dist = std::sqrt(dx * dx + dy * dy);
+            if (!std::isfinite(dist)) return fail(UCF_ERR_BAD_ARGUMENT, "the distance of location %d from well %d is not finite", i, j);
+            if (dist < P.rw)
+                return fail(UCF_ERR_BAD_ARGUMENT, "location %d lies %g from well %d: inside its bore (rw = %g)", i, dist, j, P.rw);
+            r[i * nw + a] = dist / D.Lc;
+        }
+    A.rD = r;
+    std::sort(A.rD.begin(), A.rD.end());
+    A.rD.erase(std::unique(A.rD.begin(), A.rD.end()), A.rD.end());      // (positive and finite: equal values are equal bits)
+    A.nr = (int)A.rD.size();
+    A.col.assign((size_t)f->nloc * f->nwell, -1);
+    for (int i = 0; i < f->nloc; i++)
+        for (size_t a = 0; a < nw; a++)
+            A.col[(size_t)i * f->nwell + G.wells[a]] = (int)(std::lower_bound(A.rD.begin(), A.rD.end(), r[i * nw + a]) - A.rD.begin());
+    if ((long long)A.nt * A.nr > 0x7fffffffLL)
+        return fail(UCF_ERR_BAD_ARGUMENT, "group %d: %d times x %d distinct distances is a grid larger than 2^31-1 points", g, A.nt, A.nr);
+    if (A.nt > 0) {
+        split_vector(P.j0s, A.nt, A.tD.data(), A.sv.data());
+        int rc = check_grid_sv_of(P, D, A.nt, A.sv.data());
+        if (rc) return rc;
+    }
+    return UCF_OK;
+}
+
+int field_group_out(const ucf_field* f, const ucf_params& P, const ucf_derived& D, int g, int* k0, int* nt_g, double* tD, int* sv,
+                    int* nr_g, double* rD, int* col, double* tfac)
+{
+    if (g < 0 || g >= (int)f->groups.size()) return fail(UCF_ERR_BAD_ARGUMENT, "group %d outside 0..%d", g, (int)f->groups.size() - 1);
+    field_launch A;
+    int rc = field_group_core(f, P, D, g, A);
+    if (rc) return rc;
+    if (k0) *k0 = A.k0;
+    if (nt_g) *nt_g = A.nt;
+    if (nr_g) *nr_g = A.nr;
+    if (tD) std::copy(A.tD.begin(), A.tD.end(), tD);
+    if (sv) std::copy(A.sv.begin(), A.sv.end(), sv);
+    if (rD) std::copy(A.rD.begin(), A.rD.end(), rD);
+    if (col) std::copy(A.col.begin(), A.col.end(), col);
+    if (tfac) std::copy(A.tfac.begin(), A.tfac.end(), tfac);
+    return UCF_OK;
+}
+
+int field_check_finite(const char* name, int n, const double* v)
+{
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(v[i])) return fail(UCF_ERR_BAD_ARGUMENT, "%s[%d]=%g is not finite", name, i, v[i]);
+    return UCF_OK;
+}
+
+// every group's block of a shared buffer starts at a multiple of 32 entries (256 bytes of doubles)
+size_t field_pad(size_t n) { return (n + 31) & ~(size_t)31; }
+}  // namespace
+
+extern "C" {
+
+int ucf_field_create(int nwell, const double* xw, const double* yw, const double* qw, const double* t0w, int nloc, const double* x,
+                     const double* y, int nt, const double* t, ucf_field** out)
+{
+    if (out) *out = nullptr;
+    if (!out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (nwell < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nwell=%d: at least one well", nwell);
+    if (nloc < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nloc=%d: at least one location", nloc);
+    if (nt < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nt=%d: at least one time", nt);
+    if (!xw || !yw || !qw || !t0w || !x || !y || !t) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
+    int rc;
+    if ((rc = field_check_finite("xw", nwell, xw)) || (rc = field_check_finite("yw", nwell, yw)) || (rc = field_check_finite("qw", nwell, qw)) ||
+        (rc = field_check_finite("t0w", nwell, t0w)) || (rc = field_check_finite("x", nloc, x)) || (rc = field_check_finite("y", nloc, y)) ||
+        (rc = field_check_finite("t", nt, t))) return rc;
+    for (int j = 0; j < nwell; j++) {
+        if (qw[j] == 0.0) return fail(UCF_ERR_BAD_ARGUMENT, "qw[%d] is 0: a well without a rate", j);
+        if (!(t0w[j] >= 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "t0w[%d]=%g is negative", j, t0w[j]);
+    }
+    if (!(t[0] > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "t[0]=%g is not a positive time", t[0]);
+    for (int k = 1; k < nt; k++)
+        if (!(t[k] > t[k - 1])) return fail(UCF_ERR_BAD_ARGUMENT, "t[%d]=%g does not lie after t[%d]=%g: times must increase strictly", k, t[k], k - 1, t[k - 1]);
+    ucf_field* f = new (std::nothrow) ucf_field();
+    if (!f) return fail(UCF_ERR_NOMEM, "host allocation failed");
+    f->nwell = nwell; f->nloc = nloc; f->nt = nt;
+    f->xw.assign(xw, xw + nwell); f->yw.assign(yw, yw + nwell); f->qw.assign(qw, qw + nwell); f->t0w.assign(t0w, t0w + nwell);
+    f->x.assign(x, x + nloc); f->y.assign(y, y + nloc); f->t.assign(t, t + nt);
+    for (double& v : f->t0w) v = v + 0.0;                        // -0.0 is the start time +0.0
+    // wells with the same start time form a group; groups in ascending t0, wells in the caller's order
+    std::vector<double> starts = f->t0w;
+    std::sort(starts.begin(), starts.end());
+    starts.erase(std::unique(starts.begin(), starts.end()), starts.end());
+    f->groups.resize(starts.size());
+    f->well_group.resize(nwell);
+    for (size_t g = 0; g < starts.size(); g++) f->groups[g].t0 = starts[g];
+    for (int j = 0; j < nwell; j++) {
+        const int g = (int)(std::lower_bound(starts.begin(), starts.end(), f->t0w[j]) - starts.begin());
+        f->well_group[j] = g;
+        f->groups[g].wells.push_back(j);
+    }
+    *out = f;
+    return UCF_OK;
+}
+
+void ucf_field_destroy(ucf_field* f)
+{
+    if (!f) return;
+    if (f->device >= 0) {
+        device_switch sw(f->device);
+        for (ucf_buffer* b : f->buffers()) free_buffer(*b);
+    }
+    delete f;
+}
+
+int ucf_field_group_count(const ucf_field* f, int* ngroups)
+{
+    if (!f || !ngroups) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    *ngroups = (int)f->groups.size();
+    return UCF_OK;
+}
+
+int ucf_field_group(const ucf_field* f, const ucf_plan* pl, int g, int* k0, int* nt_g, double* tD, int* sv, int* nr_g, double* rD,
+                    int* col, double* tfac)
+{
+    if (!f || !pl) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    return field_group_out(f, pl->P, pl->D, g, k0, nt_g, tD, sv, nr_g, rD, col, tfac);
+}
+
+int ucf_field_group_from_params(const ucf_field* f, const ucf_params* P, int g, int* k0, int* nt_g, double* tD, int* sv, int* nr_g,
+                                double* rD, int* col, double* tfac)
+{
+    if (!f || !P) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = validate(*P);
+    if (rc) return rc;
+    ucf_derived D;
+    nondimensionalise(*P, D);
+    return field_group_out(f, *P, D, g, k0, nt_g, tD, sv, nr_g, rD, col, tfac);
+}
+
+long long ucf_field_alloc_count(const ucf_field* f) { return f ? f->n_alloc : 0; }
+
+int ucf_field_drawdown(ucf_field* f, ucf_plan* pl, int nz, const double* z, int dimensionless, double* s, double* ds, ucf_stats* stats)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL field");
+    if (nz < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nz=%d: at least one depth", nz);
+    if (!z || !s || !ds) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
+    int rc = field_check_finite("z", nz, z);
+    if (rc) return rc;
+    const long long nout = (long long)f->nt * f->nloc * nz;
+    if (nout > 0x7fffffffLL * 256) return fail(UCF_ERR_BAD_ARGUMENT, "%d times x %d locations x %d depths: too many outputs for one call", f->nt, f->nloc, nz);
+    if (!pl) {
+        // a plan cannot exist without a device: say that first where it is the reason
+        rc = require_device();
+        return rc ? rc : fail(UCF_ERR_BAD_ARGUMENT, "NULL plan");
+    }
+    const int ng = (int)f->groups.size();
+    std::vector<field_launch> L(ng);
+    for (int g = 0; g < ng; g++)
+        if ((rc = field_group_core(f, pl->P, pl->D, g, L[g]))) return rc;
+    rc = require_device();
+    if (rc) return rc;
+    if (f->device >= 0 && f->device != pl->device)
+        return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    // zD, zLay as in ucf_drawdown_multi
+    std::vector<double> zD(nz);
+    std::vector<int> zl(nz);
+    for (int j = 0; j < nz; j++) zD[j] = z[j] / pl->D.Lc;
+    rc = ucf_zlay(pl, nz, zD.data(), zl.data());
+    if (rc) return rc;
+    // one staging image per array, the groups one after the other
+    std::vector<size_t> toff(ng), roff(ng), hoff(ng);
+    size_t nT = 0, nR = 0, nH = 0;
+    for (int g = 0; g < ng; g++) {
+        toff[g] = nT; roff[g] = nR; hoff[g] = nH;
+        nT += field_pad(L[g].nt); nR += field_pad(L[g].nr); nH += field_pad((size_t)L[g].nt * L[g].nr * nz);
+    }
+    if (nT > 0x7fffffffULL) return fail(UCF_ERR_BAD_ARGUMENT, "too many launched times");
+    std::vector<double> tD(nT, 1.0), rD(nR, 1.0), tfac(nT, 0.0);
+    std::vector<int> sv(nT, 0), col((size_t)f->nloc * f->nwell);
+    std::vector<ucf_field_well> wells(f->nwell);
+    for (int g = 0; g < ng; g++) {
+        std::copy(L[g].tD.begin(), L[g].tD.end(), tD.begin() + toff[g]);
+        std::copy(L[g].sv.begin(), L[g].sv.end(), sv.begin() + toff[g]);
+        std::copy(L[g].tfac.begin(), L[g].tfac.end(), tfac.begin() + toff[g]);
+        std::copy(L[g].rD.begin(), L[g].rD.end(), rD.begin() + roff[g]);
+    }
+    for (int j = 0; j < f->nwell; j++) {
+        const int g = f->well_group[j];
+        wells[j] = ucf_field_well{f->qw[j], (long long)hoff[g], L[g].k0, L[g].nr, (int)toff[g], 0};
+        for (int i = 0; i < f->nloc; i++) col[(size_t)i * f->nwell + j] = L[g].col[(size_t)i * f->nwell + j];
+    }
+    device_switch dg(pl->device);
+    f->device = pl->device;
+    const size_t so = sizeof(double) * (size_t)nout;
+    if ((rc = grow_buffer(f->b_tD, sizeof(double) * nT, "group times", f->n_alloc)) || (rc = grow_buffer(f->b_sv, sizeof(int) * nT, "split vectors", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_tfac, sizeof(double) * nT, "time factors", f->n_alloc)) || (rc = grow_buffer(f->b_rD, sizeof(double) * nR, "group distances", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_col, sizeof(int) * col.size(), "columns", f->n_alloc)) || (rc = grow_buffer(f->b_wells, sizeof(ucf_field_well) * wells.size(), "wells", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_h, sizeof(double) * nH, "group drawdowns", f->n_alloc)) || (rc = grow_buffer(f->b_dh, sizeof(double) * nH, "group derivatives", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_s, so, "superposed drawdown", f->n_alloc)) || (rc = grow_buffer(f->b_ds, so, "superposed derivative", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_stats, sizeof(ucf_stats) * ng, "counters", f->n_alloc))) return rc;
+    hipStream_t st = plan_stream(pl);
+    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
+    struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};     // the staging above outlives the copies
+    if (hipMemcpyAsync(f->b_tD.p, tD.data(), sizeof(double) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_sv.p, sv.data(), sizeof(int) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_tfac.p, tfac.data(), sizeof(double) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_rD.p, rD.data(), sizeof(double) * nR, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_col.p, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_wells.p, wells.data(), sizeof(ucf_field_well) * wells.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(f->b_stats.p, 0, sizeof(ucf_stats) * ng, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the field's launch arrays failed: %s", hipGetErrorString(hipGetLastError()));
+    // per group one call of the grid path, results into the field's buffers
+    for (int g = 0; g < ng; g++) {
+        if (L[g].nt == 0) continue;
+        rc = ucf_drawdown_grid_device(pl, L[g].nt, (const double*)f->b_tD.p + toff[g], (const int*)f->b_sv.p + toff[g], L[g].nr,
+                                      (const double*)f->b_rD.p + roff[g], nz, zD.data(), zl.data(), (double*)f->b_h.p + hoff[g],
+                                      (double*)f->b_dh.p + hoff[g], stats ? (ucf_stats*)f->b_stats.p + g : nullptr, st);
+        if (rc) return rc;
+    }
+    rc = ucf_field_launch_superpose(f->nt, f->nloc, nz, f->nwell, (const ucf_field_well*)f->b_wells.p, (const int*)f->b_col.p,
+                                    (const double*)f->b_tfac.p, (const double*)f->b_h.p, (const double*)f->b_dh.p, dimensionless ? 0 : 1,
+                                    pl->D.Hc, (double*)f->b_s.p, (double*)f->b_ds.p, st);
+    if (rc) return fail(rc, "superposition kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    std::vector<ucf_stats> gst(ng);
+    if (hipMemcpyAsync(s, f->b_s.p, so, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(ds, f->b_ds.p, so, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (stats && hipMemcpyAsync(gst.data(), f->b_stats.p, sizeof(ucf_stats) * ng, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
+    if (stats)
+        for (int g = 0; g < ng; g++) stats_add(*stats, gst[g]);
+    return UCF_OK;
+}
+
+int ucf_field_images(int nwell, const double* xw, const double* yw, const double* qw, const double* t0w, double a, double b, double c,
+                     int kind, double* xo, double* yo, double* qo, double* t0o)
+{
+    if (nwell < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nwell=%d: at least one well", nwell);
+    if (!xw || !yw || !qw || !t0w || !xo || !yo || !qo || !t0o) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
+    if (kind != 0 && kind != 1) return fail(UCF_ERR_BAD_ARGUMENT, "kind=%d: 0 (no-flow) or 1 (constant head)", kind);
+    if (!std::isfinite(a) || !std::isfinite(b) || !std::isfinite(c)) return fail(UCF_ERR_BAD_ARGUMENT, "the line a x + b y = c has a coefficient that is not finite");
+    if (a == 0.0 && b == 0.0) return fail(UCF_ERR_BAD_ARGUMENT, "a = b = 0 describes no line");
+    int rc;
+    if ((rc = field_check_finite("xw", nwell, xw)) || (rc = field_check_finite("yw", nwell, yw)) || (rc = field_check_finite("qw", nwell, qw)) ||
+        (rc = field_check_finite("t0w", nwell, t0w))) return rc;
+    // the mirror point x - 2 a d, y - 2 b d with d = (a x + b y - c) / (a^2 + b^2), in extended precision and rounded once
+    const long double la = a, lb = b, lc = c, n2 = la * la + lb * lb;
+    for (int j = 0; j < nwell; j++) {
+        const long double d = (la * xw[j] + lb * yw[j] - lc) / n2;
+        if (d == 0.0L) return fail(UCF_ERR_BAD_ARGUMENT, "well %d lies on the boundary line", j);
+        xo[j] = xw[j]; yo[j] = yw[j]; qo[j] = qw[j]; t0o[j] = t0w[j];
+        xo[nwell + j] = (double)(xw[j] - 2.0L * la * d);
+        yo[nwell + j] = (double)(yw[j] - 2.0L * lb * d);
+        qo[nwell + j] = kind == 0 ? qw[j] : -qw[j];
+        t0o[nwell + j] = t0w[j];
+    }
+    return UCF_OK;
+}
+
+}  // extern "C"

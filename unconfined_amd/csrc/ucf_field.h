@@ -1,4 +1,4 @@
-// ucf_field.h -- launcher of the well-field superposition (ucf_field.hip), called by ucf_field_drawdown (ucf_api.cpp).
+// ucf_field.h -- launcher of the well-field superposition (ucf_field.hip), called by ucf_field_drawdown (ucf_field.cpp).
 #pragma once
 #include <cstddef>
 

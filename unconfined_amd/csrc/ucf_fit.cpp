@@ -1,0 +1,732 @@
+// ucf_fit.cpp -- parameter fitting (ucf.h: ucf_fit_*): observations resident on the device, base and perturbed parameter sets through
+// the shared core of ucf_drawdown_multi, residuals / objective / Jacobian / normal equations in fit_reduce_kernel
+// (ucf_fit.hip), Levenberg-Marquardt for many starts at once on the host (npar x npar arithmetic).
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "ucf_host.h"
+#include "ucf_fit.h"
+
+using namespace ucf_host;
+
+// Points per block of a network launch: one tile of the lane = point layout, so that a wave never straddles two blocks.
+#define UCF_FIT_PPP UCF_WAVE
+// The used wells of a network that have `nz` depths each, in order of radius.  Per plan the group evaluates
+// pts = 64 x (blocks of all its wells) points: the distinct times of a well in ascending order, its last block padded by
+// repeating the last time.  In the buffers of an evaluation over nplans plans the group's points start at
+// nplans * pt_prefix (values: nplans * prefix), plan k of it at k * pts (k * stride).
+struct fit_group {
+    int nz = 0;
+    std::vector<int> wells, blk0, nt;      // per used well: its index, its first block, its distinct times
+    std::vector<int> blk_well;             // per block: position of its well in `wells`
+    std::vector<double> t, r;              // [pts] dimensional times and radii of one plan
+    size_t pts = 0, stride = 0;            // stride = pts * nz
+    size_t pt_prefix = 0, prefix = 0;      // sums of pts / stride over the groups before this one
+};
+
+struct ucf_fit {
+    ucf_params base = {};
+    int npar = 0, ids[UCF_FIT_MAX_PAR] = {};
+    int nobs = 0, nz = 0, device = 0;
+    std::vector<double> t_s, r_s, z;       // observation times / radii in order of radius (the order the core evaluates in), depths
+    std::vector<ucf_plan*> plans;          // the pool: made once, refreshed by ucf_plan_update
+    multi_io io;
+    ucf_buffer b_slot, b_obs, b_w;         // fixed at create
+    ucf_buffer b_t, b_r, b_s, b_h, b_d, b_hc, b_sums, b_nbad, b_J, b_sim;      // grown on demand
+    std::vector<double> h_hc, h_sums;
+    long long n_alloc = 0;                 // device allocations of the fit itself + plans created
+    // where observation i finds its value in b_h (host copy; ucf_fit_create: prefix 0, stride nobs * nz, at = its slot)
+    std::vector<ucf_fit_obs_ref> refs;
+    int last_nplans = 0;                   // plans of the last evaluation (ucf_fit_debug_h)
+    // an observation network (ucf_fit_create_network)
+    bool network = false;
+    std::vector<double> well_r, well_z;    // radius per well; depths of well w at well_z[well_z0[w] ..)
+    std::vector<int> well_nz, well_z0;
+    std::vector<fit_group> groups;         // wells with the same number of depths: one launch sequence each
+    size_t net_pts = 0, net_vals = 0;      // per plan, all groups: points launched, (point, depth) values
+    long long dense = 0;                   // (point, depth) evaluations per plan of the dense form
+    ucf_buffer b_ref;
+    // every device buffer above: the one list (ucf_fit_destroy frees through it)
+    std::array<ucf_buffer*, 14> buffers()
+    {
+        return {{&b_slot, &b_obs, &b_w, &b_t, &b_r, &b_s, &b_h, &b_d, &b_hc, &b_sums, &b_nbad, &b_J, &b_sim, &b_ref}};
+    }
+    std::vector<double> st_t;              // staging of one plan: its tD over all groups ...
+    std::vector<int> st_s;                 // ... and their split vector
+};
+
+namespace {
+const char* fit_par_name(int id, char* buf, size_t n)
+{
+    static const char* const names[] = {"Kr", "kappa", "Ss", "Sy", "ac", "ak", "usL"};
+    if (id >= 0 && id < UCF_PAR_MOENCH_ALPHA0) return names[id];
+    std::snprintf(buf, n, "MoenchAlpha[%d]", id - UCF_PAR_MOENCH_ALPHA0);
+    return buf;
+}
+
+double* fit_field(ucf_params& P, int id)
+{
+    switch (id) {
+    case UCF_PAR_KR: return &P.Kr;
+    case UCF_PAR_KAPPA: return &P.kappa;
+    case UCF_PAR_SS: return &P.Ss;
+    case UCF_PAR_SY: return &P.Sy;
+    case UCF_PAR_AC: return &P.ac;
+    case UCF_PAR_AK: return &P.ak;
+    case UCF_PAR_USL: return &P.usL;
+    default: break;
+    }
+    if (id >= UCF_PAR_MOENCH_ALPHA0 && id < UCF_PAR_MOENCH_ALPHA0 + UCF_MAX_MOENCH) return &P.MoenchAlpha[id - UCF_PAR_MOENCH_ALPHA0];
+    return nullptr;
+}
+
+// does the model of P read parameter `id`?  (Kr, Ss: every model; kappa: all but Theis; Sy: the unconfined models 3..6;
+// ak: model 6; ac, usL: model 6 in its finite-difference form -- the Malama form replaces ac by ak and has no usL;
+// Moench alpha i: model 3, i < MoenchM)
+bool fit_reads(const ucf_params& P, int id)
+{
+    switch (id) {
+    case UCF_PAR_KR: case UCF_PAR_SS: return true;
+    case UCF_PAR_KAPPA: return P.model >= 1;
+    case UCF_PAR_SY: return P.model >= 3;
+    case UCF_PAR_AK: return P.model == 6;
+    case UCF_PAR_AC: case UCF_PAR_USL: return P.model == 6 && P.MNtype != 1;
+    default: break;
+    }
+    return P.model == 3 && id >= UCF_PAR_MOENCH_ALPHA0 && id < UCF_PAR_MOENCH_ALPHA0 + P.MoenchM;
+}
+
+int fit_check_ids(const ucf_params& P, int npar, const int* ids)
+{
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (!ids) return fail(UCF_ERR_BAD_ARGUMENT, "ids is NULL");
+    char nb[32];
+    for (int j = 0; j < npar; j++) {
+        if (ids[j] < 0 || ids[j] >= UCF_PAR_MOENCH_ALPHA0 + UCF_MAX_MOENCH) return fail(UCF_ERR_BAD_ARGUMENT, "ids[%d]=%d is no parameter id", j, ids[j]);
+        for (int k = 0; k < j; k++)
+            if (ids[k] == ids[j]) return fail(UCF_ERR_BAD_ARGUMENT, "ids[%d] and ids[%d] both name %s (duplicate id %d)", k, j, fit_par_name(ids[j], nb, sizeof(nb)), ids[j]);
+        if (!fit_reads(P, ids[j]))
+            return fail(UCF_ERR_BAD_ARGUMENT, "ids[%d]=%d (%s) is not read by model %d%s", j, ids[j], fit_par_name(ids[j], nb, sizeof(nb)), P.model,
+                        P.model == 3 ? " with this number of Moench alphas" : (P.model == 6 ? " in this Mishra/Neuman form" : ""));
+    }
+    return UCF_OK;
+}
+
+// Cholesky of the n x n matrix M (row-major, overwritten by its lower factor): UCF_ERR_SINGULAR if a pivot is not positive
+int fit_cholesky(int n, double* M)
+{
+    for (int j = 0; j < n; j++) {
+        double d = M[j * n + j];
+        for (int k = 0; k < j; k++) d -= M[j * n + k] * M[j * n + k];
+        if (!(d > 0.0) || !std::isfinite(d)) return UCF_ERR_SINGULAR;
+        d = std::sqrt(d);
+        M[j * n + j] = d;
+        for (int i = j + 1; i < n; i++) {
+            double v = M[i * n + j];
+            for (int k = 0; k < j; k++) v -= M[i * n + k] * M[j * n + k];
+            M[i * n + j] = v / d;
+        }
+    }
+    return UCF_OK;
+}
+void fit_chol_solve(int n, const double* L, const double* b, double* x)
+{
+    for (int i = 0; i < n; i++) {
+        double v = b[i];
+        for (int k = 0; k < i; k++) v -= L[i * n + k] * x[k];
+        x[i] = v / L[i * n + i];
+    }
+    for (int i = n - 1; i >= 0; i--) {
+        double v = x[i];
+        for (int k = i + 1; k < n; k++) v -= L[k * n + i] * x[k];
+        x[i] = v / L[i * n + i];
+    }
+}
+
+// The layout of a network: per well the distinct times that observations name, ascending; the used wells grouped by their
+// number of depths (groups in ascending number, wells by radius where radii are given); pt_of[i] = place of observation
+// i's point among the points of one plan of its group.  The arguments have been validated.
+void network_layout(int nwell, const double* well_r, const int* well_nz, int nobs, const double* t, const int* well,
+                    std::vector<fit_group>& groups, std::vector<int>* grp_of, std::vector<int>* pt_of, long long* distinct_points)
+{
+    std::vector<std::vector<double>> times(nwell);
+    for (int i = 0; i < nobs; i++) times[well[i]].push_back(t[i]);
+    long long npoints = 0;
+    for (auto& v : times) {
+        std::sort(v.begin(), v.end());
+        v.erase(std::unique(v.begin(), v.end()), v.end());
+        npoints += (long long)v.size();
+    }
+    if (distinct_points) *distinct_points = npoints;
+    groups.clear();
+    std::vector<int> first_pt(nwell, 0), grp_w(nwell, -1);
+    for (int nz = 1; nz <= UCF_MAX_NZ; nz++) {
+        fit_group G;
+        G.nz = nz;
+        for (int w = 0; w < nwell; w++)
+            if (well_nz[w] == nz && !times[w].empty()) G.wells.push_back(w);
+        if (G.wells.empty()) continue;
+        if (well_r) std::stable_sort(G.wells.begin(), G.wells.end(), [&](int a, int b) { return well_r[a] < well_r[b]; });
+        int nblk = 0;
+        for (size_t j = 0; j < G.wells.size(); j++) {
+            const int w = G.wells[j];
+            const std::vector<double>& tw = times[w];
+            const int nb = ((int)tw.size() + UCF_FIT_PPP - 1) / UCF_FIT_PPP;
+            G.blk0.push_back(nblk);
+            G.nt.push_back((int)tw.size());
+            first_pt[w] = nblk * UCF_FIT_PPP;
+            grp_w[w] = (int)groups.size();
+            for (int b = 0; b < nb; b++) G.blk_well.push_back((int)j);
+            for (int q = 0; q < nb * UCF_FIT_PPP; q++) {
+                G.t.push_back(tw[q < (int)tw.size() ? q : (int)tw.size() - 1]);      // padding: the last time again
+                G.r.push_back(well_r ? well_r[w] : 0.0);
+            }
+            nblk += nb;
+        }
+        G.pts = (size_t)nblk * UCF_FIT_PPP;
+        G.stride = G.pts * nz;
+        if (!groups.empty()) { G.pt_prefix = groups.back().pt_prefix + groups.back().pts; G.prefix = groups.back().prefix + groups.back().stride; }
+        groups.push_back(std::move(G));
+    }
+    if (!grp_of) return;
+    grp_of->resize(nobs); pt_of->resize(nobs);
+    for (int i = 0; i < nobs; i++) {
+        const std::vector<double>& tw = times[well[i]];
+        (*grp_of)[i] = grp_w[well[i]];
+        (*pt_of)[i] = first_pt[well[i]] + (int)(std::lower_bound(tw.begin(), tw.end(), t[i]) - tw.begin());
+    }
+}
+
+int network_check(int nwell, const int* well_nz, int nobs, const double* t, const int* well)
+{
+    if (nwell < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nwell=%d: at least one well", nwell);
+    if (nobs < 0 || nobs > (1 << 24)) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: too many observations", nobs);
+    if (!well_nz || (nobs > 0 && (!t || !well))) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
+    for (int w = 0; w < nwell; w++)
+        if (well_nz[w] < 1 || well_nz[w] > UCF_MAX_NZ) return fail(UCF_ERR_BAD_ARGUMENT, "well_nz[%d]=%d outside 1..%d", w, well_nz[w], UCF_MAX_NZ);
+    for (int i = 0; i < nobs; i++) {
+        if (well[i] < 0 || well[i] >= nwell) return fail(UCF_ERR_BAD_ARGUMENT, "well[%d]=%d outside 0..%d", i, well[i], nwell - 1);
+        if (!std::isfinite(t[i]) || !(t[i] > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "t[%d]=%g is not a finite positive time", i, t[i]);
+    }
+    return UCF_OK;
+}
+
+// The launches of a network fit over the first nplans plans of the pool; the dimensionless h, dh stay in f->io.d_h, d_d in
+// the layout of fit_group.  As multi_core: every stream the call used has drained when it returns.
+int network_core(ucf_fit* f, int nplans)
+{
+    ucf_plan* const* plans = f->plans.data();
+    multi_io& io = f->io;
+    const size_t P = f->net_pts, ptot = (size_t)nplans * P;
+    const int nwell = (int)f->well_nz.size(), nzs = (int)f->well_z.size();
+    std::vector<double>&tD = io.tD, &rD = io.rD, &zD = io.zD;      // tD, rD, sv as uploaded; zD, zl: [nplans][all depths of all wells]
+    std::vector<int>&sv = io.sv, &zl = io.zl;
+    tD.resize(ptot); rD.resize(ptot); sv.resize(ptot);
+    zD.resize((size_t)nplans * nzs); zl.resize((size_t)nplans * nzs);
+    f->st_t.resize(P); f->st_s.resize(P);
+    for (int k = 0; k < nplans; k++) {
+        const ucf_derived& D = plans[k]->D;
+        // the split vector of a plan is taken over all its launched times, whatever group they fall into
+        for (const fit_group& G : f->groups)
+            for (size_t q = 0; q < G.pts; q++) f->st_t[G.pt_prefix + q] = G.t[q] / D.Tc;
+        int rc = ucf_split_vector(plans[k], (int)P, f->st_t.data(), f->st_s.data());
+        if (rc) return rc;
+        rc = check_sv(plans[k], (int)P, f->st_s.data());
+        if (rc) return rc;
+        for (const fit_group& G : f->groups) {
+            const size_t at = (size_t)nplans * G.pt_prefix + (size_t)k * G.pts;
+            for (size_t q = 0; q < G.pts; q++) { tD[at + q] = f->st_t[G.pt_prefix + q]; rD[at + q] = G.r[q] / D.Lc; sv[at + q] = f->st_s[G.pt_prefix + q]; }
+        }
+        for (int j = 0; j < nzs; j++) zD[(size_t)k * nzs + j] = f->well_z[j] / D.Lc;
+        for (int w = 0; w < nwell; w++) {
+            rc = ucf_zlay(plans[k], f->well_nz[w], &zD[(size_t)k * nzs + f->well_z0[w]], &zl[(size_t)k * nzs + f->well_z0[w]]);
+            if (rc) return rc;
+        }
+    }
+    HIP_TRY(hipMemcpy(io.d_t, tD.data(), sizeof(double) * ptot, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(io.d_r, rD.data(), sizeof(double) * ptot, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(io.d_s, sv.data(), sizeof(int) * ptot, hipMemcpyHostToDevice));
+    const bool share = plans_share_launch(plans, nplans);
+    hipStream_t streams[8];
+    int ns = 0;
+    int rc = UCF_OK;
+    for (const fit_group& G : f->groups) {
+        const int nz = G.nz, nblk = (int)G.blk_well.size();
+        const size_t p0 = (size_t)nplans * G.pt_prefix, v0 = (size_t)nplans * G.prefix;
+        if (share && (size_t)nplans * nblk > 1) {
+            if ((size_t)nplans * G.pts > 0x7fffffffULL) return fail(UCF_ERR_BAD_ARGUMENT, "%d plans x %zu points: too many points for one call", nplans, G.pts);
+            // block = (plan, tile of a well): the plan's parameter block with the well's depths and layers
+            auto fill = [&](int z0, int nzc, std::vector<ucf_dev_params>& dps) {
+                for (int k = 0; k < nplans; k++)
+                    for (int b = 0; b < nblk; b++) {
+                        const size_t zw = (size_t)k * nzs + f->well_z0[G.wells[G.blk_well[b]]] + z0;
+                        int rc2 = fill_call_params(plans[k], nzc, &zD[zw], &zl[zw], dps[(size_t)k * nblk + b], nz, z0);
+                        if (rc2) return rc2;
+                    }
+                return (int)UCF_OK;
+            };
+            rc = shared_launch(plans[0], nplans * nblk, UCF_FIT_PPP, nz, fill, io.dps, io.d_t + p0, io.d_r + p0, io.d_s + p0, io.d_h + v0, io.d_d + v0);
+            if (rc) return rc;
+            continue;
+        }
+        // no shared launch for these plans: plan by plan and well by well (each well has its own depths), unpadded
+        if (ns == 0) ns = stream_pool(f->device, nplans, streams);
+        if (ns == 0) return fail(UCF_ERR_HIP, "cannot create a HIP stream");
+        for (int k = 0; k < nplans && rc == UCF_OK; k++)
+            for (size_t j = 0; j < G.wells.size() && rc == UCF_OK; j++) {
+                const size_t at = p0 + (size_t)k * G.pts + (size_t)G.blk0[j] * UCF_FIT_PPP;
+                const size_t vat = v0 + (size_t)k * G.stride + (size_t)G.blk0[j] * UCF_FIT_PPP * nz;
+                const size_t zw = (size_t)k * nzs + f->well_z0[G.wells[j]];
+                rc = ucf_drawdown_batch_device(plans[k], G.nt[j], (const double*)io.d_t + at, (const double*)io.d_r + at, (const int*)io.d_s + at,
+                                               nz, &zD[zw], &zl[zw], io.d_h + vat, io.d_d + vat, nullptr, streams[k % ns]);
+            }
+        if (rc) break;
+    }
+    for (int i = 0; i < ns; i++) (void)hipStreamSynchronize(streams[i]);
+    return rc;
+}
+
+// jac != 0: base and perturbed plans, everything; jac == 0: the base plans only, phi and nbad (the trial points of ucf_fit_lm)
+int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int jac, double* phi, double* g, double* A, int* nbad,
+                 double* J, double* sim_all)
+{
+    if (!f || !theta) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (nsets < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nsets=%d: at least one parameter set", nsets);
+    if (jac && (!(dlog > 0.0) || !std::isfinite(dlog))) return fail(UCF_ERR_BAD_ARGUMENT, "dlog=%g must be positive and finite", dlog);
+    const int npar = f->npar, per = jac ? 1 + 2 * npar : 1, nobs = f->nobs, nz = f->nz;
+    if ((long long)nsets * per > (1 << 20)) return fail(UCF_ERR_BAD_ARGUMENT, "%d sets x %d plans: too many plans for one call", nsets, per);
+    const int nplans = nsets * per;
+    char nb[32];
+    for (int s = 0; s < nsets; s++)
+        for (int j = 0; j < npar; j++) {
+            const double v = theta[(size_t)s * npar + j];
+            if (!(v > 0.0) || !std::isfinite(v))
+                return fail(UCF_ERR_BAD_ARGUMENT, "set %d: %s=%g must be positive and finite (parameters are fitted in their logarithm)", s,
+                            fit_par_name(f->ids[j], nb, sizeof(nb)), v);
+        }
+    device_switch dg(f->device);
+    // the plans: refreshed in place, made on first use
+    const double up = std::exp(dlog), down = std::exp(-dlog);
+    std::vector<double> th(npar);
+    for (int s = 0; s < nsets; s++)
+        for (int v = 0; v < per; v++) {
+            for (int j = 0; j < npar; j++) th[j] = theta[(size_t)s * npar + j];
+            const int j = (v - 1) / 2;
+            if (v > 0) th[j] = th[j] * ((v & 1) ? up : down);
+            ucf_params P;
+            int rc = ucf_fit_perturb(&f->base, npar, f->ids, th.data(), &P);
+            if (rc) return rc;
+            const size_t k = (size_t)s * per + v;
+            if (k < f->plans.size()) {
+                rc = ucf_plan_update(f->plans[k], &P);
+            } else {
+                ucf_plan* pl = nullptr;
+                rc = ucf_plan_create(&P, &pl);
+                if (rc == UCF_OK) { (void)ucf_plan_set_mode(pl, 1); f->plans.push_back(pl); f->n_alloc++; }
+            }
+            if (rc) {
+                std::string why = ucf_last_error();
+                if (v == 0) return fail(rc, "set %d: %s", s, why.c_str());
+                return fail(rc, "set %d, %s moved by %+g in its logarithm: %s", s, fit_par_name(f->ids[j], nb, sizeof(nb)), (v & 1) ? dlog : -dlog, why.c_str());
+            }
+        }
+    const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_, nsum = (size_t)ucf_fit_nsums(jac ? npar : 0);
+    // points and (point, depth) values that are launched: every depth at every observation, or the network's blocks
+    const size_t ptot = (size_t)nplans * (f->network ? f->net_pts : np_), vtot = (size_t)nplans * (f->network ? f->net_vals : np_ * nz);
+    int rc;
+    if ((rc = grow_buffer(f->b_t, sizeof(double) * ptot, "tD", f->n_alloc)) || (rc = grow_buffer(f->b_r, sizeof(double) * ptot, "rD", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_s, sizeof(int) * ptot, "sv", f->n_alloc)) || (rc = grow_buffer(f->b_h, sizeof(double) * vtot, "h", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_d, sizeof(double) * vtot, "dh", f->n_alloc)) || (rc = grow_buffer(f->b_hc, sizeof(double) * nplans, "Hc", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_sums, sizeof(double) * nsets * nsum, "sums", f->n_alloc)) || (rc = grow_buffer(f->b_nbad, sizeof(int) * nsets, "nbad", f->n_alloc)))
+        return rc;
+    if (J && jac && (rc = grow_buffer(f->b_J, sizeof(double) * nsets * np_ * npar, "J", f->n_alloc))) return rc;
+    if (sim_all && (rc = grow_buffer(f->b_sim, sizeof(double) * tot, "sim_all", f->n_alloc))) return rc;
+    f->io.d_t = (double*)f->b_t.p; f->io.d_r = (double*)f->b_r.p; f->io.d_s = (int*)f->b_s.p;
+    f->io.d_h = (double*)f->b_h.p; f->io.d_d = (double*)f->b_d.p;
+    f->last_nplans = 0;
+    rc = f->network ? network_core(f, nplans) : multi_core(f->plans.data(), nplans, nobs, f->t_s.data(), f->r_s.data(), nz, f->z.data(), f->io);
+    if (rc) return rc;
+    f->last_nplans = nplans;
+    f->h_hc.resize(nplans);
+    for (int k = 0; k < nplans; k++) f->h_hc[k] = f->plans[k]->D.Hc;
+    HIP_TRY(hipMemcpy(f->b_hc.p, f->h_hc.data(), sizeof(double) * nplans, hipMemcpyHostToDevice));
+    if (f->network)
+        rc = ucf_fit_launch_network_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
+                                           (const double*)f->b_hc.p, (const ucf_fit_obs_ref*)f->b_ref.p, (const double*)f->b_obs.p,
+                                           (const double*)f->b_w.p, (double*)f->b_sums.p, (int*)f->b_nbad.p,
+                                           (J && jac) ? (double*)f->b_J.p : nullptr, sim_all ? (double*)f->b_sim.p : nullptr, nullptr);
+    else
+        rc = ucf_fit_launch_reduce(jac ? npar : 0, nsets, nobs, np_ * nz, 2.0 * dlog, (const double*)f->b_h.p, (const double*)f->b_hc.p,
+                                   (const int*)f->b_slot.p, (const double*)f->b_obs.p, (const double*)f->b_w.p, (double*)f->b_sums.p,
+                                   (int*)f->b_nbad.p, (J && jac) ? (double*)f->b_J.p : nullptr, sim_all ? (double*)f->b_sim.p : nullptr, nullptr);
+    if (rc) return fail(rc, "fit reduction kernel launch failed");
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    f->h_sums.resize(nsets * nsum);
+    HIP_TRY(hipMemcpy(f->h_sums.data(), f->b_sums.p, sizeof(double) * nsets * nsum, hipMemcpyDeviceToHost));
+    if (nbad) HIP_TRY(hipMemcpy(nbad, f->b_nbad.p, sizeof(int) * nsets, hipMemcpyDeviceToHost));
+    if (J && jac) HIP_TRY(hipMemcpy(J, f->b_J.p, sizeof(double) * nsets * np_ * npar, hipMemcpyDeviceToHost));
+    if (sim_all) HIP_TRY(hipMemcpy(sim_all, f->b_sim.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
+    for (int s = 0; s < nsets; s++) {
+        const double* v = &f->h_sums[s * nsum];
+        if (phi) phi[s] = v[0];
+        if (!jac) continue;
+        if (g) for (int j = 0; j < npar; j++) g[(size_t)s * npar + j] = v[1 + j];
+        if (A) {
+            int q = 1 + npar;
+            for (int j = 0; j < npar; j++)
+                for (int k = j; k < npar; k++, q++) A[((size_t)s * npar + j) * npar + k] = A[((size_t)s * npar + k) * npar + j] = v[q];
+        }
+    }
+    return UCF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ucf_fit_perturb(const ucf_params* base, int npar, const int* ids, const double* theta, ucf_params* out)
+{
+    if (!base || !theta || !out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = fit_check_ids(*base, npar, ids);
+    if (rc) return rc;
+    ucf_params P = *base;
+    for (int j = 0; j < npar; j++) *fit_field(P, ids[j]) = theta[j];
+    *out = P;
+    return UCF_OK;
+}
+
+int ucf_fit_solve_step(int npar, const double* A, const double* g, double lambda, double* step)
+{
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (!A || !g || !step) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (!(lambda >= 0.0) || !std::isfinite(lambda)) return fail(UCF_ERR_BAD_ARGUMENT, "lambda=%g must be >= 0 and finite", lambda);
+    double M[UCF_FIT_MAX_PAR * UCF_FIT_MAX_PAR];
+    for (int i = 0; i < npar; i++)
+        for (int k = 0; k < npar; k++) M[i * npar + k] = A[i * npar + k];
+    for (int i = 0; i < npar; i++) M[i * npar + i] = A[i * npar + i] + lambda * A[i * npar + i];
+    for (int i = 0; i < npar; i++) step[i] = 0.0;
+    if (fit_cholesky(npar, M) != UCF_OK) return fail(UCF_ERR_SINGULAR, "A + %g diag A is not positive definite (%d x %d)", lambda, npar, npar);
+    fit_chol_solve(npar, M, g, step);
+    for (int i = 0; i < npar; i++)
+        if (!std::isfinite(step[i])) {
+            for (int k = 0; k < npar; k++) step[k] = 0.0;
+            return fail(UCF_ERR_SINGULAR, "A + %g diag A is singular to working precision (%d x %d)", lambda, npar, npar);
+        }
+    return UCF_OK;
+}
+
+int ucf_fit_create(const ucf_params* base, int npar, const int* ids, int nobs, const double* t, const double* r, const int* iz,
+                   int nz, const double* z, const double* obs, const double* weight, int device, ucf_fit** out)
+{
+    if (out) *out = nullptr;
+    if (!base || !out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = validate(*base);
+    if (rc) return rc;
+    rc = fit_check_ids(*base, npar, ids);
+    if (rc) return rc;
+    if (nobs < npar) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: fewer observations than the %d parameters to fit", nobs, npar);
+    if (nobs > (1 << 24)) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: too many observations", nobs);
+    if (nz < 1 || nz > 4096) return fail(UCF_ERR_BAD_ARGUMENT, "nz=%d: at least one depth (at most 4096)", nz);
+    if (!t || !r || !iz || !z || !obs || !weight) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
+    for (int j = 0; j < nz; j++)
+        if (!std::isfinite(z[j])) return fail(UCF_ERR_BAD_ARGUMENT, "z[%d]=%g is not finite", j, z[j]);
+    for (int i = 0; i < nobs; i++) {
+        if (iz[i] < 0 || iz[i] >= nz) return fail(UCF_ERR_BAD_ARGUMENT, "iz[%d]=%d outside 0..%d", i, iz[i], nz - 1);
+        if (!(weight[i] >= 0.0) || !std::isfinite(weight[i])) return fail(UCF_ERR_BAD_ARGUMENT, "weight[%d]=%g is negative or not finite", i, weight[i]);
+        if (!std::isfinite(obs[i])) return fail(UCF_ERR_BAD_ARGUMENT, "obs[%d]=%g is not finite", i, obs[i]);
+        if (!std::isfinite(t[i]) || !(t[i] > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "t[%d]=%g is not a finite positive time", i, t[i]);
+        if (!std::isfinite(r[i]) || !(r[i] > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "r[%d]=%g is not a finite positive radius", i, r[i]);
+    }
+    int ndev = 0;
+    rc = ucf_device_count(&ndev);
+    if (rc) return rc;
+    if (device < 0 || device >= ndev) return fail(UCF_ERR_BAD_ARGUMENT, "device %d does not exist (%d visible)", device, ndev);
+    ucf_fit* f = new (std::nothrow) ucf_fit();
+    if (!f) return fail(UCF_ERR_NOMEM, "host allocation failed");
+    f->base = *base; f->npar = npar; f->nobs = nobs; f->nz = nz; f->device = device;
+    for (int j = 0; j < npar; j++) f->ids[j] = ids[j];
+    // the core evaluates in order of radius (see ucf_drawdown_batch): the observations are ordered once, here
+    std::vector<int> perm(nobs);
+    for (int i = 0; i < nobs; i++) perm[i] = i;
+    std::stable_sort(perm.begin(), perm.end(), [&](int x, int y) { return r[x] < r[y]; });
+    f->t_s.resize(nobs); f->r_s.resize(nobs); f->z.assign(z, z + nz);
+    std::vector<int> slot(nobs);
+    for (int i = 0; i < nobs; i++) { f->t_s[i] = t[perm[i]]; f->r_s[i] = r[perm[i]]; slot[perm[i]] = i * nz + iz[perm[i]]; }
+    f->refs.resize(nobs);
+    for (int i = 0; i < nobs; i++) f->refs[i] = ucf_fit_obs_ref{0, (long long)nobs * nz, slot[i], 1};
+    f->dense = (long long)nobs * nz;
+    device_switch dg(device);
+    if ((rc = grow_buffer(f->b_slot, sizeof(int) * nobs, "observation places", f->n_alloc)) || (rc = grow_buffer(f->b_obs, sizeof(double) * nobs, "observations", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_w, sizeof(double) * nobs, "weights", f->n_alloc))) { ucf_fit_destroy(f); return rc; }
+    if (hipMemcpy(f->b_slot.p, slot.data(), sizeof(int) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->b_obs.p, obs, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->b_w.p, weight, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess) {
+        ucf_fit_destroy(f);
+        return fail(UCF_ERR_HIP, "upload of the observations failed");
+    }
+    *out = f;
+    return UCF_OK;
+}
+
+void ucf_fit_destroy(ucf_fit* f)
+{
+    if (!f) return;
+    for (ucf_plan* pl : f->plans) ucf_plan_destroy(pl);
+    {
+        device_switch dg(f->device);
+        for (ucf_buffer* b : f->buffers()) free_buffer(*b);
+    }
+    delete f;
+}
+
+int ucf_fit_create_network(const ucf_params* base, int npar, const int* ids, int nwell, const double* well_r, const int* well_nz,
+                           const double* well_z, int nobs, const double* t, const int* well, const int* iz, const double* obs,
+                           const double* weight, int device, ucf_fit** out)
+{
+    if (out) *out = nullptr;
+    if (!base || !out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = validate(*base);
+    if (rc) return rc;
+    rc = fit_check_ids(*base, npar, ids);
+    if (rc) return rc;
+    if (nobs < npar) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: fewer observations than the %d parameters to fit", nobs, npar);
+    if (!well_r || !well_z || !iz || !obs || !weight) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
+    rc = network_check(nwell, well_nz, nobs, t, well);
+    if (rc) return rc;
+    std::vector<int> z0(nwell);
+    int nzs = 0;
+    for (int w = 0; w < nwell; w++) {
+        if (!std::isfinite(well_r[w]) || !(well_r[w] > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "well_r[%d]=%g is not a finite positive radius", w, well_r[w]);
+        z0[w] = nzs;
+        for (int j = 0; j < well_nz[w]; j++)
+            if (!std::isfinite(well_z[nzs + j])) return fail(UCF_ERR_BAD_ARGUMENT, "well_z[%d]=%g (depth %d of well %d) is not finite", nzs + j, well_z[nzs + j], j, w);
+        nzs += well_nz[w];
+    }
+    for (int i = 0; i < nobs; i++) {
+        if (iz[i] < UCF_FIT_SCREEN || iz[i] >= well_nz[well[i]])
+            return fail(UCF_ERR_BAD_ARGUMENT, "iz[%d]=%d outside -1..%d (well %d)", i, iz[i], well_nz[well[i]] - 1, well[i]);
+        if (!(weight[i] >= 0.0) || !std::isfinite(weight[i])) return fail(UCF_ERR_BAD_ARGUMENT, "weight[%d]=%g is negative or not finite", i, weight[i]);
+        if (!std::isfinite(obs[i])) return fail(UCF_ERR_BAD_ARGUMENT, "obs[%d]=%g is not finite", i, obs[i]);
+    }
+    int ndev = 0;
+    rc = ucf_device_count(&ndev);
+    if (rc) return rc;
+    if (device < 0 || device >= ndev) return fail(UCF_ERR_BAD_ARGUMENT, "device %d does not exist (%d visible)", device, ndev);
+    ucf_fit* f = new (std::nothrow) ucf_fit();
+    if (!f) return fail(UCF_ERR_NOMEM, "host allocation failed");
+    f->base = *base; f->npar = npar; f->nobs = nobs; f->nz = 0; f->device = device; f->network = true;
+    for (int j = 0; j < npar; j++) f->ids[j] = ids[j];
+    f->well_r.assign(well_r, well_r + nwell); f->well_nz.assign(well_nz, well_nz + nwell);
+    f->well_z.assign(well_z, well_z + nzs); f->well_z0 = z0;
+    std::vector<int> grp_of, pt_of;
+    long long npoints = 0;
+    network_layout(nwell, well_r, well_nz, nobs, t, well, f->groups, &grp_of, &pt_of, &npoints);
+    f->net_pts = f->groups.back().pt_prefix + f->groups.back().pts;
+    f->net_vals = f->groups.back().prefix + f->groups.back().stride;
+    f->dense = npoints * nzs;
+    f->refs.resize(nobs);
+    for (int i = 0; i < nobs; i++) {
+        const fit_group& G = f->groups[grp_of[i]];
+        const bool screen = iz[i] == UCF_FIT_SCREEN;
+        f->refs[i] = ucf_fit_obs_ref{(long long)G.prefix, (long long)G.stride, pt_of[i] * G.nz + (screen ? 0 : iz[i]), screen ? G.nz : 1};
+    }
+    device_switch dg(device);
+    if ((rc = grow_buffer(f->b_ref, sizeof(ucf_fit_obs_ref) * nobs, "observation places", f->n_alloc)) || (rc = grow_buffer(f->b_obs, sizeof(double) * nobs, "observations", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_w, sizeof(double) * nobs, "weights", f->n_alloc))) { ucf_fit_destroy(f); return rc; }
+    if (hipMemcpy(f->b_ref.p, f->refs.data(), sizeof(ucf_fit_obs_ref) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->b_obs.p, obs, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->b_w.p, weight, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess) {
+        ucf_fit_destroy(f);
+        return fail(UCF_ERR_HIP, "upload of the observations failed");
+    }
+    *out = f;
+    return UCF_OK;
+}
+
+int ucf_fit_eval_counts(const ucf_fit* f, long long* launched, long long* dense)
+{
+    if (!f || !launched || !dense) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    *launched = f->network ? (long long)f->net_vals : f->dense;
+    *dense = f->dense;
+    return UCF_OK;
+}
+
+int ucf_fit_network_eval_counts(int nwell, const int* well_nz, int nobs, const double* t, const int* well, long long* launched,
+                                long long* dense)
+{
+    if (!launched || !dense) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = network_check(nwell, well_nz, nobs, t, well);
+    if (rc) return rc;
+    std::vector<fit_group> groups;
+    long long npoints = 0, nzs = 0;
+    network_layout(nwell, nullptr, well_nz, nobs, t, well, groups, nullptr, nullptr, &npoints);
+    for (int w = 0; w < nwell; w++) nzs += well_nz[w];
+    *launched = groups.empty() ? 0 : (long long)(groups.back().prefix + groups.back().stride);
+    *dense = npoints * nzs;
+    return UCF_OK;
+}
+
+int ucf_fit_debug_h(ucf_fit* f, int plan, int i, int cap, double* h, int* n)
+{
+    if (!f || !h || !n) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (f->last_nplans < 1) return fail(UCF_ERR_BAD_ARGUMENT, "no evaluation to read from");
+    if (plan < 0 || plan >= f->last_nplans) return fail(UCF_ERR_BAD_ARGUMENT, "plan %d outside 0..%d", plan, f->last_nplans - 1);
+    if (i < 0 || i >= f->nobs) return fail(UCF_ERR_BAD_ARGUMENT, "observation %d outside 0..%d", i, f->nobs - 1);
+    const ucf_fit_obs_ref& o = f->refs[i];
+    if (cap < o.count) return fail(UCF_ERR_BAD_ARGUMENT, "cap=%d: observation %d reads %d values", cap, i, o.count);
+    device_switch dg(f->device);
+    const size_t at = (size_t)o.prefix * f->last_nplans + (size_t)plan * o.stride + o.at;
+    HIP_TRY(hipMemcpy(h, (const double*)f->b_h.p + at, sizeof(double) * o.count, hipMemcpyDeviceToHost));
+    *n = o.count;
+    return UCF_OK;
+}
+
+long long ucf_fit_alloc_count(const ucf_fit* f)
+{
+    if (!f) return 0;
+    long long n = f->n_alloc;
+    for (const ucf_plan* pl : f->plans) n += ucf_plan_alloc_count(pl);
+    return n;
+}
+
+int ucf_fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, double* phi, double* g, double* A, int* nbad, double* J,
+                     double* sim_all)
+{
+    return fit_evaluate(f, nsets, theta, dlog, 1, phi, g, A, nbad, J, sim_all);
+}
+
+int ucf_fit_default_options(ucf_fit_options* opt)
+{
+    if (!opt) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    opt->max_iter = 50; opt->dlog = 1.0e-3; opt->lambda0 = 1.0e-2; opt->lambda_up = 10.0; opt->lambda_down = 0.1;
+    opt->tol_step = 1.0e-6; opt->tol_phi = 1.0e-9;
+    return UCF_OK;
+}
+
+int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_options* opt_in, double* theta, double* phi, int* iters,
+               int* status, double* cov)
+{
+    if (!f || !theta0 || !theta || !phi || !iters || !status) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (nstarts < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nstarts=%d: at least one start", nstarts);
+    ucf_fit_options opt;
+    (void)ucf_fit_default_options(&opt);
+    if (opt_in) opt = *opt_in;
+    if (opt.max_iter < 1 || !(opt.dlog > 0.0) || !(opt.lambda0 > 0.0) || !(opt.lambda_up > 1.0) || !(opt.lambda_down > 0.0) || !(opt.lambda_down < 1.0) ||
+        !(opt.tol_step >= 0.0) || !(opt.tol_phi >= 0.0))
+        return fail(UCF_ERR_BAD_ARGUMENT, "bad options: max_iter >= 1, dlog > 0, lambda0 > 0, lambda_up > 1, 0 < lambda_down < 1, tolerances >= 0");
+    const int P = f->npar;
+    const size_t PP = (size_t)P * P;
+    std::vector<double> x((size_t)nstarts * P), lam(nstarts, opt.lambda0), g((size_t)nstarts * P), A(nstarts * PP), step((size_t)nstarts * P);
+    std::vector<char> active(nstarts, 1), needJ(nstarts, 1), first(nstarts, 1);
+    for (int s = 0; s < nstarts; s++) {
+        iters[s] = 0; status[s] = UCF_FIT_MAX_ITER; phi[s] = NAN;
+        for (int j = 0; j < P; j++) {
+            const double v = theta0[(size_t)s * P + j];
+            if (!(v > 0.0) || !std::isfinite(v)) return fail(UCF_ERR_BAD_ARGUMENT, "start %d: parameter %d = %g must be positive and finite", s, j, v);
+            theta[(size_t)s * P + j] = v;
+            x[(size_t)s * P + j] = std::log(v);
+        }
+    }
+    std::vector<int> idx;
+    std::vector<double> th, ph, gg, AA;
+    std::vector<int> nb;
+    int rc = UCF_OK;
+    for (;;) {
+        // 1. objective, gradient and normal equations where the point has moved (one call for all of them)
+        idx.clear();
+        for (int s = 0; s < nstarts; s++) if (active[s] && needJ[s]) idx.push_back(s);
+        if (!idx.empty()) {
+            const int n = (int)idx.size();
+            th.resize((size_t)n * P); ph.resize(n); gg.resize((size_t)n * P); AA.resize(n * PP); nb.resize(n);
+            for (int q = 0; q < n; q++) for (int j = 0; j < P; j++) th[(size_t)q * P + j] = theta[(size_t)idx[q] * P + j];
+            rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), gg.data(), AA.data(), nb.data(), nullptr, nullptr);
+            if (rc) return rc;
+            for (int q = 0; q < n; q++) {
+                const int s = idx[q];
+                needJ[s] = 0;
+                if (first[s]) {
+                    first[s] = 0;
+                    if (nb[q] > 0 || !std::isfinite(ph[q])) { status[s] = UCF_FIT_NONFINITE_START; active[s] = 0; phi[s] = ph[q]; continue; }
+                } else if (nb[q] > 0) {
+                    // the perturbed plans of an accepted point left the finite range: the point stays, its step is damped as after a rejection
+                    lam[s] *= opt.lambda_up;
+                }
+                phi[s] = ph[q];
+                std::memcpy(&g[(size_t)s * P], &gg[(size_t)q * P], sizeof(double) * P);
+                std::memcpy(&A[s * PP], &AA[q * PP], sizeof(double) * PP);
+            }
+        }
+        // 2. damped steps and trial points
+        idx.clear();
+        for (int s = 0; s < nstarts; s++) {
+            if (!active[s]) continue;
+            if (ucf_fit_solve_step(P, &A[s * PP], &g[(size_t)s * P], lam[s], &step[(size_t)s * P]) != UCF_OK) { status[s] = UCF_FIT_SINGULAR; active[s] = 0; continue; }
+            idx.push_back(s);
+        }
+        if (idx.empty()) break;
+        const int n = (int)idx.size();
+        th.resize((size_t)n * P); ph.resize(n); nb.resize(n);
+        for (int q = 0; q < n; q++)
+            for (int j = 0; j < P; j++) th[(size_t)q * P + j] = std::exp(x[(size_t)idx[q] * P + j] + step[(size_t)idx[q] * P + j]);
+        bool finite_trial = true;
+        for (double v : th) finite_trial = finite_trial && std::isfinite(v) && v > 0.0;
+        if (finite_trial) {
+            rc = fit_evaluate(f, n, th.data(), opt.dlog, 0, ph.data(), nullptr, nullptr, nb.data(), nullptr, nullptr);
+            if (rc != UCF_OK && rc != UCF_ERR_BAD_ARGUMENT && rc != UCF_ERR_HIP && rc != UCF_ERR_NOMEM && rc != UCF_ERR_NO_DEVICE) finite_trial = false;   // a trial outside the model's range: rejected below
+            else if (rc) return rc;
+        }
+        // 3. accept or reject, per start
+        for (int q = 0; q < n; q++) {
+            const int s = idx[q];
+            iters[s]++;
+            double smax = 0.0;
+            for (int j = 0; j < P; j++) smax = std::fmax(smax, std::fabs(step[(size_t)s * P + j]));
+            const bool ok = finite_trial && nb[q] == 0 && std::isfinite(ph[q]) && ph[q] <= phi[s];
+            bool done = smax <= opt.tol_step;
+            if (ok) {
+                if (phi[s] - ph[q] <= opt.tol_phi * phi[s]) done = true;
+                for (int j = 0; j < P; j++) { x[(size_t)s * P + j] += step[(size_t)s * P + j]; theta[(size_t)s * P + j] = th[(size_t)q * P + j]; }
+                phi[s] = ph[q];
+                lam[s] *= opt.lambda_down;
+                needJ[s] = 1;
+            } else {
+                lam[s] *= opt.lambda_up;
+                if (!std::isfinite(lam[s])) done = true;
+            }
+            if (done) { status[s] = UCF_FIT_CONVERGED; active[s] = 0; }
+            else if (iters[s] >= opt.max_iter) { status[s] = UCF_FIT_MAX_ITER; active[s] = 0; }
+        }
+    }
+    if (cov) {
+        // cov = phi / (nobs - npar) A^-1 at the final point (NaN where A is singular, the start was not finite or nobs == npar)
+        for (size_t i = 0; i < nstarts * PP; i++) cov[i] = NAN;
+        idx.clear();
+        for (int s = 0; s < nstarts; s++) if (status[s] != UCF_FIT_NONFINITE_START) idx.push_back(s);
+        if (!idx.empty() && f->nobs > P) {
+            const int n = (int)idx.size();
+            th.resize((size_t)n * P); ph.resize(n); AA.resize(n * PP); nb.resize(n);
+            for (int q = 0; q < n; q++) for (int j = 0; j < P; j++) th[(size_t)q * P + j] = theta[(size_t)idx[q] * P + j];
+            rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), nullptr, AA.data(), nb.data(), nullptr, nullptr);
+            if (rc) return rc;
+            for (int q = 0; q < n; q++) {
+                const int s = idx[q];
+                double e[UCF_FIT_MAX_PAR], col[UCF_FIT_MAX_PAR];
+                bool good = nb[q] == 0;
+                for (int j = 0; j < P && good; j++) {
+                    for (int k = 0; k < P; k++) e[k] = (k == j) ? 1.0 : 0.0;
+                    good = ucf_fit_solve_step(P, &AA[q * PP], e, 0.0, col) == UCF_OK;
+                    for (int k = 0; k < P && good; k++) cov[s * PP + (size_t)k * P + j] = phi[s] / (double)(f->nobs - P) * col[k];
+                }
+                if (!good) for (size_t i = 0; i < PP; i++) cov[s * PP + i] = NAN;
+            }
+        }
+    }
+    return UCF_OK;
+}
+
+}  // extern "C"

@@ -1,4 +1,4 @@
-// ucf_fit.h -- launcher of the fit reduction (ucf_fit.hip), called by ucf_fit_evaluate (ucf_api.cpp).
+// ucf_fit.h -- launcher of the fit reduction (ucf_fit.hip), called by ucf_fit_evaluate (ucf_fit.cpp).
 #pragma once
 
 // sums per parameter set: phi | g[npar] | upper triangle of A, row by row (j <= k)

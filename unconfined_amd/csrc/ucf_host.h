@@ -1,0 +1,126 @@
+// ucf_host.h -- what the host sources of the library share (ucf_api.cpp, ucf_plan.cpp, ucf_drawdown.cpp, ucf_multi.cpp,
+// ucf_debug.cpp, ucf_fit.cpp, ucf_field.cpp).  Internal: everything is in namespace ucf_host with hidden visibility, so
+// the names link between the objects and are not exported from libucf.so.  Declarations only; the comment that explains
+// a function stands at its definition, in the file named here.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <functional>
+#include <vector>
+
+#include "ucf_plan.h"
+
+#define HIP_TRY(expr)                                                                          \
+    do {                                                                                       \
+        hipError_t e_ = (expr);                                                                \
+        if (e_ != hipSuccess) return fail(UCF_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+namespace ucf_host __attribute__((visibility("hidden"))) {
+
+// ---- ucf_api.cpp
+int fail(int code, const char* fmt, ...);      // sets what ucf_last_error() returns; returns code
+
+// What differs between the two builds of the kernels (ucf_kernels_*.hip), indexed by ucf_plan::mode: 0 faithful, 1 fast.
+struct ucf_flavour {
+    decltype(&ucf_fast::launch_points) launch_points, launch_grid_transposed, launch_points_chunked, launch_points_lanes;
+    decltype(&ucf_fast::launch_samples) launch_samples;
+    decltype(&ucf_fast::state_bytes_per_item) state_bytes_per_item;
+    decltype(&ucf_fast::lt_table_bytes) lt_table_bytes;
+    decltype(&ucf_fast::launch_wynn_regs) launch_wynn_regs;
+    decltype(&ucf_fast::launch_dehoog_tiles_hook) launch_dehoog_tiles_hook;
+};
+const ucf_flavour& flavour(int mode);
+inline const ucf_flavour& flavour_of(const ucf_plan* pl) { return flavour(pl->mode); }
+
+int launch_failed(int rc, const ucf_dev_params& dp);
+void stats_add(ucf_stats& a, const ucf_stats& b);
+int require_device();
+
+// Host point lists are evaluated in order of radius (ucf_drawdown_batch says why): the order, and the way back
+struct radius_order {
+    std::vector<int> perm;       // perm[i]: the caller's index of the i-th point in order of radius
+    radius_order(int npts, const double* r);
+    template <class T>
+    std::vector<T> gather(const T* v) const;      // (double and int)
+    // hs, ds: [nblk][npts][nz] in order of radius -> h, dh in the caller's order
+    void scatter(int nblk, int nz, const double* hs, const double* ds, double* h, double* dh) const;
+};
+
+// runs the rest of the scope with HIP device `dev` current (a process may drive several devices: ucf_drawdown_grid_multi)
+struct device_switch {
+    int prev = -1;
+    bool switched = false;
+    explicit device_switch(int dev)
+    {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = (hipSetDevice(dev) == hipSuccess);
+    }
+    ~device_switch() { if (switched) (void)hipSetDevice(prev); }
+};
+
+// device buffers.  guarded_malloc is the one allocator (UCF_GUARD); dev_buf lives for one call; a ucf_buffer that an
+// owner (ucf_fit, ucf_field) keeps between calls grows through grow_buffer and goes through free_buffer; the workspaces
+// of a plan have a policy of their own (ws_ensure)
+hipError_t guarded_malloc(void** p, void** base, size_t bytes);
+struct dev_buf {
+    void* p = nullptr;
+    void* base = nullptr;
+    ~dev_buf() { if (base) (void)hipFree(base); }
+    int alloc(size_t bytes) { return guarded_malloc(&p, &base, bytes) == hipSuccess ? 0 : 1; }
+};
+int grow_buffer(ucf_buffer& b, size_t bytes, const char* what, long long& n_alloc);
+void free_buffer(ucf_buffer& b);
+
+// ---- ucf_plan.cpp
+int validate(const ucf_params& P);
+void nondimensionalise(const ucf_params& P, ucf_derived& D);
+int z_chunk(const ucf_plan* plan);
+int fill_call_params(const ucf_plan* plan, int nz, const double* zD, const int* zLay, ucf_dev_params& dp, int nz_out = 0, int z_off = 0);
+void split_vector(const int* j0s, int nt, const double* tD, int* sv);
+
+// ---- ucf_drawdown.cpp
+ucf_workspace* ws_for(ucf_plan* pl, void* stream);
+void ws_destroy(ucf_workspace* ws);
+hipStream_t plan_stream(ucf_plan* pl);
+int ws_ensure(ucf_plan* pl, ucf_workspace* ws, ucf_buffer& b, size_t bytes, const char* what);
+// state of a work item between integrate_kernel and point_kernel (fast flavour, Hantush-based models)
+inline size_t state_item_bytes(const ucf_plan* pl, const ucf_dev_params& dp) { return flavour_of(pl).state_bytes_per_item(dp); }
+// abscissa-table bytes per chunk of an arbitrary point list (UCF_TABLE_BYTES, default 256 MiB)
+inline size_t table_budget() { return ucf_env_get().table_bytes; }
+int launch_points_any(ucf_plan* pl, ucf_workspace* ws, const ucf_launch& call, int npts_call);
+int batch_device_impl(ucf_plan* pl, ucf_workspace* ws, int npts, const double* d_tD, const double* d_rD, const int* d_sv,
+                      int nz, const double* zD, const int* zLay, double* d_h, double* d_dh, ucf_stats* d_stats, void* stream,
+                      bool presorted);
+int grid_device_locked(ucf_plan* pl, ucf_workspace* ws, int nt, const double* d_tD, const int* d_sv, int nr, const double* d_rD,
+                       int nz, const double* zD, const int* zLay, double* d_h, double* d_dh, ucf_stats* d_stats, void* stream);
+int check_grid_args(const ucf_plan* pl, int nt, const void* d_tD, const void* d_sv, int nr, const void* d_rD, int nz, const double* zD,
+                    const int* zLay, const void* d_h, const void* d_dh);
+int check_batch_args(const ucf_plan* pl, int npts, const void* tD, const void* rD, const void* sv, int nz, const double* zD,
+                     const int* zLay, const void* h, const void* dh);
+int check_sv(const ucf_plan* pl, int n, const int* sv);
+int check_grid_sv_of(const ucf_params& P, const ucf_derived& D, int nt, const int* sv);
+int check_grid_sv(const ucf_plan* pl, int nt, const int* sv);
+int check_depths(int nz, const int* zLay);
+
+// ---- ucf_multi.cpp
+// What one pass of the shared core reads and writes: host staging (kept between calls by an owner that calls often) and
+// device arrays that the CALLER owns -- d_t, d_r, d_s: nplans x npts, d_h, d_d: nplans x npts x nz.
+struct multi_io {
+    std::vector<double> tD, rD, zD;
+    std::vector<int> sv, zl;
+    std::vector<ucf_dev_params> dps;       // parameter blocks of a shared launch
+    double* d_t = nullptr;
+    double* d_r = nullptr;
+    int* d_s = nullptr;
+    double* d_h = nullptr;
+    double* d_d = nullptr;
+};
+bool plans_share_launch(ucf_plan* const* plans, int nplans);
+// fill(z0, nzc, dps) writes the parameter blocks of depths [z0, z0 + nzc): once per depth chunk
+typedef std::function<int(int z0, int nzc, std::vector<ucf_dev_params>& dps)> fill_blocks;
+int shared_launch(ucf_plan* pl, int nblk, int ppp, int nz, const fill_blocks& fill, std::vector<ucf_dev_params>& dps, const double* d_t,
+                  const double* d_r, const int* d_s, double* d_h, double* d_d);
+int stream_pool(int device, int want, hipStream_t* streams);
+int multi_core(ucf_plan* const* plans, int nplans, int npts, const double* t, const double* r, int nz, const double* z, multi_io& io);
+
+}  // namespace ucf_host

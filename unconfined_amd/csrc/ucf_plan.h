@@ -99,7 +99,8 @@ struct ucf_debug_rec {
 // Everything a call in flight writes.  A plan keeps one workspace per HIP stream that has called into it, so calls on
 // different streams never share scratch; calls that name the same stream are enqueued under the workspace's lock and
 // run in stream order.  Buffers only ever grow; a buffer that is outgrown is RETIRED (kept until ucf_plan_reserve /
-// ucf_plan_destroy), never freed while kernels may still read it -- no synchronisation inside the *_device entries.
+// ucf_plan_destroy), never freed while kernels may still read it -- no synchronisation inside the *_device entries.  ws_buffers
+// (ucf_drawdown.cpp) lists the buffers of a workspace: a new one goes there too.
 struct ucf_buffer {
     void* p = nullptr;
     size_t bytes = 0;
@@ -189,7 +190,7 @@ int launch_extrap(int n, int R, const double* d_x, const double* d_y, double* d_
 int launch_debug_gather(const ucf_dev_params& dp, int layout, int nwork, int per_point, int nr, int nt, int ir0, const double* d_state,
                         const int* d_ndone, double* d_out_state, int* d_out_ndone, void* stream);
 }
-// what both flavours define, entry by entry the ucf_flavour table of ucf_api.cpp.  state_bytes_per_item: bytes of integrate
+// what both flavours define, entry by entry the ucf_flavour table (ucf_host.h, filled in ucf_api.cpp).  state_bytes_per_item: bytes of integrate
 // kernel -> finish / point kernel state per work item (0: the model has no integrate kernel)
 namespace ucf_faithful {
 int launch_points(const ucf_launch& L);             // lane layout 0
