@@ -70,7 +70,7 @@ int ucf_debug_stages(ucf_plan* pl, int grid, int nt, const double* tD, const int
     if (state_item_bytes(pl, dp) != 0 && ws->state.p) {
         info[1] = slots;
         rc = ucf_faithful::launch_debug_gather(dp, rec.layout, rec.nwork, rec.per_point, rec.nr, rec.nt, rec.ir0, (const double*)ws->state.p,
-                                               (const int*)ws->ndone.p, (double*)b_os.p, (int*)b_on.p, nullptr);
+                                               (const int*)ws->ndone.p + buffers_of(pl, dp, rec.nwork, 0).ndone, (double*)b_os.p, (int*)b_on.p, nullptr);
         if (rc) return fail(rc, "gather kernel launch failed");
         HIP_TRY(hipStreamSynchronize(nullptr));
         HIP_TRY(hipMemcpy(state, b_os.p, nb * np * slots * 2, hipMemcpyDeviceToHost));

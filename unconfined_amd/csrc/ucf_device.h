@@ -68,9 +68,7 @@ UCF_DEV void stat_add(long long* ctr, bool pred)
 typedef double2 lds_c;   // one complex per lane per slot
 UCF_DEV cplx lds_ld(const lds_c* base, int slot, int lane) { lds_c v = base[slot * UCF_WAVE + lane]; return cmake(v.x, v.y); }
 UCF_DEV void lds_st(lds_c* base, int slot, int lane, cplx z) { base[slot * UCF_WAVE + lane] = make_double2(z.re, z.im); }
-// scratch columns hold UCF_PART lanes per slot: the per-lane tails (Neville, Wynn) run on one
-// quarter-wave at a time, which quarters their LDS footprint at ~2 % of the point's time
-#define UCF_PART 16
+// scratch columns hold UCF_PART lanes per slot (ucf_launch_plan.h)
 // (finish_kernel picks wider parts when its LDS budget allows: PART lanes work at a time, 64/PART turns)
 template <int PART = UCF_PART>
 UCF_DEV cplx scr_ld(const lds_c* base, int slot, int lane) { lds_c v = base[slot * PART + (lane & (PART - 1))]; return cmake(v.x, v.y); }
@@ -1319,7 +1317,6 @@ UCF_DEV work_item decode_item(const ucf_dev_params& P, int pt, int lane, int per
 // J0-interval areas, then the transform goes to the workspace (LAYOUT 1, 2) or straight through de Hoog
 // (LAYOUT 0).  accTS: [R][nz] level sums in LDS; the finished areas come from LDS (accGL) or global memory.
 // PART lanes of the wave work at a time on the scratch columns scr ([max(2 nacc, R)][PART]).
-#define UCF_WYNN_REGS 12      /* terms the register-resident Wynn-epsilon of finish_kernel holds */
 // MODE (finish_kernel, WREG, fast flavour): 0 = everything here; 1 = the unguarded epsilon table only -- a (item, depth) in
 // which some lane needs one of the reference's guards (:297-311: a zero difference, the early exit, an all-zero series) is
 // appended to the list `defer` = [count | pt * nz + z ...] and left alone; 2 = the depths [z0, z1) of a listed item with the
@@ -1568,16 +1565,6 @@ laptime_kernel(const ucf_dev_params P0, int nrows, const double* __restrict__ tD
 // The level sums, the running interval area and the finished interval areas go to the item's state
 // (HBM, written once, coalesced 1 KB per slot); point_kernel resumes from there: remaining abscissae
 // with the generic evaluator (the overflow regime the fast one leaves alone), Richardson, Wynn, de Hoog.
-#ifndef UCF_FOLD_WAVES
-#define UCF_FOLD_WAVES 5
-#endif
-#ifndef UCF_UNFOLD_WAVES
-#define UCF_UNFOLD_WAVES 4
-#endif
-// parts (2^k) of the work items of the last round of a launch (launch_transform_)
-#ifndef UCF_TAIL_LSPLIT_DEFAULT
-#define UCF_TAIL_LSPLIT_DEFAULT 3
-#endif
 // constants of sincos_tab_ / exp_tab_ kept in VGPRs (sc_ctx::kv)
 #ifndef UCF_KV
 #define UCF_KV(FAMILY, FOLD) ((FAMILY) == 4 ? 0 : 4)
@@ -2356,560 +2343,8 @@ extrap_kernel(int n, int R, const double* __restrict__ x, const double* __restri
 }
 #endif
 
-// ------------------------------------------------------------------ launchers
-#ifdef UCF_PROBE      /* tools/probe_kernel.sh: one kernel instantiation on its own (seconds instead of minutes), no launchers */
+#ifdef UCF_PROBE      /* tools/probe_kernel.sh: one kernel instantiation on its own (seconds instead of minutes; the launchers are in ucf_launchers.h) */
 const void* ucf_probe_kernel_address = (const void*)&UCF_PROBE;
-#else
-static inline int family_of(const ucf_dev_params& dp)
-{
-    switch (dp.model) {
-    case 0: return 0;
-    case 1: return 1;
-    case 2: return 5;
-    case 3: case 4: case 5: return 2;
-    case 6: return dp.MNtype == 1 ? 3 : (dp.MNtype == 2 ? 4 : -1);
-    default: return -1;
-    }
-}
-
-// finished interval areas stay in LDS while the footprint still admits 8 single-wave workgroups per CU
-static inline bool areas_in_lds(const ucf_dev_params& dp)
-{
-    const size_t with_areas = ((size_t)(dp.R + 1 + dp.nacc) * dp.nz * UCF_WAVE + (size_t)(2 * dp.nacc > dp.R ? 2 * dp.nacc : dp.R) * UCF_PART) * sizeof(lds_c);
-    return with_areas <= 20 * 1024;
-}
-
-static inline size_t point_lds_bytes(const ucf_dev_params& dp, bool resume = false)
-{
-    size_t bytes = ((size_t)(dp.R + 1 + ((areas_in_lds(dp) && !resume) ? dp.nacc : 0)) * dp.nz * UCF_WAVE + (size_t)(2 * dp.nacc > dp.R ? 2 * dp.nacc : dp.R) * UCF_PART) * sizeof(lds_c);
-#if !UCF_FAST
-    if (family_of(dp) == 4) bytes += 2 * (size_t)dp.order * UCF_WAVE * sizeof(lds_c);
 #endif
-    return bytes;
-}
-
-#if !UCF_FAST
-// (time, radius) grid -> the point list it stands for, point = it * nr + ir (the grid's own output order)
-__global__ void __launch_bounds__(256)
-expand_grid_kernel(int nt, int nr, const double* __restrict__ tDv, const int* __restrict__ svv, const double* __restrict__ rDv,
-                   double* __restrict__ tDp, double* __restrict__ rDp, int* __restrict__ svp)
-{
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= (long long)nt * nr) return;
-    const int it = (int)(q / nr), ir = (int)(q % nr);
-    tDp[q] = tDv[it];
-    svp[q] = svv[it];
-    rDp[q] = rDv[ir];
-}
-int launch_expand_grid(int nt, int nr, const double* d_tD, const int* d_sv, const double* d_rD, double* d_tDp, double* d_rDp,
-                       int* d_svp, void* stream)
-{
-    const long long n = (long long)nt * nr;
-    hipLaunchKernelGGL(expand_grid_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, nt, nr, d_tD, d_sv, d_rD,
-                       d_tDp, d_rDp, d_svp);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-
-int launch_abscissae(const ucf_dev_params& dp, int nrows, int per_point, int nsv, int svmin, const double* d_rD,
-                     const int* d_sv, double* d_tab, void* stream)
-{
-    const long long total = (long long)nrows * (dp.N + dp.nacc * dp.ngl);
-    const int threads = 256;
-    const long long blocks = (total + threads - 1) / threads;
-    hipLaunchKernelGGL(abscissa_kernel, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, dp, nrows, per_point,
-                       nsv, svmin, d_rD, d_sv, (double2*)d_tab);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-#endif
-
-// How the abscissa loop is run: 0 inside point_kernel; 1 integrate_kernel with the fast evaluators (fast flavour,
-// Hantush-based models), point_kernel resumes the items it leaves unfinished; 2 integrate_generic_kernel with the
-// reference-order evaluators (everything else, unless the finite-difference Thomas buffer makes the footprint huge)
-static inline int split_kind(const ucf_dev_params& dp)
-{
-    const int fam = family_of(dp);
-#if UCF_FAST
-    if (fam >= 0 && fam <= 5) return 1;
-#else
-    if (fam == 4 && 2 * (size_t)dp.order * UCF_WAVE * sizeof(lds_c) > 16 * 1024) return 0;
-#endif
-    return 2;
-}
-#if UCF_TU_HAS(1)
-// bytes of state per work item (0: no state needed)
-size_t state_bytes_per_item(const ucf_dev_params& dp)
-{
-    return split_kind(dp) ? (size_t)(dp.R + 1 + dp.nacc) * dp.nz * UCF_WAVE * sizeof(lds_c) : 0;
-}
-#if UCF_FAST
-// bytes of the lapTime table of a launch over `rows` rows of tD (behind the state in the same buffer; laptime_kernel)
-size_t lt_table_bytes(const ucf_dev_params& dp, size_t rows)
-{
-    return split_kind(dp) == 1 ? rows * dp.np * sizeof(lds_c) : 0;
-}
-#endif
-#endif
-
-// The transform stage for `nwork` work items of lane layout LAYOUT: [integrate kernel -> finish_kernel ->] point_kernel.
-// tm (optional): every kernel of the stage is bracketed by HIP events on the launch stream (ucf_timers).
-// (L.npts is not read here: nwork, from the layout launcher, says how much there is to do)
-template <int LAYOUT, bool MULTI>
-static int launch_transform_(const ucf_launch& L, int nwork)
-{
-    const ucf_env& env = ucf_env_get();
-    const ucf_dev_params& dp = *L.dp;
-    const int per_point = L.per_point, nr = L.nr, nsv = L.nsv, svmin = L.svmin, nt = L.nt, ir0 = L.ir0, nrc = L.nrc;
-    const double *d_tD = L.tD, *d_rD = L.rD, *d_tab = L.tab;
-    const int* d_sv = L.sv;
-    double *d_h = L.h, *d_dh = L.dh, *d_totlap = L.totlap, *d_glscr = L.glscr, *d_state = L.state;
-    int* d_ndone = L.ndone;
-    ucf_stats* const d_stats = L.stats;
-    ucf_timers* const tm = L.tm;
-    // only a parameter batch reads these
-    const ucf_dev_params* d_params = MULTI ? L.params : nullptr;
-    const int ppp = MULTI ? L.ppp : 1, pbase = MULTI ? L.pbase : 0;
-    char kname[96];
-    int* d_todo = d_ndone ? d_ndone + nwork : nullptr;     // [count | items]: the caller sizes d_ndone for 2 nwork + 1 ints
-    const int fam = family_of(dp);
-    if (fam < 0) return UCF_ERR_UNSUPPORTED;
-    const int kind = split_kind(dp);
-    const bool split = kind != 0;
-    if (split && (!d_state || !d_ndone)) return UCF_ERR_BAD_ARGUMENT;
-    const size_t lds = point_lds_bytes(dp, split);
-    if (lds > 160 * 1024) return UCF_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)L.stream;
-    const bool al = areas_in_lds(dp) || split;
-    if (al) d_glscr = nullptr;
-    if (!split) { d_state = nullptr; d_ndone = nullptr; d_todo = nullptr; }
-    dim3 grid((unsigned)((al || nwork < env.grid_slots) ? nwork : env.grid_slots)), block(UCF_WAVE);
-    if (split) {
-        (void)hipMemsetAsync(d_todo, 0, sizeof(int), s);
-    }
-#if UCF_FAST
-    if (kind == 1) {
-        // every item starts as "all abscissae done"; the parts that must stop lower it (integrate_kernel)
-        (void)hipMemsetD32Async((hipDeviceptr_t)d_ndone, dp.N + dp.nacc * dp.ngl, (size_t)nwork, s);
-        // parts per item: launches of fewer than ~8 rounds of resident waves (256 CUs x 4 SIMDs x <= 6 waves) run two parts
-        // per item -- measured on the 1/8 shard of C2 (27 136 items, tools/gpu_shard.sh): 5.37 / 5.26 / 5.35 / 5.58 ms with
-        // 1 / 2 / 4 / 8 parts (every part pays the item's set-up again).  UCF_NSPLIT (diagnostic): force 1, 2, 4 or 8 parts.
-        const int force_split = env.nsplit;
-        int lsplit = 0;
-        while (lsplit < 1 && ((long long)nwork << lsplit) < 8LL * 256 * 4 * 6) lsplit++;
-        if (force_split > 0) { lsplit = 0; while ((1 << (lsplit + 1)) <= force_split && lsplit < 3) lsplit++; }
-        if ((1 << lsplit) > dp.nacc + 1) lsplit = 0;
-        // ... and the last items of EVERY launch run in finer parts: ntail = one round of resident waves, 2^ltail parts each
-        // (UCF_TAIL_ITEMS / UCF_TAIL_LSPLIT: diagnostic overrides; UCF_TAIL_LSPLIT=0 turns the finer tail off).  Measured
-        // (tools/gpu_tail_parts.sh): C2 34.78 -> 34.64 ms, its 1/8 shard 4.835 -> 4.79 ms with 8 parts for the last 5 120
-        // items (2 or 4 parts, or 10 240 items: the same within 0.2 %) -- a small gain: a wave on an emptying SIMD does
-        // speed up enough to hide most of the quantisation of a launch into rounds.  Bit-neutral like every cut
-        // (test_results_do_not_depend_on_how_work_items_are_cut).
-        const int tail_ls_env = env.tail_lsplit, tail_items_env = env.tail_items;
-        int ltail = tail_ls_env >= 0 ? tail_ls_env : UCF_TAIL_LSPLIT_DEFAULT;
-        if (ltail > 3) ltail = 3;
-        while (ltail > 0 && (1 << ltail) > dp.nacc + 1) ltail--;
-        if (ltail < lsplit) ltail = lsplit;
-        int ntail = tail_items_env >= 0 ? tail_items_env : 256 * 4 * 5;
-        if (ntail > nwork) ntail = nwork;
-        const int nhead = (ltail == lsplit) ? nwork : nwork - ntail;
-        const long long nworkw = ((long long)nhead << lsplit) + ((long long)(nwork - nhead) << ltail);
-        if (nworkw > 0x7fffffffLL) return UCF_ERR_UNSUPPORTED;
-        // per workgroup: the sin/cos table + UCF_IWPB waves' accumulators; wlds = the footprint one wave accounts for
-        const size_t wlds = (size_t)(dp.R + 1) * dp.nz * UCF_WAVE * sizeof(lds_c) + UCF_SC_ENTRIES * sizeof(lds_c) / UCF_IWPB;
-        const size_t ilds = wlds * UCF_IWPB;
-        // persistent grid: at most 8 workgroups per CU (more than any register / LDS budget admits; the ones that do not fit
-        // start when others have finished and find the counter exhausted).  UCF_PERSIST=0 (diagnostic): one workgroup per
-        // UCF_IWPB work units, as before round 3's last pass
-        const bool persist = env.persist;
-        const long long nwg = (nworkw + UCF_IWPB - 1) / UCF_IWPB;
-        const dim3 igrid((unsigned)((persist && nwg > 256 * 8) ? 256 * 8 : nwg)), iblock(UCF_WAVE * UCF_IWPB);
-        int* const d_wcount = d_ndone + 2 * (size_t)nwork + 2 + (size_t)nwork * dp.nz;      // behind the deferred list (finish_kernel)
-        if (persist) (void)hipMemsetAsync(d_wcount, 0, sizeof(int), s);
-        // lapTime(p) x constants for every (row of the call's tD, m): rows = the times of a grid / the points of a list.
-        // The table lives behind the state of this launch's work items (the caller sized the buffer for it: lt_table_bytes)
-        // (LAYOUT 1: the nt times; 3: the nt points of the launch; 0 / 2: the points, or -- a small grid walked point by point,
-        //  per_point = 0 -- the time rows those points stand on: tD has no more entries than that)
-        const int npts_l = (LAYOUT == 2) ? nwork / ((dp.np + UCF_WAVE - 1) / UCF_WAVE) : nwork;
-        const int nrows = (LAYOUT == 1 || LAYOUT == 3) ? nt : (per_point ? npts_l : (npts_l + nr - 1) / nr);
-        double* const d_ltab = d_state + (size_t)nwork * (dp.R + 1 + dp.nacc) * dp.nz * UCF_WAVE * 2;
-        {
-            const long long nlt = (long long)nrows * dp.np;
-            const dim3 lgrid((unsigned)((nlt + 255) / 256)), lblock(256);
-#define UCF_LAUNCH_LT(F) hipLaunchKernelGGL((laptime_kernel<F, MULTI>), lgrid, lblock, 0, s, dp, nrows, d_tD, (double2*)d_ltab, d_params, ppp, pbase)
-            ucf_tm_mark(tm, UCF_STR(UCF_NS) "::laptime_kernel", s);
-            switch (fam) {
-            case 0: UCF_LAUNCH_LT(0); break;
-            case 1: UCF_LAUNCH_LT(1); break;
-            case 2: UCF_LAUNCH_LT(2); break;
-            case 3: UCF_LAUNCH_LT(3); break;
-            case 4: UCF_LAUNCH_LT(4); break;
-            case 5: UCF_LAUNCH_LT(5); break;
-            }
-#undef UCF_LAUNCH_LT
-        }
-        const bool nzc2_on = env.nzc2;      // diagnostic: 0 = off
-#define UCF_LAUNCH_I4(F, W, FO, L3, NZC, L1, NF)                                                                     \
-    do {                                                                                                       \
-        const size_t ilds = ((size_t)((NZC) ? dp.R : dp.R + 1) * dp.nz * UCF_WAVE * sizeof(lds_c)) * UCF_IWPB + UCF_SC_ENTRIES * sizeof(lds_c); \
-        if (ilds > 64 * 1024)                                                                                  \
-            (void)hipFuncSetAttribute((const void*)integrate_kernel<F, LAYOUT, W, MULTI, FO, L3, NZC, L1, NF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds); \
-        std::snprintf(kname, sizeof(kname), UCF_STR(UCF_NS) "::integrate_kernel<%d, %d, %d, %s, %s, %s, %d, %s, %s>", F, LAYOUT, W, MULTI ? "true" : "false", FO ? "true" : "false", L3 ? "true" : "false", NZC, L1 ? "true" : "false", NF ? "true" : "false"); \
-        ucf_tm_mark(tm, kname, s);                                                                             \
-        hipLaunchKernelGGL((integrate_kernel<F, LAYOUT, W, MULTI, FO, L3, NZC, L1, NF>), igrid, iblock, ilds, s, dp, nwork, per_point, nr, nsv, svmin, \
-                           d_tD, d_rD, d_sv, (const double2*)d_tab, nt, ir0, (double2*)d_state, d_ndone, d_todo, d_params, ppp, pbase, lsplit | (ltail << 8), \
-                           (const double2*)d_ltab, nrows, nhead << lsplit, (int)nworkw, persist ? d_wcount : (int*)nullptr);                                                     \
-    } while (0)
-    // launches of ONE depth of the fully penetrating water-table family in the lane = time layout (the headline sweep) run
-    // an instantiation that knows nz = 1 at compile time: no depth loop, no running area in LDS (measured on C2: -2.4 %).
-    // Only there: the unfolded and the finite-difference kernels LOSE 12 ... 46 % to it (C2pp 88 -> 100 ms, C4 237 -> 266,
-    // C5 204 -> 297: the compiler hoists the depth's constants into registers those kernels do not have)
-    // Launches of TWO depths in that layout (a screened observation well, C3; every pair of depths of a contour-style call,
-    // which the host walks two at a time) run NZC = 2 in every family: the two running areas in registers, so that the wave's
-    // LDS holds the level sums alone and a fourth workgroup fits the CU (C3 130.5 -> 115.2 ms per launch; 21-depth calls on
-    // 128 x 64 points: +5 ... +27 %, Theis +52 %; tools/gpu_depths.sh).  UCF_NZC2=0 (diagnostic) turns it off.
-#ifndef UCF_NZC
-#define UCF_NZC(F, FO) (LAYOUT == 1 && (F) == 2 && (FO) ? 1 : 0)
-#endif
-#ifndef UCF_NZC2
-#define UCF_NZC2(F, FO) ((LAYOUT == 1 || LAYOUT == 3) ? 2 : 0)
-#endif
-#define UCF_LAUNCH_I3(F, W, FO, L3, L1, NF)                                                                    \
-    do {                                                                                                       \
-        if (UCF_NZC(F, FO) && dp.nz == 1) UCF_LAUNCH_I4(F, W, FO, L3, UCF_NZC(F, FO), L1, NF);                 \
-        else if (UCF_NZC2(F, FO) && dp.nz == 2 && nzc2_on) UCF_LAUNCH_I4(F, W, FO, L3, UCF_NZC2(F, FO), L1, NF); \
-        else UCF_LAUNCH_I4(F, W, FO, L3, 0, L1, NF);                                                           \
-    } while (0)
-        // a depth above the screen top anywhere in the call (in any plan of a parameter batch)?
-        const bool lay3 = dp.any_lay3 != 0;
-        // ... below the screen bottom?  Three instantiations of an unfolded kernel: every layer / beside and below the screen /
-        // beside the screen only (the usual piezometer or observation well)
-        const bool lay1 = dp.any_lay1 != 0;
-#define UCF_LAUNCH_FOLD(F, W) UCF_LAUNCH_I3(F, W, true, false, true, false)
-        // neither screen term folds (d > 0 and l < b: the usual partially penetrating well) -- known at compile time in an
-        // instantiation of its own (NOFOLD, ucf_fastpath.h); a plan that folds exactly one term, and a parameter batch with
-        // such a plan or a fully penetrating one in it, run the general one.  UCF_NOFOLD=0 (diagnostic): always the general one
-        const bool nofold = env.nofold && !dp.any_fold;
-#define UCF_LAUNCH_UNF_(F, W, NF)                                                                              \
-    do {                                                                                                       \
-        if (lay3) UCF_LAUNCH_I3(F, W, false, true, true, NF);                                                  \
-        else if (lay1) UCF_LAUNCH_I3(F, W, false, false, true, NF);                                            \
-        else UCF_LAUNCH_I3(F, W, false, false, false, NF);                                                     \
-    } while (0)
-#define UCF_LAUNCH_UNF(F, W)                                                                                   \
-    do {                                                                                                       \
-        if (nofold) { UCF_LAUNCH_UNF_(F, W, true); break; }                                                    \
-        UCF_LAUNCH_UNF_(F, W, false);                                                                          \
-    } while (0)
-        // fully penetrating pumping well (every plan of a parameter batch must be): the screen terms are compiled out
-        const bool fold = dp.fold_dD && dp.fold_lD1 && !MULTI;
-        // two depths of the water-table family in the lane = time layout: running areas in registers (NZC = 2), level sums
-        // alone in LDS -- at R = 4 a workgroup then needs 38 instead of 46 KB and FOUR of them fit a CU (measured on C3:
-        // 130.5 -> 115.2 ms per launch with the 4-waves register budget; 127.3 ms with 3)
-        const bool nzc2 = UCF_NZC2(2, false) != 0 && fam == 2 && nzc2_on && dp.nz == 2;
-        const size_t wlds_eff = (nzc2 || (UCF_NZC(2, true) != 0 && fam == 2 && fold && dp.nz == 1))
-                                    ? (size_t)dp.R * dp.nz * UCF_WAVE * sizeof(lds_c) + UCF_SC_ENTRIES * sizeof(lds_c) / UCF_IWPB : wlds;
-        const bool w5 = wlds_eff * 20 <= 160 * 1024;
-        // (parameter batches: the water-table and Hantush families only, ucf_drawdown_multi)
-        if (MULTI && (fam == 0 || fam == 3 || fam == 5)) return UCF_ERR_UNSUPPORTED;
-        switch (fam) {
-        case 0: if constexpr (!MULTI) { if (wlds * 24 <= 160 * 1024) UCF_LAUNCH_FOLD(0, 6); else UCF_LAUNCH_FOLD(0, 4); } break;
-        case 3: if constexpr (!MULTI) UCF_LAUNCH_FOLD(3, 4); break;       // (MNtype 1 is fully penetrating by construction, driver_io.f90:159-186)
-        case 5: if constexpr (!MULTI) { if (fold) UCF_LAUNCH_FOLD(5, 4); else UCF_LAUNCH_UNF(5, 4); } break;
-        case 1: if (fold) UCF_LAUNCH_FOLD(1, 4); else UCF_LAUNCH_UNF(1, 4); break;
-        case 2:
-            if (fold) {
-                // register budget: 5 waves per SIMD (96 VGPRs, 8 of them spilled around the abscissa loop) where the LDS
-                // footprint admits them.  Round 3, C2: 35.8 / 34.8 / 34.8 ms at 4 / 5 / 6 waves -- the sixth wave buys nothing
-                // any more and costs 16 more spilled registers per item (2 GB of scratch traffic per sweep); the 1/8 shard
-                // runs 5.29 against 5.33 ms.  UCF_FOLD_WAVES_RT (diagnostic): force 4, 5 or 6.
-                const int force_w = env.fold_waves_rt;
-                if (force_w == 4) UCF_LAUNCH_FOLD(2, 4);
-                else if (force_w == 6 && wlds_eff * 24 <= 160 * 1024) UCF_LAUNCH_FOLD(2, 6);
-                else if (w5) UCF_LAUNCH_FOLD(2, UCF_FOLD_WAVES);
-                else UCF_LAUNCH_FOLD(2, 4);
-            }
-            // the screen terms need the registers: 4 waves/SIMD (128 VGPRs, ~60 spilled; 5 waves: -31 %); with two or more
-            // depths per launch 3 waves/SIMD and no spills are 3 % faster (C3), with one depth 5 % slower (C2pp)
-            else {
-                const int unf_w = env.unfold_waves_rt;      // diagnostic: 3 or 4
-                if (unf_w == 3 || (unf_w != 4 && dp.nz >= 2 && !nzc2)) UCF_LAUNCH_UNF(2, 3);
-                else UCF_LAUNCH_UNF(2, UCF_UNFOLD_WAVES);
-            }
-            break;
-        case 4: if (fold) UCF_LAUNCH_FOLD(4, 4); else UCF_LAUNCH_UNF(4, 4); break;
-        }
-#undef UCF_LAUNCH_FOLD
-#undef UCF_LAUNCH_UNF
-#undef UCF_LAUNCH_UNF_
-#undef UCF_LAUNCH_I3
-#undef UCF_LAUNCH_I4
-    }
-#endif
-    if (kind == 2) {
-        if (MULTI) return UCF_ERR_UNSUPPORTED;
-        size_t ilds = (size_t)(dp.R + 1) * dp.nz * UCF_WAVE * sizeof(lds_c);
-#if !UCF_FAST
-        if (fam == 4) ilds += 2 * (size_t)dp.order * UCF_WAVE * sizeof(lds_c);
-#endif
-#define UCF_LAUNCH_G(F)                                                                                        \
-    do {                                                                                                       \
-        if (ilds > 64 * 1024)                                                                                  \
-            (void)hipFuncSetAttribute((const void*)integrate_generic_kernel<F, LAYOUT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ilds); \
-        std::snprintf(kname, sizeof(kname), UCF_STR(UCF_NS) "::integrate_generic_kernel<%d, %d>", F, LAYOUT);  \
-        ucf_tm_mark(tm, kname, s);                                                                             \
-        hipLaunchKernelGGL((integrate_generic_kernel<F, LAYOUT>), dim3((unsigned)nwork), block, ilds, s, dp, nwork, per_point, nr, nsv, svmin, \
-                           d_tD, d_rD, d_sv, (const double2*)d_tab, nt, ir0, (double2*)d_state, d_ndone);      \
-    } while (0)
-        switch (fam) {
-#if !UCF_FAST                   /* the fast flavour has integrate_kernel for every family */
-        case 0: UCF_LAUNCH_G(0); break;
-        case 3: UCF_LAUNCH_G(3); break;
-        case 5: UCF_LAUNCH_G(5); break;
-        case 1: UCF_LAUNCH_G(1); break;
-        case 2: UCF_LAUNCH_G(2); break;
-        case 4: UCF_LAUNCH_G(4); break;
-#endif
-        }
-#undef UCF_LAUNCH_G
-    }
-    if (split) {
-        if (hipGetLastError() != hipSuccess) return UCF_ERR_HIP;
-        // tails of the completed items.  nacc <= UCF_WYNN_REGS: epsilon table in registers, LDS only for the level sums
-        // and the Neville column; else the widest scratch part that still leaves 4 waves per CU (measured on C2:
-        // 4.8 / 3.6 / 3.1 ms for parts of 16 / 32 / 64 lanes)
-        const bool wreg = dp.nacc <= UCF_WYNN_REGS && !env.finish_part;
-        const size_t scols = wreg ? (size_t)dp.R : (size_t)(2 * dp.nacc > dp.R ? 2 * dp.nacc : dp.R);
-        auto flds = [&](int part) { return ((size_t)dp.R * dp.nz * UCF_WAVE + scols * part) * sizeof(lds_c); };
-        int part = env.finish_part;
-        if (part != 16 && part != 32 && part != 64) part = (flds(64) <= 40 * 1024) ? 64 : (flds(32) <= 40 * 1024) ? 32 : 16;
-        const size_t fl = flds(part);
-        if (fl > 160 * 1024) return UCF_ERR_UNSUPPORTED;
-#define UCF_LAUNCH_FM(PART, WR, MODE, GRID)                                                                     \
-    do {                                                                                                       \
-        if (fl > 64 * 1024)                                                                                    \
-            (void)hipFuncSetAttribute((const void*)finish_kernel<LAYOUT, PART, WR, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl); \
-        std::snprintf(kname, sizeof(kname), UCF_STR(UCF_NS) "::finish_kernel<%d, %d, %s, %d>", LAYOUT, PART, WR ? "true" : "false", MODE); \
-        ucf_tm_mark(tm, kname, s);                                                                             \
-        hipLaunchKernelGGL((finish_kernel<LAYOUT, PART, WR, MODE>), dim3((unsigned)(GRID)), block, fl, s, dp, nwork, per_point, nr, nsv, svmin, \
-                           d_tD, d_rD, d_sv, d_h, d_dh, d_stats, nt, ir0, (double2*)d_totlap, (const double2*)d_state, \
-                           (const int*)d_ndone, d_defer);                                                      \
-    } while (0)
-        // fast flavour, epsilon table in registers: the pass with the unguarded table over all items, then the guarded one over
-        // what that pass listed (d_defer: [count | pt * nz + z ...] behind the two lists of integrate_kernel)
-        int* const d_defer = d_ndone + 2 * (size_t)nwork + 1;
-        const bool two_pass = UCF_FAST && wreg;
-        if (two_pass) (void)hipMemsetAsync(d_defer, 0, sizeof(int), s);
-        // (a grid-stride pass with 4 096 ... 65 536 workgroups instead of one per item: 0.92 ms on C2 either way -- the pass is
-        //  bound by the 3.3 GB of state it reads, not by workgroup launches)
-#define UCF_LAUNCH_F(PART, WR)                                                                                 \
-    do {                                                                                                       \
-        if constexpr (UCF_FAST && (WR)) {                                                                      \
-            UCF_LAUNCH_FM(PART, WR, 1, nwork);                                                                 \
-            UCF_LAUNCH_FM(PART, WR, 2, (nwork < 12288 ? nwork : 12288));      /* (4 rounds of resident waves; an empty list costs ~6 us) */ \
-        } else UCF_LAUNCH_FM(PART, WR, 0, nwork);                                                              \
-    } while (0)
-        if (wreg) { if (part == 64) UCF_LAUNCH_F(64, true); else if (part == 32) UCF_LAUNCH_F(32, true); else UCF_LAUNCH_F(16, true); }
-        else if (part == 64) UCF_LAUNCH_F(64, false);
-        else if (part == 32) UCF_LAUNCH_F(32, false);
-        else UCF_LAUNCH_F(16, false);
-#undef UCF_LAUNCH_F
-#undef UCF_LAUNCH_FM
-        if (hipGetLastError() != hipSuccess) return UCF_ERR_HIP;
-        if (kind == 2) { ucf_tm_close(tm, s); return UCF_OK; }      // the generic evaluators leave nothing unfinished
-        // the unfinished ones (overflow regime): point_kernel over the list integrate_kernel left
-        grid = dim3((unsigned)(nwork < 2048 ? nwork : 2048));
-    }
-#define UCF_LAUNCH(F)                                                                                          \
-    do {                                                                                                       \
-        if (lds > 64 * 1024)                                                                                   \
-            (void)hipFuncSetAttribute((const void*)point_kernel<F, LAYOUT, MULTI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        std::snprintf(kname, sizeof(kname), UCF_STR(UCF_NS) "::point_kernel<%d, %d, %s>", F, LAYOUT, MULTI ? "true" : "false"); \
-        ucf_tm_mark(tm, kname, s);                                                                             \
-        hipLaunchKernelGGL((point_kernel<F, LAYOUT, MULTI>), grid, block, lds, s, dp, nwork, per_point, nr, nsv, svmin, d_tD, d_rD, d_sv, \
-                           (const double2*)d_tab, d_h, d_dh, d_stats, nt, ir0, nrc, (double2*)d_totlap, (double2*)d_glscr,          \
-                           (double2*)d_state, (const int*)d_ndone, (const int*)d_todo, d_params, ppp, pbase);  \
-    } while (0)
-    switch (fam) {
-    case 0: UCF_LAUNCH(0); break;
-    case 1: UCF_LAUNCH(1); break;
-    case 2: UCF_LAUNCH(2); break;
-    case 3: UCF_LAUNCH(3); break;
-    case 4: UCF_LAUNCH(4); break;
-    case 5: UCF_LAUNCH(5); break;
-    }
-#undef UCF_LAUNCH
-    ucf_tm_close(tm, s);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-
-// L.params != NULL: parameter-batched launch (per-point layouts of the fast flavour only), plan k owns points
-// [k ppp, (k+1) ppp) and reads L.params[k]; L.dp is plan 0's block
-template <int LAYOUT>
-static int launch_transform(const ucf_launch& L, int nwork)
-{
-#if UCF_FAST
-    if (L.params) {
-        // parameter batches run in the per-point layouts 0, 2, 3 (the lane = time translation unit instantiates none of it)
-        if constexpr (LAYOUT == 1) return UCF_ERR_BAD_ARGUMENT;
-        else return L.per_point ? launch_transform_<LAYOUT, true>(L, nwork) : UCF_ERR_BAD_ARGUMENT;
-    }
-#else
-    if (L.params) return UCF_ERR_UNSUPPORTED;
-#endif
-    return launch_transform_<LAYOUT, false>(L, nwork);
-}
-
-#if UCF_TU_HAS(0)
-// LAYOUT 0 (lane = Laplace sample, de Hoog in the same wave)
-int launch_points(const ucf_launch& L)
-{
-    ucf_launch T = L;
-    T.nt = T.ir0 = T.nrc = 0; T.tm = nullptr;      // a point list has neither
-    return launch_transform<0>(T, L.npts);
-}
-
-#endif
-
-#if UCF_TU_HAS(1)
-// LAYOUT 1 (lane = time): transform kernel(s) over (radius chunk x time tiles x Laplace index), then de Hoog
-int launch_grid_transposed(const ucf_launch& L)
-{
-    const ucf_dev_params& dp = *L.dp;
-    const int nt = L.nt, nr = L.nr, ir0 = L.ir0, nrc = L.nrc;
-    ucf_timers* tm = L.tm;
-    hipStream_t s = (hipStream_t)L.stream;
-    const int ntiles = (nt + UCF_WAVE - 1) / UCF_WAVE;
-    const long long nwork = (long long)nrc * ntiles * dp.np;
-    if (nwork > 0x7fffffffLL) return UCF_ERR_BAD_ARGUMENT;
-    ucf_launch T = L;         // one split index for all times, no parameter batch
-    T.per_point = 0; T.nsv = 1; T.sv = nullptr; T.params = nullptr;
-    int rc = launch_transform<1>(T, (int)nwork);
-    if (rc) return rc;
-    const long long ntl = (long long)nrc * ((nt + UCF_DH_TILE - 1) / UCF_DH_TILE);
-    const size_t dlds = 2 * (size_t)dp.np * (UCF_DH_TILE + 1) * sizeof(lds_c) + 2 * UCF_DH_TILE * sizeof(int);
-    // (one workgroup per tile: a capped grid walking the tiles with a stride is SLOWER -- C2 1.34 ms against 1.99 / 1.55 / 1.44 /
-    //  1.37 ms with 2 048 / 4 096 / 8 192 / 16 384 workgroups, measured: a static stride cannot rebalance what the dispatcher does)
-    const dim3 dgrid((unsigned)(ntl > 0x7fffffffLL ? 0x7fffffff : ntl));
-    if (dp.np <= UCF_WAVE) {
-        ucf_tm_mark(tm, UCF_STR(UCF_NS) "::dehoog_tiles_kernel<1, false>", s);
-        hipLaunchKernelGGL((dehoog_tiles_kernel<1, false>), dgrid, dim3(UCF_WAVE), dlds, s, dp, nt, nr, ir0, nrc, L.tD, (const double2*)L.totlap, L.h, L.dh, L.stats);
-    } else {
-        ucf_tm_mark(tm, UCF_STR(UCF_NS) "::dehoog_tiles_kernel<1, true>", s);
-        hipLaunchKernelGGL((dehoog_tiles_kernel<1, true>), dgrid, dim3(UCF_WAVE), dlds, s, dp, nt, nr, ir0, nrc, L.tD, (const double2*)L.totlap, L.h, L.dh, L.stats);
-    }
-    ucf_tm_close(tm, s);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-
-#endif
-
-#if UCF_TU_HAS(3)
-// LAYOUT 3 (lane = point of an arbitrary list, 2M+1 <= 64): npts points, ppp of them per plan (npts for one plan);
-// transform over (64-point tiles x Laplace index), then the tiled de Hoog with the points in the place of the times
-int launch_points_lanes(const ucf_launch& L)
-{
-    const ucf_dev_params& dp = *L.dp;
-    const int npts = L.npts, ppp = L.params ? L.ppp : npts;
-    hipStream_t s = (hipStream_t)L.stream;
-    if (ppp < 1 || npts % ppp != 0 || dp.np > UCF_WAVE) return UCF_ERR_BAD_ARGUMENT;
-    const long long nwork = (long long)(npts / ppp) * ((ppp + UCF_WAVE - 1) / UCF_WAVE) * dp.np;
-    if (nwork > 0x7fffffffLL) return UCF_ERR_BAD_ARGUMENT;
-    ucf_launch T = L;         // the transform sees a plan's points as the radii of one row, the launch's points as its times
-    T.per_point = 1; T.nr = ppp; T.ppp = ppp; T.nsv = 1; T.svmin = 0; T.nt = npts; T.ir0 = T.nrc = 0;
-    T.glscr = nullptr; T.tm = nullptr;
-    int rc = launch_transform<3>(T, (int)nwork);
-    if (rc) return rc;
-    const long long ntl = (npts + UCF_DH_TILE - 1) / UCF_DH_TILE;
-    const size_t dlds = 2 * (size_t)dp.np * (UCF_DH_TILE + 1) * sizeof(lds_c) + 2 * UCF_DH_TILE * sizeof(int);
-    if (dp.np <= UCF_WAVE)
-        hipLaunchKernelGGL((dehoog_tiles_kernel<3, false>), dim3((unsigned)ntl), dim3(UCF_WAVE), dlds, s, dp, npts, 1, 0, 1, L.tD,
-                           (const double2*)L.totlap, L.h, L.dh, L.stats);
-    else
-        hipLaunchKernelGGL((dehoog_tiles_kernel<3, true>), dim3((unsigned)ntl), dim3(UCF_WAVE), dlds, s, dp, npts, 1, 0, 1, L.tD,
-                           (const double2*)L.totlap, L.h, L.dh, L.stats);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-#endif
-
-#if UCF_TU_HAS(2)
-// LAYOUT 2 (2M+1 > 64): (point, 64-sample chunk) work items write the transform, dehoog_points_kernel inverts.
-// Same addressing as launch_points; d_h/d_dh/d_totlap point at this chunk of points.
-int launch_points_chunked(const ucf_launch& L)
-{
-    const ucf_dev_params& dp = *L.dp;
-    const int npts = L.npts;
-    hipStream_t s = (hipStream_t)L.stream;
-    const int nchunk = (dp.np + UCF_WAVE - 1) / UCF_WAVE;
-    const long long nwork = (long long)npts * nchunk;
-    if (nwork > 0x7fffffffLL) return UCF_ERR_BAD_ARGUMENT;
-    ucf_launch T = L;
-    T.nt = T.ir0 = T.nrc = 0; T.tm = nullptr;      // a point list has neither
-    int rc = launch_transform<2>(T, (int)nwork);
-    if (rc) return rc;
-    hipLaunchKernelGGL(dehoog_points_kernel, dim3((unsigned)npts), dim3(UCF_WAVE), 0, s, dp, (long long)npts, 1, L.per_point, L.nr, 0, 0, L.tD,
-                       (const double2*)L.totlap, L.h, L.dh, L.stats);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-
-#endif
-
-#if UCF_TU_HAS(1)
-int launch_samples(const ucf_dev_params& dp, int n_a, const double* d_a, double rD, const double* d_p, double* d_fp,
-                   void* stream)
-{
-    const int fam = family_of(dp);
-    if (fam < 0) return UCF_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    size_t lds = (fam == 4 && !UCF_FAST) ? 2 * (size_t)dp.order * UCF_WAVE * sizeof(lds_c) : 16;
-    if (UCF_FAST) lds = UCF_SC_ENTRIES * sizeof(lds_c);
-    dim3 grid(n_a), block(UCF_WAVE);
-#define UCF_LAUNCH(F)                                                                                          \
-    do {                                                                                                       \
-        if (lds > 64 * 1024)                                                                                   \
-            (void)hipFuncSetAttribute((const void*)samples_kernel<F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(samples_kernel<F>, grid, block, lds, s, dp, n_a, d_a, rD, d_p, d_fp);               \
-    } while (0)
-    switch (fam) {
-    case 0: UCF_LAUNCH(0); break;
-    case 1: UCF_LAUNCH(1); break;
-    case 2: UCF_LAUNCH(2); break;
-    case 3: UCF_LAUNCH(3); break;
-    case 4: UCF_LAUNCH(4); break;
-    case 5: UCF_LAUNCH(5); break;
-    }
-#undef UCF_LAUNCH
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-
-#endif
-
-#if !UCF_FAST
-int launch_bessel(int n, const double* d_z, double* d_k, int* d_ierr, void* stream)
-{
-    hipLaunchKernelGGL(bessel_kernel, dim3((n + UCF_WAVE - 1) / UCF_WAVE), dim3(UCF_WAVE), 0, (hipStream_t)stream, n, d_z, d_k, d_ierr);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-int launch_dehoog(int n, int M, double alpha, double logtol, const double* d_t, const double* d_tee,
-                  const double* d_fp, double* d_ft, void* stream)
-{
-    hipLaunchKernelGGL(dehoog_kernel, dim3(n), dim3(UCF_WAVE), 0, (hipStream_t)stream, n, M, alpha, logtol, d_t, d_tee,
-                       d_fp, d_ft);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-int launch_wynn(int n, int nterms, const double* d_series, double* d_acc, int* d_status, void* stream)
-{
-    const size_t lds = 2 * (size_t)nterms * UCF_PART * sizeof(lds_c);
-    hipLaunchKernelGGL(wynn_kernel, dim3((n + UCF_WAVE - 1) / UCF_WAVE), dim3(UCF_WAVE), lds, (hipStream_t)stream, n,
-                       nterms, d_series, d_acc, d_status);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-int launch_extrap(int n, int R, const double* d_x, const double* d_y, double* d_out, void* stream)
-{
-    const size_t lds = ((size_t)R * UCF_WAVE + (size_t)R * UCF_PART) * sizeof(lds_c);
-    hipLaunchKernelGGL(extrap_kernel, dim3((n + UCF_WAVE - 1) / UCF_WAVE), dim3(UCF_WAVE), lds, (hipStream_t)stream, n,
-                       R, d_x, d_y, d_out);
-    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
-}
-#endif
-#endif   // UCF_PROBE
 
 }  // namespace UCF_NS

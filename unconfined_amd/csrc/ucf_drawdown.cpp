@@ -33,17 +33,14 @@ int ensure_glscr(ucf_plan* pl, ucf_workspace* ws, int nz)
 }
 
 // (lt_rows: rows of the call's tD array that one launch covers -- the fast flavour keeps lapTime(p) of every (row, m) behind
-//  the state of the launch's items, ucf_fast::lt_table_bytes)
+//  the state of the launch's items; ucf_transform_buffers has the layout of both buffers)
 int ensure_state(ucf_plan* pl, ucf_workspace* ws, const ucf_dev_params& dp, size_t items, size_t lt_rows)
 {
-    size_t need = state_item_bytes(pl, dp) * items;
-    if (need == 0) return UCF_OK;
-    need += flavour_of(pl).lt_table_bytes(dp, lt_rows);
-    int rc = ws_ensure(pl, ws, ws->state, need, "integration state");
+    const ucf_transform_buffers b = buffers_of(pl, dp, items, lt_rows);
+    if (items == 0 || b.state_item_bytes == 0) return UCF_OK;
+    int rc = ws_ensure(pl, ws, ws->state, b.state_bytes, "integration state");
     if (rc) return rc;
-    // [done per item | count of unfinished | unfinished items | count of (item, depth) pairs left to the guarded epsilon
-    //  table | those pairs]
-    return ws_ensure(pl, ws, ws->ndone, (2 * items + 2 + items * (size_t)dp.nz + 2) * sizeof(int), "work-item counters");
+    return ws_ensure(pl, ws, ws->ndone, b.ints * sizeof(int), "work-item counters");
 }
 
 // work items per launch such that their state stays within UCF_STATE_BYTES (default 8 GiB of the 288 GB)

@@ -9,7 +9,7 @@
 #include <stdlib.h>
 
 struct ucf_env {
-    // launch_transform_ (ucf_device.h), integrate_kernel of the fast flavour
+    // plan_transform (ucf_launch_plan.h), integrate_kernel of the fast flavour
     int nsplit;            // UCF_NSPLIT (0): force 1, 2, 4 or 8 parts per work item.  cut
     int tail_lsplit;       // UCF_TAIL_LSPLIT (-1 = built-in): log2 of the parts of a launch's last items; 0 turns the finer tail off.  cut
     int tail_items;        // UCF_TAIL_ITEMS (-1 = built-in, one round of resident waves): how many items that tail holds.  cut
@@ -18,7 +18,7 @@ struct ucf_env {
     bool nofold;           // UCF_NOFOLD (on; '0' off): plans that fold no screen term run the NOFOLD instantiations.  kernel
     int fold_waves_rt;     // UCF_FOLD_WAVES_RT (0): force 4, 5 or 6 waves per SIMD in the folded water-table kernel.  kernel
     int unfold_waves_rt;   // UCF_UNFOLD_WAVES_RT (0): force 3 or 4 waves per SIMD in the unfolded water-table kernel.  kernel
-    // launch_transform_, finish_kernel and point_kernel
+    // plan_transform, finish_kernel and point_kernel
     int finish_part;       // UCF_FINISH_PART (0 = from the LDS footprint): 16 / 32 / 64 lanes per scratch part, epsilon table in LDS.  kernel
     int grid_slots;        // UCF_GRID_SLOTS (8192; <= 0 = default): workgroups per launch when the interval areas live in global scratch.  cut
     // host side (ucf_plan.cpp, ucf_drawdown.cpp, ucf_multi.cpp, ucf_debug.cpp)

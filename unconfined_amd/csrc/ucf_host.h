@@ -25,8 +25,6 @@ int fail(int code, const char* fmt, ...);      // sets what ucf_last_error() ret
 struct ucf_flavour {
     decltype(&ucf_fast::launch_points) launch_points, launch_grid_transposed, launch_points_chunked, launch_points_lanes;
     decltype(&ucf_fast::launch_samples) launch_samples;
-    decltype(&ucf_fast::state_bytes_per_item) state_bytes_per_item;
-    decltype(&ucf_fast::lt_table_bytes) lt_table_bytes;
     decltype(&ucf_fast::launch_wynn_regs) launch_wynn_regs;
     decltype(&ucf_fast::launch_dehoog_tiles_hook) launch_dehoog_tiles_hook;
 };
@@ -83,8 +81,10 @@ ucf_workspace* ws_for(ucf_plan* pl, void* stream);
 void ws_destroy(ucf_workspace* ws);
 hipStream_t plan_stream(ucf_plan* pl);
 int ws_ensure(ucf_plan* pl, ucf_workspace* ws, ucf_buffer& b, size_t bytes, const char* what);
-// state of a work item between integrate_kernel and point_kernel (fast flavour, Hantush-based models)
-inline size_t state_item_bytes(const ucf_plan* pl, const ucf_dev_params& dp) { return flavour_of(pl).state_bytes_per_item(dp); }
+// the buffers that the kernels of a launch sequence share (ucf_launch_plan.h), in the plan's flavour
+inline ucf_transform_buffers buffers_of(const ucf_plan* pl, const ucf_dev_params& dp, size_t items, size_t lt_rows) { return transform_buffers(dp, pl->mode == 1, items, lt_rows); }
+// state of a work item between the integrate kernel and finish / point_kernel (0: the abscissa loop has no kernel of its own)
+inline size_t state_item_bytes(const ucf_plan* pl, const ucf_dev_params& dp) { return buffers_of(pl, dp, 0, 0).state_item_bytes; }
 // abscissa-table bytes per chunk of an arbitrary point list (UCF_TABLE_BYTES, default 256 MiB)
 inline size_t table_budget() { return ucf_env_get().table_bytes; }
 int launch_points_any(ucf_plan* pl, ucf_workspace* ws, const ucf_launch& call, int npts_call);

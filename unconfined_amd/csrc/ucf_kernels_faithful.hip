@@ -3,3 +3,4 @@
 #define UCF_FAST 0
 #define UCF_NS ucf_faithful
 #include "ucf_device.h"
+#include "ucf_launchers.h"

@@ -2,3 +2,4 @@
 #define UCF_FAST 1
 #define UCF_NS ucf_fast
 #include "ucf_device.h"
+#include "ucf_launchers.h"

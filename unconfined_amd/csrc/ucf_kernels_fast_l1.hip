@@ -4,3 +4,4 @@
 #define UCF_NS ucf_fast
 #define UCF_TU 1
 #include "ucf_device.h"
+#include "ucf_launchers.h"

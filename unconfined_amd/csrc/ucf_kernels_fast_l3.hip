@@ -3,3 +3,4 @@
 #define UCF_NS ucf_fast
 #define UCF_TU 3
 #include "ucf_device.h"
+#include "ucf_launchers.h"

@@ -382,7 +382,7 @@ int z_chunk(const ucf_plan* plan)
     const int R = plan->P.R, nacc = plan->P.nacc;
     ucf_dev_params one = plan->dev;
     one.nz = 1;
-    const bool split = flavour_of(plan).state_bytes_per_item(one) != 0;
+    const bool split = state_item_bytes(plan, one) != 0;
     int n;
     if (split) {
         n = (int)(((size_t)12 * 1024) / ((size_t)(R + 1) * UCF_WAVE * 16));

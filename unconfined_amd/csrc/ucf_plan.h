@@ -2,55 +2,10 @@
 #pragma once
 #include "../../include/ucf.h"
 #include "ucf_env.h"
+#include "ucf_launch_plan.h"     // ucf_dev_params and the sizes that host and kernels share
 #include <cstdio>
 #include <mutex>
 #include <vector>
-
-#define UCF_WAVE 64
-#define UCF_MAX_R 16
-
-// Everything a kernel needs, passed by value as one kernel argument (lives in
-// SGPRs / the scalar cache: it is wave-uniform).  Table pointers are device
-// pointers into one small per-plan allocation that stays L2/scalar-cache hot.
-struct ucf_dev_params {
-    int model, MNtype, order, timeType, MoenchM;
-    int M, np, k, N, R, nacc, ngl, nz;
-    int tab_premul;        // the abscissa table's Gauss-Lobatto entries carry their quadrature weight (fast flavour; abscissa_kernel)
-    int nj0z, any_lay3;    // any_lay3: some depth of the launch (of any plan of a parameter batch) lies above the screen top
-    int any_lay1;          // ... below the screen bottom
-    int any_fold;          // some plan of the launch folds a screen term (fold_dD or fold_lD1) or is model 4 (no screen terms): 0 = the NOFOLD instantiations may run
-    int nz_out, z_off;     // depths of the whole call / offset of this launch's chunk: out index = pt*nz_out + z_off + z
-    double timePar[2];
-    double kappa, alphaD, beta;
-    double lD, dD, bD, dD1, lD1;              // dD1 = 1-dD, lD1 = 1-lD (laplace_hankel_solutions.f90:157-158)
-    double MoenchInvGamma[UCF_MAX_MOENCH];    // 1.0/gamma_m (:74)
-    double alpha, logtol, maxexp;
-    // fast flavour: hoisted reciprocals, plan-level exact folds, validity bound of the fast evaluation
-    double inv_kappa, inv_bD, fast_eta_max, fast_im_max;
-    int fold_dD, fold_lD1, share_g1top, _pad2;
-    double g1_delta;       // (dD1 - 1) + dD, exact: the argument of cosh(eta (dD1 - 1)) is -(dD - g1_delta) (share_g1top = 2)
-    // Hantush with wellbore storage (:204-301): rDw, CDw (:250), tDb (:253)
-    double hs_rDw, hs_CDw, hs_tDb;
-    // Mishra/Neuman (Malama form, :404-442): host-evaluated scalar prefactors
-    double mn_vartheta, mn_u0, mn_c3;         // mn_c3 = 1 / (kappa u0^2): (eta1 / u0)^2 = (p vartheta + a^2) mn_c3
-    // Mishra/Neuman FD (:444-544)
-    double fd_h, fd_invhsq, fd_beta0, fd_beta3, fd_expmb2;   // exp(-beta2)
-    double fd_isk, fd_gmax;                   // 1/sqrt(K), K = (1/h^2 - beta3/h)/h^2 (0 if K <= 0); 2^(500/order) - 1 (fd_inverse_B2)
-    double hv[UCF_MAX_R];                     // Richardson spacings (driver.f90:91)
-    double zD[UCF_MAX_NZ];
-    int zLay[UCF_MAX_NZ];
-    const double* ts_x;    // [N]      tanh(u2)+1 of the densest level (integration.f90:62 without *s/2)
-    const double* ts_w;    // [R][N]   normalised weights of level j in row j-1 (first Nv(j) entries)
-    const double* gl_x;    // [ngl]
-    const double* gl_w;    // [ngl]
-    const double* j0z;     // [nj0z]
-    const double* fd_e;    // [order]  exp(-beta1*(j-1)*h)
-    const double* sched;   // timeType = -n: [n] start times | [n] rate increments | final time | sum of increments
-    const double* sc_tab;  // [256] x (sin, cos)(k pi / 128) | [128] x (hi, lo) of 2^(j/128): copied into LDS by the fast flavour's kernels
-                           // (sincos_tab_, exp_tab_)
-};
-#define UCF_SC_ENTRIES (256 + 128)   /* 16-byte units of that table */
-#define UCF_IWPB 4             /* waves per workgroup of integrate_kernel: they share the sin/cos table in LDS */
 
 // HIP events around the kernels of the last lane = time grid call issued through a workspace (measurement only):
 // bracket i = ev[2i] .. ev[2i+1] around the kernel called name[i].
@@ -153,7 +108,7 @@ struct ucf_plan {
     void* own_stream = nullptr;
 };
 
-// One launch sequence: everything the layout launchers and launch_transform_ (ucf_device.h) read and write.  A caller
+// One launch sequence: everything the layout launchers and launch_transform_ (ucf_launchers.h) read and write.  A caller
 // fills one and, inside its chunk loops, moves only the bases and counts.
 struct ucf_launch {
     const ucf_dev_params* dp = nullptr;    // the parameter block (plan 0's in a parameter batch)
@@ -175,7 +130,7 @@ struct ucf_launch {
     int ppp = 1, pbase = 0;
 };
 
-// launchers implemented in ucf_kernels_*.hip (one set per build flavour)
+// launchers implemented in ucf_launchers.h and, the stage hooks, ucf_device.h; compiled by ucf_kernels_*.hip (one set per build flavour)
 namespace ucf_faithful {
 // abscissa tables (shared by both flavours): tab[row][nabs] of (a, a*J0(a*rD))
 int launch_abscissae(const ucf_dev_params& dp, int nrows, int per_point, int nsv, int svmin, const double* d_rD,
@@ -190,15 +145,13 @@ int launch_extrap(int n, int R, const double* d_x, const double* d_y, double* d_
 int launch_debug_gather(const ucf_dev_params& dp, int layout, int nwork, int per_point, int nr, int nt, int ir0, const double* d_state,
                         const int* d_ndone, double* d_out_state, int* d_out_ndone, void* stream);
 }
-// what both flavours define, entry by entry the ucf_flavour table (ucf_host.h, filled in ucf_api.cpp).  state_bytes_per_item: bytes of integrate
-// kernel -> finish / point kernel state per work item (0: the model has no integrate kernel)
+// what both flavours define, entry by entry the ucf_flavour table (ucf_host.h, filled in ucf_api.cpp)
 namespace ucf_faithful {
 int launch_points(const ucf_launch& L);             // lane layout 0
 int launch_grid_transposed(const ucf_launch& L);    // 1
 int launch_points_chunked(const ucf_launch& L);     // 2
 int launch_points_lanes(const ucf_launch& L);       // 3
 int launch_samples(const ucf_dev_params& dp, int n_a, const double* d_a, double rD, const double* d_p, double* d_fp, void* stream);
-size_t state_bytes_per_item(const ucf_dev_params& dp);
 int launch_wynn_regs(int n, int nterms, const double* d_series, double* d_acc, int* d_status, void* stream);
 int launch_dehoog_tiles_hook(const ucf_dev_params& dp, int n, const double* d_tD, const double* d_totlap, double* d_h, double* d_dh, void* stream);
 }
@@ -208,8 +161,6 @@ int launch_grid_transposed(const ucf_launch& L);    // 1
 int launch_points_chunked(const ucf_launch& L);     // 2
 int launch_points_lanes(const ucf_launch& L);       // 3
 int launch_samples(const ucf_dev_params& dp, int n_a, const double* d_a, double rD, const double* d_p, double* d_fp, void* stream);
-size_t state_bytes_per_item(const ucf_dev_params& dp);
 int launch_wynn_regs(int n, int nterms, const double* d_series, double* d_acc, int* d_status, void* stream);
 int launch_dehoog_tiles_hook(const ucf_dev_params& dp, int n, const double* d_tD, const double* d_totlap, double* d_h, double* d_dh, void* stream);
-size_t lt_table_bytes(const ucf_dev_params& dp, size_t rows);      // the lapTime table behind the state (laptime_kernel)
 }
