@@ -383,8 +383,60 @@ int ucf_fit_network_eval_counts(int nwell, const int* well_nz, int nobs, const d
                                 long long* launched, long long* dense);
 /* diagnostic: the dimensionless h behind observation i under plan `plan` (set * (1 + 2 npar) + row) as the LAST
  * ucf_fit_evaluate left it in device memory: n = 1 value for a point observation, the n depths of the well for a screen
- * average (what its average was formed from).  cap < n: UCF_ERR_BAD_ARGUMENT. */
+ * average (what its average was formed from).  cap < n: UCF_ERR_BAD_ARGUMENT.  On a fit made by ucf_fit_create_field i is a
+ * TERM index (ucf_fit_field_terms): the h behind that term, at its own time and distance. */
 int ucf_fit_debug_h(ucf_fit* fit, int plan, int i, int cap, double* h, int* n);
+
+/* A field fit: the observations of an interference test -- several pumping wells, wells that start at different times, image
+ * wells for a river or an outcrop -- fitted against the superposition that ucf_field_* maps.  npump pumping wells (xw, yw, qw,
+ * t0w) with the meaning of ucf_field_create (qw a factor on the plan's Q, never 0; t0w >= 0); an image well is a plain entry,
+ * so the output of ucf_field_images can be passed as it is.  nwell observation wells at (well_x, well_y) with depths well_nz /
+ * well_z as in ucf_fit_create_network.  Observation i: dimensional drawdown at time t[i] in well well[i], at depth iz[i] of
+ * that well or, with iz[i] == UCF_FIT_SCREEN, its screen average.
+ *   value        acc = +0.0;  for j = 0..npump-1 in the caller's order, only where t[i] > t0w[j]:
+ *                    v = the plan's dimensionless h at time t[i] - t0w[j] and distance |well - pumping well j|, at the
+ *                        observation's depth or averaged over the well's depths by the rule of ucf_screen_average (what
+ *                        a network observation is before x Hc);   acc = acc + qw[j] * v;
+ *                sim = acc * Hc.  Every operation is rounded on its own.  An observation that no well's start precedes has
+ *                sim = +0.0 and is legal.  Nothing is scrubbed: a term that is not finite makes sim not finite and the
+ *                observation is counted in nbad.
+ *   layout       host arithmetic, stated by ucf_fit_field_terms.  dist = sqrt(dx dx + dy dy), dimensional, as in ucf_field_group.
+ *                One VIRTUAL WELL per (observation well, distinct distance): pairs of one observation well whose distances
+ *                are equal bit for bit share it; it carries the depths of its observation well; virtual wells are ordered by
+ *                observation well, then by ascending distance.  One TERM per (observation i, pumping well j with t[i] >
+ *                t0w[j]): time t[i] - t0w[j] (one rounding), its virtual well, qw[j]; the terms of an observation keep the
+ *                caller's order of pumping wells.
+ *   launch       the virtual wells with the term times as their observation times are the network of
+ *                ucf_fit_create_network, launched as stated there: distinct times per virtual well in blocks of 64, groups
+ *                by number of depths, one split vector per plan over all launched term times, the shared launch where the
+ *                plans have one and plan by plan, virtual well by virtual well otherwise.  Terms that land on the same
+ *                (virtual well, time) share one evaluation.  A map of ucf_field_drawdown takes one split vector per
+ *                group of wells, this fit one over all term times: where wells start at different times the two differ by
+ *                that choice, not by rounding alone.
+ *   reduction    fit_field_reduce_kernel: as fit_network_reduce_kernel, the value of an observation being the sum above.
+ * ucf_fit_evaluate, ucf_fit_lm, ucf_fit_destroy and ucf_fit_alloc_count work on the object unchanged; J and sim_all come back
+ * in the caller's observation order; ucf_fit_eval_counts reports launched and dense of the network of virtual wells (every
+ * virtual well's depths count in dense); ucf_fit_debug_h takes a term index.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything
+ * ucf_fit_create_network checks, with well_x / well_y (finite) in place of well_r; what ucf_field_create checks on the pumping
+ * wells (npump < 1, NULL, a number that is not finite, t0w < 0, qw == 0); a distance that is not finite or below base->rw --
+ * the observation well is inside a bore -- naming the (observation well, pumping well) pair; more than 2^24 pairs or terms;
+ * no term at all.  Then UCF_ERR_NO_DEVICE. */
+int ucf_fit_create_field(const ucf_params* base, int npar, const int* ids,
+                         int npump, const double* xw, const double* yw, const double* qw, const double* t0w,
+                         int nwell, const double* well_x, const double* well_y, const int* well_nz, const double* well_z,
+                         int nobs, const double* t, const int* well, const int* iz,
+                         const double* obs, const double* weight, int device, ucf_fit** out);
+/* host only: what the fit above launches and sums -- nvirt virtual wells (virt_well: the observation well, virt_r: the
+ * distance), term_first[i] .. term_first[i + 1] the terms of observation i, per term its pumping well, its virtual well and
+ * its time.  Arrays sized for the worst case; any output may be NULL.  The checks of ucf_fit_create_field that concern these
+ * arguments (base as by ucf_plan_create). */
+int ucf_fit_field_terms(const ucf_params* base,
+                        int npump, const double* xw, const double* yw, const double* qw, const double* t0w,
+                        int nwell, const double* well_x, const double* well_y,
+                        int nobs, const double* t, const int* well,
+                        int* nvirt, int* virt_well /*[nwell*npump]*/, double* virt_r /*[nwell*npump], dimensional*/,
+                        int* term_first /*[nobs+1]*/, int* term_pump, int* term_virt, double* term_t /*[nobs*npump] each*/);
 
 /* ---- well fields: the drawdown of several pumping wells -- wells that start at different times, image wells for a river or an
  * outcrop -- is the sum over wells of q_j h(t - t0_j, |x - x_j|, z).  All wells share the plan's aquifer, well geometry and

@@ -14,7 +14,7 @@ PAR_KR, PAR_KAPPA, PAR_SS, PAR_SY, PAR_AC, PAR_AK, PAR_USL, PAR_MOENCH_ALPHA0 = 
 PAR_IDS = {"Kr": PAR_KR, "kappa": PAR_KAPPA, "Ss": PAR_SS, "Sy": PAR_SY, "ac": PAR_AC, "ak": PAR_AK, "usL": PAR_USL}
 # status of a start of ucf_fit_lm (enum UCF_FIT_*)
 FIT_CONVERGED, FIT_MAX_ITER, FIT_SINGULAR, FIT_NONFINITE_START = range(4)
-# iz of an observation of ucf_fit_create_network that is the screen average of its well's depths (UCF_FIT_SCREEN)
+# iz of an observation of ucf_fit_create_network / ucf_fit_create_field that is the screen average of its well's depths (UCF_FIT_SCREEN)
 FIT_SCREEN = -1
 UCF_ERR_BAD_ARGUMENT, UCF_ERR_NO_DEVICE, UCF_ERR_SINGULAR = -11, -12, -16
 

@@ -11,6 +11,13 @@
 
 using namespace ucf_host;
 
+int ucf_host::field_check_finite(const char* name, int n, const double* v)
+{
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(v[i])) return fail(UCF_ERR_BAD_ARGUMENT, "%s[%d]=%g is not finite", name, i, v[i]);
+    return UCF_OK;
+}
+
 struct field_group {
     double t0 = 0.0;
     std::vector<int> wells;                // in the caller's order
@@ -97,13 +104,6 @@ int field_group_out(const ucf_field* f, const ucf_params& P, const ucf_derived& 
     if (rD) std::copy(A.rD.begin(), A.rD.end(), rD);
     if (col) std::copy(A.col.begin(), A.col.end(), col);
     if (tfac) std::copy(A.tfac.begin(), A.tfac.end(), tfac);
-    return UCF_OK;
-}
-
-int field_check_finite(const char* name, int n, const double* v)
-{
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(v[i])) return fail(UCF_ERR_BAD_ARGUMENT, "%s[%d]=%g is not finite", name, i, v[i]);
     return UCF_OK;
 }
 

@@ -1,6 +1,8 @@
 // ucf_fit.cpp -- parameter fitting (ucf.h: ucf_fit_*): observations resident on the device, base and perturbed parameter sets through
 // the shared core of ucf_drawdown_multi, residuals / objective / Jacobian / normal equations in fit_reduce_kernel
-// (ucf_fit.hip), Levenberg-Marquardt for many starts at once on the host (npar x npar arithmetic).
+// (ucf_fit.hip), Levenberg-Marquardt for many starts at once on the host (npar x npar arithmetic).  An observation network
+// (ucf_fit_create_network) launches per-well blocks; a field fit (ucf_fit_create_field) is the network of its virtual wells
+// -- one per (observation well, distinct distance to a pumping well) -- whose reduction sums over pumping wells.
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -52,10 +54,14 @@ struct ucf_fit {
     size_t net_pts = 0, net_vals = 0;      // per plan, all groups: points launched, (point, depth) values
     long long dense = 0;                   // (point, depth) evaluations per plan of the dense form
     ucf_buffer b_ref;
+    // a field fit (ucf_fit_create_field): a network whose wells are the virtual wells and whose `refs` are per TERM;
+    // observation i sums the terms b_first[i] .. b_first[i + 1] of b_term (ucf_fit_term: place and rate factor)
+    bool field = false;
+    ucf_buffer b_term, b_first;
     // every device buffer above: the one list (ucf_fit_destroy frees through it)
-    std::array<ucf_buffer*, 14> buffers()
+    std::array<ucf_buffer*, 16> buffers()
     {
-        return {{&b_slot, &b_obs, &b_w, &b_t, &b_r, &b_s, &b_h, &b_d, &b_hc, &b_sums, &b_nbad, &b_J, &b_sim, &b_ref}};
+        return {{&b_slot, &b_obs, &b_w, &b_t, &b_r, &b_s, &b_h, &b_d, &b_hc, &b_sums, &b_nbad, &b_J, &b_sim, &b_ref, &b_term, &b_first}};
     }
     std::vector<double> st_t;              // staging of one plan: its tD over all groups ...
     std::vector<int> st_s;                 // ... and their split vector
@@ -217,6 +223,92 @@ int network_check(int nwell, const int* well_nz, int nobs, const double* t, cons
     return UCF_OK;
 }
 
+// The geometry of a field fit (ucf_fit_field_terms states it): the virtual wells -- per observation well its distinct
+// distances to the pumping wells, ascending -- and per observation its terms, one per pumping well that started before it.
+struct field_geometry {
+    std::vector<int> virt_well;            // per virtual well: its observation well
+    std::vector<double> virt_r;            // ... and its distance, dimensional
+    std::vector<int> first, pump, virt;    // first [nobs + 1]; per term: pumping well, virtual well
+    std::vector<double> t;                 // per term: t[i] - t0w[j]
+};
+
+// the checks of ucf_field_create on the pumping wells, then those on the observation wells' positions
+int field_check(int npump, const double* xw, const double* yw, const double* qw, const double* t0w, int nwell, const double* well_x,
+                const double* well_y)
+{
+    if (npump < 1) return fail(UCF_ERR_BAD_ARGUMENT, "npump=%d: at least one pumping well", npump);
+    if (nwell < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nwell=%d: at least one well", nwell);
+    if ((long long)nwell * npump > (1 << 24)) return fail(UCF_ERR_BAD_ARGUMENT, "%d observation wells x %d pumping wells: too many pairs", nwell, npump);
+    if (!xw || !yw || !qw || !t0w || !well_x || !well_y) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
+    int rc;
+    if ((rc = field_check_finite("xw", npump, xw)) || (rc = field_check_finite("yw", npump, yw)) || (rc = field_check_finite("qw", npump, qw)) ||
+        (rc = field_check_finite("t0w", npump, t0w)) || (rc = field_check_finite("well_x", nwell, well_x)) ||
+        (rc = field_check_finite("well_y", nwell, well_y))) return rc;
+    for (int j = 0; j < npump; j++) {
+        if (qw[j] == 0.0) return fail(UCF_ERR_BAD_ARGUMENT, "qw[%d] is 0: a well without a rate", j);
+        if (!(t0w[j] >= 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "t0w[%d]=%g is negative", j, t0w[j]);
+    }
+    return UCF_OK;
+}
+
+// The arguments have passed field_check and network_check.  Distances as in field_group_core: every operation rounded on
+// its own (host code is compiled without FMA contraction).
+int field_layout(const ucf_params& P, int npump, const double* xw, const double* yw, const double* t0w, int nwell, const double* well_x,
+                 const double* well_y, int nobs, const double* t, const int* well, field_geometry& F)
+{
+    if ((long long)nobs * npump > (1 << 24)) return fail(UCF_ERR_BAD_ARGUMENT, "%d observations x %d pumping wells: too many terms", nobs, npump);
+    std::vector<int> vmap((size_t)nwell * npump);      // virtual well of the pair (observation well, pumping well)
+    std::vector<double> d(npump), u;
+    for (int w = 0; w < nwell; w++) {
+        for (int j = 0; j < npump; j++) {
+            const double dx = well_x[w] - xw[j], dy = well_y[w] - yw[j];
+            const double dist = std::sqrt(dx * dx + dy * dy);
+            if (!std::isfinite(dist)) return fail(UCF_ERR_BAD_ARGUMENT, "the distance of observation well %d from pumping well %d is not finite", w, j);
+            if (dist < P.rw)
+                return fail(UCF_ERR_BAD_ARGUMENT, "observation well %d lies %g from pumping well %d: inside its bore (rw = %g)", w, dist, j, P.rw);
+            d[j] = dist;
+        }
+        u = d;
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());      // (positive and finite: equal values are equal bits)
+        for (int j = 0; j < npump; j++)
+            vmap[(size_t)w * npump + j] = (int)F.virt_well.size() + (int)(std::lower_bound(u.begin(), u.end(), d[j]) - u.begin());
+        for (double r : u) { F.virt_well.push_back(w); F.virt_r.push_back(r); }
+    }
+    F.first.resize((size_t)nobs + 1);
+    for (int i = 0; i < nobs; i++) {
+        F.first[i] = (int)F.pump.size();
+        for (int j = 0; j < npump; j++)
+            if (t[i] > t0w[j]) { F.pump.push_back(j); F.virt.push_back(vmap[(size_t)well[i] * npump + j]); F.t.push_back(t[i] - t0w[j]); }
+    }
+    F.first[nobs] = (int)F.pump.size();
+    return UCF_OK;
+}
+
+// After network_check: the radii (where the wells have one: well_r may be NULL) and depths of the wells, then iz, weight and
+// obs of every observation.  z0[w] = place of well w's depths in well_z, z0[nwell] = their number.
+int network_check_wells(int nwell, const double* well_r, const int* well_nz, const double* well_z, int nobs, const int* well, const int* iz,
+                        const double* obs, const double* weight, std::vector<int>& z0)
+{
+    z0.assign((size_t)nwell + 1, 0);
+    int nzs = 0;
+    for (int w = 0; w < nwell; w++) {
+        if (well_r && (!std::isfinite(well_r[w]) || !(well_r[w] > 0.0))) return fail(UCF_ERR_BAD_ARGUMENT, "well_r[%d]=%g is not a finite positive radius", w, well_r[w]);
+        z0[w] = nzs;
+        for (int j = 0; j < well_nz[w]; j++)
+            if (!std::isfinite(well_z[nzs + j])) return fail(UCF_ERR_BAD_ARGUMENT, "well_z[%d]=%g (depth %d of well %d) is not finite", nzs + j, well_z[nzs + j], j, w);
+        nzs += well_nz[w];
+    }
+    z0[nwell] = nzs;
+    for (int i = 0; i < nobs; i++) {
+        if (iz[i] < UCF_FIT_SCREEN || iz[i] >= well_nz[well[i]])
+            return fail(UCF_ERR_BAD_ARGUMENT, "iz[%d]=%d outside -1..%d (well %d)", i, iz[i], well_nz[well[i]] - 1, well[i]);
+        if (!(weight[i] >= 0.0) || !std::isfinite(weight[i])) return fail(UCF_ERR_BAD_ARGUMENT, "weight[%d]=%g is negative or not finite", i, weight[i]);
+        if (!std::isfinite(obs[i])) return fail(UCF_ERR_BAD_ARGUMENT, "obs[%d]=%g is not finite", i, obs[i]);
+    }
+    return UCF_OK;
+}
+
 // The launches of a network fit over the first nplans plans of the pool; the dimensionless h, dh stay in f->io.d_h, d_d in
 // the layout of fit_group.  As multi_core: every stream the call used has drained when it returns.
 int network_core(ucf_fit* f, int nplans)
@@ -356,7 +448,12 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     f->h_hc.resize(nplans);
     for (int k = 0; k < nplans; k++) f->h_hc[k] = f->plans[k]->D.Hc;
     HIP_TRY(hipMemcpy(f->b_hc.p, f->h_hc.data(), sizeof(double) * nplans, hipMemcpyHostToDevice));
-    if (f->network)
+    if (f->field)
+        rc = ucf_fit_launch_field_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
+                                         (const double*)f->b_hc.p, (const ucf_fit_term*)f->b_term.p, (const int*)f->b_first.p,
+                                         (const double*)f->b_obs.p, (const double*)f->b_w.p, (double*)f->b_sums.p, (int*)f->b_nbad.p,
+                                         (J && jac) ? (double*)f->b_J.p : nullptr, sim_all ? (double*)f->b_sim.p : nullptr, nullptr);
+    else if (f->network)
         rc = ucf_fit_launch_network_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
                                            (const double*)f->b_hc.p, (const ucf_fit_obs_ref*)f->b_ref.p, (const double*)f->b_obs.p,
                                            (const double*)f->b_w.p, (double*)f->b_sums.p, (int*)f->b_nbad.p,
@@ -498,21 +595,10 @@ int ucf_fit_create_network(const ucf_params* base, int npar, const int* ids, int
     if (!well_r || !well_z || !iz || !obs || !weight) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
     rc = network_check(nwell, well_nz, nobs, t, well);
     if (rc) return rc;
-    std::vector<int> z0(nwell);
-    int nzs = 0;
-    for (int w = 0; w < nwell; w++) {
-        if (!std::isfinite(well_r[w]) || !(well_r[w] > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "well_r[%d]=%g is not a finite positive radius", w, well_r[w]);
-        z0[w] = nzs;
-        for (int j = 0; j < well_nz[w]; j++)
-            if (!std::isfinite(well_z[nzs + j])) return fail(UCF_ERR_BAD_ARGUMENT, "well_z[%d]=%g (depth %d of well %d) is not finite", nzs + j, well_z[nzs + j], j, w);
-        nzs += well_nz[w];
-    }
-    for (int i = 0; i < nobs; i++) {
-        if (iz[i] < UCF_FIT_SCREEN || iz[i] >= well_nz[well[i]])
-            return fail(UCF_ERR_BAD_ARGUMENT, "iz[%d]=%d outside -1..%d (well %d)", i, iz[i], well_nz[well[i]] - 1, well[i]);
-        if (!(weight[i] >= 0.0) || !std::isfinite(weight[i])) return fail(UCF_ERR_BAD_ARGUMENT, "weight[%d]=%g is negative or not finite", i, weight[i]);
-        if (!std::isfinite(obs[i])) return fail(UCF_ERR_BAD_ARGUMENT, "obs[%d]=%g is not finite", i, obs[i]);
-    }
+    std::vector<int> z0;
+    rc = network_check_wells(nwell, well_r, well_nz, well_z, nobs, well, iz, obs, weight, z0);
+    if (rc) return rc;
+    const int nzs = z0[nwell];
     int ndev = 0;
     rc = ucf_device_count(&ndev);
     if (rc) return rc;
@@ -522,7 +608,7 @@ int ucf_fit_create_network(const ucf_params* base, int npar, const int* ids, int
     f->base = *base; f->npar = npar; f->nobs = nobs; f->nz = 0; f->device = device; f->network = true;
     for (int j = 0; j < npar; j++) f->ids[j] = ids[j];
     f->well_r.assign(well_r, well_r + nwell); f->well_nz.assign(well_nz, well_nz + nwell);
-    f->well_z.assign(well_z, well_z + nzs); f->well_z0 = z0;
+    f->well_z.assign(well_z, well_z + nzs); f->well_z0.assign(z0.begin(), z0.begin() + nwell);
     std::vector<int> grp_of, pt_of;
     long long npoints = 0;
     network_layout(nwell, well_r, well_nz, nobs, t, well, f->groups, &grp_of, &pt_of, &npoints);
@@ -545,6 +631,105 @@ int ucf_fit_create_network(const ucf_params* base, int npar, const int* ids, int
         return fail(UCF_ERR_HIP, "upload of the observations failed");
     }
     *out = f;
+    return UCF_OK;
+}
+
+int ucf_fit_create_field(const ucf_params* base, int npar, const int* ids, int npump, const double* xw, const double* yw, const double* qw,
+                         const double* t0w, int nwell, const double* well_x, const double* well_y, const int* well_nz, const double* well_z,
+                         int nobs, const double* t, const int* well, const int* iz, const double* obs, const double* weight, int device,
+                         ucf_fit** out)
+{
+    if (out) *out = nullptr;
+    if (!base || !out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = validate(*base);
+    if (rc) return rc;
+    rc = fit_check_ids(*base, npar, ids);
+    if (rc) return rc;
+    if (nobs < npar) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: fewer observations than the %d parameters to fit", nobs, npar);
+    if (!well_z || !iz || !obs || !weight) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
+    rc = field_check(npump, xw, yw, qw, t0w, nwell, well_x, well_y);
+    if (rc) return rc;
+    rc = network_check(nwell, well_nz, nobs, t, well);
+    if (rc) return rc;
+    std::vector<int> z0;
+    rc = network_check_wells(nwell, nullptr, well_nz, well_z, nobs, well, iz, obs, weight, z0);
+    if (rc) return rc;
+    field_geometry F;
+    rc = field_layout(*base, npump, xw, yw, t0w, nwell, well_x, well_y, nobs, t, well, F);
+    if (rc) return rc;
+    const int nvirt = (int)F.virt_well.size(), nterm = (int)F.pump.size();
+    if (nterm < 1) return fail(UCF_ERR_BAD_ARGUMENT, "no observation lies after the start of a pumping well: nothing to fit");
+    int ndev = 0;
+    rc = ucf_device_count(&ndev);
+    if (rc) return rc;
+    if (device < 0 || device >= ndev) return fail(UCF_ERR_BAD_ARGUMENT, "device %d does not exist (%d visible)", device, ndev);
+    ucf_fit* f = new (std::nothrow) ucf_fit();
+    if (!f) return fail(UCF_ERR_NOMEM, "host allocation failed");
+    f->base = *base; f->npar = npar; f->nobs = nobs; f->nz = 0; f->device = device; f->network = true; f->field = true;
+    for (int j = 0; j < npar; j++) f->ids[j] = ids[j];
+    // the network of the virtual wells: each carries the depths of its observation well
+    f->well_r = F.virt_r;
+    f->well_nz.resize(nvirt); f->well_z0.resize(nvirt);
+    for (int v = 0; v < nvirt; v++) {
+        const int w = F.virt_well[v];
+        f->well_nz[v] = well_nz[w];
+        f->well_z0[v] = (int)f->well_z.size();
+        f->well_z.insert(f->well_z.end(), well_z + z0[w], well_z + z0[w] + well_nz[w]);
+    }
+    std::vector<int> grp_of, pt_of;
+    long long npoints = 0;
+    network_layout(nvirt, f->well_r.data(), f->well_nz.data(), nterm, F.t.data(), F.virt.data(), f->groups, &grp_of, &pt_of, &npoints);
+    f->net_pts = f->groups.back().pt_prefix + f->groups.back().pts;
+    f->net_vals = f->groups.back().prefix + f->groups.back().stride;
+    f->dense = npoints * (long long)f->well_z.size();
+    f->refs.resize(nterm);
+    std::vector<ucf_fit_term> terms(nterm);
+    for (int i = 0; i < nobs; i++) {
+        const bool screen = iz[i] == UCF_FIT_SCREEN;
+        for (int k = F.first[i]; k < F.first[i + 1]; k++) {
+            const fit_group& G = f->groups[grp_of[k]];
+            f->refs[k] = ucf_fit_obs_ref{(long long)G.prefix, (long long)G.stride, pt_of[k] * G.nz + (screen ? 0 : iz[i]), screen ? G.nz : 1};
+            terms[k] = ucf_fit_term{f->refs[k], qw[F.pump[k]]};
+        }
+    }
+    device_switch dg(device);
+    if ((rc = grow_buffer(f->b_term, sizeof(ucf_fit_term) * nterm, "terms", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_first, sizeof(int) * ((size_t)nobs + 1), "term lists", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_obs, sizeof(double) * nobs, "observations", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_w, sizeof(double) * nobs, "weights", f->n_alloc))) { ucf_fit_destroy(f); return rc; }
+    if (hipMemcpy(f->b_term.p, terms.data(), sizeof(ucf_fit_term) * nterm, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->b_first.p, F.first.data(), sizeof(int) * ((size_t)nobs + 1), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->b_obs.p, obs, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(f->b_w.p, weight, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess) {
+        ucf_fit_destroy(f);
+        return fail(UCF_ERR_HIP, "upload of the observations failed");
+    }
+    *out = f;
+    return UCF_OK;
+}
+
+int ucf_fit_field_terms(const ucf_params* base, int npump, const double* xw, const double* yw, const double* qw, const double* t0w, int nwell,
+                        const double* well_x, const double* well_y, int nobs, const double* t, const int* well, int* nvirt, int* virt_well,
+                        double* virt_r, int* term_first, int* term_pump, int* term_virt, double* term_t)
+{
+    if (!base) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = validate(*base);
+    if (rc) return rc;
+    rc = field_check(npump, xw, yw, qw, t0w, nwell, well_x, well_y);
+    if (rc) return rc;
+    const std::vector<int> one(nwell, 1);      // the depths play no part in the geometry
+    rc = network_check(nwell, one.data(), nobs, t, well);
+    if (rc) return rc;
+    field_geometry F;
+    rc = field_layout(*base, npump, xw, yw, t0w, nwell, well_x, well_y, nobs, t, well, F);
+    if (rc) return rc;
+    if (nvirt) *nvirt = (int)F.virt_well.size();
+    if (virt_well) std::copy(F.virt_well.begin(), F.virt_well.end(), virt_well);
+    if (virt_r) std::copy(F.virt_r.begin(), F.virt_r.end(), virt_r);
+    if (term_first) std::copy(F.first.begin(), F.first.end(), term_first);
+    if (term_pump) std::copy(F.pump.begin(), F.pump.end(), term_pump);
+    if (term_virt) std::copy(F.virt.begin(), F.virt.end(), term_virt);
+    if (term_t) std::copy(F.t.begin(), F.t.end(), term_t);
     return UCF_OK;
 }
 
@@ -576,9 +761,10 @@ int ucf_fit_debug_h(ucf_fit* f, int plan, int i, int cap, double* h, int* n)
     if (!f || !h || !n) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (f->last_nplans < 1) return fail(UCF_ERR_BAD_ARGUMENT, "no evaluation to read from");
     if (plan < 0 || plan >= f->last_nplans) return fail(UCF_ERR_BAD_ARGUMENT, "plan %d outside 0..%d", plan, f->last_nplans - 1);
-    if (i < 0 || i >= f->nobs) return fail(UCF_ERR_BAD_ARGUMENT, "observation %d outside 0..%d", i, f->nobs - 1);
+    const char* what = f->field ? "term" : "observation";      // a field fit has one place per term
+    if (i < 0 || i >= (int)f->refs.size()) return fail(UCF_ERR_BAD_ARGUMENT, "%s %d outside 0..%d", what, i, (int)f->refs.size() - 1);
     const ucf_fit_obs_ref& o = f->refs[i];
-    if (cap < o.count) return fail(UCF_ERR_BAD_ARGUMENT, "cap=%d: observation %d reads %d values", cap, i, o.count);
+    if (cap < o.count) return fail(UCF_ERR_BAD_ARGUMENT, "cap=%d: %s %d reads %d values", cap, what, i, o.count);
     device_switch dg(f->device);
     const size_t at = (size_t)o.prefix * f->last_nplans + (size_t)plan * o.stride + o.at;
     HIP_TRY(hipMemcpy(h, (const double*)f->b_h.p + at, sizeof(double) * o.count, hipMemcpyDeviceToHost));

@@ -27,3 +27,17 @@ struct ucf_fit_obs_ref {
 int ucf_fit_launch_network_reduce(int npar, int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_Hc,
                                   const ucf_fit_obs_ref* d_ref, const double* d_obs, const double* d_w, double* d_sums, int* d_nbad,
                                   double* d_J, double* d_sim, void* stream);
+
+// One term of an observation of a field fit (ucf_fit_create_field): the value that `ref` finds in the h of the network of
+// virtual wells, times the rate factor q of its pumping well.
+struct ucf_fit_term {
+    ucf_fit_obs_ref ref;
+    double q;
+};
+
+// as ucf_fit_launch_network_reduce, the simulated value of observation i being the sum of its terms
+// d_term[d_first[i] .. d_first[i + 1]) in that order: acc = +0.0; acc = acc + q * (value at ref, dimensionless); acc x Hc.
+// d_first [nobs + 1] ascending; an observation without terms is +0.0.
+int ucf_fit_launch_field_reduce(int npar, int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_Hc,
+                                const ucf_fit_term* d_term, const int* d_first, const double* d_obs, const double* d_w, double* d_sums,
+                                int* d_nbad, double* d_J, double* d_sim, void* stream);

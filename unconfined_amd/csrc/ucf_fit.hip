@@ -1,7 +1,8 @@
 // ucf_fit.hip -- residuals, objective, central-difference Jacobian and normal equations of a least-squares fit, from the
-// drawdowns that the evaluators left in device memory (ucf_fit_evaluate, include/ucf.h).  Two kernels over one body:
-// fit_reduce_kernel (ucf_fit_create: one double per observation and plan) and fit_network_reduce_kernel
-// (ucf_fit_create_network: ragged per-group h, point observations and screen averages).
+// drawdowns that the evaluators left in device memory (ucf_fit_evaluate, include/ucf.h).  Three kernels over one body:
+// fit_reduce_kernel (ucf_fit_create: one double per observation and plan), fit_network_reduce_kernel
+// (ucf_fit_create_network: ragged per-group h, point observations and screen averages) and fit_field_reduce_kernel
+// (ucf_fit_create_field: an observation is the sum over pumping wells of rate factor x such a value).
 //
 // Tiny and HBM-bound: (1 + 2 NPAR) x nobs doubles per parameter set are read once.  Built with -ffp-contract=off: every
 // product and sum below is rounded on its own, so that the result is the arithmetic written here.  The sums are reduced in
@@ -116,9 +117,19 @@ struct slot_value {
     }
 };
 
-// observation i of a network = ref[i].count consecutive depths of one point in the ragged per-group h: one value, or the
-// screen average over the well's depths in the operation order of ucf_screen_average (driver.f90:234-243, quirk Q2), formed
-// on the dimensionless h and then scaled
+// `o.count` consecutive depths of one point in the ragged per-group h of a network: one value, or the screen average over
+// the well's depths in the operation order of ucf_screen_average (driver.f90:234-243, quirk Q2); dimensionless
+__device__ __forceinline__ double network_h(const double* __restrict__ h, const ucf_fit_obs_ref o, size_t nplans, size_t plan)
+{
+    const double* v = h + ((size_t)o.prefix * nplans + plan * (size_t)o.stride + (size_t)o.at);
+    const int n = o.count;
+    if (n == 1) return v[0];
+    double s = v[1];
+    for (int j = 2; j < n; j++) s = s + v[j];
+    return ((v[0] + 2.0 * s) + v[n - 1]) / (2 * n);
+}
+
+// observation i of a network = network_h at ref[i], formed on the dimensionless h and then scaled
 struct network_value {
     const double* __restrict__ h;
     const double* __restrict__ Hc;
@@ -126,13 +137,25 @@ struct network_value {
     size_t nplans;
     __device__ __forceinline__ double operator()(int i, size_t plan) const
     {
-        const ucf_fit_obs_ref o = ref[i];
-        const double* v = h + ((size_t)o.prefix * nplans + plan * (size_t)o.stride + (size_t)o.at);
-        const int n = o.count;
-        if (n == 1) return v[0] * Hc[plan];
-        double s = v[1];
-        for (int j = 2; j < n; j++) s = s + v[j];
-        return (((v[0] + 2.0 * s) + v[n - 1]) / (2 * n)) * Hc[plan];
+        return network_h(h, ref[i], nplans, plan) * Hc[plan];
+    }
+};
+
+// observation i of a field fit = the terms first[i] .. first[i + 1], one per pumping well that has started, in the
+// caller's order of pumping wells: acc = +0.0; acc = acc + q * network_h(term); then x Hc.  Every operation is rounded on
+// its own; nothing is scrubbed, so a term that is not finite makes the observation not finite.
+struct field_value {
+    const double* __restrict__ h;
+    const double* __restrict__ Hc;
+    const ucf_fit_term* __restrict__ term;
+    const int* __restrict__ first;
+    size_t nplans;
+    __device__ __forceinline__ double operator()(int i, size_t plan) const
+    {
+        double acc = 0.0;
+        const int end = first[i + 1];
+        for (int k = first[i]; k < end; k++) acc = acc + term[k].q * network_h(h, term[k].ref, nplans, plan);
+        return acc * Hc[plan];
     }
 };
 
@@ -155,6 +178,28 @@ __global__ void __launch_bounds__(FIT_THREADS) fit_network_reduce_kernel(int nob
                                                                          double* __restrict__ J, double* __restrict__ sim)
 {
     fit_reduce_body<NPAR>(nobs, two_dlog, network_value{h, Hc, ref, nplans}, obs, w, sums, nbad, J, sim);
+}
+
+template <int NPAR>
+__global__ void __launch_bounds__(FIT_THREADS) fit_field_reduce_kernel(int nobs, size_t nplans, double two_dlog, const double* __restrict__ h,
+                                                                       const double* __restrict__ Hc,
+                                                                       const ucf_fit_term* __restrict__ term,
+                                                                       const int* __restrict__ first, const double* __restrict__ obs,
+                                                                       const double* __restrict__ w, double* __restrict__ sums,
+                                                                       int* __restrict__ nbad, double* __restrict__ J,
+                                                                       double* __restrict__ sim)
+{
+    fit_reduce_body<NPAR>(nobs, two_dlog, field_value{h, Hc, term, first, nplans}, obs, w, sums, nbad, J, sim);
+}
+
+template <int NPAR>
+int launch_field(int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_Hc, const ucf_fit_term* d_term,
+                 const int* d_first, const double* d_obs, const double* d_w, double* d_sums, int* d_nbad, double* d_J, double* d_sim,
+                 hipStream_t stream)
+{
+    hipLaunchKernelGGL(fit_field_reduce_kernel<NPAR>, dim3(nsets), dim3(FIT_THREADS), 0, stream, nobs, nplans, two_dlog, d_h, d_Hc, d_term,
+                       d_first, d_obs, d_w, d_sums, d_nbad, d_J, d_sim);
+    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
 }
 
 template <int NPAR>
@@ -198,6 +243,21 @@ int ucf_fit_launch_network_reduce(int npar, int nsets, int nobs, size_t nplans, 
     if (nsets < 1 || nobs < 1) return UCF_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
 #define UCF_FIT_CASE(N) case N: return launch_network<N>(nsets, nobs, nplans, two_dlog, d_h, d_Hc, d_ref, d_obs, d_w, d_sums, d_nbad, d_J, d_sim, s)
+    switch (npar) {
+        UCF_FIT_CASE(0); UCF_FIT_CASE(1); UCF_FIT_CASE(2); UCF_FIT_CASE(3); UCF_FIT_CASE(4);
+        UCF_FIT_CASE(5); UCF_FIT_CASE(6); UCF_FIT_CASE(7); UCF_FIT_CASE(8);
+    default: return UCF_ERR_BAD_ARGUMENT;
+    }
+#undef UCF_FIT_CASE
+}
+
+int ucf_fit_launch_field_reduce(int npar, int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_Hc,
+                                const ucf_fit_term* d_term, const int* d_first, const double* d_obs, const double* d_w, double* d_sums,
+                                int* d_nbad, double* d_J, double* d_sim, void* stream)
+{
+    if (nsets < 1 || nobs < 1) return UCF_ERR_BAD_ARGUMENT;
+    hipStream_t s = (hipStream_t)stream;
+#define UCF_FIT_CASE(N) case N: return launch_field<N>(nsets, nobs, nplans, two_dlog, d_h, d_Hc, d_term, d_first, d_obs, d_w, d_sums, d_nbad, d_J, d_sim, s)
     switch (npar) {
         UCF_FIT_CASE(0); UCF_FIT_CASE(1); UCF_FIT_CASE(2); UCF_FIT_CASE(3); UCF_FIT_CASE(4);
         UCF_FIT_CASE(5); UCF_FIT_CASE(6); UCF_FIT_CASE(7); UCF_FIT_CASE(8);

@@ -123,4 +123,8 @@ int shared_launch(ucf_plan* pl, int nblk, int ppp, int nz, const fill_blocks& fi
 int stream_pool(int device, int want, hipStream_t* streams);
 int multi_core(ucf_plan* const* plans, int nplans, int npts, const double* t, const double* r, int nz, const double* z, multi_io& io);
 
+// ---- ucf_field.cpp
+// UCF_ERR_BAD_ARGUMENT naming name[i] for the first v[i] that is not finite
+int field_check_finite(const char* name, int n, const double* v);
+
 }  // namespace ucf_host

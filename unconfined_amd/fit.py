@@ -7,6 +7,9 @@ equations are formed on the device; this module only marshals arrays.
     res = fit.lm(theta0, max_iter=40)             # Levenberg-Marquardt from many starting points at once
     net = Fit.network(params, free, wells=[(r0, [z0]), (r1, [za, zb, zc])], t=t, well=well, iz=iz, obs=obs)
                                                   # an observation network: per-well radius and depths, iz = -1: screen average
+    fld = Fit.field(params, free, wells=[(0, 0, 1, 0), (40, 30, 0.6, 20)], obs_wells=[(10, 5, [z0]), (25, -8, [za, zb, zc])],
+                    t=t, well=well, iz=iz, obs=obs)
+                                                  # an interference test: pumping wells (x, y, q, t0) as WellField / images take them
 
 Parameters are positive and fitted in their logarithm; ``theta`` arrays hold the parameters themselves.
 """
@@ -85,6 +88,45 @@ def network_eval_counts(wells, t, well) -> tuple:
     return int(a.value), int(b.value)
 
 
+def _pump_wells(wells):
+    w = np.atleast_2d(_f64(wells))
+    if w.ndim != 2 or w.shape[1] != 4:
+        raise ValueError("wells: one (x, y, q, t0) per pumping well")
+    return tuple(_f64(w[:, k]) for k in range(4))
+
+
+def pack_obs_wells(obs_wells):
+    """a sequence of (x, y, z_array) -> the arrays of ucf_fit_create_field: well_x, well_y [nwell], well_nz [nwell] and
+    well_z, the depths of all wells one after the other"""
+    obs_wells = list(obs_wells)
+    well_x = _f64([float(x) for x, _, _ in obs_wells])
+    well_y = _f64([float(y) for _, y, _ in obs_wells])
+    _, well_nz, well_z = pack_wells([(0.0, z) for _, _, z in obs_wells])
+    return well_x, well_y, well_nz, well_z
+
+
+def field_terms(params: UcfParams, wells, obs_wells, t, well) -> dict:
+    """what a field fit launches and sums (ucf_fit_field_terms; no GPU): virt_well, virt_r per virtual well -- one per
+    (observation well, distinct distance to a pumping well) -- term_first [nobs + 1], and per term term_pump, term_virt and
+    term_t = t[i] - t0 of its pumping well.  ``obs_wells`` may hold (x, y) or (x, y, z_array)."""
+    xw, yw, qw, t0w = _pump_wells(wells)
+    well_x = _f64([float(o[0]) for o in obs_wells])
+    well_y = _f64([float(o[1]) for o in obs_wells])
+    t, well = _f64(t), _i32(well)
+    if len(t) != len(well):
+        raise ValueError("t and well must have one entry per observation")
+    nvirt = C.c_int()
+    npair, nmax = max(len(well_x) * len(xw), 1), max(len(t) * len(xw), 1)
+    virt_well, virt_r = np.zeros(npair, np.int32), np.zeros(npair)
+    first = np.zeros(len(t) + 1, np.int32)
+    pump, virt, tt = np.zeros(nmax, np.int32), np.zeros(nmax, np.int32), np.zeros(nmax)
+    _libmod.check(_libmod.load().ucf_fit_field_terms(C.byref(params), len(xw), xw, yw, qw, t0w, len(well_x), well_x, well_y, len(t), t,
+                                                     well, C.byref(nvirt), virt_well, virt_r, first, pump, virt, tt))
+    n = int(first[-1])
+    return {"virt_well": virt_well[:nvirt.value].copy(), "virt_r": virt_r[:nvirt.value].copy(), "term_first": first,
+            "term_pump": pump[:n].copy(), "term_virt": virt[:n].copy(), "term_t": tt[:n].copy()}
+
+
 class Fit:
     """observations (dimensional drawdown at time t[i], radius r[i], depth z[iz[i]], z up from the aquifer base) of one
     parameter set ``params`` whose ``free`` parameters are to be estimated.  All depths of ``z`` are evaluated at every
@@ -129,6 +171,34 @@ class Fit:
                                                        self.nobs, t, well, iz, obs, weight, int(device), C.byref(self._h)))
         return self
 
+    @classmethod
+    def field(cls, params: UcfParams, free, wells, obs_wells, t, well, iz, obs, weight=None, device: int = 0) -> "Fit":
+        """an interference test (ucf_fit_create_field): ``wells`` are the pumping wells, rows of (x, y, q, t0) as ``WellField``
+        and ``images`` use them (an image well is a plain row); ``obs_wells`` is a sequence of (x, y, z_array); observation
+        i is the drawdown at time t[i] in observation well well[i], at depth iz[i] of that well or, with iz[i] = -1, its
+        screen average.  Its simulated value is the sum over the pumping wells that started before t[i] of q times the
+        drawdown at time t[i] - t0 and the distance between the two wells.  ``debug_h`` takes a term index here
+        (``field_terms``)."""
+        self = cls.__new__(cls)
+        self._lib = _libmod.load()
+        self._h = C.c_void_p()
+        self.params = params
+        self.free = list(free)
+        self.ids = _i32([par_id(n) for n in free])
+        self.npar = len(self.ids)
+        xw, yw, qw, t0w = _pump_wells(wells)
+        well_x, well_y, well_nz, well_z = pack_obs_wells(obs_wells)
+        t, obs = _f64(t), _f64(obs)
+        well, iz = _i32(well), _i32(iz)
+        weight = np.ones(len(obs)) if weight is None else _f64(weight)
+        if not (len(t) == len(well) == len(iz) == len(obs) == len(weight)):
+            raise ValueError("t, well, iz, obs and weight must have one entry per observation")
+        self.nobs = len(obs)
+        _libmod.check(self._lib.ucf_fit_create_field(C.byref(params), self.npar, self.ids, len(xw), xw, yw, qw, t0w, len(well_x), well_x,
+                                                     well_y, well_nz, well_z, self.nobs, t, well, iz, obs, weight, int(device),
+                                                     C.byref(self._h)))
+        return self
+
     def eval_counts(self) -> tuple:
         """(launched, dense): (point, depth) evaluations per parameter set that this fit launches, padding included, and
         that every depth of the network at every (well, time) would take"""
@@ -137,7 +207,8 @@ class Fit:
         return int(a.value), int(b.value)
 
     def debug_h(self, plan: int, i: int) -> np.ndarray:
-        """diagnostic (ucf_fit_debug_h): the dimensionless h behind observation i under plan ``plan`` of the last evaluate"""
+        """diagnostic (ucf_fit_debug_h): the dimensionless h behind observation i (of a field fit: behind TERM i) under plan
+        ``plan`` of the last evaluate"""
         h = np.zeros(64)
         n = C.c_int()
         _libmod.check(self._lib.ucf_fit_debug_h(self._h, int(plan), int(i), len(h), h, C.byref(n)))
