@@ -828,6 +828,181 @@ UCF_DEV void dehoog_qd_tile(const ucf_dev_params& P, int lane, int ncur, const d
         for (int r = r16; r <= M; r++) qd_step<16>(Qq, Qe, r, M, lane, occ, col, pitch);
     }
 }
+
+// The same tile with the instructions that are not arithmetic taken out of the steps (-DUCF_DH_SLOTS=0: the code above).
+// Per lane every floating-point operation on a value that reaches a result is the one above, in the same order.
+//   shifts    the one-lane shift writes registers of its own (shift_down1_new: lane 63 receives 0 where it kept its own
+//             value): 4 DPP moves for a complex instead of 4 copies + 4 moves in place.  No valid entry reads what lane 63
+//             receives: e(i,r) is valid for i <= 2(M - r) and reads q(i+1,r), q(i,r+1) for i <= 2(M - r) - 1 reads e(i+1,r);
+//             at M = 31, r = 1 that is lane 61 at most, so lane 62 is the last that reads a shifted value inside a rhombus
+//             and lane 63 receives for nobody.  A group's last lane still receives its neighbour's lane 0, as above.
+//   validity  which lanes hold an entry of the rhombus is the same for every group and follows from r alone: a lane mask
+//             from the scalar unit, ANDed with the ballot of the range test, instead of a compare per step
+//   max-norm  max(|re|, |im|) is one v_max_f64 with |.| on both sources.  fmax() canonicalises each operand first (a
+//             v_max_f64 of the value with itself, for the sake of signalling NaNs); e(i,r) is the sum of two sums, a number
+//             or a QUIET NaN, and of a quiet NaN and a number v_max_f64 returns the number as fmax does: the range test
+//             behind it sees the same m, NaN (both parts NaN: the guard fires) included.
+//   store     lane 0 stores q(0,r) and e(0,r) as they are; the sign of d(2r-1) = -q(0,r), d(2r) = -e(0,r) (:100-101) is
+//             applied where dehoog_cf_slot reads the column: the same negation of the same value
+//   loops     steps come in pairs whose values change places (a, b -> b, a), so nothing is copied where a loop closes
+#ifndef UCF_DH_SLOTS
+#define UCF_DH_SLOTS 1
+#endif
+#if UCF_DH_SLOTS
+UCF_DEV double shift_down1_new(double x)
+{
+    const int lo = __double2loint(x), hi = __double2hiint(x);
+    const int l2 = __builtin_amdgcn_update_dpp(0, lo, 0x130, 0xf, 0xf, true);
+    const int h2 = __builtin_amdgcn_update_dpp(0, hi, 0x130, 0xf, 0xf, true);
+    return __hiloint2double(h2, l2);
+}
+UCF_DEV cplx shift_down1_new(cplx v) { return cmake(shift_down1_new(v.re), shift_down1_new(v.im)); }
+// lanes that hold a valid q(.,r+1), l <= 2(M - r - 1) + 1 in every group of W lanes (2(M - r) < W from the group's first step on)
+template <int W>
+UCF_DEV unsigned long long qd_valid_lanes(int r, int M)
+{
+    const unsigned long long b = (1ull << (2 * (M - r))) - 1ull;
+    if constexpr (W == 32) return b | (b << 32);
+    if constexpr (W == 16) return b * 0x0001000100010001ull;
+    return b;
+}
+// one step r < M of the rhombus in every group of W lanes: q(.,r), e(.+1,r-1) -> q2 = q(.,r+1), en2 = e(.+1,r);
+// `vmask` the lanes with a valid q(.,r+1) in a group that holds a vector, `st0` this lane is lane 0 of such a group,
+// `drow` row 2r - 1 of this lane's LDS column
+template <int W>
+UCF_DEV void qd_slot_step(cplx q, cplx en, cplx& q2, cplx& en2, unsigned long long vmask, bool st0, lds_c* drow, int pitch, int lane)
+{
+    const cplx qn = shift_down1_new(q);
+    const cplx enew = cadd(csub(qn, q), en);
+    if (st0) {
+        drow[0] = make_double2(q.re, q.im);                                                     // -d(2r-1) = q(0,r)   :100
+        drow[pitch] = make_double2(enew.re, enew.im);                                           // -d(2r)   = e(0,r)   :101
+    }
+    const cplx enn = shift_down1_new(enew);
+    double m;
+    asm("v_max_f64 %0, |%1|, |%2|" : "=v"(m) : "v"(enew.re), "v"(enew.im));
+    // (a ballot per compare and the scalar unit's OR: the ballot of the combined flag goes through a VGPR and a third compare)
+    const unsigned long long bal = (__builtin_amdgcn_ballot_w64(!(m < 1.0e150)) | __builtin_amdgcn_ballot_w64(!(m > 1.0e-150))) & vmask;
+    en2 = enn;
+    if (W == UCF_WAVE && bal != 0) {
+        q2 = cdiv(cmul(qn, enn), enew);                                                         // :93
+        return;
+    }
+    const double rc = fast_rcp(__builtin_fma(enew.re, enew.re, enew.im * enew.im));
+    const cplx num = cmul(qn, enn);
+    q2 = cmake((num.re * enew.re + num.im * enew.im) * rc, (num.im * enew.re - num.re * enew.im) * rc);
+    if (W != UCF_WAVE && __builtin_expect(bal != 0, 0)) {                // (both forms then, chosen by group: qd_quotient_groups)
+        const bool mine = ((bal >> (lane & ~(W - 1) & 63)) & ((1ull << (W & 63)) - 1)) != 0;
+        const cplx scaled = cdiv(cmul(qn, enn), enew);
+        if (mine) q2 = scaled;
+    }
+}
+// the steps r0 <= r < r1 (all below M) in pairs; `col` this lane's LDS column
+template <int W>
+UCF_DEV void qd_slot_steps(cplx& q, cplx& en, int r0, int r1, int M, unsigned long long occ_lanes, bool st0, lds_c* col, int pitch, int lane)
+{
+    lds_c* drow = col + (size_t)(2 * r0 - 1) * pitch;
+    int r = r0;
+    for (; r + 1 < r1; r += 2) {
+        cplx qb, eb;
+        qd_slot_step<W>(q, en, qb, eb, qd_valid_lanes<W>(r, M) & occ_lanes, st0, drow, pitch, lane);
+        qd_slot_step<W>(qb, eb, q, en, qd_valid_lanes<W>(r + 1, M) & occ_lanes, st0, drow + 2 * pitch, pitch, lane);
+        drow += 4 * pitch;
+    }
+    if (r < r1) {
+        cplx qb, eb;
+        qd_slot_step<W>(q, en, qb, eb, qd_valid_lanes<W>(r, M) & occ_lanes, st0, drow, pitch, lane);
+        q = qb; en = eb;
+    }
+}
+// qd_start with ONE division for q(i,1): lane 0 divides by d(0), the others by f(i) (:81-82) -- the divisor is selected, not
+// the quotient (both divisions ran in turn, each under its part of EXEC).  The same division in every lane as before.
+UCF_DEV bool qd_start_slots(cplx f, int M, int lane, ucf_stats* st, lds_c* dcol, cplx* q1)
+{
+    const int n2 = 2 * M;
+    const bool act = lane <= n2;
+    double mag = act ? fmax(fabs(f.re), fabs(f.im)) : 0.0;            // (see qd_start)
+    if (d_isnan(mag)) mag = 0.0;
+    double mx = wave_max(mag);
+    if (__builtin_expect(!(mx > UCF_DBL_MIN) && mx > 0.7 * UCF_DBL_MIN, 0)) {
+        mag = act ? cabs_(f) : 0.0;
+        if (d_isnan(mag)) mag = 0.0;
+        mx = wave_max(mag);
+    }
+    if (!(mx > UCF_DBL_MIN)) {
+        if (st) stat_add(&st->zero_vectors, lane == 0);
+        return false;
+    }
+    const bool nanp = act && (d_isnan(f.re) || d_isnan(f.im));
+    if (st) stat_add(&st->nan_scrubbed, nanp);
+    cplx ff = (nanp || !act) ? cmake(act ? 0.0 : 1.0, 0.0) : f;                                 // :71-74
+    const cplx ff0 = bcast0(ff);
+    const cplx d0 = cdivr(ff0, 2.0);                                                            // :98
+    if (lane == 0) dcol[0] = make_double2(d0.re, d0.im);
+    const cplx fnext = shift_down1_new(ff);                // (lane 63 receives 0: q(63,1) is outside every rhombus)
+    *q1 = cdiv(fnext, (lane == 0) ? d0 : ff);                                                   // :81-82  q(i,1)
+    return true;
+}
+// dehoog_qd_tile with those steps; the columns hold -d(k) for k >= 1
+UCF_DEV void dehoog_qd_tile_slots(const ucf_dev_params& P, int lane, int ncur, const double* __restrict__ tD4, lds_c* lds, lds_c* tileB,
+                                  int pitch, int* zflag, ucf_stats* st)
+{
+    const int M = P.M, np = P.np;
+    const int r32 = (M - 15 > 1) ? M - 15 : 1, r16 = (M - 7 > 1) ? M - 7 : 1;       // first step in groups of 32 / of 16 lanes
+    const cplx c0 = cmake(0.0, 0.0);
+    for (int tq = 0; tq < ncur; tq += 2) {
+        cplx Qq = c0, Qe = c0;
+        int present = 0;                                       // bit g: quarter g of the quad holds a vector
+        for (int hf = 0; hf < 2 && tq + hf < ncur; hf++) {
+            const int tt = tq + hf;
+            const double tee = 2.0 * tD4[tt];
+            const double sigma = P.alpha - P.logtol / (2.0 * tee);
+            cplx tl = c0;
+            if (lane < np) { const lds_c v = lds[lane * pitch + tt]; tl = cmake(v.x, v.y); }
+            const cplx p = cmake(sigma, UCF_PI * lane / tee);
+            cplx Pq = c0, Pe = c0;
+            for (int which = 0; which < 2; which++) {
+                lds_c* col = (which ? tileB : lds) + tt;       // (column tt of the tile is in `tl` by now)
+                cplx q;
+                const bool some = qd_start_slots(which ? cmul(tl, p) : tl, M, lane, st, col, &q);
+                const bool live = __builtin_amdgcn_ballot_w64(some) != 0;                       // (the same in every lane)
+                if (lane == 0) zflag[2 * tt + which] = !live;
+                if (!live) continue;
+                cplx en = c0;                                                                   // :80     e(i+1,0)
+                qd_slot_steps<UCF_WAVE>(q, en, 1, r32, M, ~0ull, lane == 0, col, pitch, lane);
+                present |= 1 << (2 * hf + which);
+                const cplx gq = lane_gather(q, lane & 31), ge = lane_gather(en, lane & 31);
+                if ((lane >> 5) == which) { Pq = gq; Pe = ge; }
+            }
+            const int pr = (present >> (2 * hf)) & 3;
+            if (pr == 0) continue;
+            {
+                const int g = lane >> 5;
+                const unsigned long long occ_lanes = ((pr & 1) ? 0xffffffffull : 0ull) | ((pr & 2) ? 0xffffffff00000000ull : 0ull);
+                lds_c* col = (g ? tileB : lds) + tt;
+                qd_slot_steps<32>(Pq, Pe, r32, r16, M, occ_lanes, (lane & 31) == 0 && ((pr >> g) & 1), col, pitch, lane);
+                const int src = ((lane >> 4) & 1) * 32 + (lane & 15);
+                const cplx gq = lane_gather(Pq, src), ge = lane_gather(Pe, src);
+                if ((lane >> 5) == hf) { Qq = gq; Qe = ge; }
+            }
+        }
+        if (present == 0) continue;
+        const int g = lane >> 4;
+        unsigned long long occ_lanes = 0ull;
+#pragma unroll
+        for (int k = 0; k < 4; k++) occ_lanes |= ((present >> k) & 1) ? (0xffffull << (16 * k)) : 0ull;
+        const bool st0 = (lane & 15) == 0 && ((present >> g) & 1);
+        lds_c* col = ((g & 1) ? tileB : lds) + tq + (g >> 1);
+        qd_slot_steps<16>(Qq, Qe, r16, M, M, occ_lanes, st0, col, pitch, lane);
+        const cplx qn = shift_down1_new(Qq);                   // step M: e(0,M) and no quotient (the shift by all lanes: a DPP
+        const cplx enew = cadd(csub(qn, Qq), Qe);              //  move does not read a lane that EXEC has switched off)
+        if (st0) {
+            col[(size_t)(2 * M - 1) * pitch] = make_double2(Qq.re, Qq.im);
+            col[(size_t)(2 * M) * pitch] = make_double2(enew.re, enew.im);
+        }
+    }
+}
+#endif   // UCF_DH_SLOTS
 #endif
 
 UCF_DEV double dehoog_cf_lane(const lds_c* dcol, int pitch, int M, double alpha, double logtol, double t, double tee)
@@ -854,6 +1029,41 @@ UCF_DEV double dehoog_cf_lane(const lds_c* dcol, int pitch, int M, double alpha,
     const cplx B2M = cadd(Bm1, cmul(rem, Bm2));
     return exp(gamma * t) / tee * cdiv(A2M, B2M).re;                                            // :129
 }
+
+#if UCF_FAST && UCF_DH_PACK && UCF_DH_SLOTS
+// dehoog_cf_lane on the columns of dehoog_qd_tile_slots (rows k >= 1 hold -d(k): negated as they are read), with the A and
+// the B recurrence of a vector on a lane each (`ab` = 0: A, 1: B, in neighbouring lanes): the two are the same operations
+// on other start values, so a lane runs one of them, forms the improved remainder (both lanes the same bits) and its own
+// A(2M) or B(2M); one exchange with the neighbour brings the other for the quotient.
+UCF_DEV double dehoog_cf_slot(const lds_c* dcol, int pitch, int M, double alpha, double logtol, double t, double tee, int ab)
+{
+    const double gamma = alpha - logtol / (2.0 * tee);                                          // :77
+    const lds_c v0 = dcol[0];
+    const cplx d0 = cmake(v0.x, v0.y);
+    cplx Xm2 = cmake(ab ? 1.0 : 0.0, 0.0), Xm1 = ab ? cmake(1.0, 0.0) : d0;                     // :105-107
+    const cplx z = cexp_(cdivr(cscale(cscale(cmake(0.0, 1.0), UCF_PI), t), tee));               // :110
+    auto next = [&](int n, cplx xm1, cplx xm2) {                                                // :114-117
+        const lds_c v = dcol[(size_t)n * pitch];
+        return cadd(xm1, cmul(cmul(cmake(-v.x, -v.y), xm2), z));
+    };
+    int n = 1;
+    for (; n + 1 <= 2 * M - 1; n += 2) {                   // (in pairs: the two newest change places, no copies)
+        Xm2 = next(n, Xm1, Xm2);
+        Xm1 = next(n + 1, Xm2, Xm1);
+    }
+    if (n <= 2 * M - 1) { const cplx Xn = next(n, Xm1, Xm2); Xm2 = Xm1; Xm1 = Xn; }
+    const lds_c vq = dcol[(size_t)(2 * M - 1) * pitch], ve = dcol[(size_t)(2 * M) * pitch];
+    const cplx dlast_q = cmake(-vq.x, -vq.y), dlast_e = cmake(-ve.x, -ve.y);
+    // :120-125 improved remainder
+    const cplx brem = cdivr(radd(1.0, cmul(csub(dlast_q, dlast_e), z)), 2.0);
+    const cplx inner = csqrt_(radd(1.0, cdiv(cmul(dlast_e, z), cmul(brem, brem))));
+    const cplx rem = cneg(cmul(brem, rsub(1.0, inner)));
+    const cplx X2M = cadd(Xm1, cmul(rem, Xm2));
+    const cplx other = cmake(__shfl_xor(X2M.re, 1, 64), __shfl_xor(X2M.im, 1, 64));
+    const cplx A2M = ab ? other : X2M, B2M = ab ? X2M : other;
+    return exp(gamma * t) / tee * cdiv(A2M, B2M).re;                                            // :129
+}
+#endif
 
 // Same algorithm for 2M+1 > 64: element i = lane + 64 g lives in register set g of its lane, G = 2 sets for
 // 2M+1 <= 128, G = 4 for 2M+1 <= 256 (M up to 127).  Used by dehoog_points_kernel and the big-M branch of
@@ -2033,7 +2243,9 @@ dehoog_tiles_kernel(const ucf_dev_params P, int nt, int nr, int ir0, int nrc, co
             }
             __syncthreads();
             if constexpr (!BIG) {
-#if UCF_FAST && UCF_DH_PACK
+#if UCF_FAST && UCF_DH_PACK && UCF_DH_SLOTS
+                dehoog_qd_tile_slots(P, lane, ncur, tDv + it0, lds, tileB, pitch, zflag, st);
+#elif UCF_FAST && UCF_DH_PACK
                 dehoog_qd_tile(P, lane, ncur, tDv + it0, lds, tileB, pitch, zflag, st);
 #else
                 for (int tt = 0; tt < ncur; tt++) {
@@ -2050,6 +2262,20 @@ dehoog_tiles_kernel(const ucf_dev_params P, int nt, int nr, int ir0, int nrc, co
                 }
 #endif
                 __syncthreads();
+#if UCF_FAST && UCF_DH_PACK && UCF_DH_SLOTS
+                if (lane < 4 * ncur) {                         // lane = 4 time + 2 (h | dh) + (A | B)
+                    const int tt = lane >> 2, which = (lane >> 1) & 1;
+                    const int it = it0 + tt;
+                    const double tD = tDv[it];
+                    double val = 0.0;
+                    if (!zflag[lane >> 1]) val = dehoog_cf_slot((which ? tileB : lds) + tt, pitch, P.M, P.alpha, P.logtol, tD, 2.0 * tD, lane & 1);
+                    const size_t o = ((size_t)it * nr + ir0 + irl) * P.nz_out + P.z_off + z;
+                    if ((lane & 1) == 0) {
+                        if (which) dhout[o] = val * tD;
+                        else hout[o] = val;
+                    }
+                }
+#else
                 if (lane < 2 * ncur) {
                     const int tt = lane >> 1, which = lane & 1;
                     const int it = it0 + tt;
@@ -2060,6 +2286,7 @@ dehoog_tiles_kernel(const ucf_dev_params P, int nt, int nr, int ir0, int nrc, co
                     if (which) dhout[o] = val * tD;
                     else hout[o] = val;
                 }
+#endif
             } else {
                 for (int tt = 0; tt < ncur; tt++) {
                     const int it = it0 + tt;

@@ -234,6 +234,11 @@ UCF_DEV double fast_scale(const ucf_dev_params& P)
     return (FAMILY == 2 && P.model == 4) ? 2.0 : 2.0 * P.inv_bD;
 }
 
+// UCF_ZPAIR_HALFK=0 (A/B builds): the folded water-table kernel with one depth per launch forms 0.5 (|q| + Re q) / kappa with
+// 1 / kappa and a multiplication by 0.5 of its own, as it did before the plan carried 0.5 / kappa
+#ifndef UCF_ZPAIR_HALFK
+#define UCF_ZPAIR_HALFK 1
+#endif
 // theta and eta of this abscissa.  Returns false (for this lane) if the fast evaluation is not applicable:
 // a cosh/sinh could overflow, or the argument of a sin/cos (|Im eta| times a factor <= 1) leaves the range of
 // the two-stage Cody-Waite reduction.
@@ -259,6 +264,16 @@ UCF_DEV bool fast_eta(const ucf_dev_params& P, const lane_consts& L, double a, f
         S.th = cmake(q.re * r, -(q.im * r));
     }
     if (FAMILY == 0) return q.re > 0.0;                           // Theis is that reciprocal and nothing else
+#if UCF_ZPAIR_HALFK
+    if (PAIR) {   // eta = sqrt(q/kappa) as below with 0.5 / kappa from the plan: (|q| + Re q) (0.5 / kappa) is the fma that
+        // 0.5 (|q| / kappa + Re q / kappa) was, on operands scaled by 2^-1 -- every rounding commutes with that scaling short
+        // of the subnormals, which |q| / kappa is nowhere near inside the fast range: the same bits, one multiplication less
+        const double qi = q.im * P.inv_kappa;
+        double r, hr;
+        sqrt_hrsqrt(__builtin_fma(q.re, P.half_inv_kappa, mq * P.half_inv_kappa), &r, &hr);
+        S.eta = cmake(r, qi * hr);
+    } else
+#endif
     {   // eta = sqrt(q/kappa), Re q > 0                                                         (:69,172)
         const double qr = q.re * P.inv_kappa, qi = q.im * P.inv_kappa;
         double r, hr;

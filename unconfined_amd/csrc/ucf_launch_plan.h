@@ -51,6 +51,7 @@ struct ucf_dev_params {
     const double* sched;   // timeType = -n: [n] start times | [n] rate increments | final time | sum of increments
     const double* sc_tab;  // [256] x (sin, cos)(k pi / 128) | [128] x (hi, lo) of 2^(j/128): copied into LDS by the fast flavour's kernels
                            // (sincos_tab_, exp_tab_)
+    double half_inv_kappa; // 0.5 / kappa = 0.5 * inv_kappa exactly (fast_eta<FAMILY, PAIR>); last, so that no other field moves
 };
 #define UCF_SC_ENTRIES (256 + 128)   /* 16-byte units of that table */
 #define UCF_IWPB 4             /* waves per workgroup of integrate_kernel: they share the sin/cos table in LDS */

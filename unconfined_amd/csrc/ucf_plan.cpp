@@ -251,6 +251,7 @@ int plan_set_params(ucf_plan* pl, const ucf_params& Pin, bool create)
     for (int m = 0; m < P.MoenchM; m++) dp.MoenchInvGamma[m] = 1.0 / D.MoenchGamma[m];
     dp.alpha = P.alpha; dp.logtol = std::log(P.tol); dp.maxexp = -std::log(DBL_EPSILON) / 3.0;   // constants.f90:66
     dp.inv_kappa = 1.0 / P.kappa;
+    dp.half_inv_kappa = 0.5 * dp.inv_kappa;
     dp.inv_bD = 1.0 / D.bD;
     dp.fold_dD = (D.dD == 0.0);                       // sinh(eta*0) == 0 exactly
     dp.fold_lD1 = (dp.lD1 == 0.0);
