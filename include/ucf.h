@@ -438,6 +438,53 @@ int ucf_fit_field_terms(const ucf_params* base,
                         int* nvirt, int* virt_well /*[nwell*npump]*/, double* virt_r /*[nwell*npump], dimensional*/,
                         int* term_first /*[nobs+1]*/, int* term_pump, int* term_virt, double* term_t /*[nobs*npump] each*/);
 
+/* Derivative data: the log-time derivative t ds/dt of the drawdown, fitted jointly with the drawdown itself.  The evaluators
+ * write dh = t dh/dt beside every h; a fit keeps it in device memory in the layout of h, and a fit that has derivative data
+ * reads it in the reduction.  No evaluator launch is added.
+ *   dobs[i]      the observed DIMENSIONAL derivative t ds/dt of observation i (a length: what a deck with dimensionless = F
+ *                prints in its derivative column), dweight[i] >= 0 its weight.  dweight[i] == 0: observation i has no
+ *                derivative datum and dobs[i] may be anything, NaN included.  nd = number of i with dweight[i] > 0.
+ *   simd_i       the simulated derivative of observation i under a plan, every operation rounded on its own:
+ *                  ucf_fit_create          dh[plan][place of i] * Hc[plan];
+ *                  ucf_fit_create_network  what the reduction of that entry forms from h, formed from dh: one value, or the
+ *                                          screen average over the well's depths by the rule of ucf_screen_average; then x Hc;
+ *                  ucf_fit_create_field    acc = +0.0; over the terms of i in the caller's order of pumping wells
+ *                                          acc = acc + q * (tfac * v), v as for a network on the term's dh and
+ *                                          tfac = t[i] / term_t (one division of the observation's own time by the term time
+ *                                          that ucf_fit_field_terms states: the factor tfac of ucf_field_group; exactly 1
+ *                                          for a well that starts at 0); acc * Hc.  The operation order of ds in
+ *                                          field_superpose_kernel.
+ *   Jd[i][j]     (simd_i(theta e^{+dlog e_j}) - simd_i(theta e^{-dlog e_j})) / (2 dlog).
+ *   reduction    fit_joint_reduce_kernel, fit_network_joint_reduce_kernel, fit_field_joint_reduce_kernel: per observation, in
+ *                the lane order and with the fixed reduction order of the kernels without derivative data,
+ *                  1. s[k] and sd[k] of every plan of the set; sim, simd, J, Jd are written where asked, finite or not;
+ *                  2. the observation counts when every s[k] is finite AND (dweight[i] == 0 OR every sd[k] is finite);
+ *                     otherwise it adds 1 to nbad and nothing to the sums.  With all dweight == 0 that is the rule of a fit
+ *                     without derivative data, and phi, g, A, nbad have the same bits;
+ *                  3. the drawdown term, operation for operation as without derivative data;
+ *                  4. where dweight[i] > 0 (skipped otherwise, not added as zero), into the same sums:
+ *                       wr = wd_i * (dobs_i - sd[0]);   phi = phi + wr*wr;   phi_d = phi_d + wr*wr;
+ *                       dd_j = (sd[1+2j] - sd[2+2j]) / (2 dlog);   wdd_j = wd_i * dd_j;
+ *                       g_j = g_j + wdd_j * wr;   A_jk = A_jk + wdd_j * wdd_k  (j <= k).
+ *                No floating-point atomics: a call repeated gives the same bits. */
+/* host only, no GPU.  UCF_ERR_BAD_ARGUMENT, the offender in ucf_last_error: a NULL array, a dweight[i] that is negative or not
+ * finite, a dobs[i] that is not finite where dweight[i] > 0.  *nd = number of i with dweight[i] > 0. */
+int ucf_fit_derivative_check(int nobs, const double* dobs /*[nobs]*/, const double* dweight /*[nobs]*/, int* nd);
+/* attaches dobs, dweight [nobs of the fit, in the caller's observation order] to a fit made by any of the three constructors
+ * (ucf_fit_derivative_check first; then two device buffers of the fit, counted in ucf_fit_alloc_count the first time, and for
+ * a field fit a third with tfac per term); NULL for both arrays detaches them again (the buffers stay with the fit). */
+int ucf_fit_set_derivative(ucf_fit* fit, const double* dobs, const double* dweight);
+/* On a fit WITH derivative data ucf_fit_evaluate and ucf_fit_lm return the joint phi, g, A and nbad, so that ucf_fit_lm fits
+ * both curves, and cov = phi / (nobs + nd - npar) A^-1; on a fit without, both run what they ran before these entries existed.
+ * ucf_fit_evaluate_joint is ucf_fit_evaluate plus phi_d[nsets], the derivative terms' share of phi, Jd [nsets][nobs][npar] and
+ * simd_all [nsets][1 + 2 npar][nobs] (rows as in sim_all); any output may be NULL.  UCF_ERR_BAD_ARGUMENT on a fit without
+ * derivative data. */
+int ucf_fit_evaluate_joint(ucf_fit* fit, int nsets, const double* theta /*[nsets][npar]*/, double dlog,
+                           double* phi, double* g, double* A, int* nbad, double* J, double* sim_all,
+                           double* phi_d, double* Jd, double* simd_all);
+/* diagnostic: as ucf_fit_debug_h, the dimensionless dh behind observation (field fit: term) i of the last evaluation */
+int ucf_fit_debug_dh(ucf_fit* fit, int plan, int i, int cap, double* dh, int* n);
+
 /* ---- well fields: the drawdown of several pumping wells -- wells that start at different times, image wells for a river or an
  * outcrop -- is the sum over wells of q_j h(t - t0_j, |x - x_j|, z).  All wells share the plan's aquifer, well geometry and
  * time behaviour; they differ in position (xw, yw), rate factor qw (times the plan's Q; negative: injection or a constant-head

@@ -58,10 +58,18 @@ struct ucf_fit {
     // observation i sums the terms b_first[i] .. b_first[i + 1] of b_term (ucf_fit_term: place and rate factor)
     bool field = false;
     ucf_buffer b_term, b_first;
+    std::vector<double> term_tobs, term_t; // per term: the time of its observation, and that time minus the start of its pumping well
+    // derivative data (ucf_fit_set_derivative): observed t ds/dt and its weight per observation, nd of them with a positive
+    // weight; a field fit also holds tfac per term.  The buffers stay when the data are detached.
+    bool deriv = false;
+    int nd = 0;
+    ucf_buffer b_dobs, b_wd, b_tfac;
+    ucf_buffer b_Jd, b_simd;               // grown on demand, as b_J and b_sim
     // every device buffer above: the one list (ucf_fit_destroy frees through it)
-    std::array<ucf_buffer*, 16> buffers()
+    std::array<ucf_buffer*, 21> buffers()
     {
-        return {{&b_slot, &b_obs, &b_w, &b_t, &b_r, &b_s, &b_h, &b_d, &b_hc, &b_sums, &b_nbad, &b_J, &b_sim, &b_ref, &b_term, &b_first}};
+        return {{&b_slot, &b_obs, &b_w, &b_t, &b_r, &b_s, &b_h, &b_d, &b_hc, &b_sums, &b_nbad, &b_J, &b_sim, &b_ref, &b_term, &b_first,
+                 &b_dobs, &b_wd, &b_tfac, &b_Jd, &b_simd}};
     }
     std::vector<double> st_t;              // staging of one plan: its tD over all groups ...
     std::vector<int> st_s;                 // ... and their split vector
@@ -384,9 +392,10 @@ int network_core(ucf_fit* f, int nplans)
     return rc;
 }
 
-// jac != 0: base and perturbed plans, everything; jac == 0: the base plans only, phi and nbad (the trial points of ucf_fit_lm)
+// jac != 0: base and perturbed plans, everything; jac == 0: the base plans only, phi and nbad (the trial points of ucf_fit_lm).
+// On a fit with derivative data the sums are the joint ones and phi_d, Jd, simd_all may be asked for; without, they are NULL.
 int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int jac, double* phi, double* g, double* A, int* nbad,
-                 double* J, double* sim_all)
+                 double* J, double* sim_all, double* phi_d = nullptr, double* Jd = nullptr, double* simd_all = nullptr)
 {
     if (!f || !theta) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (nsets < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nsets=%d: at least one parameter set", nsets);
@@ -428,7 +437,8 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
                 return fail(rc, "set %d, %s moved by %+g in its logarithm: %s", s, fit_par_name(f->ids[j], nb, sizeof(nb)), (v & 1) ? dlog : -dlog, why.c_str());
             }
         }
-    const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_, nsum = (size_t)ucf_fit_nsums(jac ? npar : 0);
+    const bool joint = f->deriv;
+    const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_, nsum = (size_t)(joint ? ucf_fit_joint_nsums(jac ? npar : 0) : ucf_fit_nsums(jac ? npar : 0));
     // points and (point, depth) values that are launched: every depth at every observation, or the network's blocks
     const size_t ptot = (size_t)nplans * (f->network ? f->net_pts : np_), vtot = (size_t)nplans * (f->network ? f->net_vals : np_ * nz);
     int rc;
@@ -439,6 +449,8 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
         return rc;
     if (J && jac && (rc = grow_buffer(f->b_J, sizeof(double) * nsets * np_ * npar, "J", f->n_alloc))) return rc;
     if (sim_all && (rc = grow_buffer(f->b_sim, sizeof(double) * tot, "sim_all", f->n_alloc))) return rc;
+    if (Jd && jac && (rc = grow_buffer(f->b_Jd, sizeof(double) * nsets * np_ * npar, "Jd", f->n_alloc))) return rc;
+    if (simd_all && (rc = grow_buffer(f->b_simd, sizeof(double) * tot, "simd_all", f->n_alloc))) return rc;
     f->io.d_t = (double*)f->b_t.p; f->io.d_r = (double*)f->b_r.p; f->io.d_s = (int*)f->b_s.p;
     f->io.d_h = (double*)f->b_h.p; f->io.d_d = (double*)f->b_d.p;
     f->last_nplans = 0;
@@ -448,7 +460,22 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     f->h_hc.resize(nplans);
     for (int k = 0; k < nplans; k++) f->h_hc[k] = f->plans[k]->D.Hc;
     HIP_TRY(hipMemcpy(f->b_hc.p, f->h_hc.data(), sizeof(double) * nplans, hipMemcpyHostToDevice));
-    if (f->field)
+    const ucf_fit_joint_io jio = {(const double*)f->b_obs.p, (const double*)f->b_w.p, (const double*)f->b_dobs.p, (const double*)f->b_wd.p,
+                                  (double*)f->b_sums.p, (int*)f->b_nbad.p, (J && jac) ? (double*)f->b_J.p : nullptr,
+                                  sim_all ? (double*)f->b_sim.p : nullptr, (Jd && jac) ? (double*)f->b_Jd.p : nullptr,
+                                  simd_all ? (double*)f->b_simd.p : nullptr};
+    if (joint && f->field)
+        rc = ucf_fit_launch_field_joint_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
+                                               (const double*)f->b_d.p, (const double*)f->b_hc.p, (const ucf_fit_term*)f->b_term.p,
+                                               (const double*)f->b_tfac.p, (const int*)f->b_first.p, &jio, nullptr);
+    else if (joint && f->network)
+        rc = ucf_fit_launch_network_joint_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
+                                                 (const double*)f->b_d.p, (const double*)f->b_hc.p, (const ucf_fit_obs_ref*)f->b_ref.p, &jio,
+                                                 nullptr);
+    else if (joint)
+        rc = ucf_fit_launch_joint_reduce(jac ? npar : 0, nsets, nobs, np_ * nz, 2.0 * dlog, (const double*)f->b_h.p, (const double*)f->b_d.p,
+                                         (const double*)f->b_hc.p, (const int*)f->b_slot.p, &jio, nullptr);
+    else if (f->field)
         rc = ucf_fit_launch_field_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
                                          (const double*)f->b_hc.p, (const ucf_fit_term*)f->b_term.p, (const int*)f->b_first.p,
                                          (const double*)f->b_obs.p, (const double*)f->b_w.p, (double*)f->b_sums.p, (int*)f->b_nbad.p,
@@ -469,9 +496,12 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     if (nbad) HIP_TRY(hipMemcpy(nbad, f->b_nbad.p, sizeof(int) * nsets, hipMemcpyDeviceToHost));
     if (J && jac) HIP_TRY(hipMemcpy(J, f->b_J.p, sizeof(double) * nsets * np_ * npar, hipMemcpyDeviceToHost));
     if (sim_all) HIP_TRY(hipMemcpy(sim_all, f->b_sim.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
+    if (Jd && jac) HIP_TRY(hipMemcpy(Jd, f->b_Jd.p, sizeof(double) * nsets * np_ * npar, hipMemcpyDeviceToHost));
+    if (simd_all) HIP_TRY(hipMemcpy(simd_all, f->b_simd.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
     for (int s = 0; s < nsets; s++) {
         const double* v = &f->h_sums[s * nsum];
         if (phi) phi[s] = v[0];
+        if (phi_d) phi_d[s] = v[nsum - 1];
         if (!jac) continue;
         if (g) for (int j = 0; j < npar; j++) g[(size_t)s * npar + j] = v[1 + j];
         if (A) {
@@ -683,10 +713,13 @@ int ucf_fit_create_field(const ucf_params* base, int npar, const int* ids, int n
     f->net_vals = f->groups.back().prefix + f->groups.back().stride;
     f->dense = npoints * (long long)f->well_z.size();
     f->refs.resize(nterm);
+    f->term_t = F.t;
+    f->term_tobs.resize(nterm);
     std::vector<ucf_fit_term> terms(nterm);
     for (int i = 0; i < nobs; i++) {
         const bool screen = iz[i] == UCF_FIT_SCREEN;
         for (int k = F.first[i]; k < F.first[i + 1]; k++) {
+            f->term_tobs[k] = t[i];
             const fit_group& G = f->groups[grp_of[k]];
             f->refs[k] = ucf_fit_obs_ref{(long long)G.prefix, (long long)G.stride, pt_of[k] * G.nz + (screen ? 0 : iz[i]), screen ? G.nz : 1};
             terms[k] = ucf_fit_term{f->refs[k], qw[F.pump[k]]};
@@ -756,7 +789,8 @@ int ucf_fit_network_eval_counts(int nwell, const int* well_nz, int nobs, const d
     return UCF_OK;
 }
 
-int ucf_fit_debug_h(ucf_fit* f, int plan, int i, int cap, double* h, int* n)
+// ucf_fit_debug_h / ucf_fit_debug_dh: b_h and b_d have one layout
+static int fit_debug_read(ucf_fit* f, bool dh, int plan, int i, int cap, double* h, int* n)
 {
     if (!f || !h || !n) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (f->last_nplans < 1) return fail(UCF_ERR_BAD_ARGUMENT, "no evaluation to read from");
@@ -767,8 +801,57 @@ int ucf_fit_debug_h(ucf_fit* f, int plan, int i, int cap, double* h, int* n)
     if (cap < o.count) return fail(UCF_ERR_BAD_ARGUMENT, "cap=%d: %s %d reads %d values", cap, what, i, o.count);
     device_switch dg(f->device);
     const size_t at = (size_t)o.prefix * f->last_nplans + (size_t)plan * o.stride + o.at;
-    HIP_TRY(hipMemcpy(h, (const double*)f->b_h.p + at, sizeof(double) * o.count, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h, (const double*)(dh ? f->b_d.p : f->b_h.p) + at, sizeof(double) * o.count, hipMemcpyDeviceToHost));
     *n = o.count;
+    return UCF_OK;
+}
+
+int ucf_fit_debug_h(ucf_fit* f, int plan, int i, int cap, double* h, int* n) { return fit_debug_read(f, false, plan, i, cap, h, n); }
+int ucf_fit_debug_dh(ucf_fit* f, int plan, int i, int cap, double* dh, int* n) { return fit_debug_read(f, true, plan, i, cap, dh, n); }
+
+int ucf_fit_derivative_check(int nobs, const double* dobs, const double* dweight, int* nd)
+{
+    if (nd) *nd = 0;
+    if (nobs < 0) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d is negative", nobs);
+    if (!dobs) return fail(UCF_ERR_BAD_ARGUMENT, "dobs is NULL");
+    if (!dweight) return fail(UCF_ERR_BAD_ARGUMENT, "dweight is NULL");
+    if (!nd) return fail(UCF_ERR_BAD_ARGUMENT, "nd is NULL");
+    int count = 0;
+    for (int i = 0; i < nobs; i++) {
+        if (!(dweight[i] >= 0.0) || !std::isfinite(dweight[i])) return fail(UCF_ERR_BAD_ARGUMENT, "dweight[%d]=%g is negative or not finite", i, dweight[i]);
+        if (dweight[i] > 0.0) {
+            if (!std::isfinite(dobs[i])) return fail(UCF_ERR_BAD_ARGUMENT, "dobs[%d]=%g is not finite (dweight[%d]=%g)", i, dobs[i], i, dweight[i]);
+            count++;
+        }
+    }
+    *nd = count;
+    return UCF_OK;
+}
+
+int ucf_fit_set_derivative(ucf_fit* f, const double* dobs, const double* dweight)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (!dobs && !dweight) { f->deriv = false; f->nd = 0; return UCF_OK; }
+    int nd = 0;
+    int rc = ucf_fit_derivative_check(f->nobs, dobs, dweight, &nd);
+    if (rc) return rc;
+    device_switch dg(f->device);
+    const size_t nobs = (size_t)f->nobs, nterm = f->term_t.size();
+    if ((rc = grow_buffer(f->b_dobs, sizeof(double) * nobs, "derivative observations", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_wd, sizeof(double) * nobs, "derivative weights", f->n_alloc)))
+        return rc;
+    f->deriv = false;                      // until everything is in place
+    HIP_TRY(hipMemcpy(f->b_dobs.p, dobs, sizeof(double) * nobs, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(f->b_wd.p, dweight, sizeof(double) * nobs, hipMemcpyHostToDevice));
+    if (f->field) {
+        // tfac of ucf_field_group, per term: the observation's own time over the term's time, one division
+        std::vector<double> tfac(nterm);
+        for (size_t k = 0; k < nterm; k++) tfac[k] = f->term_tobs[k] / f->term_t[k];
+        if ((rc = grow_buffer(f->b_tfac, sizeof(double) * nterm, "term time factors", f->n_alloc))) return rc;
+        HIP_TRY(hipMemcpy(f->b_tfac.p, tfac.data(), sizeof(double) * nterm, hipMemcpyHostToDevice));
+    }
+    f->deriv = true;
+    f->nd = nd;
     return UCF_OK;
 }
 
@@ -784,6 +867,14 @@ int ucf_fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, do
                      double* sim_all)
 {
     return fit_evaluate(f, nsets, theta, dlog, 1, phi, g, A, nbad, J, sim_all);
+}
+
+int ucf_fit_evaluate_joint(ucf_fit* f, int nsets, const double* theta, double dlog, double* phi, double* g, double* A, int* nbad, double* J,
+                           double* sim_all, double* phi_d, double* Jd, double* simd_all)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (!f->deriv) return fail(UCF_ERR_BAD_ARGUMENT, "the fit has no derivative data (ucf_fit_set_derivative)");
+    return fit_evaluate(f, nsets, theta, dlog, 1, phi, g, A, nbad, J, sim_all, phi_d, Jd, simd_all);
 }
 
 int ucf_fit_default_options(ucf_fit_options* opt)
@@ -889,11 +980,13 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
         }
     }
     if (cov) {
-        // cov = phi / (nobs - npar) A^-1 at the final point (NaN where A is singular, the start was not finite or nobs == npar)
+        // cov = phi / (nobs + nd - npar) A^-1 at the final point (NaN where A is singular, the start was not finite or no degree
+        // of freedom is left); nd = derivative data with a positive weight, 0 on a fit without
         for (size_t i = 0; i < nstarts * PP; i++) cov[i] = NAN;
         idx.clear();
         for (int s = 0; s < nstarts; s++) if (status[s] != UCF_FIT_NONFINITE_START) idx.push_back(s);
-        if (!idx.empty() && f->nobs > P) {
+        const int dof = f->nobs + (f->deriv ? f->nd : 0) - P;
+        if (!idx.empty() && dof > 0) {
             const int n = (int)idx.size();
             th.resize((size_t)n * P); ph.resize(n); AA.resize(n * PP); nb.resize(n);
             for (int q = 0; q < n; q++) for (int j = 0; j < P; j++) th[(size_t)q * P + j] = theta[(size_t)idx[q] * P + j];
@@ -906,7 +999,7 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
                 for (int j = 0; j < P && good; j++) {
                     for (int k = 0; k < P; k++) e[k] = (k == j) ? 1.0 : 0.0;
                     good = ucf_fit_solve_step(P, &AA[q * PP], e, 0.0, col) == UCF_OK;
-                    for (int k = 0; k < P && good; k++) cov[s * PP + (size_t)k * P + j] = phi[s] / (double)(f->nobs - P) * col[k];
+                    for (int k = 0; k < P && good; k++) cov[s * PP + (size_t)k * P + j] = phi[s] / (double)dof * col[k];
                 }
                 if (!good) for (size_t i = 0; i < PP; i++) cov[s * PP + i] = NAN;
             }

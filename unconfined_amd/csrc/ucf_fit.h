@@ -41,3 +41,30 @@ struct ucf_fit_term {
 int ucf_fit_launch_field_reduce(int npar, int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_Hc,
                                 const ucf_fit_term* d_term, const int* d_first, const double* d_obs, const double* d_w, double* d_sums,
                                 int* d_nbad, double* d_J, double* d_sim, void* stream);
+
+// ---- a fit with derivative data (ucf_fit_set_derivative): the joint reduction.  The kernels above and their launchers are
+// what a fit without derivative data runs; these read the evaluators' dh (d_dh, laid out exactly as d_h) as well.
+// sums per parameter set: phi | g[npar] | upper triangle of A | phi_d (the derivative terms' share of phi)
+static inline int ucf_fit_joint_nsums(int npar) { return ucf_fit_nsums(npar) + 1; }
+
+// what the three joint launchers share: d_obs, d_w, d_dobs, d_wd [nobs] (d_dobs[i] is read only where d_wd[i] > 0);
+// d_sums [nsets][ucf_fit_joint_nsums(npar)], d_nbad [nsets]; d_J, d_Jd [nsets][nobs][npar] and d_sim, d_simd
+// [nsets][1+2 npar][nobs] may each be NULL
+struct ucf_fit_joint_io {
+    const double *d_obs, *d_w, *d_dobs, *d_wd;
+    double* d_sums;
+    int* d_nbad;
+    double *d_J, *d_sim, *d_Jd, *d_simd;
+};
+
+// as ucf_fit_launch_reduce; the simulated derivative of observation i is d_dh[plan * plan_stride + d_slot[i]] * d_Hc[plan]
+int ucf_fit_launch_joint_reduce(int npar, int nsets, int nobs, size_t plan_stride, double two_dlog, const double* d_h, const double* d_dh,
+                                const double* d_Hc, const int* d_slot, const ucf_fit_joint_io* io, void* stream);
+// as ucf_fit_launch_network_reduce; the derivative is found through the same d_ref[i] in d_dh (a screen is averaged by the same rule)
+int ucf_fit_launch_network_joint_reduce(int npar, int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_dh,
+                                        const double* d_Hc, const ucf_fit_obs_ref* d_ref, const ucf_fit_joint_io* io, void* stream);
+// as ucf_fit_launch_field_reduce; d_tfac [terms]: t_i / (t_i - t0) of each term; the derivative of observation i is
+// acc = +0.0; acc = acc + q * (tfac * (value at ref in d_dh)); acc x Hc
+int ucf_fit_launch_field_joint_reduce(int npar, int nsets, int nobs, size_t nplans, double two_dlog, const double* d_h, const double* d_dh,
+                                      const double* d_Hc, const ucf_fit_term* d_term, const double* d_tfac, const int* d_first,
+                                      const ucf_fit_joint_io* io, void* stream);

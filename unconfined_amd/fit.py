@@ -7,6 +7,7 @@ equations are formed on the device; this module only marshals arrays.
     res = fit.lm(theta0, max_iter=40)             # Levenberg-Marquardt from many starting points at once
     net = Fit.network(params, free, wells=[(r0, [z0]), (r1, [za, zb, zc])], t=t, well=well, iz=iz, obs=obs)
                                                   # an observation network: per-well radius and depths, iz = -1: screen average
+    fit.set_derivative(dobs)                      # fit the log-time derivative t ds/dt jointly; evaluate(..., derivative=True)
     fld = Fit.field(params, free, wells=[(0, 0, 1, 0), (40, 30, 0.6, 20)], obs_wells=[(10, 5, [z0]), (25, -8, [za, zb, zc])],
                     t=t, well=well, iz=iz, obs=obs)
                                                   # an interference test: pumping wells (x, y, q, t0) as WellField / images take them
@@ -127,6 +128,21 @@ def field_terms(params: UcfParams, wells, obs_wells, t, well) -> dict:
             "term_pump": pump[:n].copy(), "term_virt": virt[:n].copy(), "term_t": tt[:n].copy()}
 
 
+def derivative_check(dobs, dweight) -> int:
+    """the checks of ``Fit.set_derivative`` (ucf_fit_derivative_check; no GPU): raises UcfError naming the offender -- a
+    weight that is negative or not finite, a derivative that is not finite under a positive weight -- and returns nd, the
+    number of positive weights.  ``None`` for an array is passed on as NULL."""
+    dobs = None if dobs is None else _f64(dobs)
+    dweight = None if dweight is None else _f64(dweight)
+    if dobs is not None and dweight is not None and len(dobs) != len(dweight):
+        raise ValueError("dobs and dweight must have one entry per observation")
+    n = len(dobs) if dobs is not None else (len(dweight) if dweight is not None else 0)
+    nd = C.c_int()
+    _libmod.check(_libmod.load().ucf_fit_derivative_check(n, None if dobs is None else dobs.ctypes.data,
+                                                          None if dweight is None else dweight.ctypes.data, C.byref(nd)))
+    return int(nd.value)
+
+
 class Fit:
     """observations (dimensional drawdown at time t[i], radius r[i], depth z[iz[i]], z up from the aquifer base) of one
     parameter set ``params`` whose ``free`` parameters are to be estimated.  All depths of ``z`` are evaluated at every
@@ -214,6 +230,28 @@ class Fit:
         _libmod.check(self._lib.ucf_fit_debug_h(self._h, int(plan), int(i), len(h), h, C.byref(n)))
         return h[:n.value].copy()
 
+    def debug_dh(self, plan: int, i: int) -> np.ndarray:
+        """diagnostic (ucf_fit_debug_dh): the dimensionless dh = t dh/dt behind observation i (of a field fit: behind TERM
+        i) under plan ``plan`` of the last evaluate"""
+        dh = np.zeros(64)
+        n = C.c_int()
+        _libmod.check(self._lib.ucf_fit_debug_dh(self._h, int(plan), int(i), len(dh), dh, C.byref(n)))
+        return dh[:n.value].copy()
+
+    def set_derivative(self, dobs, dweight=None):
+        """attach the observed log-time derivative t ds/dt (dimensional, one per observation) and its weights
+        (ucf_fit_set_derivative; None: unit weights).  A weight of 0 marks an observation without a derivative datum; its
+        dobs may be NaN.  From here on ``evaluate`` and ``lm`` return the joint objective of both curves."""
+        dobs = _f64(dobs)
+        dweight = np.ones(len(dobs)) if dweight is None else _f64(dweight)
+        if not (len(dobs) == len(dweight) == self.nobs):
+            raise ValueError("dobs and dweight must have one entry per observation")
+        _libmod.check(self._lib.ucf_fit_set_derivative(self._h, dobs.ctypes.data, dweight.ctypes.data))
+
+    def clear_derivative(self):
+        """detach the derivative data: ``evaluate`` and ``lm`` are those of the drawdown alone again"""
+        _libmod.check(self._lib.ucf_fit_set_derivative(self._h, None, None))
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.ucf_fit_destroy(self._h)
@@ -229,9 +267,11 @@ class Fit:
         """device allocations made so far by the fit and its plans"""
         return int(self._lib.ucf_fit_alloc_count(self._h))
 
-    def evaluate(self, theta, dlog: float, jacobian: bool = False, sim_all: bool = False) -> dict:
+    def evaluate(self, theta, dlog: float, jacobian: bool = False, sim_all: bool = False, derivative: bool = False) -> dict:
         """theta [nsets][npar] -> phi [nsets], g [nsets][npar], A [nsets][npar][npar], nbad [nsets]; on request J
-        [nsets][nobs][npar] and sim_all [nsets][1 + 2 npar][nobs] (row 0 base, 1 + 2j parameter j up, 2 + 2j down)"""
+        [nsets][nobs][npar] and sim_all [nsets][1 + 2 npar][nobs] (row 0 base, 1 + 2j parameter j up, 2 + 2j down).
+        ``derivative=True`` (ucf_fit_evaluate_joint; the fit must have derivative data) adds phi_d [nsets], the derivative
+        terms' share of phi, and Jd / simd_all, shaped as J / sim_all, under the same two flags."""
         theta = np.atleast_2d(_f64(theta))
         n, P = theta.shape
         if P != self.npar:
@@ -242,6 +282,16 @@ class Fit:
         if sim_all:
             out["sim_all"] = np.zeros((n, 1 + 2 * P, self.nobs))
         ptr = lambda k: out[k].ctypes.data if k in out else None
+        if derivative:
+            out["phi_d"] = np.zeros(n)
+            if jacobian:
+                out["Jd"] = np.zeros((n, self.nobs, P))
+            if sim_all:
+                out["simd_all"] = np.zeros((n, 1 + 2 * P, self.nobs))
+            _libmod.check(self._lib.ucf_fit_evaluate_joint(self._h, n, np.ascontiguousarray(theta), float(dlog), ptr("phi"), ptr("g"),
+                                                           ptr("A"), ptr("nbad"), ptr("J"), ptr("sim_all"), ptr("phi_d"), ptr("Jd"),
+                                                           ptr("simd_all")))
+            return out
         _libmod.check(self._lib.ucf_fit_evaluate(self._h, n, np.ascontiguousarray(theta), float(dlog), ptr("phi"), ptr("g"), ptr("A"),
                                                  ptr("nbad"), ptr("J"), ptr("sim_all")))
         return out

@@ -39,6 +39,7 @@ EXPORTS = [
     "ucf_fit_lm", "ucf_fit_alloc_count",
     "ucf_fit_create_network", "ucf_fit_eval_counts", "ucf_fit_network_eval_counts", "ucf_fit_debug_h",
     "ucf_fit_create_field", "ucf_fit_field_terms",
+    "ucf_fit_derivative_check", "ucf_fit_set_derivative", "ucf_fit_evaluate_joint", "ucf_fit_debug_dh",
     "ucf_field_create", "ucf_field_destroy", "ucf_field_group_count", "ucf_field_group", "ucf_field_group_from_params",
     "ucf_field_drawdown", "ucf_field_alloc_count", "ucf_field_images",
 ]
@@ -147,6 +148,10 @@ def load() -> C.CDLL:
                                          C.c_int, _dp, _ip, _ip, _dp, _dp, C.c_int, C.POINTER(vp)]
     lib.ucf_fit_field_terms.argtypes = [C.POINTER(UcfParams), C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _ip,
                                         C.POINTER(C.c_int), _ip, _dp, _ip, _ip, _ip, _dp]
+    lib.ucf_fit_derivative_check.argtypes = [C.c_int, vp, vp, C.POINTER(C.c_int)]
+    lib.ucf_fit_set_derivative.argtypes = [vp, vp, vp]
+    lib.ucf_fit_evaluate_joint.argtypes = [vp, C.c_int, _dp, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.ucf_fit_debug_dh.argtypes = [vp, C.c_int, C.c_int, C.c_int, _dp, C.POINTER(C.c_int)]
     lib.ucf_field_create.argtypes = [C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, _dp, C.c_int, _dp, C.POINTER(vp)]
     lib.ucf_field_destroy.argtypes = [vp]
     lib.ucf_field_destroy.restype = None
