@@ -10,7 +10,11 @@ usage: tools/folded_loop_phase_shares.py            the grids of tests/test_gpu_
        tools/folded_loop_phase_shares.py intervals [bench]
             the Gauss-Lobatto pairs by the class that eta at the two ends of their J0 interval proves for the whole interval
             (zpair_interval_class, ucf_fastpath.h; interval_class() below is its restatement): the grids of
-            tests/test_gpu_folded_loop_intervals.py, or the bench sweep"""
+            tests/test_gpu_folded_loop_intervals.py, or the bench sweep
+       tools/folded_loop_phase_shares.py units
+            the bench sweep's quadrature units (J0 intervals, the tanh-sinh part in 1 / 2 / 4 runs, 12-node runs of unproven
+            intervals) by what the bounds alone decide (zpair_unit_bounds; bound_class_v() below) and what the exact
+            classifier behind them still proves"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -161,6 +165,97 @@ def interval_line(tag, cnt, tr):
           f"unproven last interval after proven ones {100.0 * tr['after_proven'] / w:.1f} %")
 
 
+# ---- the same decision from bounds, without eta (zpair_unit_bounds, ucf_fastpath.h; the limits: zpair_bound_limit,
+# ucf_launch_plan.h).  A unit is a J0 interval, a run of tanh-sinh nodes or a run of Gauss-Lobatto nodes: [lob, hib] holds
+# every abscissa of it.
+UNDECIDED = -1
+
+
+def bound_limits(zD, kappa=None, fast_eta_max=FAST_ETA_MAX, fast_im_max=FAST_IM_MAX):
+    kappa = P.kappa if kappa is None else kappa
+    lim, me2, c = 0.99 * fast_eta_max, kappa * (maxexp * maxexp), 1.0 - zD
+    ys = 4.0 * kappa * (SMALL * SMALL)
+    with np.errstate(divide="ignore"):
+        yl = np.float64(ys) / np.float64(c * c)
+    return dict(range=kappa * (lim * lim) if lim > 0.0 else 0.0, im=kappa * (fast_im_max * fast_im_max),
+                cs=me2 / (1.0 + 2.0 ** -19), ex=me2 / (1.0 - 2.0 ** -19), ys=ys, yl=float(yl))
+
+
+def bound_class_v(p, lob, hib, zD, kappa=None, lim=None):
+    """the kernel's bound classifier for waves p[lane, ...] (the lanes' Laplace parameters; every trailing index is a wave
+    of its own) and one unit [lob, hib], restated in binary64: an int array over the trailing indices, the index into CLASSES
+    of the class decided or UNDECIDED.  (A comparison with a NaN is false, as on the device.)"""
+    Z = bound_limits(zD, kappa) if lim is None else lim
+    with np.errstate(all="ignore"):
+        u = np.abs(p.imag) * 0.5 + p.real
+        i2 = p.imag * p.imag
+        up_hi, lo_lo, up_lo = hib * hib + u, lob * lob + p.real, lob * lob + u
+        in_range = np.all((p.real > 0.0) & (up_hi < Z["range"]) & (i2 < Z["im"] * lo_lo), axis=0)
+        ys = np.all(i2 < Z["ys"] * lo_lo, axis=0)
+        yl = ys | np.all(i2 < Z["yl"] * lo_lo, axis=0)
+        not_ys = np.any(i2 >= Z["ys"] * up_lo, axis=0)
+        not_yl = np.any(i2 >= Z["yl"] * up_lo, axis=0)
+        cs = np.all(up_hi < Z["cs"], axis=0)
+        ex = ~cs & np.all(lo_lo > Z["ex"], axis=0)
+    out = np.full(in_range.shape, UNDECIDED)
+    out[in_range & cs & ys] = CLASSES.index("cs_short")
+    out[in_range & cs & ~ys & not_ys] = CLASSES.index("cs_tab")
+    out[in_range & ex & yl] = CLASSES.index("ex_short")
+    out[in_range & ex & ~yl & not_yl] = CLASSES.index("ex_tab")
+    return out
+
+
+def bound_class(p, lob, hib, zD, kappa=None):
+    """one wave p[lane]: the class name, or None where the bounds do not decide"""
+    c = int(bound_class_v(np.asarray(p), lob, hib, zD, kappa))
+    return None if c == UNDECIDED else CLASSES[c]
+
+
+def ts_runs(runs):
+    """[first node, end node) of the tanh-sinh part's runs, as integrate_kernel cuts them"""
+    cuts = [k * N // runs for k in range(runs + 1)]
+    return [(b, e) for b, e in zip(cuts, cuts[1:]) if e > b]
+
+
+def unit_shares(tD, radii, zD):
+    """share of the units that the bounds alone decide, and that bounds + exact classifier prove: J0 intervals, the tanh-sinh
+    part in 1 / 2 / 4 runs, the 12-node runs of the intervals that neither proves"""
+    lim = bound_limits(zD)
+    cnt = {k: [0, 0, 0] for k in ("intervals", "ts1", "ts2", "ts4", "gl12")}      # units, decided by the bounds, proven
+    cls_pairs = dict.fromkeys(CLASSES, 0)
+    stronger = 0
+
+    def exact_v(p, lob, hib):
+        return np.array([CLASSES.index(interval_class(p[:, m], lob, hib, zD)) for m in range(p.shape[1])])
+
+    def tally(key, p, lob, hib, w=1):      # w: the unit's nodes (runs differ in length)
+        b = bound_class_v(p, lob, hib, zD, lim=lim)
+        e = exact_v(p, lob, hib)
+        final = np.where(b != UNDECIDED, b, e)
+        cnt[key][0] += w * b.size
+        cnt[key][1] += w * int((b != UNDECIDED).sum())
+        cnt[key][2] += w * int((final != CLASSES.index("unproven")).sum())
+        return b, e, final
+
+    for s, p in waves(tD):
+        for rD in radii:
+            a = row(rD, s)
+            for jj in range(nacc):
+                b, e, final = tally("intervals", p, j0z[s + jj - 1] / rD, j0z[s + jj] / rD)
+                stronger += int(((b != UNDECIDED) & (b != e)).sum())
+                for c in final:
+                    cls_pairs[CLASSES[c]] += ngl
+                g = a[N + jj * ngl:N + (jj + 1) * ngl]
+                open_ = final == CLASSES.index("unproven")
+                if open_.any():
+                    for r0 in range(0, ngl, 12):                     # (the nodes descend: first node = upper end)
+                        tally("gl12", p[:, open_], g[min(r0 + 11, ngl - 1)], g[r0], min(12, ngl - r0))
+            for runs in (1, 2, 4):
+                for b0, e0 in ts_runs(runs):
+                    tally(f"ts{runs}", p, 0.0 if b0 == 0 else a[b0], a[e0 - 1], e0 - b0)
+    return cnt, cls_pairs, stronger
+
+
 def bench_grid():
     return O.logspace(-1, 8, 1024) / D.Tc, np.logspace(-1, 1, 256)[::8], 145.7 / D.Lc      # (bench.py's radii span rD = 0.1 ... 10)
 
@@ -176,6 +271,14 @@ if __name__ == "__main__":
             tD = np.concatenate([np.logspace(c, c + 0.5, 64) for c in TI.TD_CLUSTERS])
             for zD in sorted({c[2] for c in TI.CALLS}, reverse=True):
                 interval_line(f"zD = {zD}", *interval_shares(tD, np.array(TI.RD), zD))
+    elif args[:1] == ["units"]:
+        tD, rD, zD = bench_grid()
+        cnt, cls_pairs, stronger = unit_shares(tD, rD, zD)
+        for k, (n, d, pr) in cnt.items():
+            print(f"{k:10s} nodes-weighted units {n:9d}  decided by the bounds alone {100.0 * d / n:5.1f} %  proven with the exact classifier behind them {100.0 * pr / n:5.1f} %")
+        n = sum(cls_pairs.values())
+        print("Gauss-Lobatto pairs by class, bounds first:", {k: round(100.0 * v / n, 1) for k, v in cls_pairs.items()},
+              "; intervals where the bounds decide another class than the exact classifier:", stronger)
     elif args[:1] == ["bench"]:
         tD, rD, zD = bench_grid()
         line("bench C2", *shares(tD, rD, zD))

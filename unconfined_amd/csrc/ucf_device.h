@@ -1417,7 +1417,7 @@ UCF_DEV cplx extrap_lane(lds_c* colC, int strideC, lds_c* colD, const double* x,
 #if !UCF_FAST
 __global__ void __launch_bounds__(256)
 abscissa_kernel(const ucf_dev_params P, int nrows, int per_point, int nsv, int svmin,
-                const double* __restrict__ rDv, const int* __restrict__ svv, double2* __restrict__ tab)
+                const double* __restrict__ rDv, const int* __restrict__ svv, double2* __restrict__ tab, double* __restrict__ ends)
 {
     // P.tab_premul (fast flavour): the Gauss-Lobatto entries carry their quadrature weight, a J0(a rD) w_m, so that the
     // abscissa loop accumulates a sample with one FMA per component (the faithful flavour keeps the reference's
@@ -1430,6 +1430,13 @@ abscissa_kernel(const ucf_dev_params P, int nrows, int per_point, int nsv, int s
     int sv;
     if (per_point) { rD = rDv[row]; sv = svv[row]; }
     else { rD = rDv[row / nsv]; sv = svmin + row % nsv; }
+    // `ends` (grids in the lane = time layout, else NULL): the ends of the row's J0 intervals, [row][nacc + 1], by the same
+    // correctly rounded quotient that every kernel forms for itself -- the folded one-depth water-table kernel reads them
+    // with one scalar load per interval (nabs > nacc: the row has a thread for each) -- and behind the last row's the limits
+    // of its bound classifier (zpair_bound_limit, ucf_launch_plan.h), by the first thread
+    if (ends && n <= P.nacc) ends[(size_t)row * (P.nacc + 1) + n] = P.j0z[sv - 1 + n] / rD;
+    if (ends && gid == 0)
+        for (int i = 0; i < UCF_ZB_COUNT; i++) ends[(size_t)nrows * (P.nacc + 1) + i] = zpair_bound_limit(P, i);
     double a, w = 1.0;
     if (n < P.N) {
         const double arg = P.j0z[sv - 1] / rD;                                                  // driver.f90:120
@@ -1914,9 +1921,88 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
             // nothing else.
             int stopped = 0;
             zph = 0;
+            // UCF_ZPAIR_UNITS (ucf_fastpath.h).  ENDS: the ends of the J0 intervals, j0z[sv - 1 + j] / rD for j = 0 .. nacc, are
+            // read from the table abscissa_kernel wrote behind the rows (the same correctly rounded quotients: same bits) -- a
+            // scalar load per interval for the upper end, the lower one is the upper end of the interval before
+            constexpr bool ENDS = LAYOUT == 1 && !MULTI && UCF_ZPAIR_INTERVALS && (UCF_ZPAIR_UNITS & UCF_ZU_TABLE);
+            constexpr bool TS_RUNS = !MULTI && UCF_ZPAIR_INTERVALS && (UCF_ZPAIR_UNITS & UCF_ZU_TS_RUNS);
+            // SETTLE: a part that is in range up to its last abscissa (UCF_PH_RANGE) and has one unit proven exponential and
+            // short has all its later units proven with it -- Re eta only grows, |Im eta| only falls: no test at all for those
+            constexpr bool SETTLE = !MULTI && UCF_ZPAIR_INTERVALS && (UCF_ZPAIR_UNITS & UCF_ZU_BOUNDS);
+            static_assert(LAYOUT == 1 || MULTI || !UCF_ZPAIR_INTERVALS || !(UCF_ZPAIR_UNITS & (UCF_ZU_TABLE | UCF_ZU_BOUNDS)),
+                          "the interval ends and the limits of the bounds stand behind the rows of a grid's abscissa table only");
+            const double* __restrict__ ends = nullptr;
+            if constexpr (ENDS) ends = (const double*)tab + abscissa_ends_offset((size_t)nr * nsv, nabs) + (size_t)(W.ir * nsv + (sv - svmin)) * (nacc + 1);
+            const double* __restrict__ zb = nullptr;              // the limits of zpair_unit_bounds
+            if constexpr (SETTLE) zb = (const double*)tab + abscissa_limits_offset((size_t)nr * nsv, nabs, nacc);
+            int settled = 0;
+            if constexpr (ENDS) {
+                if (nlim > n0) zph = zpair_part_phase(P, LC, ends[nlim > N ? (nlim - N + ngl - 1) / ngl : 0]);
+            } else
             if (!MULTI && nlim > n0)      // (a parameter batch: no bit is ever set)
                 zph = zpair_part_phase(P, LC, P.j0z[sv - 1 + (nlim > N ? (nlim - N + ngl - 1) / ngl : 0)] / rD);
             const int nts = nlim < N ? nlim : N;
+            if constexpr (TS_RUNS) {
+                // The tanh-sinh part in UCF_ZPAIR_TS_RUNS runs of nodes (they ascend: a run lies between its own first and last
+                // node, the first run above 0), each classified like a J0 interval.  A proven run takes the one arm of its class
+                // and the level-sum update -- no `zph` test, no ballot, no `stopped` -- any other the loop with the bits.
+                auto proven_run = [&](auto cls, auto beta, int nend) {
+                    for (; n < nend; n++) {
+                        const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
+                        F.sc.salt = n;
+                        (void)fast_eta<2, true>(P, LC, aa.x, F);
+                        const cplx val = rscale(aa.y, fast_sample_zpair_proven<decltype(cls)::value, decltype(beta)::value>(P, LC, F));
+                        const int n1 = n + 1;
+                        int tz = __builtin_ctz(n1);
+                        if (tz > R - 1) tz = R - 1;
+                        for (int sh = 0; sh <= tz; sh++) {                                       // (driver.f90:129-157)
+                            const int j = R - sh;
+                            const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
+                            lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
+                        }
+                        aa = nxt;
+                    }
+                };
+                auto proven_run_class = [&](auto cls, int nend) {
+                    if (P.beta != 0.0) proven_run(cls, std::true_type(), nend);
+                    else proven_run(cls, std::false_type(), nend);
+                };
+                for (int k = 1; k <= UCF_ZPAIR_TS_RUNS && n < nts; k++) {
+                    int nend = k * N / UCF_ZPAIR_TS_RUNS;
+                    if (nend > nts) nend = nts;
+                    if (nend <= n) continue;
+                    int cls = UCF_IV_EX_SHORT;
+                    if (!settled) {
+                        int known;
+                        cls = zpair_interval_class(P, LC, n == 0 ? 0.0 : aa.x, row[nend - 1].x, P.zD[0], &known, zb);
+                        zph |= known;
+                        if (SETTLE && cls == UCF_IV_EX_SHORT && (zph & UCF_PH_RANGE)) settled = 1;
+                    }
+                    if (cls == UCF_IV_CS_TAB) proven_run_class(std::integral_constant<int, UCF_IV_CS_TAB>(), nend);
+                    else if (cls == UCF_IV_CS_SHORT) proven_run_class(std::integral_constant<int, UCF_IV_CS_SHORT>(), nend);
+                    else if (cls == UCF_IV_EX_TAB) proven_run_class(std::integral_constant<int, UCF_IV_EX_TAB>(), nend);
+                    else if (cls == UCF_IV_EX_SHORT) proven_run_class(std::integral_constant<int, UCF_IV_EX_SHORT>(), nend);
+                    else {
+                        for (; n < nend; n++) {
+                            const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
+                            F.sc.salt = n;
+                            if (!fast_eta_wave_zpair<!MULTI>(P, LC, aa.x, F, zph, 1)) { stopped = 1; break; }
+                            const cplx val = rscale(aa.y, fast_sample_zpair<!MULTI>(P, LC, F, zph, 1));
+                            const int n1 = n + 1;
+                            int tz = __builtin_ctz(n1);
+                            if (tz > R - 1) tz = R - 1;
+                            for (int sh = 0; sh <= tz; sh++) {                                   // (driver.f90:129-157)
+                                const int j = R - sh;
+                                const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
+                                lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
+                            }
+                            aa = nxt;
+                        }
+                        if (stopped) break;
+                    }
+                    UCF_UNIFORM_BLOCK();
+                }
+            } else
             for (; n < nts; n++) {
                 const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
                 F.sc.salt = n;
@@ -1938,7 +2024,8 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
             // node: a proven interval runs exactly ngl iterations of the one arm of its class -- no test, no ballot, no `zph`:
             // it cannot leave the fast evaluators, so no hand-over starts inside it -- any other interval the loop with the
             // bits, as it was.  The bits a proven interval establishes for the rest of the part are set, none is cleared.  A
-            // parameter batch keeps the loop with the tests.  (The tanh-sinh part, 63 abscissae of 543, keeps its loop too.)
+            // parameter batch keeps the loop with the tests.  The interval's ends come from the table (ENDS), the classifier
+            // tries its bounds before it evaluates eta, and a settled part (SETTLE) classifies nothing any more.
             auto proven_interval = [&](auto cls, auto beta) {
                 for (int i = 0; i < ngl; i++, n++) {
                     const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
@@ -1953,14 +2040,26 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                 if (P.beta != 0.0) proven_interval(cls, std::true_type());
                 else proven_interval(cls, std::false_type());
             };
+            double lob_next = 0.0;                                // ENDS: the lower end of the next interval
+            if constexpr (ENDS) { if (!stopped && n < nlim) lob_next = ends[jj]; }
             if (!stopped) while (n < nlim) {
-                const double lob = P.j0z[sv + jj - 1] / rD;
-                const double hib = P.j0z[sv + jj] / rD;
+                double lob, hib;
+                if constexpr (ENDS) {
+                    lob = lob_next;
+                    hib = lob_next = ends[jj + 1];
+                } else {
+                    lob = P.j0z[sv + jj - 1] / rD;
+                    hib = P.j0z[sv + jj] / rD;
+                }
                 int cls = UCF_IV_UNPROVEN;
                 if constexpr (!MULTI) {
-                    int known;
-                    cls = zpair_interval_class(P, LC, lob, hib, P.zD[0], &known);
-                    zph |= known;
+                    if (SETTLE && settled) cls = UCF_IV_EX_SHORT;
+                    else {
+                        int known;
+                        cls = zpair_interval_class(P, LC, lob, hib, P.zD[0], &known, zb);
+                        zph |= known;
+                        if (SETTLE && cls == UCF_IV_EX_SHORT && (zph & UCF_PH_RANGE)) settled = 1;
+                    }
                 }
                 if (cls == UCF_IV_CS_TAB) proven_class(std::integral_constant<int, UCF_IV_CS_TAB>());
                 else if (cls == UCF_IV_CS_SHORT) proven_class(std::integral_constant<int, UCF_IV_CS_SHORT>());

@@ -96,7 +96,8 @@ int grid_device_chunk(ucf_plan* pl, ucf_workspace* ws, int nt, const double* d_t
     const int svmin = j0s[0] < j0s[1] ? j0s[0] : j0s[1];
     const int nsv = (j0s[0] > j0s[1] ? j0s[0] - j0s[1] : j0s[1] - j0s[0]) + 1;     // driver_io.f90:660-664: sv in [min,max]
     const size_t nabs = (size_t)pl->D.nabs;
-    rc = ws_ensure(pl, ws, ws->work, (size_t)nr * nsv * nabs * 2 * sizeof(double), "abscissa table");
+    // (the rows, and behind them the ends of every row's J0 intervals: abscissa_ends_offset, ucf_launch_plan.h)
+    rc = ws_ensure(pl, ws, ws->work, abscissa_table_doubles((size_t)nr * nsv, nabs, (size_t)pl->P.nacc) * sizeof(double), "abscissa table");
     if (rc) return rc;
     const int ntiles = (nt + UCF_WAVE - 1) / UCF_WAVE;
     const bool lane_time = grid_lane_time(pl, nt);
@@ -122,7 +123,8 @@ int grid_device_chunk(ucf_plan* pl, ucf_workspace* ws, int nt, const double* d_t
     }
     if (!ws->dry) {
         ucf_tm_mark(tm, "ucf_faithful::abscissa_kernel", stream);
-        rc = ucf_faithful::launch_abscissae(dp, nr * nsv, 0, nsv, svmin, d_rD, d_sv, (double*)ws->work.p, stream);
+        rc = ucf_faithful::launch_abscissae(dp, nr * nsv, 0, nsv, svmin, d_rD, d_sv, (double*)ws->work.p, stream,
+                                            (double*)ws->work.p + abscissa_ends_offset((size_t)nr * nsv, nabs));
         if (rc) return fail(rc, "abscissa kernel launch failed");
     }
     ucf_launch L;

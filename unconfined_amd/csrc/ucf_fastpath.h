@@ -766,10 +766,68 @@ enum {
     UCF_IV_EX_TAB = 3,       // exponential form in every lane at every node, sin/cos from the table
     UCF_IV_EX_SHORT = 4      // ... from sincos_small_
 };
+// UCF_ZPAIR_UNITS (bit mask; A/B builds measure each part on its own; 0 = none of it):
+//   1  the ends of the J0 intervals come from the table abscissa_kernel writes behind the rows (lane = time layout: the
+//      radius is wave-uniform), one scalar load per interval, instead of two IEEE divisions
+//   2  a unit is first tried with the bounds below (zpair_unit_bounds), and only an undecided one pays for the two
+//      fast_eta evaluations of the exact classifier
+//   4  the tanh-sinh part is classified in UCF_ZPAIR_TS_RUNS runs of nodes, and a proven run takes a loop without tests
+#ifndef UCF_ZPAIR_UNITS
+#define UCF_ZPAIR_UNITS 7
+#endif
+#ifndef UCF_ZPAIR_TS_RUNS
+#define UCF_ZPAIR_TS_RUNS 2
+#endif
+enum { UCF_ZU_TABLE = 1, UCF_ZU_BOUNDS = 2, UCF_ZU_TS_RUNS = 4 };
+static_assert(UCF_ZB_SC_SMALL == UCF_SC_SMALL, "the plan's short sin/cos limit (ucf_launch_plan.h) is sincos_small_'s");
+// The same decision from bounds, without eta.  For a lane with Re p > 0: q = p + a^2 has Re q = Re p + a^2 > 0 and
+// Im q = Im p, (Re eta)^2 = (|q| + Re q) / (2 kappa) and Re q <= |q| <= Re q + |Im q|, so
+//     (Re p + a^2) / kappa  <=  (Re eta)^2  <=  (Re p + a^2 + |Im p| / 2) / kappa
+//     (Im p)^2 / (4 kappa (Re p + a^2 + |Im p| / 2))  <=  (Im eta)^2 = (Im p)^2 / (4 kappa^2 (Re eta)^2)  <=  (Im p)^2 / (4 kappa (Re p + a^2))
+// all monotone in a: the two ends of a unit [lob, hib] bound every abscissa in it.  Every test of the exact classifier has a
+// squared, division-free form on them, against limits that come pre-multiplied (zb[UCF_ZB_*], ucf_launch_plan.h: the margins
+// of the exact classifier squared -- 0.99^2 on fast_eta_max^2, 1/4 on fast_im_max^2, 1 -+ 2^-19 on maxexp^2 -- are in the
+// limits; the bounds carry three roundings of positive terms).  Two FMAs, a product or two and the compares, in the place
+// of two fast_eta with their four quarter-rate seeds.  Every compare fails on a NaN.
+// Returns a class (UCF_IV_*, with *ph_proven as zpair_interval_class) or -1: the bounds do not decide.  Decided means
+// what the exact classifier decides: the form proven, and the short sin/cos form either proven by the upper bound of
+// (Im eta)^2 or refuted in some lane by the lower one (a refuted unit takes the table, which is always valid).
+UCF_DEV int zpair_unit_bounds(const double* __restrict__ zb, const lane_consts& L, double lob, double hib, int* ph_proven)
+{
+    *ph_proven = 0;
+    const double u = __builtin_fma(fabs(L.p.im), 0.5, L.p.re), i2 = L.p.im * L.p.im;
+    const double up_hi = __builtin_fma(hib, hib, u);             // kappa (Re eta)^2 <= up_hi in [lob, hib]
+    const double lo_lo = __builtin_fma(lob, lob, L.p.re);        // kappa (Re eta)^2 >= lo_lo
+    const bool in_range = (L.p.re > 0.0) & (up_hi < zb[UCF_ZB_RANGE]) & (i2 < zb[UCF_ZB_IM] * lo_lo);
+    if (__builtin_amdgcn_ballot_w64(!in_range) != 0) return -1;
+    const bool ys = __builtin_amdgcn_ballot_w64(!(i2 < zb[UCF_ZB_YS] * lo_lo)) == 0;
+    if (__builtin_amdgcn_ballot_w64(!(up_hi < zb[UCF_ZB_CS])) == 0) {
+        if (ys) { *ph_proven = UCF_PH_IM | UCF_PH_YS | UCF_PH_YL; return UCF_IV_CS_SHORT; }
+        if (__builtin_amdgcn_ballot_w64(i2 >= zb[UCF_ZB_YS] * __builtin_fma(lob, lob, u)) == 0) return -1;
+        *ph_proven = UCF_PH_IM;
+        return UCF_IV_CS_TAB;
+    }
+    if (__builtin_amdgcn_ballot_w64(!(lo_lo > zb[UCF_ZB_EX])) == 0) {
+        if (ys || __builtin_amdgcn_ballot_w64(!(i2 < zb[UCF_ZB_YL] * lo_lo)) == 0) {
+            *ph_proven = UCF_PH_IM | UCF_PH_LARGE | UCF_PH_YL | (ys ? UCF_PH_YS : 0);
+            return UCF_IV_EX_SHORT;
+        }
+        if (__builtin_amdgcn_ballot_w64(i2 >= zb[UCF_ZB_YL] * __builtin_fma(lob, lob, u)) == 0) return -1;
+        *ph_proven = UCF_PH_IM | UCF_PH_LARGE;
+        return UCF_IV_EX_TAB;
+    }
+    return -1;
+}
 // lob < hib: the interval's ends.  *ph_proven: the UCF_PH_* bits that hold from lob on (every later abscissa of the part
 // lies above it), whatever the class
-UCF_DEV int zpair_interval_class(const ucf_dev_params& P, const lane_consts& L, double lob, double hib, double zD, int* ph_proven)
+UCF_DEV int zpair_interval_class(const ucf_dev_params& P, const lane_consts& L, double lob, double hib, double zD, int* ph_proven,
+                                 const double* __restrict__ zb = nullptr)
 {
+    if (UCF_ZPAIR_UNITS & UCF_ZU_BOUNDS) {
+        const int c = zpair_unit_bounds(zb, L, lob, hib, ph_proven);
+        if (c >= 0) return c;
+        UCF_UNIFORM_BLOCK();
+    }
     *ph_proven = 0;
     fast_common T;                                   // (eta only: nothing else of it is read)
     (void)fast_eta<2, true>(P, L, hib, T);

@@ -53,6 +53,40 @@ struct ucf_dev_params {
                            // (sincos_tab_, exp_tab_)
     double half_inv_kappa; // 0.5 / kappa = 0.5 * inv_kappa exactly (fast_eta<FAMILY, PAIR>); last, so that no other field moves
 };
+// The limits of the folded one-depth water-table kernel's bound classifier (zpair_unit_bounds, ucf_fastpath.h): the plan's
+// limits squared, each pre-multiplied by kappa with its margin -- kappa (Re eta)^2 and (Im p)^2 / (kappa (Re eta)^2) are what
+// the bounds compare.  The kernel reads them from the abscissa table (below), not from the parameter block: the block keeps
+// its size, and with it every other kernel its code.
+//   UCF_ZB_RANGE  kappa (0.99 fast_eta_max)^2     upper bound of kappa (Re eta)^2 below it: in range (0: fast evaluators off)
+//   UCF_ZB_IM     kappa fast_im_max^2             (Im p)^2 < it times (Re p + a^2): |Im eta| < fast_im_max / 2
+//   UCF_ZB_CS     kappa maxexp^2 / (1 + 2^-19)    upper bound below it: cosh/sinh form
+//   UCF_ZB_EX     kappa maxexp^2 / (1 - 2^-19)    lower bound above it: exponential form
+//   UCF_ZB_YS     4 kappa UCF_SC_SMALL^2          (Im p)^2 < it times (Re p + a^2): |Im eta| < UCF_SC_SMALL
+//   UCF_ZB_YL     that / (1 - zD[0])^2            ... |Im eta| (1 - zD) < UCF_SC_SMALL (infinite at zD = 1: always)
+#define UCF_ZB_SC_SMALL 0.012   /* UCF_SC_SMALL (ucf_math.h) */
+enum { UCF_ZB_RANGE = 0, UCF_ZB_IM, UCF_ZB_CS, UCF_ZB_EX, UCF_ZB_YS, UCF_ZB_YL, UCF_ZB_COUNT = 8 };
+// limit `which` of a call's parameter block (constexpr: host and device; every operation rounded on its own where
+// abscissa_kernel is compiled)
+static constexpr double zpair_bound_limit(const ucf_dev_params& dp, int which)
+{
+    const double lim = 0.99 * dp.fast_eta_max, me2 = dp.kappa * (dp.maxexp * dp.maxexp), c = 1.0 - dp.zD[0];
+    const double ys = 4.0 * dp.kappa * (UCF_ZB_SC_SMALL * UCF_ZB_SC_SMALL);
+    switch (which) {
+    case UCF_ZB_RANGE: return lim > 0.0 ? dp.kappa * (lim * lim) : 0.0;
+    case UCF_ZB_IM: return dp.kappa * (dp.fast_im_max * dp.fast_im_max);
+    case UCF_ZB_CS: return me2 / (1.0 + 0x1p-19);
+    case UCF_ZB_EX: return me2 / (1.0 - 0x1p-19);
+    case UCF_ZB_YS: return ys;
+    case UCF_ZB_YL: return ys / (c * c);
+    default: return 0.0;
+    }
+}
+// The abscissa table of a grid launch with `nrows` rows of `nabs` (abscissa, weight) pairs, in doubles: the rows, behind them
+// the interval ends j0z[sv - 1 + j] / rD, j = 0 .. nacc, of every row, and behind those the UCF_ZB_COUNT limits (abscissa_kernel
+// writes all three; point lists have the rows alone)
+static constexpr size_t abscissa_ends_offset(size_t nrows, size_t nabs) { return nrows * nabs * 2; }
+static constexpr size_t abscissa_limits_offset(size_t nrows, size_t nabs, size_t nacc) { return nrows * (nabs * 2 + nacc + 1); }
+static constexpr size_t abscissa_table_doubles(size_t nrows, size_t nabs, size_t nacc) { return abscissa_limits_offset(nrows, nabs, nacc) + UCF_ZB_COUNT; }
 #define UCF_SC_ENTRIES (256 + 128)   /* 16-byte units of that table */
 #define UCF_IWPB 4             /* waves per workgroup of integrate_kernel: they share the sin/cos table in LDS */
 

@@ -27,13 +27,13 @@ int launch_expand_grid(int nt, int nr, const double* d_tD, const int* d_sv, cons
 }
 
 int launch_abscissae(const ucf_dev_params& dp, int nrows, int per_point, int nsv, int svmin, const double* d_rD,
-                     const int* d_sv, double* d_tab, void* stream)
+                     const int* d_sv, double* d_tab, void* stream, double* d_ends)
 {
     const long long total = (long long)nrows * (dp.N + dp.nacc * dp.ngl);
     const int threads = 256;
     const long long blocks = (total + threads - 1) / threads;
     hipLaunchKernelGGL(abscissa_kernel, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, dp, nrows, per_point,
-                       nsv, svmin, d_rD, d_sv, (double2*)d_tab);
+                       nsv, svmin, d_rD, d_sv, (double2*)d_tab, d_ends);
     return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
 }
 #endif

@@ -132,9 +132,10 @@ struct ucf_launch {
 
 // launchers implemented in ucf_launchers.h and, the stage hooks, ucf_device.h; compiled by ucf_kernels_*.hip (one set per build flavour)
 namespace ucf_faithful {
-// abscissa tables (shared by both flavours): tab[row][nabs] of (a, a*J0(a*rD))
+// abscissa tables (shared by both flavours): tab[row][nabs] of (a, a*J0(a*rD)); d_ends (optional): [row][nacc + 1] ends of the
+// row's J0 intervals (abscissa_ends_offset, ucf_launch_plan.h)
 int launch_abscissae(const ucf_dev_params& dp, int nrows, int per_point, int nsv, int svmin, const double* d_rD,
-                     const int* d_sv, double* d_tab, void* stream);
+                     const int* d_sv, double* d_tab, void* stream, double* d_ends = nullptr);
 int launch_expand_grid(int nt, int nr, const double* d_tD, const int* d_sv, const double* d_rD, double* d_tDp, double* d_rDp,
                        int* d_svp, void* stream);
 int launch_bessel(int n, const double* d_z, double* d_k, int* d_ierr, void* stream);
