@@ -532,8 +532,58 @@ int ucf_field_group_from_params(const ucf_field* field, const ucf_params* P, int
  * nothing.  stats: summed over the groups. */
 int ucf_field_drawdown(ucf_field* field, ucf_plan* plan, int nz, const double* z, int dimensionless,
                        double* s, double* ds /*[nt][nloc][nz]*/, ucf_stats* stats /*NULL ok*/);
-/* device allocations made so far by the field (the plan's own workspaces count in ucf_plan_alloc_count) */
+/* device allocations made so far by the field (the plan's own workspaces count in ucf_plan_alloc_count; the scratch plan of
+ * ucf_field_forecast counts once when it is made) */
 long long ucf_field_alloc_count(const ucf_field* field);
+
+/* ---- forecasts: what a fitted well field will do, how sure that is and which parameter it is sensitive to.  theta and cov are
+ * those of ucf_fit_lm, passed as they are (cov in ln theta).  One call maps the field under the base parameter set and its
+ * 2 npar log-perturbed neighbours, keeps all 1 + 2 npar superposed maps in device memory and forms there the central-difference
+ * sensitivities d s / d ln theta_j and the first-order standard error sqrt(j' C j), for the drawdown and for its log-time
+ * derivative; only the maps that are asked for cross the bus.
+ *   sets         ucf_field_forecast_sets(&plan->P, ...): set 0 the base, set 1 + 2j / 2 + 2j parameter j up / down.
+ *   plan         supplies the base parameters, the device, the numerical settings and the flavour; it is never modified.  The
+ *                field owns ONE scratch plan on the plan's device (ucf_plan_create_on from set 0, the plan's mode, timing off),
+ *                refreshed with ucf_plan_update for every set, kept for later calls, rebuilt only when ucf_plan_update refuses
+ *                set 0 because the model or the numerical settings changed, destroyed with the field.
+ *   per set      for k = 0 .. 2 npar in this order exactly what ucf_field_drawdown(field, plan of set k, nz, z, 0, ...) runs: the
+ *                launch arrays that ucf_field_group_from_params(field, &sets[k], g, ...) states, one grid call per group, then
+ *                field_superpose_kernel with that set's Hc into slot k of two device buffers [1 + 2 npar][nout],
+ *                nout = nt nloc nz.  Slot k has the bits of ucf_field_drawdown on a fresh field and a fresh plan of sets[k].
+ *                Outputs are always dimensional (Hc depends on Kr: a dimensionless sensitivity would be another quantity).
+ *   combination  field_forecast_kernel, one thread per output e = (k, i, z), once on the s slots (a = s_all) and once on the ds
+ *                slots (a = ds_all), every operation rounded on its own:
+ *                    J_j = (a[1+2j][e] - a[2+2j][e]) / two_dlog,   two_dlog = 2.0 * dlog formed once on the host;
+ *                    sens[j][e] = J_j;
+ *                    var = +0.0;  for j = 0..npar-1:  inner = +0.0;  for k = 0..npar-1: inner = inner + cov[j][k] * J_k;
+ *                                                     var = var + J_j * inner;
+ *                    se[e] = (var < 0) ? +0.0 : sqrt(var)   (a NaN var stays NaN).
+ *                nbad[0] (s) and nbad[1] (ds) count the outputs e for which any of the 1 + 2 npar slot values is not finite (a
+ *                ballot per wave, one integer atomic per wave, no floating-point atomics: a call repeated gives the same bits).
+ *                Nothing is scrubbed: non-finite values and the Wynn sentinel propagate as ucf_field_drawdown states.
+ *   outputs      s, ds are slot 0, copied, not recomputed.  stats: summed over all sets and groups.
+ * The slot buffers, the staging of sens / se and cov are buffers of the field, grown on demand and kept: a repeated call of the
+ * same size allocates nothing.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything ucf_field_drawdown
+ * checks; NULL ids, theta, s or ds; npar outside 1..UCF_FIT_MAX_PAR; dlog not positive and finite; se or dse without cov; a cov
+ * entry that is not finite, cov[j][k] != cov[k][j], a negative cov[j][j]; (1 + 2 npar) nout beyond what one buffer may hold.
+ * With a NULL plan UCF_ERR_NO_DEVICE comes before "NULL plan", as in ucf_field_drawdown; with a plan the checks of
+ * ucf_field_forecast_sets on plan->P run before any launch.  A set that ucf_plan_update refuses: that status, with the set and
+ * the parameter moved in ucf_last_error. */
+/* host only, no GPU: the 1 + 2 npar parameter sets a forecast evaluates.  sets[0] = ucf_fit_perturb(base, ids, theta);
+ * sets[1 + 2j] / sets[2 + 2j] = the same with theta[j] * exp(+dlog) / theta[j] * exp(-dlog) (one product each; exactly the
+ * sets ucf_fit_evaluate makes for one theta).  Checks: those of ucf_fit_perturb; theta positive and finite; dlog positive
+ * and finite; every set valid as by ucf_nondimensionalise (its status, set and parameter named in ucf_last_error). */
+int ucf_field_forecast_sets(const ucf_params* base, int npar, const int* ids, const double* theta, double dlog,
+                            ucf_params* sets /*[1 + 2 npar]*/);
+int ucf_field_forecast(ucf_field* field, ucf_plan* plan, int npar, const int* ids, const double* theta /*[npar]*/, double dlog,
+                       const double* cov /*[npar][npar], in ln theta as ucf_fit_lm returns it; NULL: no standard error*/,
+                       int nz, const double* z,
+                       double* s, double* ds            /*[nt][nloc][nz], the base set; required*/,
+                       double* sens, double* dsens      /*[npar][nt][nloc][nz]; NULL ok*/,
+                       double* se, double* dse          /*[nt][nloc][nz]; NULL ok; not NULL needs cov*/,
+                       double* s_all, double* ds_all    /*[1 + 2 npar][nt][nloc][nz]; NULL ok*/,
+                       long long* nbad /*[2]: s, ds; NULL ok*/, ucf_stats* stats /*NULL ok*/);
 /* Host only: the nwell real wells followed by their mirror images in the straight line a x + b y = c (xo, yo, qo, t0o
  * [2 nwell]).  An image has q = +q for a no-flow boundary (kind 0), -q for a constant-head boundary (kind 1), and the t0 of its
  * real well.  One boundary only (two parallel boundaries need an infinite image series).  UCF_ERR_BAD_ARGUMENT: a = b = 0, a

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "ucf_host.h"
@@ -30,11 +31,15 @@ struct ucf_field {
     std::vector<int> well_group;
     int device = -1;                       // where the buffers live: the device of the plan of the first ucf_field_drawdown
     ucf_buffer b_tD, b_sv, b_rD, b_tfac, b_col, b_wells, b_h, b_dh, b_s, b_ds, b_stats;      // grown on demand, kept
+    // ucf_field_forecast: the slots [1 + 2 npar][nout] of s and ds, the staging of sens / dsens / se / dse, cov, the two counts
+    ucf_buffer b_sall, b_dsall, b_sens, b_dsens, b_se, b_dse, b_cov, b_nbad;
+    ucf_plan* scratch = nullptr;           // the plan that ucf_field_forecast refreshes for every parameter set
     long long n_alloc = 0;
     // every device buffer above: the one list (ucf_field_destroy frees through it)
-    std::array<ucf_buffer*, 11> buffers()
+    std::array<ucf_buffer*, 19> buffers()
     {
-        return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats}};
+        return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats, &b_sall, &b_dsall, &b_sens, &b_dsens,
+                 &b_se, &b_dse, &b_cov, &b_nbad}};
     }
 };
 
@@ -109,6 +114,101 @@ int field_group_out(const ucf_field* f, const ucf_params& P, const ucf_derived& 
 
 // every group's block of a shared buffer starts at a multiple of 32 entries (256 bytes of doubles)
 size_t field_pad(size_t n) { return (n + 31) & ~(size_t)31; }
+
+// what ucf_field_drawdown checks before it looks at the plan (null_what: the message for a NULL array, NULL if there is none);
+// nout = nt nloc nz
+int field_check_call(const ucf_field* f, int nz, const char* null_what, const double* z, long long& nout)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL field");
+    if (nz < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nz=%d: at least one depth", nz);
+    if (null_what) return fail(UCF_ERR_BAD_ARGUMENT, "%s", null_what);
+    int rc = field_check_finite("z", nz, z);
+    if (rc) return rc;
+    nout = (long long)f->nt * f->nloc * nz;
+    if (nout > 0x7fffffffLL * 256) return fail(UCF_ERR_BAD_ARGUMENT, "%d times x %d locations x %d depths: too many outputs for one call", f->nt, f->nloc, nz);
+    return UCF_OK;
+}
+
+// One map of the field under plan pl, whose launch arrays are L (field_group_core under pl's parameters): the arrays go to the
+// device, every group takes one call of the grid path, and field_superpose_kernel leaves s, ds [nt][nloc][nz] at d_s, d_ds --
+// device memory of the caller on pl's device, which is current.  The counters of the groups are ADDED to *stats (NULL ok).
+// The plan's stream has drained when the call returns.
+int field_map_core(ucf_field* f, ucf_plan* pl, const std::vector<field_launch>& L, int nz, const double* z, int dimensionless, double* d_s,
+                   double* d_ds, ucf_stats* stats)
+{
+    const int ng = (int)f->groups.size();
+    // zD, zLay as in ucf_drawdown_multi
+    std::vector<double> zD(nz);
+    std::vector<int> zl(nz);
+    for (int j = 0; j < nz; j++) zD[j] = z[j] / pl->D.Lc;
+    int rc = ucf_zlay(pl, nz, zD.data(), zl.data());
+    if (rc) return rc;
+    // one staging image per array, the groups one after the other
+    std::vector<size_t> toff(ng), roff(ng), hoff(ng);
+    size_t nT = 0, nR = 0, nH = 0;
+    for (int g = 0; g < ng; g++) {
+        toff[g] = nT; roff[g] = nR; hoff[g] = nH;
+        nT += field_pad(L[g].nt); nR += field_pad(L[g].nr); nH += field_pad((size_t)L[g].nt * L[g].nr * nz);
+    }
+    if (nT > 0x7fffffffULL) return fail(UCF_ERR_BAD_ARGUMENT, "too many launched times");
+    std::vector<double> tD(nT, 1.0), rD(nR, 1.0), tfac(nT, 0.0);
+    std::vector<int> sv(nT, 0), col((size_t)f->nloc * f->nwell);
+    std::vector<ucf_field_well> wells(f->nwell);
+    for (int g = 0; g < ng; g++) {
+        std::copy(L[g].tD.begin(), L[g].tD.end(), tD.begin() + toff[g]);
+        std::copy(L[g].sv.begin(), L[g].sv.end(), sv.begin() + toff[g]);
+        std::copy(L[g].tfac.begin(), L[g].tfac.end(), tfac.begin() + toff[g]);
+        std::copy(L[g].rD.begin(), L[g].rD.end(), rD.begin() + roff[g]);
+    }
+    for (int j = 0; j < f->nwell; j++) {
+        const int g = f->well_group[j];
+        wells[j] = ucf_field_well{f->qw[j], (long long)hoff[g], L[g].k0, L[g].nr, (int)toff[g], 0};
+        for (int i = 0; i < f->nloc; i++) col[(size_t)i * f->nwell + j] = L[g].col[(size_t)i * f->nwell + j];
+    }
+    if ((rc = grow_buffer(f->b_tD, sizeof(double) * nT, "group times", f->n_alloc)) || (rc = grow_buffer(f->b_sv, sizeof(int) * nT, "split vectors", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_tfac, sizeof(double) * nT, "time factors", f->n_alloc)) || (rc = grow_buffer(f->b_rD, sizeof(double) * nR, "group distances", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_col, sizeof(int) * col.size(), "columns", f->n_alloc)) || (rc = grow_buffer(f->b_wells, sizeof(ucf_field_well) * wells.size(), "wells", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_h, sizeof(double) * nH, "group drawdowns", f->n_alloc)) || (rc = grow_buffer(f->b_dh, sizeof(double) * nH, "group derivatives", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_stats, sizeof(ucf_stats) * ng, "counters", f->n_alloc))) return rc;
+    hipStream_t st = plan_stream(pl);
+    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
+    struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};     // the staging above outlives the copies
+    if (hipMemcpyAsync(f->b_tD.p, tD.data(), sizeof(double) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_sv.p, sv.data(), sizeof(int) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_tfac.p, tfac.data(), sizeof(double) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_rD.p, rD.data(), sizeof(double) * nR, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_col.p, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(f->b_wells.p, wells.data(), sizeof(ucf_field_well) * wells.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(f->b_stats.p, 0, sizeof(ucf_stats) * ng, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the field's launch arrays failed: %s", hipGetErrorString(hipGetLastError()));
+    // per group one call of the grid path, results into the field's buffers
+    for (int g = 0; g < ng; g++) {
+        if (L[g].nt == 0) continue;
+        rc = ucf_drawdown_grid_device(pl, L[g].nt, (const double*)f->b_tD.p + toff[g], (const int*)f->b_sv.p + toff[g], L[g].nr,
+                                      (const double*)f->b_rD.p + roff[g], nz, zD.data(), zl.data(), (double*)f->b_h.p + hoff[g],
+                                      (double*)f->b_dh.p + hoff[g], stats ? (ucf_stats*)f->b_stats.p + g : nullptr, st);
+        if (rc) return rc;
+    }
+    rc = ucf_field_launch_superpose(f->nt, f->nloc, nz, f->nwell, (const ucf_field_well*)f->b_wells.p, (const int*)f->b_col.p,
+                                    (const double*)f->b_tfac.p, (const double*)f->b_h.p, (const double*)f->b_dh.p, dimensionless ? 0 : 1,
+                                    pl->D.Hc, d_s, d_ds, st);
+    if (rc) return fail(rc, "superposition kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    if (!stats) return UCF_OK;
+    std::vector<ucf_stats> gst(ng);
+    if (hipMemcpyAsync(gst.data(), f->b_stats.p, sizeof(ucf_stats) * ng, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
+    for (int g = 0; g < ng; g++) stats_add(*stats, gst[g]);
+    return UCF_OK;
+}
+
+// the status of a parameter set of a forecast that a check refused, naming the set and the parameter moved (as fit_evaluate)
+int forecast_set_failed(int rc, int k, const int* ids, double dlog)
+{
+    std::string why = ucf_last_error();
+    char nb[32];
+    if (k == 0) return fail(rc, "set 0: %s", why.c_str());
+    return fail(rc, "set %d, %s moved by %+g in its logarithm: %s", k, fit_par_name(ids[(k - 1) / 2], nb, sizeof(nb)), (k & 1) ? dlog : -dlog, why.c_str());
+}
 }  // namespace
 
 extern "C" {
@@ -158,6 +258,7 @@ int ucf_field_create(int nwell, const double* xw, const double* yw, const double
 void ucf_field_destroy(ucf_field* f)
 {
     if (!f) return;
+    ucf_plan_destroy(f->scratch);
     if (f->device >= 0) {
         device_switch sw(f->device);
         for (ucf_buffer* b : f->buffers()) free_buffer(*b);
@@ -194,13 +295,9 @@ long long ucf_field_alloc_count(const ucf_field* f) { return f ? f->n_alloc : 0;
 
 int ucf_field_drawdown(ucf_field* f, ucf_plan* pl, int nz, const double* z, int dimensionless, double* s, double* ds, ucf_stats* stats)
 {
-    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL field");
-    if (nz < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nz=%d: at least one depth", nz);
-    if (!z || !s || !ds) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
-    int rc = field_check_finite("z", nz, z);
+    long long nout = 0;
+    int rc = field_check_call(f, nz, (!z || !s || !ds) ? "NULL array" : nullptr, z, nout);
     if (rc) return rc;
-    const long long nout = (long long)f->nt * f->nloc * nz;
-    if (nout > 0x7fffffffLL * 256) return fail(UCF_ERR_BAD_ARGUMENT, "%d times x %d locations x %d depths: too many outputs for one call", f->nt, f->nloc, nz);
     if (!pl) {
         // a plan cannot exist without a device: say that first where it is the reason
         rc = require_device();
@@ -215,74 +312,124 @@ int ucf_field_drawdown(ucf_field* f, ucf_plan* pl, int nz, const double* z, int 
     if (f->device >= 0 && f->device != pl->device)
         return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
     if (stats) std::memset(stats, 0, sizeof(*stats));
-    // zD, zLay as in ucf_drawdown_multi
-    std::vector<double> zD(nz);
-    std::vector<int> zl(nz);
-    for (int j = 0; j < nz; j++) zD[j] = z[j] / pl->D.Lc;
-    rc = ucf_zlay(pl, nz, zD.data(), zl.data());
-    if (rc) return rc;
-    // one staging image per array, the groups one after the other
-    std::vector<size_t> toff(ng), roff(ng), hoff(ng);
-    size_t nT = 0, nR = 0, nH = 0;
-    for (int g = 0; g < ng; g++) {
-        toff[g] = nT; roff[g] = nR; hoff[g] = nH;
-        nT += field_pad(L[g].nt); nR += field_pad(L[g].nr); nH += field_pad((size_t)L[g].nt * L[g].nr * nz);
-    }
-    if (nT > 0x7fffffffULL) return fail(UCF_ERR_BAD_ARGUMENT, "too many launched times");
-    std::vector<double> tD(nT, 1.0), rD(nR, 1.0), tfac(nT, 0.0);
-    std::vector<int> sv(nT, 0), col((size_t)f->nloc * f->nwell);
-    std::vector<ucf_field_well> wells(f->nwell);
-    for (int g = 0; g < ng; g++) {
-        std::copy(L[g].tD.begin(), L[g].tD.end(), tD.begin() + toff[g]);
-        std::copy(L[g].sv.begin(), L[g].sv.end(), sv.begin() + toff[g]);
-        std::copy(L[g].tfac.begin(), L[g].tfac.end(), tfac.begin() + toff[g]);
-        std::copy(L[g].rD.begin(), L[g].rD.end(), rD.begin() + roff[g]);
-    }
-    for (int j = 0; j < f->nwell; j++) {
-        const int g = f->well_group[j];
-        wells[j] = ucf_field_well{f->qw[j], (long long)hoff[g], L[g].k0, L[g].nr, (int)toff[g], 0};
-        for (int i = 0; i < f->nloc; i++) col[(size_t)i * f->nwell + j] = L[g].col[(size_t)i * f->nwell + j];
-    }
     device_switch dg(pl->device);
     f->device = pl->device;
     const size_t so = sizeof(double) * (size_t)nout;
-    if ((rc = grow_buffer(f->b_tD, sizeof(double) * nT, "group times", f->n_alloc)) || (rc = grow_buffer(f->b_sv, sizeof(int) * nT, "split vectors", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_tfac, sizeof(double) * nT, "time factors", f->n_alloc)) || (rc = grow_buffer(f->b_rD, sizeof(double) * nR, "group distances", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_col, sizeof(int) * col.size(), "columns", f->n_alloc)) || (rc = grow_buffer(f->b_wells, sizeof(ucf_field_well) * wells.size(), "wells", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_h, sizeof(double) * nH, "group drawdowns", f->n_alloc)) || (rc = grow_buffer(f->b_dh, sizeof(double) * nH, "group derivatives", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_s, so, "superposed drawdown", f->n_alloc)) || (rc = grow_buffer(f->b_ds, so, "superposed derivative", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_stats, sizeof(ucf_stats) * ng, "counters", f->n_alloc))) return rc;
+    if ((rc = grow_buffer(f->b_s, so, "superposed drawdown", f->n_alloc)) || (rc = grow_buffer(f->b_ds, so, "superposed derivative", f->n_alloc))) return rc;
+    rc = field_map_core(f, pl, L, nz, z, dimensionless, (double*)f->b_s.p, (double*)f->b_ds.p, stats);
+    if (rc) return rc;
     hipStream_t st = plan_stream(pl);
-    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
-    struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};     // the staging above outlives the copies
-    if (hipMemcpyAsync(f->b_tD.p, tD.data(), sizeof(double) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(f->b_sv.p, sv.data(), sizeof(int) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(f->b_tfac.p, tfac.data(), sizeof(double) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(f->b_rD.p, rD.data(), sizeof(double) * nR, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(f->b_col.p, col.data(), sizeof(int) * col.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(f->b_wells.p, wells.data(), sizeof(ucf_field_well) * wells.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(f->b_stats.p, 0, sizeof(ucf_stats) * ng, st) != hipSuccess)
-        return fail(UCF_ERR_HIP, "upload of the field's launch arrays failed: %s", hipGetErrorString(hipGetLastError()));
-    // per group one call of the grid path, results into the field's buffers
-    for (int g = 0; g < ng; g++) {
-        if (L[g].nt == 0) continue;
-        rc = ucf_drawdown_grid_device(pl, L[g].nt, (const double*)f->b_tD.p + toff[g], (const int*)f->b_sv.p + toff[g], L[g].nr,
-                                      (const double*)f->b_rD.p + roff[g], nz, zD.data(), zl.data(), (double*)f->b_h.p + hoff[g],
-                                      (double*)f->b_dh.p + hoff[g], stats ? (ucf_stats*)f->b_stats.p + g : nullptr, st);
-        if (rc) return rc;
-    }
-    rc = ucf_field_launch_superpose(f->nt, f->nloc, nz, f->nwell, (const ucf_field_well*)f->b_wells.p, (const int*)f->b_col.p,
-                                    (const double*)f->b_tfac.p, (const double*)f->b_h.p, (const double*)f->b_dh.p, dimensionless ? 0 : 1,
-                                    pl->D.Hc, (double*)f->b_s.p, (double*)f->b_ds.p, st);
-    if (rc) return fail(rc, "superposition kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-    std::vector<ucf_stats> gst(ng);
     if (hipMemcpyAsync(s, f->b_s.p, so, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(ds, f->b_ds.p, so, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (stats && hipMemcpyAsync(gst.data(), f->b_stats.p, sizeof(ucf_stats) * ng, hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        hipStreamSynchronize(st) != hipSuccess)
+        hipMemcpyAsync(ds, f->b_ds.p, so, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
-    if (stats)
-        for (int g = 0; g < ng; g++) stats_add(*stats, gst[g]);
+    return UCF_OK;
+}
+
+int ucf_field_forecast_sets(const ucf_params* base, int npar, const int* ids, const double* theta, double dlog, ucf_params* sets)
+{
+    if (!base || !theta || !sets) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = ucf_fit_perturb(base, npar, ids, theta, &sets[0]);      // the checks on npar and ids
+    if (rc) return rc;
+    char nb[32];
+    for (int j = 0; j < npar; j++)
+        if (!(theta[j] > 0.0) || !std::isfinite(theta[j]))
+            return fail(UCF_ERR_BAD_ARGUMENT, "%s=%g must be positive and finite (sensitivities are taken in the logarithm of a parameter)",
+                        fit_par_name(ids[j], nb, sizeof(nb)), theta[j]);
+    if (!(dlog > 0.0) || !std::isfinite(dlog)) return fail(UCF_ERR_BAD_ARGUMENT, "dlog=%g must be positive and finite", dlog);
+    rc = fit_theta_sets(*base, npar, ids, theta, dlog, 1 + 2 * npar, sets);
+    if (rc) return rc;
+    for (int k = 0; k <= 2 * npar; k++)
+        if ((rc = validate(sets[k]))) return forecast_set_failed(rc, k, ids, dlog);
+    return UCF_OK;
+}
+
+int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, const double* theta, double dlog, const double* cov, int nz,
+                       const double* z, double* s, double* ds, double* sens, double* dsens, double* se, double* dse, double* s_all,
+                       double* ds_all, long long* nbad, ucf_stats* stats)
+{
+    long long nout = 0;
+    int rc = field_check_call(f, nz, !z ? "NULL z" : !s ? "NULL s" : !ds ? "NULL ds" : !ids ? "NULL ids" : !theta ? "NULL theta" : nullptr, z, nout);
+    if (rc) return rc;
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (!(dlog > 0.0) || !std::isfinite(dlog)) return fail(UCF_ERR_BAD_ARGUMENT, "dlog=%g must be positive and finite", dlog);
+    if ((se || dse) && !cov) return fail(UCF_ERR_BAD_ARGUMENT, "%s is asked for without cov: a standard error needs the covariance", se ? "se" : "dse");
+    if (cov)
+        for (int j = 0; j < npar; j++)
+            for (int k = 0; k < npar; k++) {
+                const double c = cov[j * npar + k];
+                if (!std::isfinite(c)) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g is not finite", j, k, c);
+                if (c != cov[k * npar + j]) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g differs from cov[%d][%d]=%g: not symmetric", j, k, c, k, j, cov[k * npar + j]);
+                if (j == k && c < 0.0) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g: a negative variance", j, j, c);
+            }
+    const int nset = 1 + 2 * npar;
+    if (nset * nout > 0x7fffffffLL * 256)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d parameter sets x %d times x %d locations x %d depths: too many values for one buffer", nset, f->nt, f->nloc, nz);
+    if (!pl) {
+        rc = require_device();
+        return rc ? rc : fail(UCF_ERR_BAD_ARGUMENT, "NULL plan");
+    }
+    // the parameter sets and what every group launches under each of them: all of it before any launch
+    ucf_params sets[1 + 2 * UCF_FIT_MAX_PAR];
+    if ((rc = ucf_field_forecast_sets(&pl->P, npar, ids, theta, dlog, sets))) return rc;
+    const int ng = (int)f->groups.size();
+    std::vector<std::vector<field_launch>> L(nset, std::vector<field_launch>(ng));
+    for (int k = 0; k < nset; k++) {
+        ucf_derived D;
+        nondimensionalise(sets[k], D);
+        for (int g = 0; g < ng; g++)
+            if ((rc = field_group_core(f, sets[k], D, g, L[k][g]))) return forecast_set_failed(rc, k, ids, dlog);
+    }
+    rc = require_device();
+    if (rc) return rc;
+    if (f->device >= 0 && f->device != pl->device)
+        return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    // the scratch plan: made once, refreshed per set; made anew where the caller's plan has another model or other settings
+    const int mode = pl->mode | (pl->force_layout0 << 1);
+    if (f->scratch && ucf_plan_update(f->scratch, &sets[0]) != UCF_OK) {
+        ucf_plan_destroy(f->scratch);
+        f->scratch = nullptr;
+    }
+    if (!f->scratch) {
+        if ((rc = ucf_plan_create_on(&sets[0], pl->device, &f->scratch))) return rc;
+        f->n_alloc++;
+    }
+    ucf_plan* sp = f->scratch;
+    (void)ucf_plan_set_mode(sp, mode);
+    device_switch dg(pl->device);
+    f->device = pl->device;
+    const size_t so = sizeof(double) * (size_t)nout, sa = so * nset, sj = so * npar;
+    if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every set", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every set", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_nbad, sizeof(long long) * 2, "counts", f->n_alloc)) ||
+        (sens && (rc = grow_buffer(f->b_sens, sj, "sensitivities", f->n_alloc))) || (dsens && (rc = grow_buffer(f->b_dsens, sj, "derivative sensitivities", f->n_alloc))) ||
+        (se && (rc = grow_buffer(f->b_se, so, "standard error", f->n_alloc))) || (dse && (rc = grow_buffer(f->b_dse, so, "derivative standard error", f->n_alloc))) ||
+        (cov && (rc = grow_buffer(f->b_cov, sizeof(double) * UCF_FIT_MAX_PAR * UCF_FIT_MAX_PAR, "cov", f->n_alloc)))) return rc;
+    for (int k = 0; k < nset; k++) {
+        if (k > 0 && (rc = ucf_plan_update(sp, &sets[k]))) return forecast_set_failed(rc, k, ids, dlog);
+        rc = field_map_core(f, sp, L[k], nz, z, 0, (double*)f->b_sall.p + (size_t)k * nout, (double*)f->b_dsall.p + (size_t)k * nout, stats);
+        if (rc) return forecast_set_failed(rc, k, ids, dlog);
+    }
+    hipStream_t st = plan_stream(sp);
+    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
+    struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};
+    if (hipMemsetAsync(f->b_nbad.p, 0, sizeof(long long) * 2, st) != hipSuccess ||
+        (cov && hipMemcpyAsync(f->b_cov.p, cov, sizeof(double) * npar * npar, hipMemcpyHostToDevice, st) != hipSuccess))
+        return fail(UCF_ERR_HIP, "upload of the forecast's arrays failed: %s", hipGetErrorString(hipGetLastError()));
+    const double two_dlog = 2.0 * dlog;
+    rc = ucf_field_launch_forecast(npar, nout, two_dlog, (const double*)f->b_sall.p, cov ? (const double*)f->b_cov.p : nullptr,
+                                   sens ? (double*)f->b_sens.p : nullptr, se ? (double*)f->b_se.p : nullptr, (long long*)f->b_nbad.p, st);
+    if (rc == UCF_OK)
+        rc = ucf_field_launch_forecast(npar, nout, two_dlog, (const double*)f->b_dsall.p, cov ? (const double*)f->b_cov.p : nullptr,
+                                       dsens ? (double*)f->b_dsens.p : nullptr, dse ? (double*)f->b_dse.p : nullptr, (long long*)f->b_nbad.p + 1, st);
+    if (rc) return fail(rc, "forecast kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    // s, ds are slot 0 as it stands; everything else only where asked for
+    const struct { void* host; const void* dev; size_t bytes; } back[] = {
+        {s, f->b_sall.p, so}, {ds, f->b_dsall.p, so}, {sens, f->b_sens.p, sj}, {dsens, f->b_dsens.p, sj}, {se, f->b_se.p, so}, {dse, f->b_dse.p, so},
+        {s_all, f->b_sall.p, sa}, {ds_all, f->b_dsall.p, sa}, {nbad, f->b_nbad.p, sizeof(long long) * 2}};
+    for (const auto& c : back)
+        if (c.host && hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
     return UCF_OK;
 }
 

@@ -1,4 +1,5 @@
-// ucf_field.h -- launcher of the well-field superposition (ucf_field.hip), called by ucf_field_drawdown (ucf_field.cpp).
+// ucf_field.h -- launchers of the well-field kernels (ucf_field.hip): the superposition, called by ucf_field_drawdown and
+// ucf_field_forecast (ucf_field.cpp), and the combination of a forecast.
 #pragma once
 #include <cstddef>
 
@@ -18,3 +19,13 @@ struct ucf_field_well {
 int ucf_field_launch_superpose(int nt, int nloc, int nz, int nwell, const ucf_field_well* d_wells, const int* d_col,
                                const double* d_tfac, const double* d_h, const double* d_dh, int scaled, double scale,
                                double* d_s, double* d_ds, void* stream);
+
+// The combination of a forecast, field_forecast_kernel<npar>: one thread per output e of the slots d_a [1 + 2 npar][nout]
+// (slot 0 the base set, slot 1 + 2j / 2 + 2j parameter j up / down), every operation rounded on its own:
+//   J_j = (a[1+2j][e] - a[2+2j][e]) / two_dlog;   d_sens[j][e] = J_j   (d_sens NULL: not stored)
+//   var = +0.0;  for j = 0..npar-1:  inner = +0.0;  for k = 0..npar-1: inner = inner + cov[j][k] * J_k;   var = var + J_j * inner
+//   d_se[e] = (var < 0) ? +0.0 : sqrt(var), a NaN var stays NaN   (d_se NULL: not formed; not NULL needs d_cov [npar][npar])
+//   *d_nbad += the number of outputs e for which any of the 1 + 2 npar values a[.][e] is not finite (the caller zeroes it).
+// UCF_ERR_BAD_ARGUMENT for npar outside 1..UCF_FIT_MAX_PAR.
+int ucf_field_launch_forecast(int npar, long long nout, double two_dlog, const double* d_a, const double* d_cov, double* d_sens,
+                              double* d_se, long long* d_nbad, void* stream);

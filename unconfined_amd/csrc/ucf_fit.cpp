@@ -75,8 +75,7 @@ struct ucf_fit {
     std::vector<int> st_s;                 // ... and their split vector
 };
 
-namespace {
-const char* fit_par_name(int id, char* buf, size_t n)
+const char* ucf_host::fit_par_name(int id, char* buf, size_t n)
 {
     static const char* const names[] = {"Kr", "kappa", "Ss", "Sy", "ac", "ak", "usL"};
     if (id >= 0 && id < UCF_PAR_MOENCH_ALPHA0) return names[id];
@@ -84,6 +83,20 @@ const char* fit_par_name(int id, char* buf, size_t n)
     return buf;
 }
 
+int ucf_host::fit_theta_sets(const ucf_params& base, int npar, const int* ids, const double* theta, double dlog, int count, ucf_params* sets)
+{
+    const double up = std::exp(dlog), down = std::exp(-dlog);
+    double th[UCF_FIT_MAX_PAR];
+    for (int v = 0; v < count; v++) {
+        for (int j = 0; j < npar && j < UCF_FIT_MAX_PAR; j++) th[j] = theta[j];
+        if (v > 0 && (v - 1) / 2 < UCF_FIT_MAX_PAR) th[(v - 1) / 2] = th[(v - 1) / 2] * ((v & 1) ? up : down);
+        int rc = ucf_fit_perturb(&base, npar, ids, th, &sets[v]);      // (refuses an npar outside 1..UCF_FIT_MAX_PAR)
+        if (rc) return rc;
+    }
+    return UCF_OK;
+}
+
+namespace {
 double* fit_field(ucf_params& P, int id)
 {
     switch (id) {
@@ -413,16 +426,13 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
         }
     device_switch dg(f->device);
     // the plans: refreshed in place, made on first use
-    const double up = std::exp(dlog), down = std::exp(-dlog);
-    std::vector<double> th(npar);
-    for (int s = 0; s < nsets; s++)
+    std::vector<ucf_params> sets(per);
+    for (int s = 0; s < nsets; s++) {
+        int rc = fit_theta_sets(f->base, npar, f->ids, theta + (size_t)s * npar, dlog, per, sets.data());
+        if (rc) return rc;
         for (int v = 0; v < per; v++) {
-            for (int j = 0; j < npar; j++) th[j] = theta[(size_t)s * npar + j];
             const int j = (v - 1) / 2;
-            if (v > 0) th[j] = th[j] * ((v & 1) ? up : down);
-            ucf_params P;
-            int rc = ucf_fit_perturb(&f->base, npar, f->ids, th.data(), &P);
-            if (rc) return rc;
+            const ucf_params& P = sets[v];
             const size_t k = (size_t)s * per + v;
             if (k < f->plans.size()) {
                 rc = ucf_plan_update(f->plans[k], &P);
@@ -437,6 +447,7 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
                 return fail(rc, "set %d, %s moved by %+g in its logarithm: %s", s, fit_par_name(f->ids[j], nb, sizeof(nb)), (v & 1) ? dlog : -dlog, why.c_str());
             }
         }
+    }
     const bool joint = f->deriv;
     const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_, nsum = (size_t)(joint ? ucf_fit_joint_nsums(jac ? npar : 0) : ucf_fit_nsums(jac ? npar : 0));
     // points and (point, depth) values that are launched: every depth at every observation, or the network's blocks

@@ -123,6 +123,13 @@ int shared_launch(ucf_plan* pl, int nblk, int ppp, int nz, const fill_blocks& fi
 int stream_pool(int device, int want, hipStream_t* streams);
 int multi_core(ucf_plan* const* plans, int nplans, int npts, const double* t, const double* r, int nz, const double* z, multi_io& io);
 
+// ---- ucf_fit.cpp
+const char* fit_par_name(int id, char* buf, size_t n);
+// The parameter sets of one theta, in the order a fit evaluates them: sets[0] = ucf_fit_perturb(base, ids, theta), and for
+// count = 1 + 2 npar also sets[1 + 2j] / sets[2 + 2j] = the same with theta[j] * exp(+dlog) / theta[j] * exp(-dlog), one
+// product each (count = 1: the base set alone, dlog is not read).  Returns what ucf_fit_perturb returns.
+int fit_theta_sets(const ucf_params& base, int npar, const int* ids, const double* theta, double dlog, int count, ucf_params* sets);
+
 // ---- ucf_field.cpp
 // UCF_ERR_BAD_ARGUMENT naming name[i] for the first v[i] that is not finite
 int field_check_finite(const char* name, int n, const double* v);

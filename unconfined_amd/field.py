@@ -8,6 +8,12 @@ of wells that share a start time the library runs ONE product grid (times after 
     s, ds = field.drawdown(plan, z=[145.7, 100.0])                                            # [nt, nloc, nz] each
 
 All wells share the plan's aquifer, well geometry and time behaviour; q multiplies the plan's Q (negative: injection).
+
+A forecast takes what a fit returns as it is -- ``theta`` and ``cov`` of ``Fit.lm`` -- and maps, besides s and ds of the fitted
+parameters, their sensitivities to ln theta_j and their first-order standard error sqrt(j' cov j) (ucf_field_forecast):
+
+    out = field.forecast(plan, ["Kr", "Ss"], res["theta"][0], z=[145.7, 100.0], cov=res["cov"][0])
+    out["s"], out["se"], out["sens"]                                                          # [nt, nloc, nz], same, [npar, nt, nloc, nz]
 """
 from __future__ import annotations
 
@@ -17,12 +23,29 @@ import numpy as np
 
 from . import lib as _libmod
 from .abi import UcfParams, UcfStats
+from .fit import par_id
 
 KINDS = {"no_flow": 0, "constant_head": 1, 0: 0, 1: 1}
 
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _addr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def forecast_sets(params: UcfParams, free, theta, dlog: float) -> list:
+    """the 1 + 2 npar parameter sets that a forecast evaluates (ucf_field_forecast_sets; no GPU): the base set, then per free
+    parameter the set with it moved by +dlog and by -dlog in its logarithm"""
+    ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
+    theta = np.atleast_1d(_f64(theta))
+    if len(theta) != len(ids):
+        raise ValueError("theta: one value per free parameter")
+    sets = (UcfParams * (1 + 2 * len(ids)))()
+    _libmod.check(_libmod.load().ucf_field_forecast_sets(C.byref(params), len(ids), _addr(ids), _addr(theta), float(dlog), sets))
+    return [UcfParams.from_buffer_copy(p) for p in sets]
 
 
 def _wells(wells):
@@ -107,6 +130,42 @@ class WellField:
         if with_stats:
             return s, ds, {k: getattr(st, k) for k, _ in UcfStats._fields_}
         return s, ds
+
+    def forecast(self, plan, free, theta, z, cov=None, dlog: float = 1e-3, sensitivities: bool = True, all_maps: bool = False,
+                 with_stats: bool = False) -> dict:
+        """the field under ``plan``'s parameter set with the free parameters (names as for ``fit.par_id``) at ``theta``, all
+        dimensional: s, ds [nt, nloc, nz]; with ``sensitivities`` sens, dsens [npar, nt, nloc, nz], the central differences
+        of s and ds in ln theta_j with step ``dlog``; with ``cov`` [npar, npar] (in ln theta, as ``Fit.lm`` returns it) se, dse
+        [nt, nloc, nz], the first-order standard errors; with ``all_maps`` s_all, ds_all [1 + 2 npar, nt, nloc, nz], the maps
+        of every parameter set of ``forecast_sets``; nbad [2], the outputs of s and of ds with a value that is not finite
+        under any of the sets.  ``plan`` is not modified."""
+        ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
+        theta = np.atleast_1d(_f64(theta))
+        if len(theta) != len(ids):
+            raise ValueError("theta: one value per free parameter")
+        npar = len(ids)
+        z = np.atleast_1d(_f64(z))
+        if cov is not None:
+            cov = _f64(cov)
+            if cov.shape != (npar, npar):
+                raise ValueError("cov: [npar, npar]")
+        shape = (self.nt, self.nloc, len(z))
+        out = {"s": np.zeros(shape), "ds": np.zeros(shape)}
+        if sensitivities:
+            out["sens"], out["dsens"] = np.zeros((npar,) + shape), np.zeros((npar,) + shape)
+        if cov is not None:
+            out["se"], out["dse"] = np.zeros(shape), np.zeros(shape)
+        if all_maps:
+            out["s_all"], out["ds_all"] = np.zeros((1 + 2 * npar,) + shape), np.zeros((1 + 2 * npar,) + shape)
+        out["nbad"] = np.zeros(2, np.int64)
+        st = UcfStats()
+        _libmod.check(self._lib.ucf_field_forecast(
+            self._h, plan._h, npar, _addr(ids), _addr(theta), float(dlog), _addr(cov), len(z), _addr(z),
+            *(_addr(out.get(k)) for k in ("s", "ds", "sens", "dsens", "se", "dse", "s_all", "ds_all")), _addr(out["nbad"]),
+            C.byref(st) if with_stats else None))
+        if with_stats:
+            out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
+        return out
 
     def alloc_count(self) -> int:
         """device allocations made so far by the field"""

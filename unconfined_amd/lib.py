@@ -42,6 +42,7 @@ EXPORTS = [
     "ucf_fit_derivative_check", "ucf_fit_set_derivative", "ucf_fit_evaluate_joint", "ucf_fit_debug_dh",
     "ucf_field_create", "ucf_field_destroy", "ucf_field_group_count", "ucf_field_group", "ucf_field_group_from_params",
     "ucf_field_drawdown", "ucf_field_alloc_count", "ucf_field_images",
+    "ucf_field_forecast_sets", "ucf_field_forecast",
 ]
 
 
@@ -163,6 +164,9 @@ def load() -> C.CDLL:
     lib.ucf_field_alloc_count.argtypes = [vp]
     lib.ucf_field_alloc_count.restype = C.c_longlong
     lib.ucf_field_images.argtypes = [C.c_int, _dp, _dp, _dp, _dp, C.c_double, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp]
+    lib.ucf_field_forecast_sets.argtypes = [C.POINTER(UcfParams), C.c_int, vp, vp, C.c_double, C.POINTER(UcfParams)]
+    # ids, theta, cov and every output may be NULL: plain addresses
+    lib.ucf_field_forecast.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, vp, C.c_int, vp] + [vp] * 8 + [vp, C.POINTER(UcfStats)]
     _lib = lib
     return lib
 
