@@ -360,7 +360,7 @@ long long ucf_fit_alloc_count(const ucf_fit* fit);
  *                ucf_drawdown_multi, unchanged.  Models without a shared launch run plan by plan and well by well through
  *                ucf_drawdown_batch_device on the stream pool.  Each plan's split vector is taken over all the launched times
  *                of the network, so a value does not depend on how the wells fall into groups.
- *   reduction    fit_network_reduce_kernel: as fit_reduce_kernel, but an observation finds its value through (offset, count):
+ *   reduction    fit_reduce_kernel over network_source: as above, but an observation finds its value through (offset, count):
  *                count 1 reads one double per plan; count n > 1 forms s = v[1]; s = s + v[j], j = 2..n-1;
  *                ((v[0] + 2 s) + v[n-1]) / (2 n) on the dimensionless h, then x Hc -- the operations of ucf_screen_average.
  * A well that no observation names is never launched; observations that share a (well, time) share one evaluation.  J and
@@ -413,7 +413,7 @@ int ucf_fit_debug_h(ucf_fit* fit, int plan, int i, int cap, double* h, int* n);
  *                (virtual well, time) share one evaluation.  A map of ucf_field_drawdown takes one split vector per
  *                group of wells, this fit one over all term times: where wells start at different times the two differ by
  *                that choice, not by rounding alone.
- *   reduction    fit_field_reduce_kernel: as fit_network_reduce_kernel, the value of an observation being the sum above.
+ *   reduction    fit_reduce_kernel over field_source: as for a network, the value of an observation being the sum above.
  * ucf_fit_evaluate, ucf_fit_lm, ucf_fit_destroy and ucf_fit_alloc_count work on the object unchanged; J and sim_all come back
  * in the caller's observation order; ucf_fit_eval_counts reports launched and dense of the network of virtual wells (every
  * virtual well's depths count in dense); ucf_fit_debug_h takes a term index.

@@ -1,13 +1,15 @@
 // ucf_fit.cpp -- parameter fitting (ucf.h: ucf_fit_*): observations resident on the device, base and perturbed parameter sets through
 // the shared core of ucf_drawdown_multi, residuals / objective / Jacobian / normal equations in fit_reduce_kernel
-// (ucf_fit.hip), Levenberg-Marquardt for many starts at once on the host (npar x npar arithmetic).  An observation network
-// (ucf_fit_create_network) launches per-well blocks; a field fit (ucf_fit_create_field) is the network of its virtual wells
-// -- one per (observation well, distinct distance to a pumping well) -- whose reduction sums over pumping wells.
+// (ucf_fit.hip, one launcher: ucf_fit_launch_reduce), Levenberg-Marquardt for many starts at once on the host (npar x npar
+// arithmetic).  An observation network (ucf_fit_create_network) launches per-well blocks; a field fit
+// (ucf_fit_create_field) is the network of its virtual wells -- one per (observation well, distinct distance to a pumping
+// well) -- whose reduction sums over pumping wells.
 #include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -46,8 +48,11 @@ struct ucf_fit {
     // where observation i finds its value in b_h (host copy; ucf_fit_create: prefix 0, stride nobs * nz, at = its slot)
     std::vector<ucf_fit_obs_ref> refs;
     int last_nplans = 0;                   // plans of the last evaluation (ucf_fit_debug_h)
-    // an observation network (ucf_fit_create_network)
-    bool network = false;
+    // how an observation finds its value: ucf_fit_create | ucf_fit_create_network | ucf_fit_create_field.  A field fit is
+    // a network for everything but the reduction.
+    ucf_fit_source kind = UCF_FIT_SLOTS;
+    bool is_network() const { return kind != UCF_FIT_SLOTS; }
+    // an observation network
     std::vector<double> well_r, well_z;    // radius per well; depths of well w at well_z[well_z0[w] ..)
     std::vector<int> well_nz, well_z0;
     std::vector<fit_group> groups;         // wells with the same number of depths: one launch sequence each
@@ -56,7 +61,6 @@ struct ucf_fit {
     ucf_buffer b_ref;
     // a field fit (ucf_fit_create_field): a network whose wells are the virtual wells and whose `refs` are per TERM;
     // observation i sums the terms b_first[i] .. b_first[i + 1] of b_term (ucf_fit_term: place and rate factor)
-    bool field = false;
     ucf_buffer b_term, b_first;
     std::vector<double> term_tobs, term_t; // per term: the time of its observation, and that time minus the start of its pumping well
     // derivative data (ucf_fit_set_derivative): observed t ds/dt and its weight per observation, nd of them with a positive
@@ -451,7 +455,7 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     const bool joint = f->deriv;
     const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_, nsum = (size_t)(joint ? ucf_fit_joint_nsums(jac ? npar : 0) : ucf_fit_nsums(jac ? npar : 0));
     // points and (point, depth) values that are launched: every depth at every observation, or the network's blocks
-    const size_t ptot = (size_t)nplans * (f->network ? f->net_pts : np_), vtot = (size_t)nplans * (f->network ? f->net_vals : np_ * nz);
+    const size_t ptot = (size_t)nplans * (f->is_network() ? f->net_pts : np_), vtot = (size_t)nplans * (f->is_network() ? f->net_vals : np_ * nz);
     int rc;
     if ((rc = grow_buffer(f->b_t, sizeof(double) * ptot, "tD", f->n_alloc)) || (rc = grow_buffer(f->b_r, sizeof(double) * ptot, "rD", f->n_alloc)) ||
         (rc = grow_buffer(f->b_s, sizeof(int) * ptot, "sv", f->n_alloc)) || (rc = grow_buffer(f->b_h, sizeof(double) * vtot, "h", f->n_alloc)) ||
@@ -465,41 +469,25 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     f->io.d_t = (double*)f->b_t.p; f->io.d_r = (double*)f->b_r.p; f->io.d_s = (int*)f->b_s.p;
     f->io.d_h = (double*)f->b_h.p; f->io.d_d = (double*)f->b_d.p;
     f->last_nplans = 0;
-    rc = f->network ? network_core(f, nplans) : multi_core(f->plans.data(), nplans, nobs, f->t_s.data(), f->r_s.data(), nz, f->z.data(), f->io);
+    rc = f->is_network() ? network_core(f, nplans) : multi_core(f->plans.data(), nplans, nobs, f->t_s.data(), f->r_s.data(), nz, f->z.data(), f->io);
     if (rc) return rc;
     f->last_nplans = nplans;
     f->h_hc.resize(nplans);
     for (int k = 0; k < nplans; k++) f->h_hc[k] = f->plans[k]->D.Hc;
     HIP_TRY(hipMemcpy(f->b_hc.p, f->h_hc.data(), sizeof(double) * nplans, hipMemcpyHostToDevice));
-    const ucf_fit_joint_io jio = {(const double*)f->b_obs.p, (const double*)f->b_w.p, (const double*)f->b_dobs.p, (const double*)f->b_wd.p,
-                                  (double*)f->b_sums.p, (int*)f->b_nbad.p, (J && jac) ? (double*)f->b_J.p : nullptr,
-                                  sim_all ? (double*)f->b_sim.p : nullptr, (Jd && jac) ? (double*)f->b_Jd.p : nullptr,
-                                  simd_all ? (double*)f->b_simd.p : nullptr};
-    if (joint && f->field)
-        rc = ucf_fit_launch_field_joint_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
-                                               (const double*)f->b_d.p, (const double*)f->b_hc.p, (const ucf_fit_term*)f->b_term.p,
-                                               (const double*)f->b_tfac.p, (const int*)f->b_first.p, &jio, nullptr);
-    else if (joint && f->network)
-        rc = ucf_fit_launch_network_joint_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
-                                                 (const double*)f->b_d.p, (const double*)f->b_hc.p, (const ucf_fit_obs_ref*)f->b_ref.p, &jio,
-                                                 nullptr);
-    else if (joint)
-        rc = ucf_fit_launch_joint_reduce(jac ? npar : 0, nsets, nobs, np_ * nz, 2.0 * dlog, (const double*)f->b_h.p, (const double*)f->b_d.p,
-                                         (const double*)f->b_hc.p, (const int*)f->b_slot.p, &jio, nullptr);
-    else if (f->field)
-        rc = ucf_fit_launch_field_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
-                                         (const double*)f->b_hc.p, (const ucf_fit_term*)f->b_term.p, (const int*)f->b_first.p,
-                                         (const double*)f->b_obs.p, (const double*)f->b_w.p, (double*)f->b_sums.p, (int*)f->b_nbad.p,
-                                         (J && jac) ? (double*)f->b_J.p : nullptr, sim_all ? (double*)f->b_sim.p : nullptr, nullptr);
-    else if (f->network)
-        rc = ucf_fit_launch_network_reduce(jac ? npar : 0, nsets, nobs, (size_t)nplans, 2.0 * dlog, (const double*)f->b_h.p,
-                                           (const double*)f->b_hc.p, (const ucf_fit_obs_ref*)f->b_ref.p, (const double*)f->b_obs.p,
-                                           (const double*)f->b_w.p, (double*)f->b_sums.p, (int*)f->b_nbad.p,
-                                           (J && jac) ? (double*)f->b_J.p : nullptr, sim_all ? (double*)f->b_sim.p : nullptr, nullptr);
-    else
-        rc = ucf_fit_launch_reduce(jac ? npar : 0, nsets, nobs, np_ * nz, 2.0 * dlog, (const double*)f->b_h.p, (const double*)f->b_hc.p,
-                                   (const int*)f->b_slot.p, (const double*)f->b_obs.p, (const double*)f->b_w.p, (double*)f->b_sums.p,
-                                   (int*)f->b_nbad.p, (J && jac) ? (double*)f->b_J.p : nullptr, sim_all ? (double*)f->b_sim.p : nullptr, nullptr);
+    ucf_fit_reduce_args ra = {};
+    ra.npar = jac ? npar : 0; ra.nsets = nsets; ra.nobs = nobs;
+    ra.nplans = (size_t)nplans; ra.plan_stride = np_ * nz; ra.two_dlog = 2.0 * dlog;
+    ra.d_h = (const double*)f->b_h.p; ra.d_dh = joint ? (const double*)f->b_d.p : nullptr; ra.d_Hc = (const double*)f->b_hc.p;
+    ra.source = f->kind;
+    ra.d_slot = (const int*)f->b_slot.p; ra.d_ref = (const ucf_fit_obs_ref*)f->b_ref.p;
+    ra.d_term = (const ucf_fit_term*)f->b_term.p; ra.d_first = (const int*)f->b_first.p; ra.d_tfac = (const double*)f->b_tfac.p;
+    ra.d_obs = (const double*)f->b_obs.p; ra.d_w = (const double*)f->b_w.p;
+    ra.d_dobs = (const double*)f->b_dobs.p; ra.d_wd = (const double*)f->b_wd.p;
+    ra.d_sums = (double*)f->b_sums.p; ra.d_nbad = (int*)f->b_nbad.p;
+    ra.d_J = (J && jac) ? (double*)f->b_J.p : nullptr; ra.d_sim = sim_all ? (double*)f->b_sim.p : nullptr;
+    ra.d_Jd = (Jd && jac) ? (double*)f->b_Jd.p : nullptr; ra.d_simd = simd_all ? (double*)f->b_simd.p : nullptr;
+    rc = ucf_fit_launch_reduce(&ra, nullptr);
     if (rc) return fail(rc, "fit reduction kernel launch failed");
     HIP_TRY(hipStreamSynchronize(nullptr));
     f->h_sums.resize(nsets * nsum);
@@ -522,6 +510,76 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
         }
     }
     return UCF_OK;
+}
+
+// ---- what the three ucf_fit_create* share
+// the opening: checks that do not depend on the kind of fit, in the order every kind makes them
+int fit_create_check(const ucf_params* base, int npar, const int* ids, int nobs, ucf_fit** out)
+{
+    if (out) *out = nullptr;
+    if (!base || !out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    int rc = validate(*base);
+    if (rc) return rc;
+    rc = fit_check_ids(*base, npar, ids);
+    if (rc) return rc;
+    if (nobs < npar) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: fewer observations than the %d parameters to fit", nobs, npar);
+    return UCF_OK;
+}
+
+// after the checks of the kind: the device, then the fit with what every kind sets
+int fit_new(const ucf_params* base, int npar, const int* ids, int nobs, int nz, int device, ucf_fit_source kind, ucf_fit** f_out)
+{
+    int ndev = 0;
+    int rc = ucf_device_count(&ndev);
+    if (rc) return rc;
+    if (device < 0 || device >= ndev) return fail(UCF_ERR_BAD_ARGUMENT, "device %d does not exist (%d visible)", device, ndev);
+    ucf_fit* f = new (std::nothrow) ucf_fit();
+    if (!f) return fail(UCF_ERR_NOMEM, "host allocation failed");
+    f->base = *base; f->npar = npar; f->nobs = nobs; f->nz = nz; f->device = device; f->kind = kind;
+    for (int j = 0; j < npar; j++) f->ids[j] = ids[j];
+    *f_out = f;
+    return UCF_OK;
+}
+
+// the closing: the buffers that are fixed at create, in the order given, and their contents; the fit is destroyed on failure
+struct fit_upload {
+    ucf_buffer* b;
+    const void* from;
+    size_t bytes;
+    const char* what;
+};
+int fit_create_upload(ucf_fit* f, std::initializer_list<fit_upload> ups, ucf_fit** out)
+{
+    device_switch dg(f->device);
+    for (const fit_upload& u : ups) {
+        int rc = grow_buffer(*u.b, u.bytes, u.what, f->n_alloc);
+        if (rc) { ucf_fit_destroy(f); return rc; }
+    }
+    for (const fit_upload& u : ups)
+        if (hipMemcpy(u.b->p, u.from, u.bytes, hipMemcpyHostToDevice) != hipSuccess) {
+            ucf_fit_destroy(f);
+            return fail(UCF_ERR_HIP, "upload of the observations failed");
+        }
+    *out = f;
+    return UCF_OK;
+}
+
+// The network of f's wells (well_r, well_nz, well_z are set) over n places (t[k] in well[k], depth iz[k] or the screen):
+// the groups, what a plan launches and f->refs, one per place -- the observations of a network fit, the terms of a field fit.
+void fit_network_places(ucf_fit* f, int n, const double* t, const int* well, const int* iz)
+{
+    std::vector<int> grp_of, pt_of;
+    long long npoints = 0;
+    network_layout((int)f->well_nz.size(), f->well_r.data(), f->well_nz.data(), n, t, well, f->groups, &grp_of, &pt_of, &npoints);
+    f->net_pts = f->groups.back().pt_prefix + f->groups.back().pts;
+    f->net_vals = f->groups.back().prefix + f->groups.back().stride;
+    f->dense = npoints * (long long)f->well_z.size();
+    f->refs.resize(n);
+    for (int k = 0; k < n; k++) {
+        const fit_group& G = f->groups[grp_of[k]];
+        const bool screen = iz[k] == UCF_FIT_SCREEN;
+        f->refs[k] = ucf_fit_obs_ref{(long long)G.prefix, (long long)G.stride, pt_of[k] * G.nz + (screen ? 0 : iz[k]), screen ? G.nz : 1};
+    }
 }
 }  // namespace
 
@@ -561,13 +619,8 @@ int ucf_fit_solve_step(int npar, const double* A, const double* g, double lambda
 int ucf_fit_create(const ucf_params* base, int npar, const int* ids, int nobs, const double* t, const double* r, const int* iz,
                    int nz, const double* z, const double* obs, const double* weight, int device, ucf_fit** out)
 {
-    if (out) *out = nullptr;
-    if (!base || !out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
-    int rc = validate(*base);
+    int rc = fit_create_check(base, npar, ids, nobs, out);
     if (rc) return rc;
-    rc = fit_check_ids(*base, npar, ids);
-    if (rc) return rc;
-    if (nobs < npar) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: fewer observations than the %d parameters to fit", nobs, npar);
     if (nobs > (1 << 24)) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: too many observations", nobs);
     if (nz < 1 || nz > 4096) return fail(UCF_ERR_BAD_ARGUMENT, "nz=%d: at least one depth (at most 4096)", nz);
     if (!t || !r || !iz || !z || !obs || !weight) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
@@ -580,14 +633,9 @@ int ucf_fit_create(const ucf_params* base, int npar, const int* ids, int nobs, c
         if (!std::isfinite(t[i]) || !(t[i] > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "t[%d]=%g is not a finite positive time", i, t[i]);
         if (!std::isfinite(r[i]) || !(r[i] > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "r[%d]=%g is not a finite positive radius", i, r[i]);
     }
-    int ndev = 0;
-    rc = ucf_device_count(&ndev);
+    ucf_fit* f = nullptr;
+    rc = fit_new(base, npar, ids, nobs, nz, device, UCF_FIT_SLOTS, &f);
     if (rc) return rc;
-    if (device < 0 || device >= ndev) return fail(UCF_ERR_BAD_ARGUMENT, "device %d does not exist (%d visible)", device, ndev);
-    ucf_fit* f = new (std::nothrow) ucf_fit();
-    if (!f) return fail(UCF_ERR_NOMEM, "host allocation failed");
-    f->base = *base; f->npar = npar; f->nobs = nobs; f->nz = nz; f->device = device;
-    for (int j = 0; j < npar; j++) f->ids[j] = ids[j];
     // the core evaluates in order of radius (see ucf_drawdown_batch): the observations are ordered once, here
     std::vector<int> perm(nobs);
     for (int i = 0; i < nobs; i++) perm[i] = i;
@@ -598,17 +646,9 @@ int ucf_fit_create(const ucf_params* base, int npar, const int* ids, int nobs, c
     f->refs.resize(nobs);
     for (int i = 0; i < nobs; i++) f->refs[i] = ucf_fit_obs_ref{0, (long long)nobs * nz, slot[i], 1};
     f->dense = (long long)nobs * nz;
-    device_switch dg(device);
-    if ((rc = grow_buffer(f->b_slot, sizeof(int) * nobs, "observation places", f->n_alloc)) || (rc = grow_buffer(f->b_obs, sizeof(double) * nobs, "observations", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_w, sizeof(double) * nobs, "weights", f->n_alloc))) { ucf_fit_destroy(f); return rc; }
-    if (hipMemcpy(f->b_slot.p, slot.data(), sizeof(int) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->b_obs.p, obs, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->b_w.p, weight, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess) {
-        ucf_fit_destroy(f);
-        return fail(UCF_ERR_HIP, "upload of the observations failed");
-    }
-    *out = f;
-    return UCF_OK;
+    return fit_create_upload(f, {{&f->b_slot, slot.data(), sizeof(int) * nobs, "observation places"},
+                                 {&f->b_obs, obs, sizeof(double) * nobs, "observations"},
+                                 {&f->b_w, weight, sizeof(double) * nobs, "weights"}}, out);
 }
 
 void ucf_fit_destroy(ucf_fit* f)
@@ -626,13 +666,8 @@ int ucf_fit_create_network(const ucf_params* base, int npar, const int* ids, int
                            const double* well_z, int nobs, const double* t, const int* well, const int* iz, const double* obs,
                            const double* weight, int device, ucf_fit** out)
 {
-    if (out) *out = nullptr;
-    if (!base || !out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
-    int rc = validate(*base);
+    int rc = fit_create_check(base, npar, ids, nobs, out);
     if (rc) return rc;
-    rc = fit_check_ids(*base, npar, ids);
-    if (rc) return rc;
-    if (nobs < npar) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: fewer observations than the %d parameters to fit", nobs, npar);
     if (!well_r || !well_z || !iz || !obs || !weight) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
     rc = network_check(nwell, well_nz, nobs, t, well);
     if (rc) return rc;
@@ -640,39 +675,15 @@ int ucf_fit_create_network(const ucf_params* base, int npar, const int* ids, int
     rc = network_check_wells(nwell, well_r, well_nz, well_z, nobs, well, iz, obs, weight, z0);
     if (rc) return rc;
     const int nzs = z0[nwell];
-    int ndev = 0;
-    rc = ucf_device_count(&ndev);
+    ucf_fit* f = nullptr;
+    rc = fit_new(base, npar, ids, nobs, 0, device, UCF_FIT_NETWORK, &f);
     if (rc) return rc;
-    if (device < 0 || device >= ndev) return fail(UCF_ERR_BAD_ARGUMENT, "device %d does not exist (%d visible)", device, ndev);
-    ucf_fit* f = new (std::nothrow) ucf_fit();
-    if (!f) return fail(UCF_ERR_NOMEM, "host allocation failed");
-    f->base = *base; f->npar = npar; f->nobs = nobs; f->nz = 0; f->device = device; f->network = true;
-    for (int j = 0; j < npar; j++) f->ids[j] = ids[j];
     f->well_r.assign(well_r, well_r + nwell); f->well_nz.assign(well_nz, well_nz + nwell);
     f->well_z.assign(well_z, well_z + nzs); f->well_z0.assign(z0.begin(), z0.begin() + nwell);
-    std::vector<int> grp_of, pt_of;
-    long long npoints = 0;
-    network_layout(nwell, well_r, well_nz, nobs, t, well, f->groups, &grp_of, &pt_of, &npoints);
-    f->net_pts = f->groups.back().pt_prefix + f->groups.back().pts;
-    f->net_vals = f->groups.back().prefix + f->groups.back().stride;
-    f->dense = npoints * nzs;
-    f->refs.resize(nobs);
-    for (int i = 0; i < nobs; i++) {
-        const fit_group& G = f->groups[grp_of[i]];
-        const bool screen = iz[i] == UCF_FIT_SCREEN;
-        f->refs[i] = ucf_fit_obs_ref{(long long)G.prefix, (long long)G.stride, pt_of[i] * G.nz + (screen ? 0 : iz[i]), screen ? G.nz : 1};
-    }
-    device_switch dg(device);
-    if ((rc = grow_buffer(f->b_ref, sizeof(ucf_fit_obs_ref) * nobs, "observation places", f->n_alloc)) || (rc = grow_buffer(f->b_obs, sizeof(double) * nobs, "observations", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_w, sizeof(double) * nobs, "weights", f->n_alloc))) { ucf_fit_destroy(f); return rc; }
-    if (hipMemcpy(f->b_ref.p, f->refs.data(), sizeof(ucf_fit_obs_ref) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->b_obs.p, obs, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->b_w.p, weight, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess) {
-        ucf_fit_destroy(f);
-        return fail(UCF_ERR_HIP, "upload of the observations failed");
-    }
-    *out = f;
-    return UCF_OK;
+    fit_network_places(f, nobs, t, well, iz);
+    return fit_create_upload(f, {{&f->b_ref, f->refs.data(), sizeof(ucf_fit_obs_ref) * nobs, "observation places"},
+                                 {&f->b_obs, obs, sizeof(double) * nobs, "observations"},
+                                 {&f->b_w, weight, sizeof(double) * nobs, "weights"}}, out);
 }
 
 int ucf_fit_create_field(const ucf_params* base, int npar, const int* ids, int npump, const double* xw, const double* yw, const double* qw,
@@ -680,13 +691,8 @@ int ucf_fit_create_field(const ucf_params* base, int npar, const int* ids, int n
                          int nobs, const double* t, const int* well, const int* iz, const double* obs, const double* weight, int device,
                          ucf_fit** out)
 {
-    if (out) *out = nullptr;
-    if (!base || !out) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
-    int rc = validate(*base);
+    int rc = fit_create_check(base, npar, ids, nobs, out);
     if (rc) return rc;
-    rc = fit_check_ids(*base, npar, ids);
-    if (rc) return rc;
-    if (nobs < npar) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d: fewer observations than the %d parameters to fit", nobs, npar);
     if (!well_z || !iz || !obs || !weight) return fail(UCF_ERR_BAD_ARGUMENT, "NULL array");
     rc = field_check(npump, xw, yw, qw, t0w, nwell, well_x, well_y);
     if (rc) return rc;
@@ -700,14 +706,9 @@ int ucf_fit_create_field(const ucf_params* base, int npar, const int* ids, int n
     if (rc) return rc;
     const int nvirt = (int)F.virt_well.size(), nterm = (int)F.pump.size();
     if (nterm < 1) return fail(UCF_ERR_BAD_ARGUMENT, "no observation lies after the start of a pumping well: nothing to fit");
-    int ndev = 0;
-    rc = ucf_device_count(&ndev);
+    ucf_fit* f = nullptr;
+    rc = fit_new(base, npar, ids, nobs, 0, device, UCF_FIT_FIELD, &f);
     if (rc) return rc;
-    if (device < 0 || device >= ndev) return fail(UCF_ERR_BAD_ARGUMENT, "device %d does not exist (%d visible)", device, ndev);
-    ucf_fit* f = new (std::nothrow) ucf_fit();
-    if (!f) return fail(UCF_ERR_NOMEM, "host allocation failed");
-    f->base = *base; f->npar = npar; f->nobs = nobs; f->nz = 0; f->device = device; f->network = true; f->field = true;
-    for (int j = 0; j < npar; j++) f->ids[j] = ids[j];
     // the network of the virtual wells: each carries the depths of its observation well
     f->well_r = F.virt_r;
     f->well_nz.resize(nvirt); f->well_z0.resize(nvirt);
@@ -717,39 +718,19 @@ int ucf_fit_create_field(const ucf_params* base, int npar, const int* ids, int n
         f->well_z0[v] = (int)f->well_z.size();
         f->well_z.insert(f->well_z.end(), well_z + z0[w], well_z + z0[w] + well_nz[w]);
     }
-    std::vector<int> grp_of, pt_of;
-    long long npoints = 0;
-    network_layout(nvirt, f->well_r.data(), f->well_nz.data(), nterm, F.t.data(), F.virt.data(), f->groups, &grp_of, &pt_of, &npoints);
-    f->net_pts = f->groups.back().pt_prefix + f->groups.back().pts;
-    f->net_vals = f->groups.back().prefix + f->groups.back().stride;
-    f->dense = npoints * (long long)f->well_z.size();
-    f->refs.resize(nterm);
+    // a term is a place of that network: the time since its pumping well started, at the depth of its observation
     f->term_t = F.t;
     f->term_tobs.resize(nterm);
+    std::vector<int> term_iz(nterm);
+    for (int i = 0; i < nobs; i++)
+        for (int k = F.first[i]; k < F.first[i + 1]; k++) { f->term_tobs[k] = t[i]; term_iz[k] = iz[i]; }
+    fit_network_places(f, nterm, F.t.data(), F.virt.data(), term_iz.data());
     std::vector<ucf_fit_term> terms(nterm);
-    for (int i = 0; i < nobs; i++) {
-        const bool screen = iz[i] == UCF_FIT_SCREEN;
-        for (int k = F.first[i]; k < F.first[i + 1]; k++) {
-            f->term_tobs[k] = t[i];
-            const fit_group& G = f->groups[grp_of[k]];
-            f->refs[k] = ucf_fit_obs_ref{(long long)G.prefix, (long long)G.stride, pt_of[k] * G.nz + (screen ? 0 : iz[i]), screen ? G.nz : 1};
-            terms[k] = ucf_fit_term{f->refs[k], qw[F.pump[k]]};
-        }
-    }
-    device_switch dg(device);
-    if ((rc = grow_buffer(f->b_term, sizeof(ucf_fit_term) * nterm, "terms", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_first, sizeof(int) * ((size_t)nobs + 1), "term lists", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_obs, sizeof(double) * nobs, "observations", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_w, sizeof(double) * nobs, "weights", f->n_alloc))) { ucf_fit_destroy(f); return rc; }
-    if (hipMemcpy(f->b_term.p, terms.data(), sizeof(ucf_fit_term) * nterm, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->b_first.p, F.first.data(), sizeof(int) * ((size_t)nobs + 1), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->b_obs.p, obs, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(f->b_w.p, weight, sizeof(double) * nobs, hipMemcpyHostToDevice) != hipSuccess) {
-        ucf_fit_destroy(f);
-        return fail(UCF_ERR_HIP, "upload of the observations failed");
-    }
-    *out = f;
-    return UCF_OK;
+    for (int k = 0; k < nterm; k++) terms[k] = ucf_fit_term{f->refs[k], qw[F.pump[k]]};
+    return fit_create_upload(f, {{&f->b_term, terms.data(), sizeof(ucf_fit_term) * nterm, "terms"},
+                                 {&f->b_first, F.first.data(), sizeof(int) * ((size_t)nobs + 1), "term lists"},
+                                 {&f->b_obs, obs, sizeof(double) * nobs, "observations"},
+                                 {&f->b_w, weight, sizeof(double) * nobs, "weights"}}, out);
 }
 
 int ucf_fit_field_terms(const ucf_params* base, int npump, const double* xw, const double* yw, const double* qw, const double* t0w, int nwell,
@@ -780,7 +761,7 @@ int ucf_fit_field_terms(const ucf_params* base, int npump, const double* xw, con
 int ucf_fit_eval_counts(const ucf_fit* f, long long* launched, long long* dense)
 {
     if (!f || !launched || !dense) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
-    *launched = f->network ? (long long)f->net_vals : f->dense;
+    *launched = f->is_network() ? (long long)f->net_vals : f->dense;
     *dense = f->dense;
     return UCF_OK;
 }
@@ -806,7 +787,7 @@ static int fit_debug_read(ucf_fit* f, bool dh, int plan, int i, int cap, double*
     if (!f || !h || !n) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (f->last_nplans < 1) return fail(UCF_ERR_BAD_ARGUMENT, "no evaluation to read from");
     if (plan < 0 || plan >= f->last_nplans) return fail(UCF_ERR_BAD_ARGUMENT, "plan %d outside 0..%d", plan, f->last_nplans - 1);
-    const char* what = f->field ? "term" : "observation";      // a field fit has one place per term
+    const char* what = f->kind == UCF_FIT_FIELD ? "term" : "observation";      // a field fit has one place per term
     if (i < 0 || i >= (int)f->refs.size()) return fail(UCF_ERR_BAD_ARGUMENT, "%s %d outside 0..%d", what, i, (int)f->refs.size() - 1);
     const ucf_fit_obs_ref& o = f->refs[i];
     if (cap < o.count) return fail(UCF_ERR_BAD_ARGUMENT, "cap=%d: %s %d reads %d values", cap, what, i, o.count);
@@ -854,7 +835,7 @@ int ucf_fit_set_derivative(ucf_fit* f, const double* dobs, const double* dweight
     f->deriv = false;                      // until everything is in place
     HIP_TRY(hipMemcpy(f->b_dobs.p, dobs, sizeof(double) * nobs, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(f->b_wd.p, dweight, sizeof(double) * nobs, hipMemcpyHostToDevice));
-    if (f->field) {
+    if (f->kind == UCF_FIT_FIELD) {
         // tfac of ucf_field_group, per term: the observation's own time over the term's time, one division
         std::vector<double> tfac(nterm);
         for (size_t k = 0; k < nterm; k++) tfac[k] = f->term_tobs[k] / f->term_t[k];
