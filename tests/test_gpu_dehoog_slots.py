@@ -1,8 +1,8 @@
 """dehoog_tiles_kernel<TU, false> (fast flavour) after its non-arithmetic instructions were taken out, bit for bit against
 the parent.
 
-What changed (ucf_device.h, UCF_DH_SLOTS): the one-lane shifts write registers of their own, the steps of the solo, the
-pair and the quad phase of the rhombus run two to a loop turn (values change places instead of being copied), the
+What changed (ucf_device.h: dehoog_qd_tile_slots, dehoog_cf_slot): the one-lane shifts write registers of their own, the
+steps of the solo, the pair and the quad phase of the rhombus run two to a loop turn (values change places, no copies), the
 coefficients are stored unnegated and negated where the continued fraction reads them, the validity of a lane comes from a
 scalar mask, q(i,1) is one division, and the A and the B recurrence of a vector run on a lane each.  Per lane not one
 floating-point operation on a value that reaches a result changed, so h and dh must be the SAME BITS as before:

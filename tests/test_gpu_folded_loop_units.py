@@ -1,8 +1,8 @@
 """The folded water-table kernel with one depth per launch: quadrature units settled by bounds, bit for bit against the parent.
 
 integrate_kernel<2, 1, W, false, FOLD = true, false, NZC = 1, ...> (the lane = time grid of a fully penetrating well: what
-bench.py times) decides for every quadrature unit which loop it may run.  Three things changed around its loops
-(UCF_ZPAIR_UNITS, ucf_fastpath.h), none of them a floating-point operation that reaches a result:
+bench.py times) decides for every quadrature unit which loop it may run.  Three things changed around its loops (the ZPAIR
+branch of integrate_kernel, zpair_unit_bounds in ucf_fastpath.h), none of them a floating-point operation that reaches a result:
   * the ends of the J0 intervals are read from a table that abscissa_kernel writes behind the abscissa rows (the same
     correctly rounded quotients the kernel formed for itself);
   * a unit is first tried with bounds on eta that need no eta (zpair_unit_bounds); only a unit they leave open pays for the

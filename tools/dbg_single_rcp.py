@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Why the single-reciprocal form of the water-table sample, (den - f_z) / (q den), was 2e-6 / 4e-6 off at two far-field fuzz
-points while its samples looked as good as any.  For the library named by UCF_LIB_PATH (the product, or
-a build with -DUCF_SINGLE_RCP) at the two recorded points (seed 903 set 26, seed 700 set 39):
+points while its samples looked as good as any.  For the library named by UCF_LIB_PATH (the product by
+default; the variant build of the rejected form, -DUCF_SINGLE_RCP, last existed at commit 3d6a9aa: a library built there
+still loads) at the two recorded points (seed 903 set 26, seed 700 set 39):
   1. the stages of the PRODUCTION launch sequence (ucf_debug_stages: level sums, J0-interval areas, totlap) against the
      binary128 oracle: where does the form's noise enter, and how large is it relative to each stage vector;
   2. the same point with tD moved by k x 1e-13 (k = 0..23): every rounding changes, the problem does not -- the spread of the

@@ -1,6 +1,9 @@
 #!/bin/bash
 # A/B build of the fast flavour with extra -D switches:  tools/ubench/build_variant.sh <tag> [-DUCF_FOLD_WAVES=6 ...]
 # -> tools/ubench/libucf_<tag>.so (the other objects come from the regular build); time it with run_variants.sh
+# What -D can set: the tuning constants (UCF_KV, UCF_FOLD_WAVES, UCF_UNFOLD_WAVES, UCF_NZC, UCF_NZC2, UCF_DH_TILE,
+# UCF_DH_WAVES) and the diagnostic builds (UCF_TIMELINE, UCF_PROBE, UCF_K1_ASSUME).  The kernels hold no switch back to
+# code they replaced: to time against an earlier kernel, build that commit's library and alternate (tools/gpu_ab_prev.sh).
 set -e
 tag=$1; shift
 here=$(cd "$(dirname "$0")" && pwd)

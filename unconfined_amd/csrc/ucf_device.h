@@ -728,127 +728,29 @@ UCF_DEV void dehoog_qd_wave(cplx f, int M, int lane, ucf_stats* st, bool* zero, 
     }
 }
 
-// Packed rhombus (fast flavour, -DUCF_DH_PACK=0: one vector per pass as above).  Step r of a vector needs q(i,r) of the
-// lanes i <= 2(M - r) + 1 only, so from r = M - 15 on a vector fits a group of 32 lanes and from r = M - 7 on a group of 16:
-// two, then four vectors share every instruction of a step.  No entry inside a rhombus reads a lane outside it (the one-lane
-// shift brings a group's last lane its neighbour's lane 0: that lane is outside), so per lane the arithmetic is the solo
-// arithmetic.  The one thing the lanes of a wave decide together, the form of the quotient, is decided per group.
-#ifndef UCF_DH_PACK
-#define UCF_DH_PACK 1
-#endif
-#if UCF_FAST && UCF_DH_PACK
-UCF_DEV cplx lane_gather(cplx v, int src) { return cmake(__shfl(v.re, src, 64), __shfl(v.im, src, 64)); }
-// qd_quotient for groups of W lanes: each group takes the form it would take alone in the wave (a group of the pass may need
-// cdiv while its neighbours keep the unscaled quotient: both forms then, chosen by group)
-template <int W>
-UCF_DEV cplx qd_quotient_groups(cplx qn, cplx enn, cplx enew, bool valid, int lane)
-{
-    const double m = fmax(fabs(enew.re), fabs(enew.im));
-    const unsigned long long bal = __builtin_amdgcn_ballot_w64(valid && !(m < 1.0e150 && m > 1.0e-150));
-    const double r = fast_rcp(__builtin_fma(enew.re, enew.re, enew.im * enew.im));
-    const cplx num = cmul(qn, enn);
-    cplx res = cmake((num.re * enew.re + num.im * enew.im) * r, (num.im * enew.re - num.re * enew.im) * r);
-    if (__builtin_expect(bal != 0, 0)) {
-        const bool mine = ((bal >> (lane & ~(W - 1))) & ((1ull << W) - 1)) != 0;
-        const cplx scaled = cdiv(cmul(qn, enn), enew);
-        if (mine) res = scaled;
-    }
-    return res;
-}
-// step r of the rhombus in every group of W lanes: `lane` in the wave, `occ` this lane's group holds a vector, `dcol` the LDS
-// column of this lane's vector (read by the group's lane 0)
-template <int W>
-UCF_DEV void qd_step(cplx& q, cplx& en, int r, int M, int lane, bool occ, lds_c* dcol, int pitch)
-{
-    const int l = lane & (W - 1);
-    const cplx qn = shfl_down1(q);
-    const cplx enew = cadd(csub(qn, q), en);
-    if (l == 0 && occ) {
-        dcol[(size_t)(2 * r - 1) * pitch] = make_double2(-q.re, -q.im);                         // d(2r-1) = -q(0,r)   :100
-        dcol[(size_t)(2 * r) * pitch] = make_double2(-enew.re, -enew.im);                       // d(2r)   = -e(0,r)   :101
-    }
-    if (r < M) {
-        const cplx enn = shfl_down1(enew);
-        const bool valid = occ && l <= 2 * (M - r - 1) + 1;
-        if constexpr (W == UCF_WAVE) q = qd_quotient(qn, enn, enew, valid);                     // :93
-        else q = qd_quotient_groups<W>(qn, enn, enew, valid, lane);
-        en = enn;
-    }
-}
-// The rhombi of a tile of ncur <= UCF_DH_TILE times, two times = four vectors (h, dh, h, dh) at a go: each vector starts
-// alone at full width (qd_start) and runs alone while it is wider than half a wave, moves into its half of a pair (h in
-// lanes 0..31, dh in 32..63) for the steps up to r16, and the pair into two quarters of the quad.  A zero vector and a time
-// past ncur leave their group empty (bit of `present` clear: no store, no say in the ballot).  Live: the quad, the pair and
-// the vector in progress, 8 registers each.
-UCF_DEV void dehoog_qd_tile(const ucf_dev_params& P, int lane, int ncur, const double* __restrict__ tD4, lds_c* lds, lds_c* tileB,
-                            int pitch, int* zflag, ucf_stats* st)
-{
-    const int M = P.M, np = P.np;
-    const int r32 = (M - 15 > 1) ? M - 15 : 1, r16 = (M - 7 > 1) ? M - 7 : 1;       // first step in groups of 32 / of 16 lanes
-    const cplx c0 = cmake(0.0, 0.0);
-    for (int tq = 0; tq < ncur; tq += 2) {
-        cplx Qq = c0, Qe = c0;
-        int present = 0;                                       // bit g: quarter g of the quad holds a vector
-        for (int hf = 0; hf < 2 && tq + hf < ncur; hf++) {
-            const int tt = tq + hf;
-            const double tee = 2.0 * tD4[tt];
-            const double sigma = P.alpha - P.logtol / (2.0 * tee);
-            cplx tl = c0;
-            if (lane < np) { const lds_c v = lds[lane * pitch + tt]; tl = cmake(v.x, v.y); }
-            const cplx p = cmake(sigma, UCF_PI * lane / tee);
-            cplx Pq = c0, Pe = c0;
-            for (int which = 0; which < 2; which++) {
-                lds_c* col = (which ? tileB : lds) + tt;       // (column tt of the tile is in `tl` by now)
-                cplx q;
-                const bool some = qd_start(which ? cmul(tl, p) : tl, M, lane, st, col, &q);
-                const bool live = __builtin_amdgcn_ballot_w64(some) != 0;                       // (the same in every lane)
-                if (lane == 0) zflag[2 * tt + which] = !live;
-                if (!live) continue;
-                cplx en = c0;                                                                   // :80     e(i+1,0)
-                for (int r = 1; r < r32; r++) qd_step<UCF_WAVE>(q, en, r, M, lane, true, col, pitch);
-                present |= 1 << (2 * hf + which);
-                const cplx gq = lane_gather(q, lane & 31), ge = lane_gather(en, lane & 31);
-                if ((lane >> 5) == which) { Pq = gq; Pe = ge; }
-            }
-            if (((present >> (2 * hf)) & 3) == 0) continue;
-            {
-                const int g = lane >> 5;
-                const bool occ = (present >> (2 * hf + g)) & 1;
-                lds_c* col = (g ? tileB : lds) + tt;
-                for (int r = r32; r < r16; r++) qd_step<32>(Pq, Pe, r, M, lane, occ, col, pitch);
-                const int src = ((lane >> 4) & 1) * 32 + (lane & 15);
-                const cplx gq = lane_gather(Pq, src), ge = lane_gather(Pe, src);
-                if ((lane >> 5) == hf) { Qq = gq; Qe = ge; }
-            }
-        }
-        if (present == 0) continue;
-        const int g = lane >> 4;
-        const bool occ = (present >> g) & 1;
-        lds_c* col = ((g & 1) ? tileB : lds) + tq + (g >> 1);
-        for (int r = r16; r <= M; r++) qd_step<16>(Qq, Qe, r, M, lane, occ, col, pitch);
-    }
-}
-
-// The same tile with the instructions that are not arithmetic taken out of the steps (-DUCF_DH_SLOTS=0: the code above).
-// Per lane every floating-point operation on a value that reaches a result is the one above, in the same order.
-//   shifts    the one-lane shift writes registers of its own (shift_down1_new: lane 63 receives 0 where it kept its own
-//             value): 4 DPP moves for a complex instead of 4 copies + 4 moves in place.  No valid entry reads what lane 63
-//             receives: e(i,r) is valid for i <= 2(M - r) and reads q(i+1,r), q(i,r+1) for i <= 2(M - r) - 1 reads e(i+1,r);
-//             at M = 31, r = 1 that is lane 61 at most, so lane 62 is the last that reads a shifted value inside a rhombus
-//             and lane 63 receives for nobody.  A group's last lane still receives its neighbour's lane 0, as above.
+#if UCF_FAST
+// Packed rhombus (fast flavour; the faithful one runs dehoog_qd_wave, one vector per pass).  Step r of a vector needs q(i,r)
+// of the lanes i <= 2(M - r) + 1 only, so from r = M - 15 on a vector fits a group of 32 lanes and from r = M - 7 on a group
+// of 16: two, then four vectors share every instruction of a step.  No entry inside a rhombus reads a lane outside it (the
+// one-lane shift brings a group's last lane its neighbour's lane 0: that lane is outside), so per lane the arithmetic is the
+// solo arithmetic of dehoog_qd_wave: every floating-point operation on a value that reaches a result, in the same order.
+// The one thing the lanes of a wave decide together, the form of the quotient (qd_quotient), is decided per group.
+// The steps carry no instruction that is not arithmetic where one can be spared:
+//   shifts    the one-lane shift writes registers of its own (shift_down1_new: lane 63 receives 0 where shift_down1 lets it
+//             keep its own value): 4 DPP moves for a complex instead of 4 copies + 4 moves in place.  No valid entry reads
+//             what lane 63 receives: e(i,r) is valid for i <= 2(M - r) and reads q(i+1,r), q(i,r+1) for i <= 2(M - r) - 1
+//             reads e(i+1,r); at M = 31, r = 1 that is lane 61 at most, so lane 62 is the last that reads a shifted value
+//             inside a rhombus and lane 63 receives for nobody.
 //   validity  which lanes hold an entry of the rhombus is the same for every group and follows from r alone: a lane mask
 //             from the scalar unit, ANDed with the ballot of the range test, instead of a compare per step
 //   max-norm  max(|re|, |im|) is one v_max_f64 with |.| on both sources.  fmax() canonicalises each operand first (a
 //             v_max_f64 of the value with itself, for the sake of signalling NaNs); e(i,r) is the sum of two sums, a number
 //             or a QUIET NaN, and of a quiet NaN and a number v_max_f64 returns the number as fmax does: the range test
-//             behind it sees the same m, NaN (both parts NaN: the guard fires) included.
+//             behind it sees the m of qd_quotient, NaN (both parts NaN: the guard fires) included.
 //   store     lane 0 stores q(0,r) and e(0,r) as they are; the sign of d(2r-1) = -q(0,r), d(2r) = -e(0,r) (:100-101) is
 //             applied where dehoog_cf_slot reads the column: the same negation of the same value
 //   loops     steps come in pairs whose values change places (a, b -> b, a), so nothing is copied where a loop closes
-#ifndef UCF_DH_SLOTS
-#define UCF_DH_SLOTS 1
-#endif
-#if UCF_DH_SLOTS
+UCF_DEV cplx lane_gather(cplx v, int src) { return cmake(__shfl(v.re, src, 64), __shfl(v.im, src, 64)); }
 UCF_DEV double shift_down1_new(double x)
 {
     const int lo = __double2loint(x), hi = __double2hiint(x);
@@ -891,7 +793,8 @@ UCF_DEV void qd_slot_step(cplx q, cplx en, cplx& q2, cplx& en2, unsigned long lo
     const double rc = fast_rcp(__builtin_fma(enew.re, enew.re, enew.im * enew.im));
     const cplx num = cmul(qn, enn);
     q2 = cmake((num.re * enew.re + num.im * enew.im) * rc, (num.im * enew.re - num.re * enew.im) * rc);
-    if (W != UCF_WAVE && __builtin_expect(bal != 0, 0)) {                // (both forms then, chosen by group: qd_quotient_groups)
+    if (W != UCF_WAVE && __builtin_expect(bal != 0, 0)) {                // (a group of the pass may need cdiv while its neighbours keep
+                                                                         //  the unscaled quotient: both forms then, chosen by group)
         const bool mine = ((bal >> (lane & ~(W - 1) & 63)) & ((1ull << (W & 63)) - 1)) != 0;
         const cplx scaled = cdiv(cmul(qn, enn), enew);
         if (mine) q2 = scaled;
@@ -916,7 +819,7 @@ UCF_DEV void qd_slot_steps(cplx& q, cplx& en, int r0, int r1, int M, unsigned lo
     }
 }
 // qd_start with ONE division for q(i,1): lane 0 divides by d(0), the others by f(i) (:81-82) -- the divisor is selected, not
-// the quotient (both divisions ran in turn, each under its part of EXEC).  The same division in every lane as before.
+// the quotient (in qd_start both divisions run in turn, each under its part of EXEC).  The same division in every lane.
 UCF_DEV bool qd_start_slots(cplx f, int M, int lane, ucf_stats* st, lds_c* dcol, cplx* q1)
 {
     const int n2 = 2 * M;
@@ -943,7 +846,11 @@ UCF_DEV bool qd_start_slots(cplx f, int M, int lane, ucf_stats* st, lds_c* dcol,
     *q1 = cdiv(fnext, (lane == 0) ? d0 : ff);                                                   // :81-82  q(i,1)
     return true;
 }
-// dehoog_qd_tile with those steps; the columns hold -d(k) for k >= 1
+// The rhombi of a tile of ncur <= UCF_DH_TILE times, two times = four vectors (h, dh, h, dh) at a go: each vector starts
+// alone at full width (qd_start_slots) and runs alone while it is wider than half a wave, moves into its half of a pair (h
+// in lanes 0..31, dh in 32..63) for the steps up to r16, and the pair into two quarters of the quad.  A zero vector and a
+// time past ncur leave their group empty (bit of `present` clear: no store, no say in the ballot).  Live: the quad, the pair
+// and the vector in progress, 8 registers each.  The columns hold -d(k) for k >= 1.
 UCF_DEV void dehoog_qd_tile_slots(const ucf_dev_params& P, int lane, int ncur, const double* __restrict__ tD4, lds_c* lds, lds_c* tileB,
                                   int pitch, int* zflag, ucf_stats* st)
 {
@@ -1002,7 +909,6 @@ UCF_DEV void dehoog_qd_tile_slots(const ucf_dev_params& P, int lane, int ncur, c
         }
     }
 }
-#endif   // UCF_DH_SLOTS
 #endif
 
 UCF_DEV double dehoog_cf_lane(const lds_c* dcol, int pitch, int M, double alpha, double logtol, double t, double tee)
@@ -1030,7 +936,7 @@ UCF_DEV double dehoog_cf_lane(const lds_c* dcol, int pitch, int M, double alpha,
     return exp(gamma * t) / tee * cdiv(A2M, B2M).re;                                            // :129
 }
 
-#if UCF_FAST && UCF_DH_PACK && UCF_DH_SLOTS
+#if UCF_FAST
 // dehoog_cf_lane on the columns of dehoog_qd_tile_slots (rows k >= 1 hold -d(k): negated as they are read), with the A and
 // the B recurrence of a vector on a lane each (`ab` = 0: A, 1: B, in neighbouring lanes): the two are the same operations
 // on other start values, so a lane runs one of them, forms the improved remainder (both lanes the same bits) and its own
@@ -1807,7 +1713,7 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
     //  work item, its abscissa row and the row's entries live in VGPRs and are fetched by vector loads)
     const int lane = threadIdx.x & (UCF_WAVE - 1), wv = __builtin_amdgcn_readfirstlane(threadIdx.x / UCF_WAVE);
     constexpr int EF = (FAMILY == 5) ? 1 : FAMILY;      // the evaluator: model 2 runs family 1's with its own lane constant
-    constexpr bool ZPAIR = FOLD && EF == 2 && NZC == 1;      // shared seeds: fast_eta's rsq_pair, prim_pair in fast_common_terms
+    constexpr bool ZPAIR = FOLD && EF == 2 && NZC == 1;      // the folded water-table kernel with one depth: a walk of its own
     const int nz = NZC ? NZC : P0.nz, R = P0.R, nacc = P0.nacc, N = P0.N, ngl = P0.ngl;
     __builtin_assume(nz >= 1 && R >= 1 && nacc >= 1 && ngl >= 1);     // (the launcher's business: no loop guards in the kernel)
     const int nabs = N + nacc * ngl;
@@ -1907,8 +1813,8 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
         if constexpr (ZPAIR) {
             // The folded water-table kernel with one depth walks the two parts in loops of their own: the tanh-sinh loop
             // knows the level sums and P.ts_w, the Gauss-Lobatto loop the running area -- which then stays in its registers
-            // (in the one loop the two arms met in copies: two v_mov_b64 per abscissa) -- and neither tests `ts`.  The
-            // sample is fast_sample_zpair (ucf_fastpath.h).  Same operations in the same order: same bits.
+            // (in the general loop below the two arms meet in copies: two v_mov_b64 per abscissa) -- and neither tests `ts`.
+            // The sample is fast_sample_zpair (ucf_fastpath.h).  The general loop's operations in the same order: same bits.
             // lapTime(p) is wanted when an interval is complete and after the loops, not in between: it is read again there
             // (ltab, as above) instead of being held in four registers across the loops -- the index is laundered so that the
             // load stays where it is written
@@ -1921,111 +1827,85 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
             // nothing else.
             int stopped = 0;
             zph = 0;
-            // UCF_ZPAIR_UNITS (ucf_fastpath.h).  ENDS: the ends of the J0 intervals, j0z[sv - 1 + j] / rD for j = 0 .. nacc, are
-            // read from the table abscissa_kernel wrote behind the rows (the same correctly rounded quotients: same bits) -- a
-            // scalar load per interval for the upper end, the lower one is the upper end of the interval before
-            constexpr bool ENDS = LAYOUT == 1 && !MULTI && UCF_ZPAIR_INTERVALS && (UCF_ZPAIR_UNITS & UCF_ZU_TABLE);
-            constexpr bool TS_RUNS = !MULTI && UCF_ZPAIR_INTERVALS && (UCF_ZPAIR_UNITS & UCF_ZU_TS_RUNS);
-            // SETTLE: a part that is in range up to its last abscissa (UCF_PH_RANGE) and has one unit proven exponential and
+            // The ends of the J0 intervals, j0z[sv - 1 + j] / rD for j = 0 .. nacc, are read from the table abscissa_kernel
+            // wrote behind the rows (the same correctly rounded quotients: same bits) -- a scalar load per interval for the
+            // upper end, the lower one is the upper end of the interval before.  The limits of zpair_unit_bounds stand there too.
+            // `settled`: a part that is in range up to its last abscissa (UCF_PH_RANGE) and has one unit proven exponential and
             // short has all its later units proven with it -- Re eta only grows, |Im eta| only falls: no test at all for those
-            constexpr bool SETTLE = !MULTI && UCF_ZPAIR_INTERVALS && (UCF_ZPAIR_UNITS & UCF_ZU_BOUNDS);
-            static_assert(LAYOUT == 1 || MULTI || !UCF_ZPAIR_INTERVALS || !(UCF_ZPAIR_UNITS & (UCF_ZU_TABLE | UCF_ZU_BOUNDS)),
+            static_assert(!ZPAIR || (LAYOUT == 1 && !MULTI),
                           "the interval ends and the limits of the bounds stand behind the rows of a grid's abscissa table only");
-            const double* __restrict__ ends = nullptr;
-            if constexpr (ENDS) ends = (const double*)tab + abscissa_ends_offset((size_t)nr * nsv, nabs) + (size_t)(W.ir * nsv + (sv - svmin)) * (nacc + 1);
-            const double* __restrict__ zb = nullptr;              // the limits of zpair_unit_bounds
-            if constexpr (SETTLE) zb = (const double*)tab + abscissa_limits_offset((size_t)nr * nsv, nabs, nacc);
+            const double* __restrict__ ends = (const double*)tab + abscissa_ends_offset((size_t)nr * nsv, nabs) + (size_t)(W.ir * nsv + (sv - svmin)) * (nacc + 1);
+            const double* __restrict__ zb = (const double*)tab + abscissa_limits_offset((size_t)nr * nsv, nabs, nacc);
             int settled = 0;
-            if constexpr (ENDS) {
-                if (nlim > n0) zph = zpair_part_phase(P, LC, ends[nlim > N ? (nlim - N + ngl - 1) / ngl : 0]);
-            } else
-            if (!MULTI && nlim > n0)      // (a parameter batch: no bit is ever set)
-                zph = zpair_part_phase(P, LC, P.j0z[sv - 1 + (nlim > N ? (nlim - N + ngl - 1) / ngl : 0)] / rD);
+            if (nlim > n0) zph = zpair_part_phase(P, LC, ends[nlim > N ? (nlim - N + ngl - 1) / ngl : 0]);
             const int nts = nlim < N ? nlim : N;
-            if constexpr (TS_RUNS) {
-                // The tanh-sinh part in UCF_ZPAIR_TS_RUNS runs of nodes (they ascend: a run lies between its own first and last
-                // node, the first run above 0), each classified like a J0 interval.  A proven run takes the one arm of its class
-                // and the level-sum update -- no `zph` test, no ballot, no `stopped` -- any other the loop with the bits.
-                auto proven_run = [&](auto cls, auto beta, int nend) {
+            // The tanh-sinh part in TS_RUNS runs of nodes (they ascend: a run lies between its own first and last
+            // node, the first run above 0), each classified like a J0 interval.  A proven run takes the one arm of its class
+            // and the level-sum update -- no `zph` test, no ballot, no `stopped` -- any other the loop with the bits.
+            auto proven_run = [&](auto cls, auto beta, int nend) {
+                for (; n < nend; n++) {
+                    const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
+                    F.sc.salt = n;
+                    (void)fast_eta<2, true>(P, LC, aa.x, F);
+                    const cplx val = rscale(aa.y, fast_sample_zpair_proven<decltype(cls)::value, decltype(beta)::value>(P, LC, F));
+                    const int n1 = n + 1;
+                    int tz = __builtin_ctz(n1);
+                    if (tz > R - 1) tz = R - 1;
+                    for (int sh = 0; sh <= tz; sh++) {                                       // (driver.f90:129-157)
+                        const int j = R - sh;
+                        const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
+                        lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
+                    }
+                    aa = nxt;
+                }
+            };
+            auto proven_run_class = [&](auto cls, int nend) {
+                if (P.beta != 0.0) proven_run(cls, std::true_type(), nend);
+                else proven_run(cls, std::false_type(), nend);
+            };
+            constexpr int TS_RUNS = 2;
+            for (int k = 1; k <= TS_RUNS && n < nts; k++) {
+                int nend = k * N / TS_RUNS;
+                if (nend > nts) nend = nts;
+                if (nend <= n) continue;
+                int cls = UCF_IV_EX_SHORT;
+                if (!settled) {
+                    int known;
+                    cls = zpair_interval_class(P, LC, n == 0 ? 0.0 : aa.x, row[nend - 1].x, P.zD[0], &known, zb);
+                    zph |= known;
+                    if (cls == UCF_IV_EX_SHORT && (zph & UCF_PH_RANGE)) settled = 1;
+                }
+                if (cls == UCF_IV_CS_TAB) proven_run_class(std::integral_constant<int, UCF_IV_CS_TAB>(), nend);
+                else if (cls == UCF_IV_CS_SHORT) proven_run_class(std::integral_constant<int, UCF_IV_CS_SHORT>(), nend);
+                else if (cls == UCF_IV_EX_TAB) proven_run_class(std::integral_constant<int, UCF_IV_EX_TAB>(), nend);
+                else if (cls == UCF_IV_EX_SHORT) proven_run_class(std::integral_constant<int, UCF_IV_EX_SHORT>(), nend);
+                else {
                     for (; n < nend; n++) {
                         const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
                         F.sc.salt = n;
-                        (void)fast_eta<2, true>(P, LC, aa.x, F);
-                        const cplx val = rscale(aa.y, fast_sample_zpair_proven<decltype(cls)::value, decltype(beta)::value>(P, LC, F));
+                        if (!fast_eta_wave_zpair(P, LC, aa.x, F, zph, 1)) { stopped = 1; break; }
+                        const cplx val = rscale(aa.y, fast_sample_zpair(P, LC, F, zph, 1));
                         const int n1 = n + 1;
                         int tz = __builtin_ctz(n1);
                         if (tz > R - 1) tz = R - 1;
-                        for (int sh = 0; sh <= tz; sh++) {                                       // (driver.f90:129-157)
+                        for (int sh = 0; sh <= tz; sh++) {                                   // (driver.f90:129-157)
                             const int j = R - sh;
                             const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
                             lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
                         }
                         aa = nxt;
                     }
-                };
-                auto proven_run_class = [&](auto cls, int nend) {
-                    if (P.beta != 0.0) proven_run(cls, std::true_type(), nend);
-                    else proven_run(cls, std::false_type(), nend);
-                };
-                for (int k = 1; k <= UCF_ZPAIR_TS_RUNS && n < nts; k++) {
-                    int nend = k * N / UCF_ZPAIR_TS_RUNS;
-                    if (nend > nts) nend = nts;
-                    if (nend <= n) continue;
-                    int cls = UCF_IV_EX_SHORT;
-                    if (!settled) {
-                        int known;
-                        cls = zpair_interval_class(P, LC, n == 0 ? 0.0 : aa.x, row[nend - 1].x, P.zD[0], &known, zb);
-                        zph |= known;
-                        if (SETTLE && cls == UCF_IV_EX_SHORT && (zph & UCF_PH_RANGE)) settled = 1;
-                    }
-                    if (cls == UCF_IV_CS_TAB) proven_run_class(std::integral_constant<int, UCF_IV_CS_TAB>(), nend);
-                    else if (cls == UCF_IV_CS_SHORT) proven_run_class(std::integral_constant<int, UCF_IV_CS_SHORT>(), nend);
-                    else if (cls == UCF_IV_EX_TAB) proven_run_class(std::integral_constant<int, UCF_IV_EX_TAB>(), nend);
-                    else if (cls == UCF_IV_EX_SHORT) proven_run_class(std::integral_constant<int, UCF_IV_EX_SHORT>(), nend);
-                    else {
-                        for (; n < nend; n++) {
-                            const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
-                            F.sc.salt = n;
-                            if (!fast_eta_wave_zpair<!MULTI>(P, LC, aa.x, F, zph, 1)) { stopped = 1; break; }
-                            const cplx val = rscale(aa.y, fast_sample_zpair<!MULTI>(P, LC, F, zph, 1));
-                            const int n1 = n + 1;
-                            int tz = __builtin_ctz(n1);
-                            if (tz > R - 1) tz = R - 1;
-                            for (int sh = 0; sh <= tz; sh++) {                                   // (driver.f90:129-157)
-                                const int j = R - sh;
-                                const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
-                                lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
-                            }
-                            aa = nxt;
-                        }
-                        if (stopped) break;
-                    }
-                    UCF_UNIFORM_BLOCK();
+                    if (stopped) break;
                 }
-            } else
-            for (; n < nts; n++) {
-                const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
-                F.sc.salt = n;
-                if (!fast_eta_wave_zpair<!MULTI>(P, LC, aa.x, F, zph, 1)) { stopped = 1; break; }
-                const cplx val = rscale(aa.y, fast_sample_zpair<!MULTI>(P, LC, F, zph, 1));
-                const int n1 = n + 1;
-                int tz = __builtin_ctz(n1);
-                if (tz > R - 1) tz = R - 1;
-                for (int sh = 0; sh <= tz; sh++) {                                               // (driver.f90:129-157)
-                    const int j = R - sh;
-                    const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
-                    lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
-                }
-                aa = nxt;
+                UCF_UNIFORM_BLOCK();
             }
-#if UCF_ZPAIR_INTERVALS
             // The Gauss-Lobatto part, one J0 interval at a time (a part holds whole intervals).  What eta at the interval's two
             // ends settles for all of its nodes in every lane (zpair_interval_class, ucf_fastpath.h) is decided before its first
             // node: a proven interval runs exactly ngl iterations of the one arm of its class -- no test, no ballot, no `zph`:
             // it cannot leave the fast evaluators, so no hand-over starts inside it -- any other interval the loop with the
-            // bits, as it was.  The bits a proven interval establishes for the rest of the part are set, none is cleared.  A
-            // parameter batch keeps the loop with the tests.  The interval's ends come from the table (ENDS), the classifier
-            // tries its bounds before it evaluates eta, and a settled part (SETTLE) classifies nothing any more.
+            // bits.  The bits a proven interval establishes for the rest of the part are set, none is cleared.  The
+            // interval's ends come from the table (`ends`), the classifier tries its bounds before it evaluates eta, and a
+            // settled part classifies nothing any more.
             auto proven_interval = [&](auto cls, auto beta) {
                 for (int i = 0; i < ngl; i++, n++) {
                     const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
@@ -2040,26 +1920,18 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                 if (P.beta != 0.0) proven_interval(cls, std::true_type());
                 else proven_interval(cls, std::false_type());
             };
-            double lob_next = 0.0;                                // ENDS: the lower end of the next interval
-            if constexpr (ENDS) { if (!stopped && n < nlim) lob_next = ends[jj]; }
+            double lob_next = 0.0;                                // the lower end of the next interval
+            if (!stopped && n < nlim) lob_next = ends[jj];
             if (!stopped) while (n < nlim) {
-                double lob, hib;
-                if constexpr (ENDS) {
-                    lob = lob_next;
-                    hib = lob_next = ends[jj + 1];
-                } else {
-                    lob = P.j0z[sv + jj - 1] / rD;
-                    hib = P.j0z[sv + jj] / rD;
-                }
+                const double lob = lob_next;
+                const double hib = lob_next = ends[jj + 1];
                 int cls = UCF_IV_UNPROVEN;
-                if constexpr (!MULTI) {
-                    if (SETTLE && settled) cls = UCF_IV_EX_SHORT;
-                    else {
-                        int known;
-                        cls = zpair_interval_class(P, LC, lob, hib, P.zD[0], &known, zb);
-                        zph |= known;
-                        if (SETTLE && cls == UCF_IV_EX_SHORT && (zph & UCF_PH_RANGE)) settled = 1;
-                    }
+                if (settled) cls = UCF_IV_EX_SHORT;
+                else {
+                    int known;
+                    cls = zpair_interval_class(P, LC, lob, hib, P.zD[0], &known, zb);
+                    zph |= known;
+                    if (cls == UCF_IV_EX_SHORT && (zph & UCF_PH_RANGE)) settled = 1;
                 }
                 if (cls == UCF_IV_CS_TAB) proven_class(std::integral_constant<int, UCF_IV_CS_TAB>());
                 else if (cls == UCF_IV_CS_SHORT) proven_class(std::integral_constant<int, UCF_IV_CS_SHORT>());
@@ -2070,8 +1942,8 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                         const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
                         F.sc.salt = n;
                         const int last = m == ngl - 1;
-                        if (!fast_eta_wave_zpair<!MULTI>(P, LC, aa.x, F, zph, last)) { stopped = 1; break; }
-                        const cplx fz = fast_sample_zpair<!MULTI>(P, LC, F, zph, last);
+                        if (!fast_eta_wave_zpair(P, LC, aa.x, F, zph, last)) { stopped = 1; break; }
+                        const cplx fz = fast_sample_zpair(P, LC, F, zph, last);
                         acc0 = cmake(__builtin_fma(fz.re, aa.y, acc0.re), __builtin_fma(fz.im, aa.y, acc0.im));       // :201-202
                         aa = nxt;
                     }
@@ -2087,43 +1959,20 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                     jj++;
                 }
             }
-#else
-            if (!stopped) for (; n < nlim; n++) {
-                const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
-                F.sc.salt = n;
-                const int last = m == ngl - 1;
-                if (!fast_eta_wave_zpair<!MULTI>(P, LC, aa.x, F, zph, last)) break;
-                const cplx fz = fast_sample_zpair<!MULTI>(P, LC, F, zph, last);
-                acc0 = cmake(__builtin_fma(fz.re, aa.y, acc0.re), __builtin_fma(fz.im, aa.y, acc0.im));           // :201-202
-                if (++m == ngl) {                                                                // (driver.f90:187-203)
-                    const double lob = P.j0z[sv + jj - 1] / rD;
-                    const double hib = P.j0z[sv + jj] / rD;
-                    const double hw = (hib - lob) / 2.0;
-                    const cplx ar = cmul(rscale(hw, acc0), lt_again());
-                    areas[(size_t)jj * UCF_WAVE + lane] = make_double2(ar.re, ar.im);
-                    acc0 = cmake(0.0, 0.0);
-                    m = 0;
-                    jj++;
-                }
-                aa = nxt;
-            }
-#endif
         } else
         for (; n < nlim; n++) {                   // NZC = 2: two depths known at compile time), else accCur[z] in LDS
             const double2 nxt = row[n + 1 < nabs ? n + 1 : n];
             const bool ts = n < N;
             F.sc.salt = n;
-            if (!fast_eta_wave<EF, ZPAIR>(P, LC, aa.x, F)) break;                                       // (every lane is live here)
-            if constexpr (!ZPAIR) fast_common_terms<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, LC, aa.x, need_lay1, F, need_lay3, need_lay12);
+            if (!fast_eta_wave<EF>(P, LC, aa.x, F)) break;                                              // (every lane is live here)
+            fast_common_terms<EF, FOLD, LAY3, LAY1, NOFOLD>(P, LC, aa.x, need_lay1, F, need_lay3, need_lay12);
             const int n1 = n + 1;
             int tz = __builtin_ctz(n1);
             if (tz > R - 1) tz = R - 1;
             for (int z = 0; z < nz; z++) {
                 // val = a*J0(a rD) * f(a,p,z) [* lapTime(p): at the end]                         (lhs.f90:118)
                 // (Gauss-Lobatto part: aa.y carries the node's weight, abscissa_kernel)
-                cplx fz;
-                if constexpr (ZPAIR) fz = fast_sample_zpair<!MULTI>(P, LC, F, zph, 0);
-                else fz = fast_sample_z<EF, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, F, z);
+                const cplx fz = fast_sample_z<EF, FOLD, LAY3, LAY1, NOFOLD>(P, F, z);
                 if (ts) {
                     const cplx val = rscale(aa.y, fz);
                     // tanh-sinh on [0, arg]: abscissa n+1 belongs to level j when 2^(R-j) divides it  (driver.f90:129-157)
@@ -2305,7 +2154,8 @@ finish_kernel(const ucf_dev_params P, int npts, int per_point, int nr, int nsv, 
 // (driver.f90:217-230).
 // For 2M+1 <= 64 the rhombus runs per vector (h and dh of each time) and leaves the continued-fraction
 // coefficients in LDS (h's in the column the input came from, dh's in a second tile); then 2 x UCF_DH_TILE lanes
-// each finish one vector.  The recurrence used to be uniform work repeated by all 64 lanes for every vector.
+// each finish one vector (faithful flavour: dehoog_qd_wave, dehoog_cf_lane).  The fast flavour packs the late steps of up
+// to four rhombi into one wave pass (dehoog_qd_tile_slots) and gives every vector two lanes (dehoog_cf_slot).
 // tile of 4 times and a register budget of 4 waves per SIMD (measured on C2: 2.44 ms at 8 / 2, 2.06 ms at 4 / 4: the
 // rhombus is a dependent chain per vector, resident waves are what hides it)
 #ifndef UCF_DH_TILE
@@ -2342,10 +2192,8 @@ dehoog_tiles_kernel(const ucf_dev_params P, int nt, int nr, int ir0, int nrc, co
             }
             __syncthreads();
             if constexpr (!BIG) {
-#if UCF_FAST && UCF_DH_PACK && UCF_DH_SLOTS
+#if UCF_FAST
                 dehoog_qd_tile_slots(P, lane, ncur, tDv + it0, lds, tileB, pitch, zflag, st);
-#elif UCF_FAST && UCF_DH_PACK
-                dehoog_qd_tile(P, lane, ncur, tDv + it0, lds, tileB, pitch, zflag, st);
 #else
                 for (int tt = 0; tt < ncur; tt++) {
                     const double tD = tDv[it0 + tt];
@@ -2361,7 +2209,7 @@ dehoog_tiles_kernel(const ucf_dev_params P, int nt, int nr, int ir0, int nrc, co
                 }
 #endif
                 __syncthreads();
-#if UCF_FAST && UCF_DH_PACK && UCF_DH_SLOTS
+#if UCF_FAST
                 if (lane < 4 * ncur) {                         // lane = 4 time + 2 (h | dh) + (A | B)
                     const int tt = lane >> 2, which = (lane >> 1) & 1;
                     const int it = it0 + tt;

@@ -70,26 +70,15 @@ UCF_DEV fprim prim(double x, double y, const sc_ctx& sc)
 // the primitives of eta = (x, y) and eta zD, 0 <= zD <= 1, with ONE reciprocal for both real exponentials (batch inversion:
 // 1/E = E_z / (E E_z), 1/E_z = E / (E E_z); a rounding of the product and of each quotient more than two fast_rcp).  Only
 // lanes with x < xcap read the results: x is clamped there, so that E E_z <= e^{xcap (1 + zD)} (e^24 for the water-table
-// closure's xcap = maxexp) cannot overflow in the lanes that do not
-UCF_DEV void prim_pair(double x, double y, double zD, double xcap, const sc_ctx& sc, fprim* f, fprim* fz)
-{
-    const double xc = fmin(x, xcap);
-    const double xz = xc * zD;
-    const double e = exp_tab_(xc, sc), ez = exp_tab_(xz, sc);
-    const double r = fast_rcp(e * ez);
-    *f = prim_from_e<true>(xc, xc, e, r * ez, y, sc);
-    *fz = prim_from_e<true>(xz, xz, ez, r * e, y * zD, sc);
-}
-// the same for the folded water-table kernel's own sample (fast_sample_zpair).  fmin() comes back as three instructions: the
-// compiler first canonicalises both operands (v_max_f64 of a value with itself, for the sake of signalling NaNs), one of
-// them the loop-invariant cap.  x has passed fast_eta_wave's range test, so it is a number, and v_min_f64 alone returns the
-// same bits.  UNI: xcap is wave-uniform (one plan per launch) and is read from its SGPR pair; a parameter batch keeps fmin
-template <bool UNI>
+// closure's xcap = maxexp) cannot overflow in the lanes that do not.  For the folded water-table kernel's own sample
+// (fast_sample_zpair).  The clamp is v_min_f64 alone: fmin() comes back as three instructions, because the compiler first
+// canonicalises both operands (v_max_f64 of a value with itself, for the sake of signalling NaNs), one of them the
+// loop-invariant cap.  x has passed fast_eta_wave's range test, so it is a number, and v_min_f64 returns the same bits.
+// xcap is wave-uniform (one plan per launch) and is read from its SGPR pair
 UCF_DEV void prim_pair_min(double x, double y, double zD, double xcap, const sc_ctx& sc, fprim* f, fprim* fz)
 {
     double xc;
-    if constexpr (UNI) asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(xcap));
-    else xc = fmin(x, xcap);
+    asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(xcap));
     const double xz = xc * zD;
     const double e = exp_tab_(xc, sc), ez = exp_tab_(xz, sc);
     const double r = fast_rcp(e * ez);
@@ -133,7 +122,7 @@ UCF_DEV cplx expneg_small(double x, double y, const sc_ctx& sc)
     sincos_small_(y, sc, &sn, &cs);
     return cmake(ei * cs, -(ei * sn));
 }
-// prim_pair_min<true> for 0 <= y < UCF_SC_SMALL (and so 0 <= y zD < UCF_SC_SMALL): prim_from_e<true> with both sin/cos in
+// prim_pair_min for 0 <= y < UCF_SC_SMALL (and so 0 <= y zD < UCF_SC_SMALL): prim_from_e<true> with both sin/cos in
 // the short form, operation for operation
 UCF_DEV void prim_pair_small(double x, double y, double zD, double xcap, const sc_ctx& sc, fprim* f, fprim* fz)
 {
@@ -207,13 +196,9 @@ UCF_DEV lane_consts make_lane_consts(const ucf_dev_params& P, cplx p, cplx lt)
 struct fast_common {
     sc_ctx sc;           // sin/cos table in LDS + constants (sincos_tab_), set once per kernel; sc.salt = the loop counter
     cplx th, eta, ff1, ff2, inv_she, she, che, top, g3, inv_den, ex1;   // ex1 = exp(-eta)
-    cplx chz0;           // ZPAIR: cosh(eta zD) of the launch's one depth (valid when any_small)
     fprim p1;            // primitive of eta itself (valid when have_p1)
     int have_p1;         // (wave-uniform flags are ints: a uniform bool that crosses a join is rebuilt through VALU selects)
     cplx mn_uod;         // MN-Malama: u / Delta_0                                                     (:437-439)
-#ifdef UCF_SINGLE_RCP    /* investigation build only (tools/dbg_single_rcp.py): NOT the product */
-    cplx q, den;
-#endif
     cplx fd_s1;          // FD: sigma(1)
     cplx top3, fd_s13;   // the same two for depths above the screen top (cancellation-free water-table value)
     bool small_eta, fd_use, fd_use3;
@@ -234,11 +219,6 @@ UCF_DEV double fast_scale(const ucf_dev_params& P)
     return (FAMILY == 2 && P.model == 4) ? 2.0 : 2.0 * P.inv_bD;
 }
 
-// UCF_ZPAIR_HALFK=0 (A/B builds): the folded water-table kernel with one depth per launch forms 0.5 (|q| + Re q) / kappa with
-// 1 / kappa and a multiplication by 0.5 of its own, as it did before the plan carried 0.5 / kappa
-#ifndef UCF_ZPAIR_HALFK
-#define UCF_ZPAIR_HALFK 1
-#endif
 // theta and eta of this abscissa.  Returns false (for this lane) if the fast evaluation is not applicable:
 // a cosh/sinh could overflow, or the argument of a sin/cos (|Im eta| times a factor <= 1) leaves the range of
 // the two-stage Cody-Waite reduction.
@@ -249,9 +229,6 @@ UCF_DEV bool fast_eta(const ucf_dev_params& P, const lane_consts& L, double a, f
 {
     const double a2 = a * a;
     const cplx q = caddr(L.p, a2);
-#ifdef UCF_SINGLE_RCP
-    S.q = q;
-#endif
     // PAIR: |q| and 1/|q|^2 from one seed (rsq_pair): |q|^2 is normal wherever the separate reciprocal of it was, and above
     // 4e307 (|q| > 6e153) eta = sqrt(q/kappa) passes the wave's test only for kappa > 1e148
     double mq = 0.0;
@@ -264,20 +241,17 @@ UCF_DEV bool fast_eta(const ucf_dev_params& P, const lane_consts& L, double a, f
         S.th = cmake(q.re * r, -(q.im * r));
     }
     if (FAMILY == 0) return q.re > 0.0;                           // Theis is that reciprocal and nothing else
-#if UCF_ZPAIR_HALFK
     if (PAIR) {   // eta = sqrt(q/kappa) as below with 0.5 / kappa from the plan: (|q| + Re q) (0.5 / kappa) is the fma that
-        // 0.5 (|q| / kappa + Re q / kappa) was, on operands scaled by 2^-1 -- every rounding commutes with that scaling short
+        // 0.5 (|q| / kappa + Re q / kappa) is, on operands scaled by 2^-1 -- every rounding commutes with that scaling short
         // of the subnormals, which |q| / kappa is nowhere near inside the fast range: the same bits, one multiplication less
         const double qi = q.im * P.inv_kappa;
         double r, hr;
         sqrt_hrsqrt(__builtin_fma(q.re, P.half_inv_kappa, mq * P.half_inv_kappa), &r, &hr);
         S.eta = cmake(r, qi * hr);
-    } else
-#endif
-    {   // eta = sqrt(q/kappa), Re q > 0                                                         (:69,172)
+    } else {      // eta = sqrt(q/kappa), Re q > 0                                               (:69,172)
         const double qr = q.re * P.inv_kappa, qi = q.im * P.inv_kappa;
         double r, hr;
-        const double d = PAIR ? mq * P.inv_kappa : sqrt_only(__builtin_fma(qr, qr, qi * qi));   // |q/kappa|
+        const double d = sqrt_only(__builtin_fma(qr, qr, qi * qi));                             // |q/kappa|
         sqrt_hrsqrt(0.5 * (d + qr), &r, &hr);
         S.eta = cmake(r, qi * hr);
     }
@@ -310,17 +284,7 @@ UCF_DEV bool fast_eta_wave(const ucf_dev_params& P, const lane_consts& L, double
 // intervals ascend, so the last node of an interval only.  The computed eta follows the true one to a few ulp, not
 // monotonically to the last bit (the nodes of tanh-sinh cluster at both ends of its interval: neighbours may differ by an ulp
 // of q), so a bit is only set by a compare with a margin no rounding can bridge, next to the compare that decides this
-// abscissa as before.  A NaN sets nothing.  All bits are cleared at the start of a part.
-// UCF_ZPAIR_PHASES (investigation builds: the two halves measured on their own): bit 0 = the short
-// sin/cos form, bit 1 = the range and form tests carried across abscissae.
-#ifndef UCF_ZPAIR_PHASES
-#define UCF_ZPAIR_PHASES 3
-#endif
-// UCF_ZPAIR_INTERVALS=0 (A/B builds): no J0 interval is decided as a whole (zpair_interval_class, below), every one runs the
-// loop with these bits
-#ifndef UCF_ZPAIR_INTERVALS
-#define UCF_ZPAIR_INTERVALS 1
-#endif
+// abscissa.  A NaN sets nothing.  All bits are cleared at the start of a part.
 enum {
     UCF_PH_RANGE = 1,    // Re q > 0 and Re eta <= fast_eta_max in every lane up to the part's last abscissa (zpair_part_phase)
     UCF_PH_IM = 2,       // |Im eta| < fast_im_max / 2 in every lane: in range from here on
@@ -334,17 +298,13 @@ enum {
 // off: no bit)
 UCF_DEV int zpair_part_phase(const ucf_dev_params& P, const lane_consts& L, double a_max)
 {
-    if (!(UCF_ZPAIR_PHASES & 2)) return 0;
     const double lim = 0.99 * P.fast_eta_max;
     const bool ok = (L.p.re > 0.0) & (lim > 0.0) & ((__builtin_fma(a_max, a_max, fabs(L.p.re) + fabs(L.p.im)) * P.inv_kappa) < lim * lim);
     return __builtin_amdgcn_ballot_w64(!ok) == 0 ? UCF_PH_RANGE : 0;
 }
-// fast_eta_wave<2, true> that does not repeat what `ph` already answers.  UNI = false (a parameter batch: the plan's limits
-// differ by lane): exactly fast_eta_wave
-template <bool UNI>
+// fast_eta_wave<2, true> that does not repeat what `ph` already answers (one plan per launch: its limits are wave-uniform)
 UCF_DEV bool fast_eta_wave_zpair(const ucf_dev_params& P, const lane_consts& L, double a, fast_common& S, int& ph, int may_set)
 {
-    if constexpr (!UNI) return fast_eta_wave<2, true>(P, L, a, S);
     (void)fast_eta<2, true>(P, L, a, S);
     unsigned long long bad = 0;
     if (!(ph & UCF_PH_RANGE)) {
@@ -356,7 +316,7 @@ UCF_DEV bool fast_eta_wave_zpair(const ucf_dev_params& P, const lane_consts& L, 
     if (!(ph & UCF_PH_IM)) {
         const double ai = fabs(S.eta.im);
         bad |= __builtin_amdgcn_ballot_w64(!(ai < P.fast_im_max));
-        if ((UCF_ZPAIR_PHASES & 2) && may_set && __builtin_amdgcn_ballot_w64(!(ai < 0.5 * P.fast_im_max)) == 0) ph |= UCF_PH_IM;
+        if (may_set && __builtin_amdgcn_ballot_w64(!(ai < 0.5 * P.fast_im_max)) == 0) ph |= UCF_PH_IM;
         UCF_UNIFORM_BLOCK();
     }
     return bad == 0;
@@ -375,13 +335,11 @@ UCF_DEV bool fast_eta_wave_zpair(const ucf_dev_params& P, const lane_consts& L, 
 // LAY3 = false: the launcher knows that no depth of the call lies above the screen top; LAY1 = false: none below its bottom
 // (the usual piezometer beside the screen: the terms of the layer below -- exp(-eta), g3 -- are then not even allocated:
 //  18 -> 14 spilled VGPRs in the partially penetrating water-table kernel, C2pp 87.9 -> 85.7 ms, C4 236.2 -> 230.3)
-// ZPAIR (FOLD, water-table family, one depth per launch): the primitive of eta zD, the only other one such a sample takes, is
-// formed here together with that of eta, from one reciprocal (prim_pair), and fast_sample_z reads its cosh from S.chz0
-template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false, bool ZPAIR = false>
+// (The folded water-table kernel with one depth per launch does not come here: fast_sample_zpair, below, is its whole sample.)
+template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false>
 UCF_DEV void fast_common_terms(const ucf_dev_params& P, const lane_consts& L, double a, bool need_lay1_in, fast_common& S,
                                bool need_lay3_in = false, bool need_lay12 = true)
 {
-    static_assert(!ZPAIR || (FOLD && FAMILY == 2), "ZPAIR: folded water-table kernels only");
     const double a2 = a * a;
     if (FAMILY == 0) return;
     if (FAMILY == 3) {
@@ -410,14 +368,7 @@ UCF_DEV void fast_common_terms(const ucf_dev_params& P, const lane_consts& L, do
     const bool need_p1 = (hantush && (!(z1 && z2) || need_lay1)) || FAMILY == 4 || (FAMILY == 2 && S.any_small);
     S.have_p1 = (need_p1 && !z2) ? 1 : 0;      // kept only where fast_hantush_z derives the primitive of eta (1 - zD) from it
     fprim p1;
-    if (ZPAIR && need_p1) {             // (FOLD: need_p1 = any_small, and neither S.p1 nor ex1 is wanted)
-        fprim pz;
-        prim_pair(S.eta.re, S.eta.im, P.zD[0], P.maxexp, S.sc, &p1, &pz);
-        S.chz0 = pcosh(pz);
-        S.che = pcosh(p1);
-        S.she = psinh(p1);
-        S.ex1 = cmake(0.0, 0.0);
-    } else if (need_p1) {
+    if (need_p1) {
         p1 = prim<true>(S.eta.re, S.eta.im, S.sc);
         if (!z2) S.p1 = p1;
         S.che = pcosh(p1);
@@ -488,21 +439,6 @@ UCF_DEV void fast_common_terms(const ucf_dev_params& P, const lane_consts& L, do
             if (S.small_eta) S.inv_den = cinv_plain(cfma(xi, S.she, S.che));
             else S.inv_den = cinv_plain(radd(1.0, xi));
         }
-#ifdef UCF_SINGLE_RCP
-        // the rejected form: where the Hantush factor and the water-table value are both 1/q the sample
-        // (1/q)(1 - f_z / den) is taken as (den - f_z) / (q den) -- one reciprocal, no 1/q of its own
-        if (FOLD || !hantush) {
-            cplx den;
-            if (P.beta != 0.0) {
-                const cplx one_bex = radd(1.0, cmul(rscale(P.beta, S.eta), xi));
-                den = S.small_eta ? cfma(one_bex, S.che, cmul(xi, S.she)) : cadd(one_bex, xi);
-            } else {
-                den = S.small_eta ? cfma(xi, S.she, S.che) : radd(1.0, xi);
-            }
-            S.den = den;
-            S.inv_den = cinv_auto(cmul(S.q, den));
-        }
-#endif
     }
     if (FAMILY == 4) {
         // Mishra/Neuman finite-difference vadose zone (:444-544): sigma(1) of the tridiagonal system by
@@ -545,7 +481,7 @@ UCF_DEV bool fast_prepare(const ucf_dev_params& P, const lane_consts& L, double 
 }
 
 // Hantush factor at depth zD (:133-202); chz = cosh(eta*zD) is returned for the closure
-template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false, bool ZPAIR = false>
+template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false>
 UCF_DEV cplx fast_hantush_z(const ucf_dev_params& P, const fast_common& S, double zD, int lay_in, cplx* chz_out,
                             cplx* exz_out)
 {
@@ -554,8 +490,7 @@ UCF_DEV cplx fast_hantush_z(const ucf_dev_params& P, const fast_common& S, doubl
     const bool need_chz = (lay == 1) || !z1 || (FAMILY == 2 && S.any_small) || FAMILY == 4;
     cplx chz = cmake(1.0, 0.0);
     fprim pz;
-    if (ZPAIR) { if (need_chz) chz = S.chz0; }                   // (FOLD: pz has no other use)
-    else if (need_chz) { pz = prim<true>(S.eta.re * zD, S.eta.im * zD, S.sc); chz = pcosh(pz); }  // (0 <= zD <= 1 on this path)
+    if (need_chz) { pz = prim<true>(S.eta.re * zD, S.eta.im * zD, S.sc); chz = pcosh(pz); }  // (0 <= zD <= 1 on this path)
     *chz_out = chz;
     cplx udp;
     if (lay == 1) {
@@ -602,7 +537,7 @@ UCF_DEV cplx fast_hantush_z(const ucf_dev_params& P, const fast_common& S, doubl
     return res;
 }
 
-template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false, bool ZPAIR = false>
+template <int FAMILY, bool FOLD = false, bool LAY3 = true, bool LAY1 = true, bool NOFOLD = false>
 UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz)
 {
     const double zD = P.zD[iz];
@@ -622,15 +557,12 @@ UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz
     cplx u;
     if (!NOFOLD && P.model == 4) {
         u = S.th;
-        if (S.any_small) chz = ZPAIR ? S.chz0 : pcosh(prim(S.eta.re * zD, S.eta.im * zD, S.sc));
+        if (S.any_small) chz = pcosh(prim(S.eta.re * zD, S.eta.im * zD, S.sc));
         if (S.any_large) { const double c = 1.0 - zD; exz = expneg_direct(S.eta.re * c, S.eta.im * c, S.sc); }
     } else {
-        u = fast_hantush_z<2, FOLD, LAY3, LAY1, NOFOLD, ZPAIR>(P, S, zD, lay, &chz, &exz);
+        u = fast_hantush_z<2, FOLD, LAY3, LAY1, NOFOLD>(P, S, zD, lay, &chz, &exz);
         if (LAY1 && S.any_large && lay == 1) { const double c = 1.0 - zD; exz = expneg_direct(S.eta.re * c, S.eta.im * c, S.sc); }
     }
-#ifdef UCF_SINGLE_RCP
-    if (FOLD || (!NOFOLD && P.model == 4)) return cmul(csub(S.den, S.small_eta ? chz : exz), S.inv_den);
-#endif
     const cplx top = (!FOLD && LAY3 && (NOFOLD || P.model != 4) && lay == 3) ? S.top3 : S.top;
     // u - top (cosh(eta zD) | exp(eta (zD - 1))) / den  (:85-87 | :89-91); a wave that is on one form only (the usual case)
     // does not select per lane
@@ -660,14 +592,15 @@ UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz
 // the angle addition (SMALLY; a branch of its own per form, so that nothing joins inside an arm).  Im p >= 0
 // (invlap.f90:168, m >= 0), so Im eta and every argument is >= +0, as sincos_small_ wants.  `ph` (UCF_PH_*) is what the
 // wave has established for the rest of its part: the argument test is made (where a bit may be set: `may_set`, above)
-// until it first holds, the form test until every lane is past maxexp by a margin.  A wave with lanes on both forms, and a parameter batch (UNI = false), do what they did.
+// until it first holds, the form test until every lane is past maxexp by a margin.  A wave with lanes on both forms takes
+// the general code.  (One plan per launch: a parameter batch never folds.)
 // KB: what the caller knows of beta (wave-uniform): -1 nothing (tested here), 0 beta = 0, 1 beta != 0
-template <bool UNI, bool SMALLY, int KB = -1>
+template <bool SMALLY, int KB = -1>
 UCF_DEV void zpair_arm_small(const ucf_dev_params& P, const lane_consts& L, const fast_common& S, double zD, cplx* g, cplx* den)
 {
     fprim p1, pz;
     if (SMALLY) prim_pair_small(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
-    else prim_pair_min<UNI>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
+    else prim_pair_min(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
     *g = pcosh(pz);
     const cplx che = pcosh(p1), she = psinh(p1);
     const cplx xi = cmul(S.eta, L.xifac);
@@ -682,47 +615,45 @@ UCF_DEV void zpair_arm_large(const ucf_dev_params& P, const lane_consts& L, cons
     if (KB < 0 ? P.beta != 0.0 : KB != 0) *den = cadd(radd(1.0, cmul(rscale(P.beta, S.eta), xi)), xi);
     else *den = radd(1.0, xi);
 }
-template <bool UNI>
 UCF_DEV cplx fast_sample_zpair(const ucf_dev_params& P, const lane_consts& L, const fast_common& S, int& ph, int may_set)
 {
-    constexpr bool SHORT = UNI && (UCF_ZPAIR_PHASES & 1);
     const double zD = P.zD[0];
     // the form the wave is on: 0 = cosh/sinh in every lane, 1 = lanes on both, 2 = exponential in every lane
     int form = 2;
-    if (!UNI || !(ph & UCF_PH_LARGE)) {
+    if (!(ph & UCF_PH_LARGE)) {
         const bool small_eta = S.eta.re < P.maxexp;                                             // :84
         const bool any_small = __builtin_amdgcn_ballot_w64(small_eta) != 0, any_large = __builtin_amdgcn_ballot_w64(!small_eta) != 0;
         form = !any_large ? 0 : (any_small ? 1 : 2);
-        // (with the interval loops the limit is formed where it is wanted, once per J0 interval at most: hoisted out of the
-        //  item loop it was the one value the abscissa loop read back from scratch)
+        // (the limit is formed where it is wanted, once per J0 interval at most: hoisted out of the item loop it is the one
+        //  value the abscissa loop reads back from scratch)
         double mx = P.maxexp;
-        if (UCF_ZPAIR_INTERVALS) asm volatile("" : "+s"(mx));
-        if (UNI && (UCF_ZPAIR_PHASES & 2) && may_set && form == 2 && __builtin_amdgcn_ballot_w64(!(S.eta.re > mx * (1.0 + 0x1p-20))) == 0) ph |= UCF_PH_LARGE;
+        asm volatile("" : "+s"(mx));
+        if (may_set && form == 2 && __builtin_amdgcn_ballot_w64(!(S.eta.re > mx * (1.0 + 0x1p-20))) == 0) ph |= UCF_PH_LARGE;
         UCF_UNIFORM_BLOCK();
     }
     // (xi = eta alphaD / p ... (:70-75) is formed in each arm AFTER the primitives: four registers less while they are evaluated;
     //  |den| needs no exponent scaling: fast_common_terms)
     cplx den, g;
     if (form == 0) {
-        if (SHORT && may_set && !(ph & UCF_PH_YS)) {
+        if (may_set && !(ph & UCF_PH_YS)) {
             if (__builtin_amdgcn_ballot_w64(!(fabs(S.eta.im) < UCF_SC_SMALL)) == 0) ph |= UCF_PH_YS | UCF_PH_YL;
             UCF_UNIFORM_BLOCK();
         }
-        if (SHORT && (ph & UCF_PH_YS)) {
-            zpair_arm_small<UNI, true>(P, L, S, zD, &g, &den);
+        if (ph & UCF_PH_YS) {
+            zpair_arm_small<true>(P, L, S, zD, &g, &den);
             UCF_UNIFORM_BLOCK();
         } else {
-            zpair_arm_small<UNI, false>(P, L, S, zD, &g, &den);
+            zpair_arm_small<false>(P, L, S, zD, &g, &den);
             UCF_UNIFORM_BLOCK();
         }
     } else if (form == 2) {
         const double c = 1.0 - zD;
         const double x = S.eta.re * c, y = S.eta.im * c;
-        if (SHORT && may_set && !(ph & UCF_PH_YL)) {
+        if (may_set && !(ph & UCF_PH_YL)) {
             if (__builtin_amdgcn_ballot_w64(!(fabs(y) < UCF_SC_SMALL)) == 0) ph |= UCF_PH_YL;
             UCF_UNIFORM_BLOCK();
         }
-        if (SHORT && (ph & UCF_PH_YL)) {
+        if (ph & UCF_PH_YL) {
             zpair_arm_large<true>(P, L, S, x, y, &g, &den);
             UCF_UNIFORM_BLOCK();
         } else {
@@ -732,7 +663,7 @@ UCF_DEV cplx fast_sample_zpair(const ucf_dev_params& P, const lane_consts& L, co
     } else {
         const bool small_eta = S.eta.re < P.maxexp;
         fprim p1, pz;
-        prim_pair_min<UNI>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
+        prim_pair_min(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
         const cplx chz = pcosh(pz), che = pcosh(p1), she = psinh(p1);
         const cplx xi = cmul(S.eta, L.xifac);
         if (P.beta != 0.0) {
@@ -766,19 +697,11 @@ enum {
     UCF_IV_EX_TAB = 3,       // exponential form in every lane at every node, sin/cos from the table
     UCF_IV_EX_SHORT = 4      // ... from sincos_small_
 };
-// UCF_ZPAIR_UNITS (bit mask; A/B builds measure each part on its own; 0 = none of it):
-//   1  the ends of the J0 intervals come from the table abscissa_kernel writes behind the rows (lane = time layout: the
-//      radius is wave-uniform), one scalar load per interval, instead of two IEEE divisions
-//   2  a unit is first tried with the bounds below (zpair_unit_bounds), and only an undecided one pays for the two
-//      fast_eta evaluations of the exact classifier
-//   4  the tanh-sinh part is classified in UCF_ZPAIR_TS_RUNS runs of nodes, and a proven run takes a loop without tests
-#ifndef UCF_ZPAIR_UNITS
-#define UCF_ZPAIR_UNITS 7
-#endif
-#ifndef UCF_ZPAIR_TS_RUNS
-#define UCF_ZPAIR_TS_RUNS 2
-#endif
-enum { UCF_ZU_TABLE = 1, UCF_ZU_BOUNDS = 2, UCF_ZU_TS_RUNS = 4 };
+// What the units (the J0 intervals, and the runs of tanh-sinh nodes that integrate_kernel classifies like them) cost to decide:
+//   - the ends of the J0 intervals come from the table abscissa_kernel writes behind the rows (lane = time layout: the
+//     radius is wave-uniform), one scalar load per interval, instead of two IEEE divisions
+//   - a unit is first tried with the bounds below (zpair_unit_bounds), and only an undecided one pays for the two
+//     fast_eta evaluations of the exact classifier
 static_assert(UCF_ZB_SC_SMALL == UCF_SC_SMALL, "the plan's short sin/cos limit (ucf_launch_plan.h) is sincos_small_'s");
 // The same decision from bounds, without eta.  For a lane with Re p > 0: q = p + a^2 has Re q = Re p + a^2 > 0 and
 // Im q = Im p, (Re eta)^2 = (|q| + Re q) / (2 kappa) and Re q <= |q| <= Re q + |Im q|, so
@@ -819,15 +742,12 @@ UCF_DEV int zpair_unit_bounds(const double* __restrict__ zb, const lane_consts& 
     return -1;
 }
 // lob < hib: the interval's ends.  *ph_proven: the UCF_PH_* bits that hold from lob on (every later abscissa of the part
-// lies above it), whatever the class
+// lies above it), whatever the class; `zb` the limits of zpair_unit_bounds
 UCF_DEV int zpair_interval_class(const ucf_dev_params& P, const lane_consts& L, double lob, double hib, double zD, int* ph_proven,
-                                 const double* __restrict__ zb = nullptr)
+                                 const double* __restrict__ zb)
 {
-    if (UCF_ZPAIR_UNITS & UCF_ZU_BOUNDS) {
-        const int c = zpair_unit_bounds(zb, L, lob, hib, ph_proven);
-        if (c >= 0) return c;
-        UCF_UNIFORM_BLOCK();
-    }
+    if (const int c = zpair_unit_bounds(zb, L, lob, hib, ph_proven); c >= 0) return c;
+    UCF_UNIFORM_BLOCK();
     *ph_proven = 0;
     fast_common T;                                   // (eta only: nothing else of it is read)
     (void)fast_eta<2, true>(P, L, hib, T);
@@ -858,7 +778,7 @@ UCF_DEV cplx fast_sample_zpair_proven(const ucf_dev_params& P, const lane_consts
     const double zD = P.zD[0];
     cplx den, g;
     if (CLS == UCF_IV_CS_TAB || CLS == UCF_IV_CS_SHORT) {
-        zpair_arm_small<true, CLS == UCF_IV_CS_SHORT, BETA ? 1 : 0>(P, L, S, zD, &g, &den);
+        zpair_arm_small<CLS == UCF_IV_CS_SHORT, BETA ? 1 : 0>(P, L, S, zD, &g, &den);
     } else {
         const double c = 1.0 - zD;
         const double x = S.eta.re * c, y = S.eta.im * c;
