@@ -584,6 +584,99 @@ int ucf_field_forecast(ucf_field* field, ucf_plan* plan, int npar, const int* id
                        double* se, double* dse          /*[nt][nloc][nz]; NULL ok; not NULL needs cov*/,
                        double* s_all, double* ds_all    /*[1 + 2 npar][nt][nloc][nz]; NULL ok*/,
                        long long* nbad /*[2]: s, ds; NULL ok*/, ucf_stats* stats /*NULL ok*/);
+
+/* ---- ensembles: a forecast linearises in ln theta around one point; over the width of a real posterior the drawdown of an
+ * unconfined aquifer is not linear in ln Sy, ln kappa or ln Ss.  An ensemble call maps the field under nens parameter sets --
+ * draws from cov (ucf_field_ensemble_draw), a Latin hypercube, the theta rows of a multi-start ucf_fit_lm: any source is legal
+ * -- keeps all member maps of s and of ds in device memory and reduces them there over the member axis: per output the number of
+ * finite members, their mean, standard deviation, extremes, order statistics (the 5 % / 50 % / 95 % maps) and the fraction of
+ * members above a drawdown limit.  Only the maps that are asked for cross the bus.
+ *   members      member m is ucf_fit_perturb(&plan->P, npar, ids, thetas[m]), m = 0 .. nens-1.
+ *   plan         as in ucf_field_forecast: it supplies the base parameters, the device, the numerical settings and the flavour
+ *                and is never modified; the members run on the field's ONE scratch plan (made from member 0 where the field
+ *                has none that ucf_plan_update can refresh), refreshed with ucf_plan_update for every member.
+ *   per member   for m = 0 .. nens-1 in this order exactly what ucf_field_forecast runs per set: the launch arrays that
+ *                ucf_field_group_from_params(field, member m, g, ...) states, one grid call per group, then
+ *                field_superpose_kernel with that member's Hc into slot m of two device buffers [nens][nout],
+ *                nout = nt nloc nz.  Slot m has the bits of ucf_field_drawdown on a fresh field and a fresh plan of member m.
+ *                Outputs are always dimensional.  Every member is validated, and the launch arrays of every member are formed
+ *                and checked once, before the first launch (a refused member: that status, ucf_last_error names the member and
+ *                its parameter values); they are formed again member by member for the launches, so that the host never holds
+ *                the arrays of more than one member.
+ *   reduction    two kernels, once on the s slots (a = the s slots) and once on the ds slots, every operation rounded on its
+ *                own (no FMA contraction).  For output e: F = the members m with a[m][e] finite, in member order, n = |F|;
+ *                members that are not finite take part in nothing below; the Wynn sentinel is finite and takes part.
+ *                field_ensemble_moments_kernel, one thread per output:
+ *                    nfin[e] = n;
+ *                    acc = +0.0;  for m in F:  acc = acc + a[m][e];        mean[e] = acc / (double)n          (n = 0: NaN)
+ *                    ss = +0.0;   for m in F:  d = a[m][e] - mean[e];  ss = ss + d * d;
+ *                    sd[e] = sqrt(ss / (double)(n - 1))                                                      (n < 2: NaN)
+ *                    min[e]: the first member of F, then replaced by every later v with v < min;              (n = 0: NaN)
+ *                    max[e]: the first member of F, then replaced by every later v with v >= max;             (n = 0: NaN)
+ *                            -- so min is x_0 and max is x_{n-1} of the order below, signs of zero included (the level 0
+ *                            is x_0 + 0 * (x_1 - x_0): min in value, but a -0.0 becomes +0.0; the level 1 is max bit for bit);
+ *                    pexc[l][e] = (double)#{m in F : a[m][e] > limit[l]} / (double)n, the comparison strict   (n = 0: NaN)
+ *                field_ensemble_quantile_kernel: x_0 .. x_{n-1} are the values of F in ascending order, ties broken by member
+ *                index: the value of member m has rank #{m' in F : v' < v or (v' == v and m' < m)} -- a stable sort; -0.0 and
+ *                +0.0 are equal and keep their member order.  For level p = q[i]:
+ *                    pos = p * (double)(n - 1);   k = floor(pos);
+ *                    quant[i][e] = x_{n-1}                        where k >= n - 1,
+ *                                  x_k + g * (x_{k+1} - x_k)      with g = pos - (double)k otherwise               (n = 0: NaN)
+ *                (the `linear` rule of the textbooks, in one fixed operation order).
+ *                nbad[0] (s) and nbad[1] (ds) count the outputs with n < nens (a ballot per wave, one integer atomic per wave, no
+ *                floating-point atomics: a call repeated gives the same bits).  The payload of a NaN is not part of the contract.
+ *   outputs      per map one ucf_ensemble_maps; every pointer may be NULL, and a NULL struct asks for nothing of that map (a
+ *                NULL ds still evaluates the same members: the evaluators write dh beside every h).  pexc is formed from s.
+ *                `all` [nens][nout] are the member maps as they stand.  stats: summed over all members and groups.
+ * The slots, the statistics' staging and the levels / limits are buffers of the field, grown on demand, kept and counted in
+ * ucf_field_alloc_count: a repeated call of the same or a smaller size allocates nothing.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything ucf_field_drawdown
+ * checks (its s, ds aside); NULL ids or thetas; npar outside 1..UCF_FIT_MAX_PAR; nens outside 1..UCF_ENSEMBLE_MAX; a theta that
+ * is not positive and finite (the member is named); nq or nlim outside 0..UCF_ENSEMBLE_MAX_Q, or positive with a NULL q /
+ * limit; a q outside [0,1] or not finite; a limit that is not finite; quant asked for with nq = 0; pexc asked for with nlim = 0;
+ * nens nout beyond what one buffer may hold.  With a NULL plan UCF_ERR_NO_DEVICE comes before "NULL plan"; with a plan the
+ * checks of ucf_fit_perturb and of every member run before any launch. */
+#define UCF_ENSEMBLE_MAX 1024      /* members of one ensemble call */
+#define UCF_ENSEMBLE_MAX_Q 16      /* quantile levels, and drawdown limits, per call */
+/* per map (one for s, one for ds); every pointer may be NULL */
+typedef struct ucf_ensemble_maps {
+    double* mean;  double* sd;  double* min;  double* max;   /* [nout] */
+    double* quant;                                           /* [nq][nout] */
+    double* all;                                             /* [nens][nout]: the member maps */
+    int*    nfin;                                            /* [nout]: members finite there */
+} ucf_ensemble_maps;
+int ucf_field_ensemble(ucf_field* field, ucf_plan* plan, int npar, const int* ids,
+                       int nens, const double* thetas /*[nens][npar]*/,
+                       int nz, const double* z,
+                       int nq, const double* q /*[nq], each in [0,1]*/,
+                       int nlim, const double* limit /*[nlim], dimensional drawdowns*/,
+                       const ucf_ensemble_maps* s, const ucf_ensemble_maps* ds /*either may be NULL*/,
+                       double* pexc /*[nlim][nout], of s; NULL ok*/,
+                       long long* nbad /*[2]: s, ds; NULL ok*/, ucf_stats* stats /*NULL ok*/);
+/* host only, no GPU: nens members drawn from the log-normal distribution that a fit states with theta and cov (in ln theta).
+ *   member m     thetas[m][j] = theta[j] * exp(sum_{k<=j} L[j][k] zeta[m][k]),  the sum from +0.0 in ascending k, one product and
+ *                one exp per value;
+ *   L            the lower Cholesky factor of cov, L L' = cov, by the factorisation of ucf_fit_solve_step without damping: for
+ *                j = 0 .. npar-1:  d = c_jj;  d = d - L_jk * L_jk, k = 0 .. j-1;  L_jj = sqrt(d);  then for i > j:  v = c_ij;
+ *                v = v - L_ik * L_jk, k = 0 .. j-1;  L_ij = v / L_jj.  UCF_ERR_SINGULAR where a d is not positive and finite;
+ *   zeta         standard normal deviates.  One splitmix64 stream for the whole call: state = seed; every draw is
+ *                    state += 0x9E3779B97F4A7C15;  x = state;  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9;
+ *                    x = (x ^ (x >> 27)) * 0x94D049BB133111EB;  x = x ^ (x >> 31)           (64-bit unsigned, wrapping)
+ *                and the uniform of a draw is u = ((double)(x >> 11) + 0.5) * 2^-53, in (0, 1).  Draws are taken in (member,
+ *                parameter pair) order: for m = 0 .. nens-1, for i = 0, 2, 4 .. < npar: u1, then u2;
+ *                    rad = sqrt(-2.0 * log(u1));   ang = 6.283185307179586 * u2   (the double nearest 2 pi);
+ *                    zeta[m][i] = rad * cos(ang);   zeta[m][i+1] = rad * sin(ang), discarded where i + 1 = npar.
+ * The checks are those of ucf_field_forecast on theta and cov (npar, NULL, theta positive and finite, cov finite, symmetric,
+ * no negative variance) and nens >= 1. */
+int ucf_field_ensemble_draw(int npar, const double* theta, const double* cov /*[npar][npar], ln theta*/,
+                            int nens, unsigned long long seed, double* thetas /*[nens][npar]*/);
+/* the two reduction kernels exactly as ucf_field_ensemble launches them (the same launchers, the same choice of tile), on caller
+ * data a[nens][nout]: a is uploaded, the statistics that `out` asks for (out->all is ignored; out may be NULL), pexc [nlim][nout]
+ * and nbad[0] are copied back.  The checks of ucf_field_ensemble on nens, nq, q, nlim, limit, quant and pexc, nout >= 1, then
+ * UCF_ERR_NO_DEVICE without a device. */
+int ucf_debug_ensemble(int nens, long long nout, const double* a, int nq, const double* q,
+                       int nlim, const double* limit, const ucf_ensemble_maps* out /*all ignored*/,
+                       double* pexc, long long* nbad /*[1]*/);
 /* Host only: the nwell real wells followed by their mirror images in the straight line a x + b y = c (xo, yo, qo, t0o
  * [2 nwell]).  An image has q = +q for a no-flow boundary (kind 0), -q for a constant-head boundary (kind 1), and the t0 of its
  * real well.  One boundary only (two parallel boundaries need an infinite image series).  UCF_ERR_BAD_ARGUMENT: a = b = 0, a

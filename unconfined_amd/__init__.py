@@ -1,1 +1,1 @@
-from .field import WellField, forecast_sets, images  # noqa: F401
+from .field import WellField, ensemble_draw, forecast_sets, images  # noqa: F401

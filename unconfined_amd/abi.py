@@ -9,6 +9,8 @@ UCF_MAX_NZ = 32
 UCF_MAX_LAP_M = 127
 UCF_MAX_SCHEDULE = 100
 UCF_FIT_MAX_PAR = 8
+UCF_ENSEMBLE_MAX = 1024       # members of one ucf_field_ensemble
+UCF_ENSEMBLE_MAX_Q = 16       # quantile levels, and drawdown limits, per call
 # parameter ids of a fit (enum UCF_PAR_* of include/ucf.h); a Moench alpha is PAR_MOENCH_ALPHA0 + i
 PAR_KR, PAR_KAPPA, PAR_SS, PAR_SY, PAR_AC, PAR_AK, PAR_USL, PAR_MOENCH_ALPHA0 = range(8)
 PAR_IDS = {"Kr": PAR_KR, "kappa": PAR_KAPPA, "Ss": PAR_SS, "Sy": PAR_SY, "ac": PAR_AC, "ak": PAR_AK, "usL": PAR_USL}
@@ -58,6 +60,12 @@ class UcfStats(C.Structure):
 class UcfFitOptions(C.Structure):
     _fields_ = [("max_iter", C.c_int), ("dlog", C.c_double), ("lambda0", C.c_double), ("lambda_up", C.c_double),
                 ("lambda_down", C.c_double), ("tol_step", C.c_double), ("tol_phi", C.c_double)]
+
+
+class UcfEnsembleMaps(C.Structure):
+    """ucf_ensemble_maps: the statistics of one map of an ensemble; every address may be NULL"""
+    _fields_ = [("mean", C.c_void_p), ("sd", C.c_void_p), ("min", C.c_void_p), ("max", C.c_void_p), ("quant", C.c_void_p),
+                ("all", C.c_void_p), ("nfin", C.c_void_p)]
 
 
 def params_from_deck(dk) -> UcfParams:

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <new>
 #include <string>
@@ -33,13 +34,15 @@ struct ucf_field {
     ucf_buffer b_tD, b_sv, b_rD, b_tfac, b_col, b_wells, b_h, b_dh, b_s, b_ds, b_stats;      // grown on demand, kept
     // ucf_field_forecast: the slots [1 + 2 npar][nout] of s and ds, the staging of sens / dsens / se / dse, cov, the two counts
     ucf_buffer b_sall, b_dsall, b_sens, b_dsens, b_se, b_dse, b_cov, b_nbad;
+    // ucf_field_ensemble: its slots [nens][nout] are b_sall / b_dsall; the levels, the limits and the staging of every statistic
+    ucf_buffer b_ens;
     ucf_plan* scratch = nullptr;           // the plan that ucf_field_forecast refreshes for every parameter set
     long long n_alloc = 0;
     // every device buffer above: the one list (ucf_field_destroy frees through it)
-    std::array<ucf_buffer*, 19> buffers()
+    std::array<ucf_buffer*, 20> buffers()
     {
         return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats, &b_sall, &b_dsall, &b_sens, &b_dsens,
-                 &b_se, &b_dse, &b_cov, &b_nbad}};
+                 &b_se, &b_dse, &b_cov, &b_nbad, &b_ens}};
     }
 };
 
@@ -209,7 +212,110 @@ int forecast_set_failed(int rc, int k, const int* ids, double dlog)
     if (k == 0) return fail(rc, "set 0: %s", why.c_str());
     return fail(rc, "set %d, %s moved by %+g in its logarithm: %s", k, fit_par_name(ids[(k - 1) / 2], nb, sizeof(nb)), (k & 1) ? dlog : -dlog, why.c_str());
 }
+
+// the same for member m of an ensemble, naming the member and its parameter values
+int ensemble_member_failed(int rc, int m, int npar, const int* ids, const double* theta)
+{
+    std::string why = ucf_last_error(), vals;
+    char nb[32], one[96];
+    for (int j = 0; j < npar; j++) {
+        snprintf(one, sizeof(one), "%s%s=%g", j ? ", " : "", fit_par_name(ids[j], nb, sizeof(nb)), theta[j]);
+        vals += one;
+    }
+    return fail(rc, "member %d (%s): %s", m, vals.c_str(), why.c_str());
+}
+
+// what ucf_field_forecast and ucf_field_ensemble check on a covariance in ln theta
+int field_check_cov(int npar, const double* cov)
+{
+    for (int j = 0; j < npar; j++)
+        for (int k = 0; k < npar; k++) {
+            const double c = cov[j * npar + k];
+            if (!std::isfinite(c)) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g is not finite", j, k, c);
+            if (c != cov[k * npar + j]) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g differs from cov[%d][%d]=%g: not symmetric", j, k, c, k, j, cov[k * npar + j]);
+            if (j == k && c < 0.0) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g: a negative variance", j, j, c);
+        }
+    return UCF_OK;
+}
+
+// The field's scratch plan for a sequence of parameter sets that begins with `first`, on pl's device and in pl's mode: made
+// once, refreshed per set; made anew where the caller's plan has another model or other settings
+int field_scratch_plan(ucf_field* f, const ucf_plan* pl, const ucf_params& first)
+{
+    const int mode = pl->mode | (pl->force_layout0 << 1);
+    if (f->scratch && ucf_plan_update(f->scratch, &first) != UCF_OK) {
+        ucf_plan_destroy(f->scratch);
+        f->scratch = nullptr;
+    }
+    if (!f->scratch) {
+        int rc = ucf_plan_create_on(&first, pl->device, &f->scratch);
+        if (rc) return rc;
+        f->n_alloc++;
+    }
+    (void)ucf_plan_set_mode(f->scratch, mode);
+    return UCF_OK;
+}
+
+// What ucf_field_forecast and ucf_field_ensemble run per parameter set, for k = 0 .. nset-1 in this order: the scratch plan
+// (which holds set 0) refreshed to sets[k], then field_map_core under the launch arrays that launch_of(k, L) hands out --
+// kept from the checks (forecast) or formed again (ensemble) -- into slot k of b_sall / b_dsall [nset][nout], dimensional.
+// A set that anything refuses: failed(rc, k).
+template <class Launch, class Failed>
+int field_map_sets(ucf_field* f, int nset, const ucf_params* sets, Launch launch_of, int nz, const double* z, long long nout,
+                   ucf_stats* stats, Failed failed)
+{
+    ucf_plan* sp = f->scratch;
+    for (int k = 0; k < nset; k++) {
+        int rc;
+        if (k > 0 && (rc = ucf_plan_update(sp, &sets[k]))) return failed(rc, k);
+        const std::vector<field_launch>* L = nullptr;
+        if ((rc = launch_of(k, L))) return failed(rc, k);
+        rc = field_map_core(f, sp, *L, nz, z, 0, (double*)f->b_sall.p + (size_t)k * nout, (double*)f->b_dsall.p + (size_t)k * nout, stats);
+        if (rc) return failed(rc, k);
+    }
+    return UCF_OK;
+}
+
+// the launch arrays of every group of the field under P
+int field_launches_of(const ucf_field* f, const ucf_params& P, std::vector<field_launch>& L)
+{
+    ucf_derived D;
+    nondimensionalise(P, D);
+    L.resize(f->groups.size());
+    for (size_t g = 0; g < L.size(); g++) {
+        int rc = field_group_core(f, P, D, (int)g, L[g]);
+        if (rc) return rc;
+    }
+    return UCF_OK;
+}
+
+// splitmix64 (include/ucf.h states it with ucf_field_ensemble_draw)
+double ensemble_uniform(unsigned long long& state)
+{
+    state += 0x9E3779B97F4A7C15ULL;
+    unsigned long long x = state;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+    x = x ^ (x >> 31);
+    return ((double)(x >> 11) + 0.5) * 0x1p-53;
+}
 }  // namespace
+
+int ucf_host::ensemble_check_levels(int nens, int nq, const double* q, int nlim, const double* limit, bool want_quant, bool want_pexc)
+{
+    if (nens < 1 || nens > UCF_ENSEMBLE_MAX) return fail(UCF_ERR_BAD_ARGUMENT, "nens=%d outside 1..%d", nens, UCF_ENSEMBLE_MAX);
+    if (nq < 0 || nq > UCF_ENSEMBLE_MAX_Q) return fail(UCF_ERR_BAD_ARGUMENT, "nq=%d outside 0..%d", nq, UCF_ENSEMBLE_MAX_Q);
+    if (nlim < 0 || nlim > UCF_ENSEMBLE_MAX_Q) return fail(UCF_ERR_BAD_ARGUMENT, "nlim=%d outside 0..%d", nlim, UCF_ENSEMBLE_MAX_Q);
+    if (nq > 0 && !q) return fail(UCF_ERR_BAD_ARGUMENT, "NULL q with nq=%d", nq);
+    if (nlim > 0 && !limit) return fail(UCF_ERR_BAD_ARGUMENT, "NULL limit with nlim=%d", nlim);
+    for (int i = 0; i < nq; i++)
+        if (!std::isfinite(q[i]) || q[i] < 0.0 || q[i] > 1.0) return fail(UCF_ERR_BAD_ARGUMENT, "q[%d]=%g is not a level in [0,1]", i, q[i]);
+    int rc = field_check_finite("limit", nlim, limit);
+    if (rc) return rc;
+    if (want_quant && nq == 0) return fail(UCF_ERR_BAD_ARGUMENT, "quant is asked for with nq=0: no level to form it at");
+    if (want_pexc && nlim == 0) return fail(UCF_ERR_BAD_ARGUMENT, "pexc is asked for with nlim=0: no limit to exceed");
+    return UCF_OK;
+}
 
 extern "C" {
 
@@ -353,14 +459,7 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
     if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
     if (!(dlog > 0.0) || !std::isfinite(dlog)) return fail(UCF_ERR_BAD_ARGUMENT, "dlog=%g must be positive and finite", dlog);
     if ((se || dse) && !cov) return fail(UCF_ERR_BAD_ARGUMENT, "%s is asked for without cov: a standard error needs the covariance", se ? "se" : "dse");
-    if (cov)
-        for (int j = 0; j < npar; j++)
-            for (int k = 0; k < npar; k++) {
-                const double c = cov[j * npar + k];
-                if (!std::isfinite(c)) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g is not finite", j, k, c);
-                if (c != cov[k * npar + j]) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g differs from cov[%d][%d]=%g: not symmetric", j, k, c, k, j, cov[k * npar + j]);
-                if (j == k && c < 0.0) return fail(UCF_ERR_BAD_ARGUMENT, "cov[%d][%d]=%g: a negative variance", j, j, c);
-            }
+    if (cov && (rc = field_check_cov(npar, cov))) return rc;
     const int nset = 1 + 2 * npar;
     if (nset * nout > 0x7fffffffLL * 256)
         return fail(UCF_ERR_BAD_ARGUMENT, "%d parameter sets x %d times x %d locations x %d depths: too many values for one buffer", nset, f->nt, f->nloc, nz);
@@ -384,18 +483,8 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
     if (f->device >= 0 && f->device != pl->device)
         return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
     if (stats) std::memset(stats, 0, sizeof(*stats));
-    // the scratch plan: made once, refreshed per set; made anew where the caller's plan has another model or other settings
-    const int mode = pl->mode | (pl->force_layout0 << 1);
-    if (f->scratch && ucf_plan_update(f->scratch, &sets[0]) != UCF_OK) {
-        ucf_plan_destroy(f->scratch);
-        f->scratch = nullptr;
-    }
-    if (!f->scratch) {
-        if ((rc = ucf_plan_create_on(&sets[0], pl->device, &f->scratch))) return rc;
-        f->n_alloc++;
-    }
+    if ((rc = field_scratch_plan(f, pl, sets[0]))) return rc;
     ucf_plan* sp = f->scratch;
-    (void)ucf_plan_set_mode(sp, mode);
     device_switch dg(pl->device);
     f->device = pl->device;
     const size_t so = sizeof(double) * (size_t)nout, sa = so * nset, sj = so * npar;
@@ -404,11 +493,9 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
         (sens && (rc = grow_buffer(f->b_sens, sj, "sensitivities", f->n_alloc))) || (dsens && (rc = grow_buffer(f->b_dsens, sj, "derivative sensitivities", f->n_alloc))) ||
         (se && (rc = grow_buffer(f->b_se, so, "standard error", f->n_alloc))) || (dse && (rc = grow_buffer(f->b_dse, so, "derivative standard error", f->n_alloc))) ||
         (cov && (rc = grow_buffer(f->b_cov, sizeof(double) * UCF_FIT_MAX_PAR * UCF_FIT_MAX_PAR, "cov", f->n_alloc)))) return rc;
-    for (int k = 0; k < nset; k++) {
-        if (k > 0 && (rc = ucf_plan_update(sp, &sets[k]))) return forecast_set_failed(rc, k, ids, dlog);
-        rc = field_map_core(f, sp, L[k], nz, z, 0, (double*)f->b_sall.p + (size_t)k * nout, (double*)f->b_dsall.p + (size_t)k * nout, stats);
-        if (rc) return forecast_set_failed(rc, k, ids, dlog);
-    }
+    rc = field_map_sets(f, nset, sets, [&](int k, const std::vector<field_launch>*& Lk) { Lk = &L[k]; return UCF_OK; }, nz, z, nout, stats,
+                        [&](int rc_k, int k) { return forecast_set_failed(rc_k, k, ids, dlog); });
+    if (rc) return rc;
     hipStream_t st = plan_stream(sp);
     if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
     struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};
@@ -430,6 +517,130 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
         if (c.host && hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
             return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
     if (hipStreamSynchronize(st) != hipSuccess) return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
+    return UCF_OK;
+}
+
+int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, int nz, const double* z,
+                       int nq, const double* q, int nlim, const double* limit, const ucf_ensemble_maps* s, const ucf_ensemble_maps* ds,
+                       double* pexc, long long* nbad, ucf_stats* stats)
+{
+    long long nout = 0;
+    int rc = field_check_call(f, nz, !z ? "NULL z" : !ids ? "NULL ids" : !thetas ? "NULL thetas" : nullptr, z, nout);
+    if (rc) return rc;
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if ((rc = ensemble_check_levels(nens, nq, q, nlim, limit, (s && s->quant) || (ds && ds->quant), pexc != nullptr))) return rc;
+    char nb[32];
+    for (int m = 0; m < nens; m++)
+        for (int j = 0; j < npar; j++) {
+            const double v = thetas[(size_t)m * npar + j];
+            if (!(v > 0.0) || !std::isfinite(v))
+                return fail(UCF_ERR_BAD_ARGUMENT, "member %d: %s=%g must be positive and finite", m, fit_par_name(ids[j], nb, sizeof(nb)), v);
+        }
+    if (nens * nout > 0x7fffffffLL * 256)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d times x %d locations x %d depths: too many values for one buffer", nens, f->nt, f->nloc, nz);
+    if (!pl) {
+        rc = require_device();
+        return rc ? rc : fail(UCF_ERR_BAD_ARGUMENT, "NULL plan");
+    }
+    // every member and what every group launches under it: checked before any launch, the arrays not kept
+    std::vector<ucf_params> sets(nens);
+    std::vector<field_launch> L;
+    auto failed = [&](int rc_m, int m) { return ensemble_member_failed(rc_m, m, npar, ids, thetas + (size_t)m * npar); };
+    for (int m = 0; m < nens; m++) {
+        if ((rc = ucf_fit_perturb(&pl->P, npar, ids, thetas + (size_t)m * npar, &sets[m]))) return m == 0 ? rc : failed(rc, m);
+        if ((rc = validate(sets[m])) || (rc = field_launches_of(f, sets[m], L))) return failed(rc, m);
+    }
+    rc = require_device();
+    if (rc) return rc;
+    if (f->device >= 0 && f->device != pl->device)
+        return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if ((rc = field_scratch_plan(f, pl, sets[0]))) return rc;
+    ucf_plan* sp = f->scratch;
+    device_switch dg(pl->device);
+    f->device = pl->device;
+    // b_ens: q [MAX_Q], limit [MAX_Q], then per map what is asked for of mean, sd, min, max [nout], quant [nq][nout], nfin
+    // [nout] (ints, padded to whole doubles), then pexc [nlim][nout]
+    const size_t no = (size_t)nout, so = sizeof(double) * no, sa = so * nens;
+    const ucf_ensemble_maps none = {};
+    const ucf_ensemble_maps* want[2] = {s ? s : &none, ds ? ds : &none};
+    struct map_at { double *mean, *sd, *min, *max, *quant; int* nfin; } at[2];
+    size_t used = 2 * UCF_ENSEMBLE_MAX_Q;                 // in doubles
+    auto take = [&](bool asked, size_t n) { const size_t o = used; if (asked) used += n; return asked ? o : (size_t)-1; };
+    size_t off[2][6], off_pexc;
+    for (int i = 0; i < 2; i++) {
+        off[i][0] = take(want[i]->mean, no); off[i][1] = take(want[i]->sd, no); off[i][2] = take(want[i]->min, no);
+        off[i][3] = take(want[i]->max, no); off[i][4] = take(want[i]->quant, no * nq); off[i][5] = take(want[i]->nfin, (no + 1) / 2);
+    }
+    off_pexc = take(pexc, no * nlim);
+    if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every member", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every member", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_nbad, sizeof(long long) * 2, "counts", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_ens, sizeof(double) * used, "ensemble statistics", f->n_alloc))) return rc;
+    double* base = (double*)f->b_ens.p;
+    auto dev = [&](size_t o) { return o == (size_t)-1 ? nullptr : base + o; };
+    for (int i = 0; i < 2; i++) at[i] = map_at{dev(off[i][0]), dev(off[i][1]), dev(off[i][2]), dev(off[i][3]), dev(off[i][4]), (int*)dev(off[i][5])};
+    double* d_pexc = dev(off_pexc);
+    rc = field_map_sets(f, nens, sets.data(), [&](int m, const std::vector<field_launch>*& Lm) { Lm = &L; return field_launches_of(f, sets[m], L); },
+                        nz, z, nout, stats, failed);
+    if (rc) return rc;
+    hipStream_t st = plan_stream(sp);
+    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
+    struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};
+    double ql[2 * UCF_ENSEMBLE_MAX_Q] = {};
+    for (int i = 0; i < nq; i++) ql[i] = q[i];
+    for (int i = 0; i < nlim; i++) ql[UCF_ENSEMBLE_MAX_Q + i] = limit[i];
+    if (hipMemsetAsync(f->b_nbad.p, 0, sizeof(long long) * 2, st) != hipSuccess ||
+        hipMemcpyAsync(base, ql, sizeof(ql), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the ensemble's arrays failed: %s", hipGetErrorString(hipGetLastError()));
+    const double* slots[2] = {(const double*)f->b_sall.p, (const double*)f->b_dsall.p};
+    for (int i = 0; i < 2 && rc == UCF_OK; i++) {
+        rc = ucf_field_launch_ensemble_moments(nens, nout, slots[i], nlim, base + UCF_ENSEMBLE_MAX_Q, at[i].mean, at[i].sd, at[i].min, at[i].max,
+                                               at[i].nfin, i == 0 ? d_pexc : nullptr, (long long*)f->b_nbad.p + i, st);
+        if (rc == UCF_OK && at[i].quant) rc = ucf_field_launch_ensemble_quantile(nens, nout, slots[i], nq, base, at[i].quant, st);
+    }
+    if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    // only what is asked for crosses the bus
+    struct copy { void* host; const void* dev; size_t bytes; };
+    std::vector<copy> back = {{pexc, d_pexc, so * nlim}, {nbad, f->b_nbad.p, sizeof(long long) * 2}};
+    for (int i = 0; i < 2; i++) {
+        const ucf_ensemble_maps* w = want[i];
+        back.insert(back.end(), {{w->mean, at[i].mean, so}, {w->sd, at[i].sd, so}, {w->min, at[i].min, so}, {w->max, at[i].max, so},
+                                 {w->quant, at[i].quant, so * nq}, {w->all, slots[i], sa}, {w->nfin, at[i].nfin, sizeof(int) * no}});
+    }
+    for (const copy& c : back)
+        if (c.host && hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
+    return UCF_OK;
+}
+
+int ucf_field_ensemble_draw(int npar, const double* theta, const double* cov, int nens, unsigned long long seed, double* thetas)
+{
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (!theta || !cov || !thetas) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !theta ? "theta" : !cov ? "cov" : "thetas");
+    if (nens < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nens=%d: at least one member", nens);
+    for (int j = 0; j < npar; j++)
+        if (!(theta[j] > 0.0) || !std::isfinite(theta[j])) return fail(UCF_ERR_BAD_ARGUMENT, "theta[%d]=%g must be positive and finite", j, theta[j]);
+    int rc = field_check_cov(npar, cov);
+    if (rc) return rc;
+    double L[UCF_FIT_MAX_PAR * UCF_FIT_MAX_PAR];
+    for (int i = 0; i < npar * npar; i++) L[i] = cov[i];
+    if (fit_cholesky_factor(npar, L) != UCF_OK) return fail(UCF_ERR_SINGULAR, "cov is not positive definite (%d x %d): it has no Cholesky factor", npar, npar);
+    unsigned long long state = seed;
+    double zeta[UCF_FIT_MAX_PAR + 1];
+    for (int m = 0; m < nens; m++) {
+        for (int i = 0; i < npar; i += 2) {
+            const double u1 = ensemble_uniform(state), u2 = ensemble_uniform(state);
+            const double rad = std::sqrt(-2.0 * std::log(u1)), ang = 6.283185307179586 * u2;
+            zeta[i] = rad * std::cos(ang);
+            zeta[i + 1] = rad * std::sin(ang);
+        }
+        for (int j = 0; j < npar; j++) {
+            double acc = 0.0;
+            for (int k = 0; k <= j; k++) acc = acc + L[j * npar + k] * zeta[k];
+            thetas[(size_t)m * npar + j] = theta[j] * std::exp(acc);
+        }
+    }
     return UCF_OK;
 }
 

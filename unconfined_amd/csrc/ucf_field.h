@@ -1,5 +1,6 @@
-// ucf_field.h -- launchers of the well-field kernels (ucf_field.hip): the superposition, called by ucf_field_drawdown and
-// ucf_field_forecast (ucf_field.cpp), and the combination of a forecast.
+// ucf_field.h -- launchers of the well-field kernels: the superposition, called by ucf_field_drawdown, ucf_field_forecast and
+// ucf_field_ensemble (ucf_field.cpp), the combination of a forecast (both ucf_field.hip) and the reduction of an ensemble
+// (ucf_field_ensemble.hip).
 #pragma once
 #include <cstddef>
 
@@ -29,3 +30,20 @@ int ucf_field_launch_superpose(int nt, int nloc, int nz, int nwell, const ucf_fi
 // UCF_ERR_BAD_ARGUMENT for npar outside 1..UCF_FIT_MAX_PAR.
 int ucf_field_launch_forecast(int npar, long long nout, double two_dlog, const double* d_a, const double* d_cov, double* d_sens,
                               double* d_se, long long* d_nbad, void* stream);
+
+// The reduction of an ensemble over its member axis (ucf_field_ensemble.hip), on the member maps d_a [nens][nout]; the
+// arithmetic is stated with ucf_field_ensemble in include/ucf.h.  F(e) = the members m with a[m][e] finite, in member order.
+// field_ensemble_moments_kernel, one thread per output e: d_nfin[e] = n = |F|; d_mean, d_sd, d_min, d_max [nout]; d_pexc
+// [nlim][nout] = the fraction of F above d_limit[l] (not NULL needs nlim >= 1 and d_limit [nlim] in device memory); any of the
+// six may be NULL (not formed).  *d_nbad += the number of outputs with n < nens (the caller zeroes it).
+// UCF_ERR_BAD_ARGUMENT: nens outside 1..UCF_ENSEMBLE_MAX, nlim outside 0..UCF_ENSEMBLE_MAX_Q.
+int ucf_field_launch_ensemble_moments(int nens, long long nout, const double* d_a, int nlim, const double* d_limit, double* d_mean,
+                                      double* d_sd, double* d_min, double* d_max, int* d_nfin, double* d_pexc, long long* d_nbad,
+                                      void* stream);
+// field_ensemble_quantile_kernel<T>: d_quant [nq][nout], the order statistics of F at the levels d_q [nq] (device memory),
+// 1 <= nq <= UCF_ENSEMBLE_MAX_Q.  A workgroup of 256 threads ranks the members of T = ucf_field_ensemble_tile(nens)
+// neighbouring outputs against each other in LDS: (nens + 2 UCF_ENSEMBLE_MAX_Q) T doubles, at most 144 KB.
+int ucf_field_launch_ensemble_quantile(int nens, long long nout, const double* d_a, int nq, const double* d_q, double* d_quant,
+                                       void* stream);
+// outputs per workgroup of the quantile kernel: 64 / 32 / 16 for nens <= 256 / 512 / 1024
+int ucf_field_ensemble_tile(int nens);

@@ -583,6 +583,8 @@ void fit_network_places(ucf_fit* f, int n, const double* t, const int* well, con
 }
 }  // namespace
 
+int ucf_host::fit_cholesky_factor(int n, double* M) { return fit_cholesky(n, M); }
+
 extern "C" {
 
 int ucf_fit_perturb(const ucf_params* base, int npar, const int* ids, const double* theta, ucf_params* out)

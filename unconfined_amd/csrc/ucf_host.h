@@ -129,9 +129,14 @@ const char* fit_par_name(int id, char* buf, size_t n);
 // count = 1 + 2 npar also sets[1 + 2j] / sets[2 + 2j] = the same with theta[j] * exp(+dlog) / theta[j] * exp(-dlog), one
 // product each (count = 1: the base set alone, dlog is not read).  Returns what ucf_fit_perturb returns.
 int fit_theta_sets(const ucf_params& base, int npar, const int* ids, const double* theta, double dlog, int count, ucf_params* sets);
+// the lower Cholesky factor of M [n][n] (symmetric, row-major) in its lower triangle, as ucf_fit_solve_step forms it;
+// UCF_ERR_SINGULAR (no message) where a pivot is not positive and finite
+int fit_cholesky_factor(int n, double* M);
 
 // ---- ucf_field.cpp
 // UCF_ERR_BAD_ARGUMENT naming name[i] for the first v[i] that is not finite
 int field_check_finite(const char* name, int n, const double* v);
+// what ucf_field_ensemble and ucf_debug_ensemble check on nens, the levels q [nq] and the limits [nlim]
+int ensemble_check_levels(int nens, int nq, const double* q, int nlim, const double* limit, bool want_quant, bool want_pexc);
 
 }  // namespace ucf_host

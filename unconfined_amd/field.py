@@ -14,6 +14,13 @@ parameters, their sensitivities to ln theta_j and their first-order standard err
 
     out = field.forecast(plan, ["Kr", "Ss"], res["theta"][0], z=[145.7, 100.0], cov=res["cov"][0])
     out["s"], out["se"], out["sens"]                                                          # [nt, nloc, nz], same, [npar, nt, nloc, nz]
+
+An ensemble asks what the linearisation cannot answer -- the 5 % / 50 % / 95 % maps, the chance that a limit is exceeded -- from
+many parameter sets, drawn from the fit's covariance or taken from the rows of a multi-start fit (ucf_field_ensemble):
+
+    thetas = ensemble_draw(res["theta"][0], res["cov"][0], 256, seed=1)                       # [256, npar]
+    out = field.ensemble(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], limits=[0.5])
+    out["quant"], out["pexc"]                                                                 # [3, nt, nloc, nz], [1, nt, nloc, nz]
 """
 from __future__ import annotations
 
@@ -22,7 +29,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _libmod
-from .abi import UcfParams, UcfStats
+from .abi import UcfEnsembleMaps, UcfParams, UcfStats
 from .fit import par_id
 
 KINDS = {"no_flow": 0, "constant_head": 1, 0: 0, 1: 1}
@@ -46,6 +53,19 @@ def forecast_sets(params: UcfParams, free, theta, dlog: float) -> list:
     sets = (UcfParams * (1 + 2 * len(ids)))()
     _libmod.check(_libmod.load().ucf_field_forecast_sets(C.byref(params), len(ids), _addr(ids), _addr(theta), float(dlog), sets))
     return [UcfParams.from_buffer_copy(p) for p in sets]
+
+
+def ensemble_draw(theta, cov, n: int, seed: int = 0):
+    """n parameter sets [n, npar] drawn from the log-normal distribution that a fit states with ``theta`` and ``cov`` (in
+    ln theta, as ``Fit.lm`` returns it): theta_j exp((L zeta)_j), L the Cholesky factor of cov, zeta standard normal deviates
+    from the generator that include/ucf.h states; the same seed gives the same bits (ucf_field_ensemble_draw; no GPU)"""
+    theta = np.atleast_1d(_f64(theta))
+    cov = np.atleast_2d(_f64(cov))
+    if cov.shape != (len(theta), len(theta)):
+        raise ValueError("cov: [npar, npar]")
+    out = np.zeros((max(int(n), 0), len(theta)))
+    _libmod.check(_libmod.load().ucf_field_ensemble_draw(len(theta), _addr(theta), _addr(cov), int(n), int(seed) & (2 ** 64 - 1), _addr(out)))
+    return out
 
 
 def _wells(wells):
@@ -163,6 +183,47 @@ class WellField:
             self._h, plan._h, npar, _addr(ids), _addr(theta), float(dlog), _addr(cov), len(z), _addr(z),
             *(_addr(out.get(k)) for k in ("s", "ds", "sens", "dsens", "se", "dse", "s_all", "ds_all")), _addr(out["nbad"]),
             C.byref(st) if with_stats else None))
+        if with_stats:
+            out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
+        return out
+
+    def ensemble(self, plan, free, thetas, z, quantiles=(0.05, 0.5, 0.95), limits=None, derivative: bool = True,
+                 all_maps: bool = False, with_stats: bool = False) -> dict:
+        """the field under the parameter sets ``thetas`` [nens, npar] of the free parameters (names as for ``fit.par_id``; the
+        other parameters are ``plan``'s), reduced over the members on the GPU, all dimensional: mean, sd, min, max [nt, nloc,
+        nz] of the drawdown, quant [nq, nt, nloc, nz] at the levels ``quantiles``, nfin (int32) the members that are finite at
+        an output -- the others take part in no statistic; with ``limits`` pexc [nlim, nt, nloc, nz], the fraction of the
+        finite members whose drawdown exceeds a limit; with ``derivative`` dmean, dsd, dmin, dmax, dquant, dnfin of t ds/dt;
+        with ``all_maps`` s_all (and ds_all) [nens, nt, nloc, nz], the member maps; nbad [2], the outputs of s and of ds where
+        a member is not finite.  ``plan`` is not modified."""
+        ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
+        thetas = np.atleast_2d(_f64(thetas))
+        if thetas.ndim != 2 or thetas.shape[1] != len(ids):
+            raise ValueError("thetas: [nens, npar], one value per free parameter")
+        nens = len(thetas)
+        z = np.atleast_1d(_f64(z))
+        q = np.atleast_1d(_f64(quantiles if quantiles is not None else []))
+        lim = np.atleast_1d(_f64(limits if limits is not None else []))
+        shape = (self.nt, self.nloc, len(z))
+        out, keep = {}, []
+        for pre in ("", "d") if derivative else ("",):
+            for key in ("mean", "sd", "min", "max"):
+                out[pre + key] = np.zeros(shape)
+            if len(q):
+                out[pre + "quant"] = np.zeros((len(q),) + shape)
+            out[pre + "nfin"] = np.zeros(shape, np.int32)
+            if all_maps:
+                out[pre + "s_all"] = np.zeros((nens,) + shape)
+            m = UcfEnsembleMaps(*(_addr(out.get(pre + key)) for key in ("mean", "sd", "min", "max", "quant", "s_all", "nfin")))
+            keep.append(m)
+        if len(lim):
+            out["pexc"] = np.zeros((len(lim),) + shape)
+        out["nbad"] = np.zeros(2, np.int64)
+        st = UcfStats()
+        _libmod.check(self._lib.ucf_field_ensemble(
+            self._h, plan._h, len(ids), _addr(ids), nens, _addr(thetas), len(z), _addr(z), len(q), _addr(q) if len(q) else None,
+            len(lim), _addr(lim) if len(lim) else None, C.byref(keep[0]), C.byref(keep[1]) if derivative else None,
+            _addr(out.get("pexc")), _addr(out["nbad"]), C.byref(st) if with_stats else None))
         if with_stats:
             out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
         return out

@@ -12,7 +12,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import UcfDerived, UcfFitOptions, UcfParams, UcfStats
+from .abi import UcfDerived, UcfEnsembleMaps, UcfFitOptions, UcfParams, UcfStats
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # UCF_LIB_PATH: an experimental build of the SAME library (tools/ubench/build_variant.sh) for A/B timing; the product
@@ -43,6 +43,7 @@ EXPORTS = [
     "ucf_field_create", "ucf_field_destroy", "ucf_field_group_count", "ucf_field_group", "ucf_field_group_from_params",
     "ucf_field_drawdown", "ucf_field_alloc_count", "ucf_field_images",
     "ucf_field_forecast_sets", "ucf_field_forecast",
+    "ucf_field_ensemble", "ucf_field_ensemble_draw", "ucf_debug_ensemble",
 ]
 
 
@@ -167,6 +168,11 @@ def load() -> C.CDLL:
     lib.ucf_field_forecast_sets.argtypes = [C.POINTER(UcfParams), C.c_int, vp, vp, C.c_double, C.POINTER(UcfParams)]
     # ids, theta, cov and every output may be NULL: plain addresses
     lib.ucf_field_forecast.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, vp, C.c_int, vp] + [vp] * 8 + [vp, C.POINTER(UcfStats)]
+    # ids, thetas, z, q, limit and every output may be NULL: plain addresses
+    lib.ucf_field_ensemble.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp,
+                                       C.POINTER(UcfEnsembleMaps), C.POINTER(UcfEnsembleMaps), vp, vp, C.POINTER(UcfStats)]
+    lib.ucf_field_ensemble_draw.argtypes = [C.c_int, vp, vp, C.c_int, C.c_ulonglong, vp]
+    lib.ucf_debug_ensemble.argtypes = [C.c_int, C.c_longlong, vp, C.c_int, vp, C.c_int, vp, C.POINTER(UcfEnsembleMaps), vp, vp]
     _lib = lib
     return lib
 
