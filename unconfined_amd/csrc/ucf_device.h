@@ -1435,6 +1435,46 @@ UCF_DEV work_item decode_item(const ucf_dev_params& P, int pt, int lane, int per
     return W;
 }
 
+// ------------------------------------------------------------------ state loads of the tail, a group at a time
+// Left to itself the compiler gives every slot of an item's state a round trip of its own: a copy loop through one register
+// quad waits for each load before the next, and a load whose only use sits in a later branch is sunk into that branch.  A group
+// is therefore loaded in full into an array first -- an index past the end repeats the LAST slot of the same run, so nothing
+// outside the item's state is read and no branch stands between the loads -- and pinned: the empty statement needs every
+// value of the group in its VGPR, so all loads of the group are in flight before the one wait that stands in front of it.
+template <typename T> UCF_DEV void pin_loaded(T& v) { asm volatile("" : "+v"(v)); }
+UCF_DEV void pin_loaded(double2& a, double2& b, double2& c, double2& d)
+{
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(b.x), "+v"(b.y), "+v"(c.x), "+v"(c.y), "+v"(d.x), "+v"(d.y));
+}
+// slots [s0, s0 + CH) of the run src[n][64] into t (CH a multiple of 4), issued only: pin_group is the wait
+template <int CH>
+UCF_DEV void load_group(double2* t, const double2* __restrict__ src, int stride, int s0, int n, int lane)
+{
+#pragma unroll
+    for (int k = 0; k < CH; k++) {
+        const int s = (s0 + k < n) ? s0 + k : n - 1;
+        const double2* __restrict__ slot = src + (size_t)s * stride * UCF_WAVE;      // (wave-uniform: scalar base + lane offset)
+        t[k] = slot[(unsigned)lane];
+    }
+}
+template <int CH>
+UCF_DEV void pin_group(double2* t)
+{
+#pragma unroll
+    for (int k = 0; k < CH; k += 4) pin_loaded(t[k], t[k + 1], t[k + 2], t[k + 3]);
+}
+// slots [s0, s0 + CH) of the run into LDS: one group
+template <int CH>
+UCF_DEV void stage_group(lds_c* dst, const double2* __restrict__ src, int s0, int n, int lane)
+{
+    double2 t[CH];
+    load_group<CH>(t, src, 1, s0, n, lane);
+    pin_group<CH>(t);
+#pragma unroll
+    for (int k = 0; k < CH; k++)
+        if (s0 + k < n) dst[(s0 + k) * UCF_WAVE + lane] = t[k];
+}
+
 // ------------------------------------------------------------------ the tail of a work item
 // driver.f90:159-230 per depth: scale the level sums, Richardson/Neville to h -> 0, Wynn-epsilon over the
 // J0-interval areas, then the transform goes to the workspace (LAYOUT 1, 2) or straight through de Hoog
@@ -1455,6 +1495,10 @@ UCF_DEV void finish_item(const ucf_dev_params& P, lds_c* accTS, lds_c* scr, cons
     const int nz = P.nz, R = P.R, nacc = P.nacc;
     if (z1 < 0) z1 = nz;
     for (int z = z0; z < z1; z++) {
+        // finish_kernel, nacc <= UCF_WYNN_REGS: the areas go from the state straight into registers, one group of loads issued
+        // here and waited for behind the level sums' scaling (entries from nacc on repeat area nacc - 1 and are not used)
+        double2 raw[UCF_WYNN_REGS];
+        if (WREG) load_group<UCF_WYNN_REGS>(raw, areas + (size_t)z * UCF_WAVE, nz, 0, nacc, lane);
         for (int j = 0; j < R; j++) {
             const int slot = j * nz + z;
             lds_st(accTS, slot, lane, rscale(arg / 2.0, lds_ld(accTS, slot, lane)));            // :135,154
@@ -1464,14 +1508,13 @@ UCF_DEV void finish_item(const ucf_dev_params& P, lds_c* accTS, lds_c* scr, cons
         cplx infint = cmake(0.0, 0.0);
         int wst = 0;
         if (WREG) {
-            // finish_kernel, nacc <= UCF_WYNN_REGS: the areas go from the state straight into registers
+            pin_group<UCF_WYNN_REGS>(raw);
             cplx ser[UCF_WYNN_REGS];
 #pragma unroll
             for (int jj = 0; jj < UCF_WYNN_REGS; jj++) {
                 ser[jj] = cmake(0.0, 0.0);
                 if (jj < nacc) {
-                    const double2 v = areas[(size_t)(jj * nz + z) * UCF_WAVE + lane];
-                    ser[jj] = cmake(v.x, v.y);
+                    ser[jj] = cmake(raw[jj].x, raw[jj].y);
                     any |= c_abs_positive(ser[jj]);                                              // :209
                 }
             }
@@ -1498,16 +1541,25 @@ UCF_DEV void finish_item(const ucf_dev_params& P, lds_c* accTS, lds_c* scr, cons
                 if (R > 1) finint = extrap_lane<PART>(accTS + (size_t)z * UCF_WAVE, nz, scr, P.hv, R, lane);
                 lds_c* colA = scr;
                 lds_c* colB = scr + (size_t)nacc * PART;
-                for (int jj = 0; jj < nacc; jj++) {
-                    cplx ar;
-                    if (accGL) {
-                        ar = lds_ld(accGL, jj * nz + z, lane);
-                    } else {
-                        const double2 v = areas[(size_t)(jj * nz + z) * UCF_WAVE + lane];
-                        ar = cmake(v.x, v.y);
+                if (accGL) {
+                    for (int jj = 0; jj < nacc; jj++) {
+                        const cplx ar = lds_ld(accGL, jj * nz + z, lane);
+                        any |= c_abs_positive(ar);                                               // :209
+                        scr_st<PART>(colA, jj, lane, ar);
                     }
-                    any |= c_abs_positive(ar);                                                   // :209
-                    scr_st<PART>(colA, jj, lane, ar);
+                } else {
+                    // (from global memory in groups of 4; what a group repeats of the last area is not stored, and the OR does not mind)
+                    for (int j0 = 0; j0 < nacc; j0 += 4) {
+                        double2 t[4];
+                        load_group<4>(t, areas + (size_t)z * UCF_WAVE, nz, j0, nacc, lane);
+                        pin_group<4>(t);
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const cplx ar = cmake(t[k].x, t[k].y);
+                            any |= c_abs_positive(ar);                                           // :209
+                            if (j0 + k < nacc) scr_st<PART>(colA, j0 + k, lane, ar);
+                        }
+                    }
                 }
                 if (any) infint = wynn_lane<PART>(colA, colB, nacc, lane, &wst);
             }
@@ -2133,16 +2185,35 @@ finish_kernel(const ucf_dev_params P, int npts, int per_point, int nr, int nsv, 
     for (int wi = blockIdx.x; wi < nloop; wi += gridDim.x) {
         const int pt = (MODE == 2) ? defer[1 + wi] / nz : wi;
         const int zsel = (MODE == 2) ? defer[1 + wi] % nz : 0;
-        if (MODE != 2 && ndone[pt] < nabs) continue;
         const work_item W = decode_item<LAYOUT>(P, pt, lane, per_point, nr, nt, ir0, npts);
-        const double tD = tDv[W.it], rD = rDv[W.ir];
-        const int sv = (LAYOUT == 1) ? svmin : svv[W.it];
+        double tD = tDv[W.it], rD = rDv[W.ir];
+        int sv = (LAYOUT == 1) ? svmin : svv[W.it];
+        double j0sv = (LAYOUT == 1) ? P.j0z[sv - 1] : 0.0;
+        // First group: the lane's time (radius, split index, first J0 zero) and the first four level sums, all issued before the one wait
+        // and before ndone[pt] is back -- every item's slots lie inside the workspace whether integrate_kernel completed
+        // it or not, and an item it left to point_kernel throws the values away.
+        const int nd = (MODE == 2) ? nabs : ndone[pt];
+        const int nsum = R * nz;
+        const double2* __restrict__ sti = state + (size_t)pt * state_slots(P) * UCF_WAVE;
+        double2 sum4[4];
+        load_group<4>(sum4, sti, 1, 0, nsum, lane);
+        pin_group<4>(sum4);
+        if (LAYOUT == 1) { pin_loaded(tD); pin_loaded(j0sv); }
+        if (LAYOUT == 3) { pin_loaded(tD); pin_loaded(rD); pin_loaded(sv); }
+        if (nd < nabs) continue;
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (k < nsum) lds[k * UCF_WAVE + lane] = sum4[k];
+        // (the rest of the level sums: R > 4 or several depths, groups of 4 or 8)
+        for (int s0 = 4; s0 < nsum; s0 += 8) {
+            if (nsum - s0 <= 4) stage_group<4>(lds, sti, s0, nsum, lane);
+            else stage_group<8>(lds, sti, s0, nsum, lane);
+        }
         const double tee = 2.0 * tD;
         const double sigma = P.alpha - P.logtol / (2.0 * tee);
         const cplx p = cmake(sigma, UCF_PI * W.mlap / tee);
-        const double arg = P.j0z[sv - 1] / rD;                                                  // driver.f90:120
-        const double2* __restrict__ sti = state + (size_t)pt * state_slots(P) * UCF_WAVE;
-        for (int s = 0; s < R * nz; s++) lds[s * UCF_WAVE + lane] = sti[(size_t)s * UCF_WAVE + lane];
+        if (LAYOUT != 1) j0sv = P.j0z[sv - 1];
+        const double arg = j0sv / rD;                                                           // driver.f90:120
         finish_item<LAYOUT, PART, WREG, MODE>(P, accTS, scr, nullptr, sti + (size_t)(R + 1) * nz * UCF_WAVE, arg, W, pt, tD, tee, p, st, nt, ir0,
                                               totlap, hout, dhout, zsel, (MODE == 2) ? zsel + 1 : nz, (MODE == 1) ? defer : nullptr);
     }
