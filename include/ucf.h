@@ -677,6 +677,45 @@ int ucf_field_ensemble_draw(int npar, const double* theta, const double* cov /*[
 int ucf_debug_ensemble(int nens, long long nout, const double* a, int nq, const double* q,
                        int nlim, const double* limit, const ucf_ensemble_maps* out /*all ignored*/,
                        double* pexc, long long* nbad /*[1]*/);
+/* The reduction kernel of ucf_fit_evaluate exactly as a fit launches it (the same launcher, and through it the same choice among the
+ * instantiations: npar 0..UCF_FIT_MAX_PAR x source x with / without derivative data), on caller data.  One 256-thread workgroup
+ * per parameter set; set s owns the plans s (1 + 2 npar) + (0 base | 1 + 2j: parameter j up | 2 + 2j: parameter j down);
+ * nplans = nsets (1 + 2 npar).  h [nh] is the dimensionless drawdown, dh [nh] its log-time derivative in the same layout (NULL: a
+ * fit without derivative data; then dobs, wd, tfac are not read and the sums have no phi_d), Hc [nplans] the scale of each plan.
+ *   source 0     slots: the value of observation i under a plan is h[plan * plan_stride + slot[i]];
+ *   source 1     network: observation i reads count[i] consecutive doubles at prefix[i] * nplans + plan * stride[i] + at[i] (nref =
+ *                nobs): count 1 is the value itself; otherwise, with v the n = count doubles, the screen average of
+ *                ucf_screen_average:  s = v[1];  s = s + v[j], j = 2 .. n-1;  ((v[0] + 2.0 * s) + v[n-1]) / (double)(2 n);
+ *   source 2     field: observation i is the sum of the terms first[i] .. first[i+1]-1 (nref terms; prefix, stride, at, count, q and,
+ *                with dh, tfac per term):  acc = +0.0;  acc = acc + q * (value at the term's ref);  on dh
+ *                acc = acc + q * (tfac * (value at the ref)).  An observation without terms is +0.0.
+ * The arrays of the other sources are not read and may be NULL.  Every operation is rounded on its own (no FMA contraction):
+ *   s[k] = value * Hc[plan0 + k], k = 0 .. 2 npar (sd[k] the same from dh);   d[j] = (s[1+2j] - s[2+2j]) / two_dlog (dd[j] from sd);
+ *   wr = w[i] * (obs[i] - s[0]);  wd_[j] = w[i] * d[j];   wrd = wd[i] * (dobs[i] - sd[0]);  wdd[j] = wd[i] * dd[j];
+ *   observation i counts where every s[k] is finite and (dh is NULL or wd[i] == 0 or every sd[k] is finite); nbad[set] is the number
+ *   that do not.  One that counts adds, in this order:  phi += wr * wr;  g[j] += wd_[j] * wr;  A[q] += wd_[j] * wd_[k], j <= k row by
+ *   row;  then, only where wd[i] > 0 (skipped, not added as zero; dobs[i] is read only there):  phi += wrd * wrd;
+ *   phi_d += wrd * wrd;  g[j] += wdd[j] * wrd;  A[q] += wdd[j] * wdd[k].
+ *   Order of the sums: lane l of 256 takes the observations l, l + 256, ... ascending, each accumulator from +0.0; per wave of 64
+ *   lanes the butterfly v = v + v[lane ^ m], m = 32, 16, 8, 4, 2, 1; then wave 0 + wave 1 + wave 2 + wave 3 in that order.  No
+ *   floating-point atomics: a repeated call gives the same bits.
+ * Outputs: sums [nsets][1 + npar + npar (npar+1) / 2 (+ 1 with dh)] = phi | g | upper A | phi_d;  nbad [nsets];  J, Jd
+ * [nsets][nobs][npar] = d, dd and sim, simd [nplans][nobs] = s, sd of EVERY observation, counted or not; each of the four may be
+ * NULL.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): source outside 0..2, npar outside
+ * 0..UCF_FIT_MAX_PAR, nsets outside 1..2^16, nobs outside 1..2^24, nh outside 1..2^28, a NULL array that the call would read or
+ * must write, Jd or simd without dh, and every element the kernel could read under any plan lying outside [0, nh): plan_stride < 1
+ * or nplans plan_stride
+ * > nh, a slot outside 0 .. plan_stride - 1; a ref or term with a negative prefix, stride or at, a count outside 1..UCF_MAX_NZ, or
+ * prefix nplans + (nplans - 1) stride + at + count - 1 >= nh; nref != nobs for a network; first[0] < 0, first not ascending, or
+ * first[nobs] != nref.  Then UCF_ERR_NO_DEVICE without a device. */
+int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_dlog,
+                         long long nh, const double* h, const double* dh /*NULL ok*/, const double* Hc /*[nplans]*/,
+                         const double* obs, const double* w, const double* dobs, const double* wd /*[nobs]*/,
+                         const int* slot /*[nobs]*/, long long plan_stride,
+                         int nref, const long long* prefix, const long long* stride, const int* at, const int* count /*[nref]*/,
+                         const double* q, const double* tfac /*[nref]*/, const int* first /*[nobs + 1]*/,
+                         double* sums, int* nbad, double* J, double* sim, double* Jd, double* simd);
 /* Host only: the nwell real wells followed by their mirror images in the straight line a x + b y = c (xo, yo, qo, t0o
  * [2 nwell]).  An image has q = +q for a no-flow boundary (kind 0), -q for a constant-head boundary (kind 1), and the t0 of its
  * real well.  One boundary only (two parallel boundaries need an infinite image series).  UCF_ERR_BAD_ARGUMENT: a = b = 0, a

@@ -8,7 +8,13 @@ at the deck's parameters theta_star.
 Every bound is derived: b_i = max(1e-10, 10 x the oracle's distance from its binary128 build at that observation) x
 max(|ref_i|, 1e-3) is the gate of test_parameter_batched_sweep_vs_oracle taken per observation; sums are held to the
 classical (n + 4) u sum|terms|; parameters to the first-order displacement of a least-squares minimiser under data errors
-bounded by b."""
+bounded by b.
+
+Problem moench8 is there for the largest instantiation of the fit reduction (NPAR = 8 = UCF_FIT_MAX_PAR, reached by a real call):
+deck c3_moench with a fourth Moench alpha, which the oracle and ucf_fit_perturb accept, free = Kr, kappa, Ss, Sy and the four
+alphas, 12 observations, two parameter sets, one step.  Its values and Jacobian are held to the oracle by the same gate; its
+sums are the documented arithmetic bit for bit (tests/fit_reduce_restate.py); eight log-parameters with four Moench alphas among
+them are not claimed to be identifiable, so of ucf_fit_lm only the contract is asserted."""
 import os
 
 import numpy as np
@@ -21,6 +27,7 @@ pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
 OPT_NAMES = ("max_iter", "dlog", "lambda0", "lambda_up", "lambda_down", "tol_step", "tol_phi")
 PROBLEMS = ["neuman74", "theis"]
+EVAL_PROBLEMS = PROBLEMS + ["moench8"]              # moench8 has no lm part: NPAR = 8, values, Jacobian and sums only
 # overflow regime of the neuman74_partpen deck (rD = 0.01, tD = 1e-4): the Laplace-space samples are NaN, the in-band rules
 # scrub them and the result is NaN.  (The points of test_in_band_rule_counters_match_the_oracle, rD = 0.02 ... 0.7, fire the
 # Wynn rules but every RESULT there is finite, in the oracle too: the NaN point is taken one step further into the same regime.)
@@ -51,7 +58,10 @@ def problem(ufit, key):
     """(fixture, deck parameters, Fit with unit weights)"""
     if key not in _cache:
         fx = fixture(key)
-        _, _, P = load_deck(str(fx["deck"]))
+        dk, _, P = load_deck(str(fx["deck"]))
+        if "moench_alpha" in fx.files:
+            from unconfined_amd.abi import params_from_deck
+            P = params_from_deck(dk.replace(MoenchM=len(fx["moench_alpha"]), MoenchAlpha=fx["moench_alpha"].tolist()))
         f = ufit.Fit(P, [str(n) for n in fx["free"]], fx["t"], fx["r"], fx["z"], fx["iz"], fx["obs"])
         _cache[key] = (fx, P, f)
     return _cache[key]
@@ -113,7 +123,7 @@ def test_reduction_is_the_arithmetic_it_claims(ufit):
     f.close()
 
 
-@pytest.mark.parametrize("key", PROBLEMS)
+@pytest.mark.parametrize("key", EVAL_PROBLEMS)
 def test_values_against_the_oracle(ufit, key):
     """every row of sim_all -- base and perturbed plans, both steps -- within b of the oracle at the same parameters"""
     fx, _, _ = problem(ufit, key)
@@ -126,7 +136,7 @@ def test_values_against_the_oracle(ufit, key):
         assert (err <= bound).all(), (key, d, float((err / bound).max()))
 
 
-@pytest.mark.parametrize("key", PROBLEMS)
+@pytest.mark.parametrize("key", EVAL_PROBLEMS)
 def test_jacobian_against_the_oracle(ufit, key):
     """the oracle's central difference with the same dlog: |J_dev - J_or| <= (b+ + b-) / (2 dlog) element by element (the
     truncation error is common to both sides and cancels)"""
@@ -140,6 +150,48 @@ def test_jacobian_against_the_oracle(ufit, key):
             err = np.abs(out["J"][:, :, j] - J_or)
             print(f"[fit {key}] dlog={dlog:g} parameter {j}: worst |J - J_or| / bound = {float((err / lim).max()):.3f}")
             assert (err <= lim).all(), (key, dlog, j, float((err / lim).max()))
+
+
+def test_sums_of_the_largest_npar_are_the_documented_arithmetic(ufit):
+    """moench8, NPAR = 8: the call's own sim_all fed through the restatement of tests/fit_reduce_restate.py as h (one slot per
+    observation, Hc = 1, so s[k] is the value itself) gives the bits of the call's phi, g, A and J"""
+    import fit_reduce_restate as fr
+    fx, _, f = problem(ufit, "moench8")
+    assert f.npar == 8 and fx["eval_ref"].shape[2] == 17
+    out = evaluated(ufit, "moench8", 0)
+    nsets, nplan, nobs = out["sim_all"].shape
+    inp = dict(source=fr.SLOTS, npar=8, nsets=nsets, nobs=nobs, two_dlog=2.0 * float(fx["eval_dlogs"][0]), h=out["sim_all"].ravel(), dh=None,
+               Hc=np.ones(nsets * nplan), obs=fx["obs"], w=np.ones(nobs), slot=np.arange(nobs, dtype=np.int32), plan_stride=nobs)
+    want = fr.restate(inp)
+    assert (out["nbad"] == 0).all() and (want["nbad"] == 0).all()
+    assert want["sim"].tobytes() == out["sim_all"].tobytes() and want["J"].tobytes() == out["J"].tobytes()
+    assert want["sums"][:, 0].tobytes() == out["phi"].tobytes() and want["sums"][:, 1:9].tobytes() == out["g"].tobytes()
+    iu = np.triu_indices(8)
+    for s in range(nsets):
+        assert want["sums"][s, 9:].tobytes() == out["A"][s][iu].tobytes(), s
+        assert np.array_equal(out["A"][s], out["A"][s].T)
+    # the same data through the hook: the instantiation <8, slots, no derivative data> once more
+    got = fr.debug_fit_reduce(inp)
+    for k in ("sums", "nbad", "J", "sim"):
+        assert got[k].tobytes() == want[k].tobytes(), k
+
+
+def test_lm_contract_at_the_largest_npar(ufit):
+    """moench8: two starts off theta_star (parameter j moved by 25 % up or 20 % down in turn), max_iter = 2.  The trial points run the
+    NPAR = 0 kernel, the steps ucf_fit_solve_step at npar = 8.  Only the contract: a status of the enum, no more than max_iter
+    iterations, and a phi that is not above the phi of its start (from an evaluate there)"""
+    from unconfined_amd import abi
+    fx, _, f = problem(ufit, "moench8")
+    up = np.where(np.arange(8) % 2 == 0, 1.25, 0.8)
+    starts = np.stack([fx["theta_star"] * up, fx["theta_star"] / up])
+    dlog = float(fx["eval_dlogs"][0])
+    phi0 = f.evaluate(starts, dlog, jacobian=True)["phi"]         # the evaluation that ucf_fit_lm begins with
+    res = f.lm(starts, max_iter=2, dlog=dlog)
+    print(f"[fit moench8] lm: status {res['status'].tolist()} iters {res['iters'].tolist()} phi {res['phi'].tolist()} from {phi0.tolist()}")
+    assert np.isfinite(phi0).all()
+    assert set(res["status"].tolist()) <= {abi.FIT_CONVERGED, abi.FIT_MAX_ITER, abi.FIT_SINGULAR, abi.FIT_NONFINITE_START}
+    assert (res["iters"] <= 2).all() and (res["iters"] >= 0).all()
+    assert (res["phi"] <= phi0).all(), (res["phi"], phi0)
 
 
 def lm_options(fx):

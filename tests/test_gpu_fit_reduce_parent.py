@@ -23,9 +23,11 @@ npar = 1 .. len(free) over prefixes of the free list: evaluate(jacobian, sim_all
 data -- its trial points run the NPAR = 0 kernels.  phi, g, A, nbad, phi_d and the lm results are stored in full, J, Jd,
 sim_all and simd_all as the SHA-256 of their bytes.
 
-Not covered: the instantiations with NPAR above the number of free parameters of a problem (plain: 5..8; network and field:
-3..8) are not reached on the device by this fixture; their registers, LDS and occupancy were compared with the parent's from
-the compiler's resource remarks when the bodies were merged."""
+Not covered here: the instantiations with NPAR above the number of free parameters of a problem (plain: 5..8; network and
+field: 3..8) are not reached by this fixture, and recorded bits say "as the parent", not "right".  Both gaps are closed by
+tests/test_gpu_fit_reduce_edges.py, which launches all 54 instantiations on synthetic data through ucf_debug_fit_reduce and
+holds every output bit for bit to the documented arithmetic, and by problem moench8 of tests/test_gpu_fit.py, a real call at
+NPAR = 8."""
 import hashlib
 import os
 

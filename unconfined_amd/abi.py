@@ -18,6 +18,8 @@ PAR_IDS = {"Kr": PAR_KR, "kappa": PAR_KAPPA, "Ss": PAR_SS, "Sy": PAR_SY, "ac": P
 FIT_CONVERGED, FIT_MAX_ITER, FIT_SINGULAR, FIT_NONFINITE_START = range(4)
 # iz of an observation of ucf_fit_create_network / ucf_fit_create_field that is the screen average of its well's depths (UCF_FIT_SCREEN)
 FIT_SCREEN = -1
+# source of ucf_debug_fit_reduce: how an observation finds its simulated value in h
+FIT_SLOTS, FIT_NETWORK, FIT_FIELD = range(3)
 UCF_ERR_BAD_ARGUMENT, UCF_ERR_NO_DEVICE, UCF_ERR_SINGULAR = -11, -12, -16
 
 

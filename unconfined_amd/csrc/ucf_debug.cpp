@@ -6,6 +6,7 @@
 
 #include "ucf_host.h"
 #include "ucf_field.h"
+#include "ucf_fit.h"
 
 using namespace ucf_host;
 
@@ -286,6 +287,117 @@ int ucf_debug_ensemble(int nens, long long nout, const double* a, int nq, const 
         {w->nfin, b_nfin.p, sizeof(int) * no}, {pexc, b_pexc.p, so * nlim}, {nbad, b_nbad.p, sizeof(long long)}};
     for (const auto& c : back)
         if (c.host) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
+    return UCF_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// The refs of ucf_debug_fit_reduce, packed as the kernel reads them.  Every double a ref can reach under any of the nplans
+// plans -- prefix * nplans + plan * stride + at + (0 .. count - 1), the largest at plan = nplans - 1 -- must lie in [0, nh).
+// 128-bit arithmetic: the caller's numbers are arbitrary.
+int pack_refs(const char* what, int n, const long long* prefix, const long long* stride, const int* at, const int* count, long long nplans,
+              long long nh, std::vector<ucf_fit_obs_ref>& out)
+{
+    out.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (prefix[i] < 0 || stride[i] < 0 || at[i] < 0 || count[i] < 1 || count[i] > UCF_MAX_NZ)
+            return fail(UCF_ERR_BAD_ARGUMENT, "%s %d: prefix=%lld stride=%lld at=%d count=%d (none negative, count in 1..%d)", what, i, prefix[i],
+                        stride[i], at[i], count[i], UCF_MAX_NZ);
+        const __int128 last = (__int128)prefix[i] * nplans + (__int128)(nplans - 1) * stride[i] + at[i] + count[i] - 1;
+        if (last >= (__int128)nh)
+            return fail(UCF_ERR_BAD_ARGUMENT, "%s %d: its last depth under plan %lld lies beyond h (prefix=%lld stride=%lld at=%d count=%d, nh=%lld)",
+                        what, i, nplans - 1, prefix[i], stride[i], at[i], count[i], nh);
+        out[(size_t)i] = ucf_fit_obs_ref{prefix[i], stride[i], at[i], count[i]};
+    }
+    return UCF_OK;
+}
+}  // namespace
+
+extern "C" {
+
+// The fit reduction exactly as ucf_fit_evaluate launches it (ucf_fit_launch_reduce, and through it the same choice of
+// instantiation), on caller data: the kernel is testable at its edges without paying for evaluations.  Everything the
+// kernel could read is checked against the lengths the caller gave before anything is allocated or launched.
+int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_dlog, long long nh, const double* h, const double* dh,
+                         const double* Hc, const double* obs, const double* w, const double* dobs, const double* wd, const int* slot,
+                         long long plan_stride, int nref, const long long* prefix, const long long* stride, const int* at,
+                         const int* count, const double* q, const double* tfac, const int* first, double* sums, int* nbad, double* J,
+                         double* sim, double* Jd, double* simd)
+{
+    if (source != UCF_FIT_SLOTS && source != UCF_FIT_NETWORK && source != UCF_FIT_FIELD) return fail(UCF_ERR_BAD_ARGUMENT, "source=%d outside 0..2", source);
+    if (npar < 0 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 0..%d", npar, UCF_FIT_MAX_PAR);
+    if (nsets < 1 || nsets > (1 << 16)) return fail(UCF_ERR_BAD_ARGUMENT, "nsets=%d outside 1..65536", nsets);
+    if (nobs < 1 || nobs > (1 << 24)) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d outside 1..2^24", nobs);
+    if (nh < 1 || nh > (1LL << 28)) return fail(UCF_ERR_BAD_ARGUMENT, "nh=%lld outside 1..2^28", nh);
+    if (!h || !Hc || !obs || !w || !sums || !nbad) return fail(UCF_ERR_BAD_ARGUMENT, "NULL h, Hc, obs, w, sums or nbad");
+    if (dh && (!dobs || !wd)) return fail(UCF_ERR_BAD_ARGUMENT, "dh without dobs or wd");
+    if (!dh && (Jd || simd)) return fail(UCF_ERR_BAD_ARGUMENT, "Jd or simd asked for without dh");
+    const long long nplans = (long long)nsets * (1 + 2 * npar);
+    std::vector<ucf_fit_obs_ref> refs;
+    std::vector<ucf_fit_term> terms;
+    int rc;
+    if (source == UCF_FIT_SLOTS) {
+        if (!slot) return fail(UCF_ERR_BAD_ARGUMENT, "NULL slot");
+        if (plan_stride < 1 || (__int128)plan_stride * nplans > (__int128)nh)
+            return fail(UCF_ERR_BAD_ARGUMENT, "plan_stride=%lld: %lld plans of it do not fit in nh=%lld", plan_stride, nplans, nh);
+        for (int i = 0; i < nobs; i++)
+            if (slot[i] < 0 || slot[i] >= plan_stride) return fail(UCF_ERR_BAD_ARGUMENT, "slot[%d]=%d outside 0..plan_stride-1=%lld", i, slot[i], plan_stride - 1);
+    } else {
+        if (!prefix || !stride || !at || !count) return fail(UCF_ERR_BAD_ARGUMENT, "NULL prefix, stride, at or count");
+        if (source == UCF_FIT_NETWORK) {
+            if (nref != nobs) return fail(UCF_ERR_BAD_ARGUMENT, "nref=%d: a network has one ref per observation (nobs=%d)", nref, nobs);
+            if ((rc = pack_refs("ref", nref, prefix, stride, at, count, nplans, nh, refs))) return rc;
+        } else {
+            if (nref < 0 || !first || !q || (dh && !tfac)) return fail(UCF_ERR_BAD_ARGUMENT, "nref=%d negative, or NULL first, q or (with dh) tfac", nref);
+            if (first[0] < 0) return fail(UCF_ERR_BAD_ARGUMENT, "first[0]=%d negative", first[0]);
+            for (int i = 0; i < nobs; i++)
+                if (first[i + 1] < first[i]) return fail(UCF_ERR_BAD_ARGUMENT, "first[%d]=%d below first[%d]=%d: not ascending", i + 1, first[i + 1], i, first[i]);
+            if (first[nobs] != nref) return fail(UCF_ERR_BAD_ARGUMENT, "first[nobs]=%d is not the number of terms %d", first[nobs], nref);
+            if ((rc = pack_refs("term", nref, prefix, stride, at, count, nplans, nh, refs))) return rc;
+            terms.resize((size_t)nref);
+            for (int k = 0; k < nref; k++) terms[(size_t)k] = ucf_fit_term{refs[(size_t)k], q[k]};
+        }
+    }
+    if ((rc = require_device())) return rc;
+    const bool joint = dh != nullptr;
+    const size_t so = sizeof(double) * (size_t)nobs, sh = sizeof(double) * (size_t)nh, nt = (size_t)(nref > 0 ? nref : 1);
+    const size_t nsum = (size_t)(joint ? ucf_fit_joint_nsums(npar) : ucf_fit_nsums(npar));
+    const size_t bJ = so * nsets * (npar > 0 ? npar : 1), bsim = so * (size_t)nplans;
+    dev_buf b_h, b_dh, b_hc, b_obs, b_w, b_dobs, b_wd, b_slot, b_ref, b_term, b_first, b_tfac, b_sums, b_nbad, b_J, b_sim, b_Jd, b_simd;
+    if (b_h.alloc(sh) || (joint && b_dh.alloc(sh)) || b_hc.alloc(sizeof(double) * (size_t)nplans) || b_obs.alloc(so) || b_w.alloc(so) ||
+        (joint && (b_dobs.alloc(so) || b_wd.alloc(so))) || (source == UCF_FIT_SLOTS && b_slot.alloc(sizeof(int) * (size_t)nobs)) ||
+        (source == UCF_FIT_NETWORK && b_ref.alloc(sizeof(ucf_fit_obs_ref) * nt)) ||
+        (source == UCF_FIT_FIELD && (b_term.alloc(sizeof(ucf_fit_term) * nt) || b_first.alloc(sizeof(int) * ((size_t)nobs + 1)) ||
+                                     (joint && b_tfac.alloc(sizeof(double) * nt)))) ||
+        b_sums.alloc(sizeof(double) * nsets * nsum) || b_nbad.alloc(sizeof(int) * (size_t)nsets) || (J && b_J.alloc(bJ)) || (sim && b_sim.alloc(bsim)) ||
+        (Jd && b_Jd.alloc(bJ)) || (simd && b_simd.alloc(bsim)))
+        return fail(UCF_ERR_NOMEM, "device allocation failed");
+    const struct { void* dev; const void* host; size_t bytes; } up[] = {
+        {b_h.p, h, sh}, {b_dh.p, dh, sh}, {b_hc.p, Hc, sizeof(double) * (size_t)nplans}, {b_obs.p, obs, so}, {b_w.p, w, so}, {b_dobs.p, dobs, so},
+        {b_wd.p, wd, so}, {b_slot.p, slot, sizeof(int) * (size_t)nobs}, {b_ref.p, refs.data(), sizeof(ucf_fit_obs_ref) * refs.size()},
+        {b_term.p, terms.data(), sizeof(ucf_fit_term) * terms.size()}, {b_first.p, first, sizeof(int) * ((size_t)nobs + 1)},
+        {b_tfac.p, tfac, sizeof(double) * terms.size()}};
+    for (const auto& c : up)
+        if (c.dev && c.bytes) HIP_TRY(hipMemcpy(c.dev, c.host, c.bytes, hipMemcpyHostToDevice));
+    ucf_fit_reduce_args ra = {};
+    ra.npar = npar; ra.nsets = nsets; ra.nobs = nobs;
+    ra.nplans = (size_t)nplans; ra.plan_stride = (size_t)plan_stride; ra.two_dlog = two_dlog;
+    ra.d_h = (const double*)b_h.p; ra.d_dh = (const double*)b_dh.p; ra.d_Hc = (const double*)b_hc.p;
+    ra.source = (ucf_fit_source)source;
+    ra.d_slot = (const int*)b_slot.p; ra.d_ref = (const ucf_fit_obs_ref*)b_ref.p;
+    ra.d_term = (const ucf_fit_term*)b_term.p; ra.d_first = (const int*)b_first.p; ra.d_tfac = (const double*)b_tfac.p;
+    ra.d_obs = (const double*)b_obs.p; ra.d_w = (const double*)b_w.p; ra.d_dobs = (const double*)b_dobs.p; ra.d_wd = (const double*)b_wd.p;
+    ra.d_sums = (double*)b_sums.p; ra.d_nbad = (int*)b_nbad.p;
+    ra.d_J = (double*)b_J.p; ra.d_sim = (double*)b_sim.p; ra.d_Jd = (double*)b_Jd.p; ra.d_simd = (double*)b_simd.p;
+    rc = ucf_fit_launch_reduce(&ra, nullptr);
+    if (rc) return fail(rc, "fit reduction kernel launch failed");
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    const struct { void* host; const void* dev; size_t bytes; } back[] = {
+        {sums, b_sums.p, sizeof(double) * nsets * nsum}, {nbad, b_nbad.p, sizeof(int) * (size_t)nsets}, {J, b_J.p, npar > 0 ? bJ : 0}, {sim, b_sim.p, bsim},
+        {Jd, b_Jd.p, npar > 0 ? bJ : 0}, {simd, b_simd.p, bsim}};
+    for (const auto& c : back)
+        if (c.host && c.bytes) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
     return UCF_OK;
 }
 

@@ -43,7 +43,7 @@ EXPORTS = [
     "ucf_field_create", "ucf_field_destroy", "ucf_field_group_count", "ucf_field_group", "ucf_field_group_from_params",
     "ucf_field_drawdown", "ucf_field_alloc_count", "ucf_field_images",
     "ucf_field_forecast_sets", "ucf_field_forecast",
-    "ucf_field_ensemble", "ucf_field_ensemble_draw", "ucf_debug_ensemble",
+    "ucf_field_ensemble", "ucf_field_ensemble_draw", "ucf_debug_ensemble", "ucf_debug_fit_reduce",
 ]
 
 
@@ -173,6 +173,8 @@ def load() -> C.CDLL:
                                        C.POINTER(UcfEnsembleMaps), C.POINTER(UcfEnsembleMaps), vp, vp, C.POINTER(UcfStats)]
     lib.ucf_field_ensemble_draw.argtypes = [C.c_int, vp, vp, C.c_int, C.c_ulonglong, vp]
     lib.ucf_debug_ensemble.argtypes = [C.c_int, C.c_longlong, vp, C.c_int, vp, C.c_int, vp, C.POINTER(UcfEnsembleMaps), vp, vp]
+    # every array may be NULL for a source or a call that does not read it: plain addresses
+    lib.ucf_debug_fit_reduce.argtypes = ([C.c_int] * 4 + [C.c_double, C.c_longlong] + [vp] * 8 + [C.c_longlong, C.c_int] + [vp] * 7 + [vp] * 6)
     _lib = lib
     return lib
 
