@@ -484,6 +484,16 @@ int ucf_fit_evaluate_joint(ucf_fit* fit, int nsets, const double* theta /*[nsets
                            double* phi_d, double* Jd, double* simd_all);
 /* diagnostic: as ucf_fit_debug_h, the dimensionless dh behind observation (field fit: term) i of the last evaluation */
 int ucf_fit_debug_dh(ucf_fit* fit, int plan, int i, int cap, double* dh, int* n);
+/* The objective of many parameter sets without a Jacobian: what ucf_fit_lm runs at its trial points.  Only the base plan of
+ * every set is evaluated (nsets plans, not nsets (1 + 2 npar)) and the reduction is the npar = 0 instantiation of
+ * fit_reduce_kernel, in the order of sums stated with ucf_debug_fit_reduce.  Every kind of fit (ucf_fit_create,
+ * ucf_fit_create_network, ucf_fit_create_field).  phi [nsets], nbad [nsets]; sim [nsets][nobs] the simulated value of EVERY
+ * observation, counted or not (NULL ok).  On a fit with derivative data phi is the joint sum, and phi_d [nsets], the derivative
+ * terms' share of it, and simd [nsets][nobs] may be asked for; without derivative data either of them is UCF_ERR_BAD_ARGUMENT.
+ * The checks of ucf_fit_evaluate except dlog, which is not an argument; nsets up to 2^20.  A repeated call of the same size
+ * allocates nothing (ucf_fit_alloc_count). */
+int ucf_fit_objective(ucf_fit* fit, int nsets, const double* theta /*[nsets][npar]*/,
+                      double* phi, int* nbad, double* sim /*NULL ok*/, double* phi_d /*NULL ok*/, double* simd /*NULL ok*/);
 
 /* ---- well fields: the drawdown of several pumping wells -- wells that start at different times, image wells for a river or an
  * outcrop -- is the sum over wells of q_j h(t - t0_j, |x - x_j|, z).  All wells share the plan's aquifer, well geometry and
@@ -677,6 +687,75 @@ int ucf_field_ensemble_draw(int npar, const double* theta, const double* cov /*[
 int ucf_debug_ensemble(int nens, long long nout, const double* a, int nq, const double* q,
                        int nlim, const double* limit, const ucf_ensemble_maps* out /*all ignored*/,
                        double* pexc, long long* nbad /*[1]*/);
+/* ---- weighted ensembles.  The members of ucf_field_ensemble count equally, which is right for draws from a distribution and
+ * wrong for a Latin hypercube or the rows of a multi-start fit: there every member is weighted by its likelihood against the
+ * observations (importance sampling; GLUE with a formal likelihood).  Three host functions and one call:
+ * ucf_fit_objective -> ucf_ensemble_likelihood_weights -> ucf_field_ensemble_weighted (which calls ucf_ensemble_quantise).
+ *
+ * host only, no GPU: integer weights.  wmax = the largest weight[m];
+ *     r = weight[m] / wmax;   u[m] = (unsigned long long)floor(r * 4294967296.0 + 0.5)            (0 .. 2^32, u of wmax is 2^32)
+ *     U = sum of u[m] (integer);   U2 = +0.0;  U2 = U2 + (double)u[m] * (double)u[m], m ascending;   *ess = (double)U * (double)U / U2
+ * (Kish's effective sample size; ess NULL ok).  Why integers: every cumulative weight on the device is then a 64-bit integer sum
+ * of at most 2^42 -- exact and independent of the order of summation -- so exactly one member is selected per quantile level
+ * and a repeated call gives the same bits.  A member with u[m] = 0 (a weight below 2^-33 of the largest) IS NOT IN THE ENSEMBLE:
+ * it takes part in no statistic and in no count.  With all weights equal every u is 2^32, and mean, sd and pexc below have the
+ * bits of the unweighted ones.  UCF_ERR_BAD_ARGUMENT (the member named in ucf_last_error): nens outside 1..UCF_ENSEMBLE_MAX, a
+ * NULL array, a weight that is negative or not finite, all weights 0. */
+int ucf_ensemble_quantise(int nens, const double* weight, unsigned long long* u /*[nens]*/, double* ess /*NULL ok*/);
+/* host only, no GPU: likelihood weights from the objectives of ucf_fit_objective.  Member m is admissible when phi[m] is finite
+ * and nbad[m] == 0 (nbad NULL: the first test alone); best = the admissible member of least phi, the lowest index on a tie;
+ *     weight[m] = exp(-0.5 * ((phi[m] - phi[best]) / s2))   each operation rounded on its own;   0 where m is not admissible;
+ * weight[best] is exactly 1.  s2 is the variance factor: 1 where the fit's weights are true 1 / sigma, else an estimate such as
+ * phi[best] / (nobs + nd - npar), the factor of cov in ucf_fit_lm.  best, nadmissible: NULL ok.  UCF_ERR_BAD_ARGUMENT: nens
+ * outside 1..UCF_ENSEMBLE_MAX, NULL phi or weight, s2 not positive and finite, no admissible member. */
+int ucf_ensemble_likelihood_weights(int nens, const double* phi, const int* nbad /*NULL ok*/, double s2,
+                                    double* weight /*[nens]*/, int* best, int* nadmissible);
+/* ucf_field_ensemble with a weight per member.  Everything is as stated there -- members, plan, per member, outputs, buffers,
+ * validation of every member before the first launch -- except:
+ *   weights      u = ucf_ensemble_quantise(weight), with its checks, after the other argument checks and before any GPU work;
+ *                u [nens], *ess and *nlaunched (each NULL ok) are written then, with or without a device.
+ *   per member   a member with u[m] = 0 is validated but NOT LAUNCHED; its slot in both buffers is filled with NaN bytes (0xff), so
+ *                `all` is defined.  *nlaunched = the number of members with u > 0; stats sums over them.  The scratch plan is
+ *                made from, or refreshed to, the first launched member.  A launched slot has the bits of ucf_field_drawdown on
+ *                a fresh field and a fresh plan of that member.
+ *   reduction    u [nens] is a buffer of the field (grown on demand, kept, counted in ucf_field_alloc_count), read by the kernels
+ *                at wave-uniform addresses.  For output e: F = the members m with a[m][e] finite AND u[m] > 0, in member order;
+ *                n = |F|;  U = sum_F u[m], a 64-bit integer sum.  Every operation is rounded on its own.
+ *                field_ensemble_wmoments_kernel, one thread per output:
+ *                    nfin[e] = n;
+ *                    acc = +0.0;  for m in F:  acc = acc + (double)u[m] * a[m][e];     mean[e] = acc / (double)U      (n = 0: NaN)
+ *                    U2 = +0.0;   for m in F:  U2 = U2 + (double)u[m] * (double)u[m];
+ *                    ss = +0.0;   for m in F:  d = a[m][e] - mean[e];  ss = ss + (double)u[m] * (d * d);
+ *                    den = (double)U - U2 / (double)U;
+ *                    sd[e] = sqrt(ss / den)      (NaN where n < 2 or den is not positive) -- the reliability-weights estimator;
+ *                            with equal weights den = (n - 1) 2^32 exactly;
+ *                    min[e], max[e]: the compare-and-replace rules of ucf_field_ensemble, over F;
+ *                    pexc[l][e] = (double)(sum of u[m] over the m in F with a[m][e] > limit[l]) / (double)U, an integer sum, the
+ *                            comparison strict                                                                    (n = 0: NaN)
+ *                field_ensemble_wquantile_kernel: the inverse of the weighted empirical distribution function (the rule of
+ *                numpy's quantile(weights=, method="inverted_cdf"); the cumulative-likelihood rule of GLUE).  In the stable
+ *                order of ucf_field_ensemble (ascending, ties in member order) member m has in front of it the weight
+ *                    E_m = sum of u[m'] over the m' in F with v' < v or (v' == v and m' < m)                  (an integer sum)
+ *                and for level p = q[i]:   tgt = p * (double)U   (one rounded product);
+ *                    quant[i][e] = the value of the member with (double)E_m < tgt && tgt <= (double)(E_m + u[m]);
+ *                                  where tgt == 0 the member with E_m == 0                                        (n = 0: NaN)
+ *                No interpolation.  The intervals (E_m, E_m + u[m]] partition (0, U]: exactly one member matches.  Tied members
+ *                have one value, so the order among them only decides which of -0.0 and +0.0 is returned.  With equal weights
+ *                the result is the order statistic of index ceil(p n) - 1 (index 0 at p = 0).
+ *                nbad[0] (s), nbad[1] (ds) count the outputs with n < the number of members with u > 0.
+ * ucf_field_ensemble itself runs what it ran before: its kernels take no weights. */
+int ucf_field_ensemble_weighted(ucf_field* field, ucf_plan* plan, int npar, const int* ids,
+                                int nens, const double* thetas /*[nens][npar]*/, const double* weight /*[nens]*/,
+                                int nz, const double* z, int nq, const double* q, int nlim, const double* limit,
+                                const ucf_ensemble_maps* s, const ucf_ensemble_maps* ds, double* pexc,
+                                long long* nbad /*[2]*/, ucf_stats* stats,
+                                unsigned long long* u /*[nens]; NULL ok*/, double* ess /*NULL ok*/, int* nlaunched /*NULL ok*/);
+/* the two weighted reduction kernels exactly as ucf_field_ensemble_weighted launches them, on caller data a[nens][nout] and
+ * caller weights: the twin of ucf_debug_ensemble.  Its checks, then those of ucf_ensemble_quantise, then UCF_ERR_NO_DEVICE
+ * without a device. */
+int ucf_debug_ensemble_weighted(int nens, long long nout, const double* a, const double* weight /*[nens]*/,
+                                int nq, const double* q, int nlim, const double* limit,
+                                const ucf_ensemble_maps* out /*all ignored*/, double* pexc, long long* nbad /*[1]*/);
 /* The reduction kernel of ucf_fit_evaluate exactly as a fit launches it (the same launcher, and through it the same choice among the
  * instantiations: npar 0..UCF_FIT_MAX_PAR x source x with / without derivative data), on caller data.  One 256-thread workgroup
  * per parameter set; set s owns the plans s (1 + 2 npar) + (0 base | 1 + 2j: parameter j up | 2 + 2j: parameter j down);

@@ -290,6 +290,50 @@ int ucf_debug_ensemble(int nens, long long nout, const double* a, int nq, const 
     return UCF_OK;
 }
 
+// The two weighted reduction kernels of ucf_field_ensemble_weighted on caller data a [nens][nout] and caller weights: the
+// same quantisation and the same launchers.
+int ucf_debug_ensemble_weighted(int nens, long long nout, const double* a, const double* weight, int nq, const double* q, int nlim,
+                                const double* limit, const ucf_ensemble_maps* out, double* pexc, long long* nbad)
+{
+    const ucf_ensemble_maps none = {};
+    const ucf_ensemble_maps* w = out ? out : &none;
+    int rc = ensemble_check_levels(nens, nq, q, nlim, limit, w->quant != nullptr, pexc != nullptr);
+    if (rc) return rc;
+    if (!a) return fail(UCF_ERR_BAD_ARGUMENT, "NULL a");
+    if (nout < 1 || nens * nout > 0x7fffffffLL * 256) return fail(UCF_ERR_BAD_ARGUMENT, "nout=%lld: at least one output, at most 2^39 values", nout);
+    std::vector<unsigned long long> u((size_t)nens);
+    if ((rc = ucf_ensemble_quantise(nens, weight, u.data(), nullptr))) return rc;
+    if ((rc = require_device())) return rc;
+    const size_t no = (size_t)nout, so = sizeof(double) * no;
+    dev_buf b_a, b_u, b_ql, b_mean, b_sd, b_min, b_max, b_quant, b_nfin, b_pexc, b_nbad;
+    if (b_a.alloc(so * nens) || b_u.alloc(sizeof(unsigned long long) * nens) || b_ql.alloc(sizeof(double) * 2 * UCF_ENSEMBLE_MAX_Q) ||
+        b_nbad.alloc(sizeof(long long)) || (w->mean && b_mean.alloc(so)) || (w->sd && b_sd.alloc(so)) || (w->min && b_min.alloc(so)) ||
+        (w->max && b_max.alloc(so)) || (w->quant && b_quant.alloc(so * nq)) || (w->nfin && b_nfin.alloc(sizeof(int) * no)) ||
+        (pexc && b_pexc.alloc(so * nlim)))
+        return fail(UCF_ERR_NOMEM, "device allocation failed");
+    double ql[2 * UCF_ENSEMBLE_MAX_Q] = {};
+    for (int i = 0; i < nq; i++) ql[i] = q[i];
+    for (int i = 0; i < nlim; i++) ql[UCF_ENSEMBLE_MAX_Q + i] = limit[i];
+    HIP_TRY(hipMemcpy(b_a.p, a, so * nens, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_u.p, u.data(), sizeof(unsigned long long) * nens, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_ql.p, ql, sizeof(ql), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b_nbad.p, 0, sizeof(long long)));
+    rc = ucf_field_launch_ensemble_wmoments(nens, nout, (const double*)b_a.p, (const unsigned long long*)b_u.p, nlim,
+                                            (const double*)b_ql.p + UCF_ENSEMBLE_MAX_Q, (double*)b_mean.p, (double*)b_sd.p, (double*)b_min.p,
+                                            (double*)b_max.p, (int*)b_nfin.p, (double*)b_pexc.p, (long long*)b_nbad.p, nullptr);
+    if (rc == UCF_OK && w->quant)
+        rc = ucf_field_launch_ensemble_wquantile(nens, nout, (const double*)b_a.p, (const unsigned long long*)b_u.p, nq, (const double*)b_ql.p,
+                                                 (double*)b_quant.p, nullptr);
+    if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    const struct { void* host; const void* dev; size_t bytes; } back[] = {
+        {w->mean, b_mean.p, so}, {w->sd, b_sd.p, so}, {w->min, b_min.p, so}, {w->max, b_max.p, so}, {w->quant, b_quant.p, so * nq},
+        {w->nfin, b_nfin.p, sizeof(int) * no}, {pexc, b_pexc.p, so * nlim}, {nbad, b_nbad.p, sizeof(long long)}};
+    for (const auto& c : back)
+        if (c.host) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
+    return UCF_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -36,13 +36,15 @@ struct ucf_field {
     ucf_buffer b_sall, b_dsall, b_sens, b_dsens, b_se, b_dse, b_cov, b_nbad;
     // ucf_field_ensemble: its slots [nens][nout] are b_sall / b_dsall; the levels, the limits and the staging of every statistic
     ucf_buffer b_ens;
+    // ucf_field_ensemble_weighted: the integer weights u [nens]
+    ucf_buffer b_u;
     ucf_plan* scratch = nullptr;           // the plan that ucf_field_forecast refreshes for every parameter set
     long long n_alloc = 0;
     // every device buffer above: the one list (ucf_field_destroy frees through it)
-    std::array<ucf_buffer*, 20> buffers()
+    std::array<ucf_buffer*, 21> buffers()
     {
         return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats, &b_sall, &b_dsall, &b_sens, &b_dsens,
-                 &b_se, &b_dse, &b_cov, &b_nbad, &b_ens}};
+                 &b_se, &b_dse, &b_cov, &b_nbad, &b_ens, &b_u}};
     }
 };
 
@@ -257,17 +259,21 @@ int field_scratch_plan(ucf_field* f, const ucf_plan* pl, const ucf_params& first
 }
 
 // What ucf_field_forecast and ucf_field_ensemble run per parameter set, for k = 0 .. nset-1 in this order: the scratch plan
-// (which holds set 0) refreshed to sets[k], then field_map_core under the launch arrays that launch_of(k, L) hands out --
+// (which holds the first set that runs) refreshed to sets[k], then field_map_core under the launch arrays that launch_of(k, L) hands out --
 // kept from the checks (forecast) or formed again (ensemble) -- into slot k of b_sall / b_dsall [nset][nout], dimensional.
-// A set that anything refuses: failed(rc, k).
+// A set that anything refuses: failed(rc, k).  With u (ucf_field_ensemble_weighted) a set with u[k] == 0 is left out, its slot
+// untouched; the scratch plan then holds the first set that is not.
 template <class Launch, class Failed>
 int field_map_sets(ucf_field* f, int nset, const ucf_params* sets, Launch launch_of, int nz, const double* z, long long nout,
-                   ucf_stats* stats, Failed failed)
+                   ucf_stats* stats, Failed failed, const unsigned long long* u = nullptr)
 {
     ucf_plan* sp = f->scratch;
+    bool held = true;                      // the scratch plan holds the next set that runs
     for (int k = 0; k < nset; k++) {
         int rc;
-        if (k > 0 && (rc = ucf_plan_update(sp, &sets[k]))) return failed(rc, k);
+        if (u && u[k] == 0) continue;
+        if (!held && (rc = ucf_plan_update(sp, &sets[k]))) return failed(rc, k);
+        held = false;
         const std::vector<field_launch>* L = nullptr;
         if ((rc = launch_of(k, L))) return failed(rc, k);
         rc = field_map_core(f, sp, *L, nz, z, 0, (double*)f->b_sall.p + (size_t)k * nout, (double*)f->b_dsall.p + (size_t)k * nout, stats);
@@ -520,9 +526,13 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
     return UCF_OK;
 }
 
-int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, int nz, const double* z,
-                       int nq, const double* q, int nlim, const double* limit, const ucf_ensemble_maps* s, const ucf_ensemble_maps* ds,
-                       double* pexc, long long* nbad, ucf_stats* stats)
+// ucf_field_ensemble (weighted == false: weight, u_out, ess, nlaunched are not read) and ucf_field_ensemble_weighted: one
+// sequence.  The weighted call differs in three places: the weights are quantised among the checks; a member with u = 0 is
+// validated but not launched, and its slots are filled with NaN bytes; the reduction kernels are the weighted ones.
+static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, int nz, const double* z,
+                               int nq, const double* q, int nlim, const double* limit, const ucf_ensemble_maps* s, const ucf_ensemble_maps* ds,
+                               double* pexc, long long* nbad, ucf_stats* stats, bool weighted, const double* weight,
+                               unsigned long long* u_out, double* ess, int* nlaunched)
 {
     long long nout = 0;
     int rc = field_check_call(f, nz, !z ? "NULL z" : !ids ? "NULL ids" : !thetas ? "NULL thetas" : nullptr, z, nout);
@@ -538,6 +548,19 @@ int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int
         }
     if (nens * nout > 0x7fffffffLL * 256)
         return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d times x %d locations x %d depths: too many values for one buffer", nens, f->nt, f->nloc, nz);
+    std::vector<unsigned long long> u;
+    int first = 0, nrun = nens;            // the first member that is launched, and how many are
+    if (weighted) {
+        u.resize(nens);
+        double e = 0.0;
+        if ((rc = ucf_ensemble_quantise(nens, weight, u.data(), &e))) return rc;
+        nrun = 0;
+        for (int m = nens - 1; m >= 0; m--)
+            if (u[m] != 0) { first = m; nrun++; }
+        if (u_out) std::copy(u.begin(), u.end(), u_out);
+        if (ess) *ess = e;
+        if (nlaunched) *nlaunched = nrun;
+    }
     if (!pl) {
         rc = require_device();
         return rc ? rc : fail(UCF_ERR_BAD_ARGUMENT, "NULL plan");
@@ -555,7 +578,7 @@ int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int
     if (f->device >= 0 && f->device != pl->device)
         return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
     if (stats) std::memset(stats, 0, sizeof(*stats));
-    if ((rc = field_scratch_plan(f, pl, sets[0]))) return rc;
+    if ((rc = field_scratch_plan(f, pl, sets[first]))) return rc;
     ucf_plan* sp = f->scratch;
     device_switch dg(pl->device);
     f->device = pl->device;
@@ -575,13 +598,14 @@ int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int
     off_pexc = take(pexc, no * nlim);
     if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every member", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every member", f->n_alloc)) ||
         (rc = grow_buffer(f->b_nbad, sizeof(long long) * 2, "counts", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_ens, sizeof(double) * used, "ensemble statistics", f->n_alloc))) return rc;
+        (rc = grow_buffer(f->b_ens, sizeof(double) * used, "ensemble statistics", f->n_alloc)) ||
+        (weighted && (rc = grow_buffer(f->b_u, sizeof(unsigned long long) * nens, "ensemble weights", f->n_alloc)))) return rc;
     double* base = (double*)f->b_ens.p;
     auto dev = [&](size_t o) { return o == (size_t)-1 ? nullptr : base + o; };
     for (int i = 0; i < 2; i++) at[i] = map_at{dev(off[i][0]), dev(off[i][1]), dev(off[i][2]), dev(off[i][3]), dev(off[i][4]), (int*)dev(off[i][5])};
     double* d_pexc = dev(off_pexc);
     rc = field_map_sets(f, nens, sets.data(), [&](int m, const std::vector<field_launch>*& Lm) { Lm = &L; return field_launches_of(f, sets[m], L); },
-                        nz, z, nout, stats, failed);
+                        nz, z, nout, stats, failed, weighted ? u.data() : nullptr);
     if (rc) return rc;
     hipStream_t st = plan_stream(sp);
     if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
@@ -593,10 +617,26 @@ int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int
         hipMemcpyAsync(base, ql, sizeof(ql), hipMemcpyHostToDevice, st) != hipSuccess)
         return fail(UCF_ERR_HIP, "upload of the ensemble's arrays failed: %s", hipGetErrorString(hipGetLastError()));
     const double* slots[2] = {(const double*)f->b_sall.p, (const double*)f->b_dsall.p};
+    const unsigned long long* d_u = nullptr;
+    if (weighted) {
+        // the weights, and NaN bytes into the slots of the members that were not launched, so that `all` is defined
+        d_u = (const unsigned long long*)f->b_u.p;
+        bool ok = hipMemcpyAsync(f->b_u.p, u.data(), sizeof(unsigned long long) * nens, hipMemcpyHostToDevice, st) == hipSuccess;
+        for (int m = 0; m < nens && ok; m++)
+            if (u[m] == 0)
+                ok = hipMemsetAsync((double*)f->b_sall.p + (size_t)m * no, 0xff, so, st) == hipSuccess &&
+                     hipMemsetAsync((double*)f->b_dsall.p + (size_t)m * no, 0xff, so, st) == hipSuccess;
+        if (!ok) return fail(UCF_ERR_HIP, "upload of the ensemble's weights failed: %s", hipGetErrorString(hipGetLastError()));
+    }
     for (int i = 0; i < 2 && rc == UCF_OK; i++) {
-        rc = ucf_field_launch_ensemble_moments(nens, nout, slots[i], nlim, base + UCF_ENSEMBLE_MAX_Q, at[i].mean, at[i].sd, at[i].min, at[i].max,
-                                               at[i].nfin, i == 0 ? d_pexc : nullptr, (long long*)f->b_nbad.p + i, st);
-        if (rc == UCF_OK && at[i].quant) rc = ucf_field_launch_ensemble_quantile(nens, nout, slots[i], nq, base, at[i].quant, st);
+        double* pe = i == 0 ? d_pexc : nullptr;
+        long long* nb = (long long*)f->b_nbad.p + i;
+        const double* lim = base + UCF_ENSEMBLE_MAX_Q;
+        rc = d_u ? ucf_field_launch_ensemble_wmoments(nens, nout, slots[i], d_u, nlim, lim, at[i].mean, at[i].sd, at[i].min, at[i].max, at[i].nfin, pe, nb, st)
+                 : ucf_field_launch_ensemble_moments(nens, nout, slots[i], nlim, lim, at[i].mean, at[i].sd, at[i].min, at[i].max, at[i].nfin, pe, nb, st);
+        if (rc == UCF_OK && at[i].quant)
+            rc = d_u ? ucf_field_launch_ensemble_wquantile(nens, nout, slots[i], d_u, nq, base, at[i].quant, st)
+                     : ucf_field_launch_ensemble_quantile(nens, nout, slots[i], nq, base, at[i].quant, st);
     }
     if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     // only what is asked for crosses the bus
@@ -611,6 +651,67 @@ int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int
         if (c.host && hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
             return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
     if (hipStreamSynchronize(st) != hipSuccess) return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
+    return UCF_OK;
+}
+
+int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, int nz, const double* z,
+                       int nq, const double* q, int nlim, const double* limit, const ucf_ensemble_maps* s, const ucf_ensemble_maps* ds,
+                       double* pexc, long long* nbad, ucf_stats* stats)
+{
+    return field_ensemble_core(f, pl, npar, ids, nens, thetas, nz, z, nq, q, nlim, limit, s, ds, pexc, nbad, stats, false, nullptr, nullptr,
+                               nullptr, nullptr);
+}
+
+int ucf_field_ensemble_weighted(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, const double* weight,
+                                int nz, const double* z, int nq, const double* q, int nlim, const double* limit, const ucf_ensemble_maps* s,
+                                const ucf_ensemble_maps* ds, double* pexc, long long* nbad, ucf_stats* stats, unsigned long long* u, double* ess,
+                                int* nlaunched)
+{
+    return field_ensemble_core(f, pl, npar, ids, nens, thetas, nz, z, nq, q, nlim, limit, s, ds, pexc, nbad, stats, true, weight, u, ess,
+                               nlaunched);
+}
+
+int ucf_ensemble_quantise(int nens, const double* weight, unsigned long long* u, double* ess)
+{
+    if (nens < 1 || nens > UCF_ENSEMBLE_MAX) return fail(UCF_ERR_BAD_ARGUMENT, "nens=%d outside 1..%d", nens, UCF_ENSEMBLE_MAX);
+    if (!weight || !u) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !weight ? "weight" : "u");
+    double wmax = 0.0;
+    for (int m = 0; m < nens; m++) {
+        if (!(weight[m] >= 0.0) || !std::isfinite(weight[m]))
+            return fail(UCF_ERR_BAD_ARGUMENT, "member %d: weight=%g must be finite and not negative", m, weight[m]);
+        if (weight[m] > wmax) wmax = weight[m];
+    }
+    if (!(wmax > 0.0)) return fail(UCF_ERR_BAD_ARGUMENT, "all %d weights are 0: no member is in the ensemble", nens);
+    unsigned long long U = 0;
+    double U2 = 0.0;
+    for (int m = 0; m < nens; m++) {
+        const double r = weight[m] / wmax;
+        u[m] = (unsigned long long)std::floor(r * 4294967296.0 + 0.5);
+        U += u[m];
+        U2 = U2 + (double)u[m] * (double)u[m];
+    }
+    if (ess) *ess = (double)U * (double)U / U2;
+    return UCF_OK;
+}
+
+int ucf_ensemble_likelihood_weights(int nens, const double* phi, const int* nbad, double s2, double* weight, int* best, int* nadmissible)
+{
+    if (nens < 1 || nens > UCF_ENSEMBLE_MAX) return fail(UCF_ERR_BAD_ARGUMENT, "nens=%d outside 1..%d", nens, UCF_ENSEMBLE_MAX);
+    if (!phi || !weight) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !phi ? "phi" : "weight");
+    if (!(s2 > 0.0) || !std::isfinite(s2)) return fail(UCF_ERR_BAD_ARGUMENT, "s2=%g must be positive and finite", s2);
+    int b = -1, nadm = 0;
+    for (int m = 0; m < nens; m++) {
+        if (!std::isfinite(phi[m]) || (nbad && nbad[m] != 0)) continue;
+        nadm++;
+        if (b < 0 || phi[m] < phi[b]) b = m;
+    }
+    if (b < 0) return fail(UCF_ERR_BAD_ARGUMENT, "no admissible member among %d: every phi is not finite or has nbad > 0", nens);
+    for (int m = 0; m < nens; m++) {
+        const bool adm = std::isfinite(phi[m]) && !(nbad && nbad[m] != 0);
+        weight[m] = adm ? std::exp(-0.5 * ((phi[m] - phi[b]) / s2)) : 0.0;
+    }
+    if (best) *best = b;
+    if (nadmissible) *nadmissible = nadm;
     return UCF_OK;
 }
 

@@ -47,3 +47,15 @@ int ucf_field_launch_ensemble_quantile(int nens, long long nout, const double* d
                                        void* stream);
 // outputs per workgroup of the quantile kernel: 64 / 32 / 16 for nens <= 256 / 512 / 1024
 int ucf_field_ensemble_tile(int nens);
+
+// The weighted reduction (ucf_field_ensemble_weighted in include/ucf.h states the arithmetic): d_u [nens] in device memory are
+// the integer weights of ucf_ensemble_quantise, each 0 .. 2^32; F(e) = the members m with u[m] > 0 and a[m][e] finite.
+// field_ensemble_wmoments_kernel: the outputs of the unweighted launcher; *d_nbad += the number of outputs with |F| < the
+// number of members with u > 0.  field_ensemble_wquantile_kernel<T>: d_quant [nq][nout] = the inverse of the weighted
+// empirical distribution function at the levels d_q; the same tiles; LDS (nens + UCF_ENSEMBLE_MAX_Q) T doubles, at most 136 KB.
+// The checks of the unweighted launchers, and d_u not NULL.
+int ucf_field_launch_ensemble_wmoments(int nens, long long nout, const double* d_a, const unsigned long long* d_u, int nlim,
+                                       const double* d_limit, double* d_mean, double* d_sd, double* d_min, double* d_max, int* d_nfin,
+                                       double* d_pexc, long long* d_nbad, void* stream);
+int ucf_field_launch_ensemble_wquantile(int nens, long long nout, const double* d_a, const unsigned long long* d_u, int nq, const double* d_q,
+                                        double* d_quant, void* stream);

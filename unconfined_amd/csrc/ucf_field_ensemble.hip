@@ -161,6 +161,153 @@ void quantile_launch(int nens, long long nout, const double* d_a, int nq, const 
     const long long blocks = (nout + T - 1) / T;
     hipLaunchKernelGGL(field_ensemble_quantile_kernel<T>, dim3((unsigned)blocks), dim3(ENS_THREADS), lds, st, nens, nout, d_a, nq, d_q, d_quant);
 }
+
+// ---- the weighted reduction (ucf_field_ensemble_weighted).  u [nens] are the integer weights of ucf_ensemble_quantise, 0 .. 2^32; a
+// member with u = 0 is not in the ensemble.  u[m] is read at a wave-uniform address (m is a loop counter): scalar loads, no
+// LDS.  Every cumulative weight is a 64-bit integer sum of at most 1024 * 2^32 = 2^42: exact, whatever the order, and exact
+// again as a double.
+
+// field_ensemble_moments_kernel with weights: F = the members with u > 0 and a finite value.  The exceedance sums are
+// 64-bit integers in registers.  A member with u = 0 is skipped by a wave-uniform branch, its value is not loaded.
+__global__ __launch_bounds__(ENS_THREADS) void field_ensemble_wmoments_kernel(int nens, long long nout, const double* __restrict__ a,
+                                                                               const unsigned long long* __restrict__ u, int nlim,
+                                                                               const double* __restrict__ limit, double* __restrict__ mean,
+                                                                               double* __restrict__ sd, double* __restrict__ mn,
+                                                                               double* __restrict__ mx, int* __restrict__ nfin,
+                                                                               double* __restrict__ pexc, unsigned long long* __restrict__ nbad)
+{
+    const long long e = (long long)blockIdx.x * ENS_THREADS + threadIdx.x;
+    bool bad = false;
+    if (e < nout) {
+        const size_t no = (size_t)nout;
+        double lim[UCF_ENSEMBLE_MAX_Q];
+        unsigned long long over[UCF_ENSEMBLE_MAX_Q];
+#pragma unroll
+        for (int l = 0; l < UCF_ENSEMBLE_MAX_Q; l++) {
+            lim[l] = (pexc && l < nlim) ? limit[l] : 0.0;
+            over[l] = 0;
+        }
+        const double nan = __builtin_nan("");
+        double acc = 0.0, U2 = 0.0, lo = nan, hi = nan;
+        unsigned long long U = 0;
+        int n = 0, nmem = 0;                             // nmem: the members of the ensemble (u > 0), the same in every thread
+        for (int m = 0; m < nens; m++) {
+            const unsigned long long um = u[m];
+            if (um == 0) continue;
+            nmem++;
+            const double v = a[(size_t)m * no + e];
+            if (!isfinite(v)) continue;
+            const double du = (double)um;
+            acc = acc + du * v;
+            U2 = U2 + du * du;
+            U += um;
+            n++;
+            if (!(v >= lo)) lo = v;
+            if (!(v < hi)) hi = v;
+#pragma unroll
+            for (int l = 0; l < UCF_ENSEMBLE_MAX_Q; l++) over[l] += (v > lim[l]) ? um : 0ULL;
+        }
+        const double dU = (double)U;
+        const double mu = acc / dU;                      // n = 0: +0.0 / +0.0 = NaN
+        bad = n < nmem;
+        if (mean) mean[e] = mu;
+        if (mn) mn[e] = lo;
+        if (mx) mx[e] = hi;
+        if (nfin) nfin[e] = n;
+        if (sd) {
+            double ss = 0.0;
+            for (int m = 0; m < nens; m++) {
+                const unsigned long long um = u[m];
+                if (um == 0) continue;
+                const double v = a[(size_t)m * no + e];
+                if (!isfinite(v)) continue;
+                const double d = v - mu;
+                ss = ss + (double)um * (d * d);
+            }
+            const double den = dU - U2 / dU;
+            sd[e] = (n < 2 || !(den > 0.0)) ? nan : sqrt(ss / den);
+        }
+        if (pexc) {
+#pragma unroll
+            for (int l = 0; l < UCF_ENSEMBLE_MAX_Q; l++)
+                if (l < nlim) pexc[(size_t)l * no + e] = (double)over[l] / dU;
+        }
+    }
+    // every lane of every wave arrives here (no early return above)
+    const unsigned long long b = __ballot(bad);
+    if ((threadIdx.x & 63) == 0 && b != 0) atomicAdd(nbad, (unsigned long long)__popcll(b));
+}
+
+// The inverse of the weighted empirical distribution function: the tiles, the threads and the ENS_OWN scheme of
+// field_ensemble_quantile_kernel.  A member that is not finite or has u = 0 is staged as NaN and drops out of every comparison.
+// In place of a rank a thread accumulates, without a branch, E(m) = the sum of u[m'] over the m' with v' < v or (v' == v and
+// m' < m): the weight in front of member m in the stable order (ties have one value, so that order only decides which of -0.0
+// and +0.0 a tie returns).  The intervals (E(m), E(m) + u[m]] of the staged members partition (0, U], so for a level p exactly
+// one member has E < p U <= E + u (E == 0 where p U == 0): it leaves its value in LDS, and that value is the result -- no
+// interpolation.  LDS: (nens + UCF_ENSEMBLE_MAX_Q) T doubles, dynamic.
+template <int T>
+__global__ __launch_bounds__(ENS_THREADS) void field_ensemble_wquantile_kernel(int nens, long long nout, const double* __restrict__ a,
+                                                                                const unsigned long long* __restrict__ u, int nq,
+                                                                                const double* __restrict__ q, double* __restrict__ quant)
+{
+    extern __shared__ double ens_lds[];
+    constexpr int G = ENS_THREADS / T;                   // threads per output
+    double* tile = ens_lds;                              // [nens][T]
+    double* xq = ens_lds + (size_t)nens * T;             // [UCF_ENSEMBLE_MAX_Q][T]: the selected value of every level
+    const int j = threadIdx.x % T, g = threadIdx.x / T;
+    const long long e0 = (long long)blockIdx.x * T;
+    const long long e = e0 + j;
+    const size_t no = (size_t)nout;
+    const double nan = __builtin_nan("");
+    for (int m = g; m < nens; m += G) {
+        double v = nan;
+        if (e < nout && u[m] != 0) v = a[(size_t)m * no + e];
+        tile[m * T + j] = isfinite(v) ? v : nan;
+    }
+    __syncthreads();
+    // U of this thread's output: every thread of the output adds the same rows, an integer sum
+    unsigned long long U = 0;
+    for (int m = 0; m < nens; m++) U += (tile[m * T + j] == tile[m * T + j]) ? u[m] : 0ULL;
+    const double dU = (double)U;
+    for (int base = g * ENS_OWN; base < nens; base += G * ENS_OWN) {
+        double v[ENS_OWN];
+        unsigned long long E[ENS_OWN], uo[ENS_OWN];
+#pragma unroll
+        for (int i = 0; i < ENS_OWN; i++) {
+            v[i] = (base + i < nens) ? tile[(base + i) * T + j] : nan;
+            uo[i] = (base + i < nens) ? u[base + i] : 0ULL;
+            E[i] = 0;
+        }
+        for (int m = 0; m < nens; m++) {
+            const double w = tile[m * T + j];
+            const unsigned long long um = u[m];
+#pragma unroll
+            for (int i = 0; i < ENS_OWN; i++) E[i] += ((w < v[i]) | ((w == v[i]) & (m < base + i))) ? um : 0ULL;
+        }
+        for (int l = 0; l < nq; l++) {
+            const double tgt = q[l] * dU;
+#pragma unroll
+            for (int i = 0; i < ENS_OWN; i++) {
+                const bool in = ((double)E[i] < tgt) & (tgt <= (double)(E[i] + uo[i]));
+                const bool first = (tgt == 0.0) & (E[i] == 0);
+                if (v[i] == v[i] && (in | first)) xq[l * T + j] = v[i];
+            }
+        }
+    }
+    __syncthreads();
+    if (e >= nout) return;
+    for (int l = g; l < nq; l += G) quant[(size_t)l * no + e] = (U > 0) ? xq[l * T + j] : nan;
+}
+
+template <int T>
+void wquantile_launch(int nens, long long nout, const double* d_a, const unsigned long long* d_u, int nq, const double* d_q, double* d_quant,
+                      hipStream_t st)
+{
+    const size_t lds = sizeof(double) * ((size_t)nens + UCF_ENSEMBLE_MAX_Q) * T;
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)field_ensemble_wquantile_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const long long blocks = (nout + T - 1) / T;
+    hipLaunchKernelGGL(field_ensemble_wquantile_kernel<T>, dim3((unsigned)blocks), dim3(ENS_THREADS), lds, st, nens, nout, d_a, d_u, nq, d_q, d_quant);
+}
 }  // namespace
 
 int ucf_field_ensemble_tile(int nens) { return nens <= 256 ? 64 : nens <= 512 ? 32 : 16; }
@@ -188,6 +335,33 @@ int ucf_field_launch_ensemble_quantile(int nens, long long nout, const double* d
     case 64: quantile_launch<64>(nens, nout, d_a, nq, d_q, d_quant, st); break;
     case 32: quantile_launch<32>(nens, nout, d_a, nq, d_q, d_quant, st); break;
     default: quantile_launch<16>(nens, nout, d_a, nq, d_q, d_quant, st); break;
+    }
+    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
+}
+
+int ucf_field_launch_ensemble_wmoments(int nens, long long nout, const double* d_a, const unsigned long long* d_u, int nlim,
+                                       const double* d_limit, double* d_mean, double* d_sd, double* d_min, double* d_max, int* d_nfin,
+                                       double* d_pexc, long long* d_nbad, void* stream)
+{
+    const long long blocks = (nout + ENS_THREADS - 1) / ENS_THREADS;
+    if (nens < 1 || nens > UCF_ENSEMBLE_MAX || nout < 1 || blocks > 0x7fffffffLL || !d_a || !d_u || !d_nbad || nlim < 0 || nlim > UCF_ENSEMBLE_MAX_Q ||
+        (d_pexc && (nlim < 1 || !d_limit))) return UCF_ERR_BAD_ARGUMENT;
+    hipLaunchKernelGGL(field_ensemble_wmoments_kernel, dim3((unsigned)blocks), dim3(ENS_THREADS), 0, (hipStream_t)stream, nens, nout, d_a, d_u,
+                       nlim, d_limit, d_mean, d_sd, d_min, d_max, d_nfin, d_pexc, (unsigned long long*)d_nbad);
+    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
+}
+
+int ucf_field_launch_ensemble_wquantile(int nens, long long nout, const double* d_a, const unsigned long long* d_u, int nq, const double* d_q,
+                                        double* d_quant, void* stream)
+{
+    if (nens < 1 || nens > UCF_ENSEMBLE_MAX || nout < 1 || nq < 1 || nq > UCF_ENSEMBLE_MAX_Q || !d_a || !d_u || !d_q || !d_quant) return UCF_ERR_BAD_ARGUMENT;
+    const int T = ucf_field_ensemble_tile(nens);
+    if ((nout + T - 1) / T > 0x7fffffffLL) return UCF_ERR_BAD_ARGUMENT;
+    hipStream_t st = (hipStream_t)stream;
+    switch (T) {
+    case 64: wquantile_launch<64>(nens, nout, d_a, d_u, nq, d_q, d_quant, st); break;
+    case 32: wquantile_launch<32>(nens, nout, d_a, d_u, nq, d_q, d_quant, st); break;
+    default: wquantile_launch<16>(nens, nout, d_a, d_u, nq, d_q, d_quant, st); break;
     }
     return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
 }

@@ -871,6 +871,15 @@ int ucf_fit_evaluate_joint(ucf_fit* f, int nsets, const double* theta, double dl
     return fit_evaluate(f, nsets, theta, dlog, 1, phi, g, A, nbad, J, sim_all, phi_d, Jd, simd_all);
 }
 
+// the trial-point evaluation of ucf_fit_lm with an entry of its own: base plans only, the npar = 0 reduction; dlog is not read
+int ucf_fit_objective(ucf_fit* f, int nsets, const double* theta, double* phi, int* nbad, double* sim, double* phi_d, double* simd)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if ((phi_d || simd) && !f->deriv)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%s is asked for, but the fit has no derivative data (ucf_fit_set_derivative)", phi_d ? "phi_d" : "simd");
+    return fit_evaluate(f, nsets, theta, 0.0, 0, phi, nullptr, nullptr, nbad, nullptr, sim, phi_d, nullptr, simd);
+}
+
 int ucf_fit_default_options(ucf_fit_options* opt)
 {
     if (!opt) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");

@@ -21,6 +21,13 @@ many parameter sets, drawn from the fit's covariance or taken from the rows of a
     thetas = ensemble_draw(res["theta"][0], res["cov"][0], 256, seed=1)                       # [256, npar]
     out = field.ensemble(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], limits=[0.5])
     out["quant"], out["pexc"]                                                                 # [3, nt, nloc, nz], [1, nt, nloc, nz]
+
+Members that are a design and not a sample -- a Latin hypercube, the rows of a multi-start fit -- count by their likelihood
+(ucf_field_ensemble_weighted); a member whose weight rounds to 0 is not evaluated:
+
+    lw = likelihood_weights(fit.objective(thetas)["phi"])
+    out = field.ensemble(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], limits=[0.5], weights=lw["weight"])
+    out["quant"], out["ess"], out["nlaunched"]                                                # weighted inverse CDF, effective sample size
 """
 from __future__ import annotations
 
@@ -188,14 +195,18 @@ class WellField:
         return out
 
     def ensemble(self, plan, free, thetas, z, quantiles=(0.05, 0.5, 0.95), limits=None, derivative: bool = True,
-                 all_maps: bool = False, with_stats: bool = False) -> dict:
+                 all_maps: bool = False, with_stats: bool = False, weights=None) -> dict:
         """the field under the parameter sets ``thetas`` [nens, npar] of the free parameters (names as for ``fit.par_id``; the
         other parameters are ``plan``'s), reduced over the members on the GPU, all dimensional: mean, sd, min, max [nt, nloc,
         nz] of the drawdown, quant [nq, nt, nloc, nz] at the levels ``quantiles``, nfin (int32) the members that are finite at
         an output -- the others take part in no statistic; with ``limits`` pexc [nlim, nt, nloc, nz], the fraction of the
         finite members whose drawdown exceeds a limit; with ``derivative`` dmean, dsd, dmin, dmax, dquant, dnfin of t ds/dt;
         with ``all_maps`` s_all (and ds_all) [nens, nt, nloc, nz], the member maps; nbad [2], the outputs of s and of ds where
-        a member is not finite.  ``plan`` is not modified."""
+        a member is not finite.  ``plan`` is not modified.
+        With ``weights`` [nens] (e.g. ``fit.likelihood_weights``) the members count by their weight (ucf_field_ensemble_weighted):
+        mean, sd and pexc are the weighted ones, quant is the inverse of the weighted distribution function (no interpolation), a
+        member whose integer weight is 0 is not evaluated and is not in the ensemble (its row of s_all is NaN), and the result
+        gains u [nens] (uint64, the integer weights), ess (the effective sample size) and nlaunched."""
         ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
         thetas = np.atleast_2d(_f64(thetas))
         if thetas.ndim != 2 or thetas.shape[1] != len(ids):
@@ -220,10 +231,19 @@ class WellField:
             out["pexc"] = np.zeros((len(lim),) + shape)
         out["nbad"] = np.zeros(2, np.int64)
         st = UcfStats()
-        _libmod.check(self._lib.ucf_field_ensemble(
-            self._h, plan._h, len(ids), _addr(ids), nens, _addr(thetas), len(z), _addr(z), len(q), _addr(q) if len(q) else None,
-            len(lim), _addr(lim) if len(lim) else None, C.byref(keep[0]), C.byref(keep[1]) if derivative else None,
-            _addr(out.get("pexc")), _addr(out["nbad"]), C.byref(st) if with_stats else None))
+        levels = (len(z), _addr(z), len(q), _addr(q) if len(q) else None, len(lim), _addr(lim) if len(lim) else None, C.byref(keep[0]),
+                  C.byref(keep[1]) if derivative else None, _addr(out.get("pexc")), _addr(out["nbad"]), C.byref(st) if with_stats else None)
+        if weights is None:
+            _libmod.check(self._lib.ucf_field_ensemble(self._h, plan._h, len(ids), _addr(ids), nens, _addr(thetas), *levels))
+        else:
+            w = np.atleast_1d(_f64(weights))
+            if len(w) != nens:
+                raise ValueError("weights: one value per member")
+            out["u"] = np.zeros(nens, np.uint64)
+            ess, nl = C.c_double(), C.c_int()
+            _libmod.check(self._lib.ucf_field_ensemble_weighted(self._h, plan._h, len(ids), _addr(ids), nens, _addr(thetas), _addr(w), *levels,
+                                                                _addr(out["u"]), C.addressof(ess), C.addressof(nl)))
+            out["ess"], out["nlaunched"] = float(ess.value), int(nl.value)
         if with_stats:
             out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
         return out

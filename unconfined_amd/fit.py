@@ -11,6 +11,8 @@ equations are formed on the device; this module only marshals arrays.
     fld = Fit.field(params, free, wells=[(0, 0, 1, 0), (40, 30, 0.6, 20)], obs_wells=[(10, 5, [z0]), (25, -8, [za, zb, zc])],
                     t=t, well=well, iz=iz, obs=obs)
                                                   # an interference test: pumping wells (x, y, q, t0) as WellField / images take them
+    obj = fit.objective(thetas)                   # phi, nbad of many parameter sets without a Jacobian: one plan per set
+    lw = likelihood_weights(obj["phi"], obj["nbad"])          # weights for WellField.ensemble(..., weights=lw["weight"])
 
 Parameters are positive and fitted in their logarithm; ``theta`` arrays hold the parameters themselves.
 """
@@ -143,6 +145,32 @@ def derivative_check(dobs, dweight) -> int:
     return int(nd.value)
 
 
+def likelihood_weights(phi, nbad=None, s2: float = 1.0) -> dict:
+    """likelihood weights of the members whose objectives are ``phi`` (ucf_ensemble_likelihood_weights; no GPU): weight
+    [nens] = exp(-0.5 (phi - phi[best]) / s2), 0 for a member whose phi is not finite or whose ``nbad`` is not 0; best, the
+    admissible member of least phi; nadmissible.  ``s2`` is the variance factor: 1 where the fit's weights are true 1 / sigma;
+    otherwise e.g. phi[best] / (nobs + nd - npar), the factor of cov in ``Fit.lm``."""
+    phi = np.atleast_1d(_f64(phi))
+    nb = None if nbad is None else np.atleast_1d(_i32(nbad))
+    if nb is not None and len(nb) != len(phi):
+        raise ValueError("phi and nbad must have one entry per member")
+    w = np.zeros(len(phi))
+    best, nadm = C.c_int(-1), C.c_int(0)
+    _libmod.check(_libmod.load().ucf_ensemble_likelihood_weights(len(phi), phi.ctypes.data, None if nb is None else nb.ctypes.data,
+                                                                 float(s2), w.ctypes.data, C.addressof(best), C.addressof(nadm)))
+    return {"weight": w, "best": int(best.value), "nadmissible": int(nadm.value)}
+
+
+def quantise_weights(w) -> tuple:
+    """(u, ess): the integer weights u [nens] (uint64, 0 .. 2^32, the largest weight 2^32) that a weighted ensemble reduces
+    with, and Kish's effective sample size of them (ucf_ensemble_quantise; no GPU).  A member with u = 0 is not in the ensemble."""
+    w = np.atleast_1d(_f64(w))
+    u = np.zeros(len(w), np.uint64)
+    ess = C.c_double()
+    _libmod.check(_libmod.load().ucf_ensemble_quantise(len(w), w.ctypes.data, u.ctypes.data, C.addressof(ess)))
+    return u, float(ess.value)
+
+
 class Fit:
     """observations (dimensional drawdown at time t[i], radius r[i], depth z[iz[i]], z up from the aquifer base) of one
     parameter set ``params`` whose ``free`` parameters are to be estimated.  All depths of ``z`` are evaluated at every
@@ -247,10 +275,12 @@ class Fit:
         if not (len(dobs) == len(dweight) == self.nobs):
             raise ValueError("dobs and dweight must have one entry per observation")
         _libmod.check(self._lib.ucf_fit_set_derivative(self._h, dobs.ctypes.data, dweight.ctypes.data))
+        self._deriv = True
 
     def clear_derivative(self):
         """detach the derivative data: ``evaluate`` and ``lm`` are those of the drawdown alone again"""
         _libmod.check(self._lib.ucf_fit_set_derivative(self._h, None, None))
+        self._deriv = False
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -294,6 +324,26 @@ class Fit:
             return out
         _libmod.check(self._lib.ucf_fit_evaluate(self._h, n, np.ascontiguousarray(theta), float(dlog), ptr("phi"), ptr("g"), ptr("A"),
                                                  ptr("nbad"), ptr("J"), ptr("sim_all")))
+        return out
+
+    def objective(self, thetas, sim: bool = False) -> dict:
+        """thetas [nsets][npar] -> phi [nsets], nbad [nsets] without a Jacobian (ucf_fit_objective): one plan per set, what ``lm``
+        runs at its trial points; with ``sim`` the simulated values sim [nsets][nobs].  On a fit with derivative data phi is
+        the joint objective, phi_d [nsets] the derivative terms' share of it, and ``sim`` adds simd."""
+        thetas = np.atleast_2d(_f64(thetas))
+        n, P = thetas.shape
+        if P != self.npar:
+            raise ValueError(f"thetas has {P} columns, the fit has {self.npar} free parameters")
+        out = {"phi": np.zeros(n), "nbad": np.zeros(n, np.int32)}
+        if sim:
+            out["sim"] = np.zeros((n, self.nobs))
+        if getattr(self, "_deriv", False):
+            out["phi_d"] = np.zeros(n)
+            if sim:
+                out["simd"] = np.zeros((n, self.nobs))
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        _libmod.check(self._lib.ucf_fit_objective(self._h, n, thetas.ctypes.data, ptr("phi"), ptr("nbad"), ptr("sim"), ptr("phi_d"),
+                                                  ptr("simd")))
         return out
 
     def lm(self, theta0, cov: bool = True, **opt) -> dict:

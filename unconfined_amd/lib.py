@@ -44,6 +44,8 @@ EXPORTS = [
     "ucf_field_drawdown", "ucf_field_alloc_count", "ucf_field_images",
     "ucf_field_forecast_sets", "ucf_field_forecast",
     "ucf_field_ensemble", "ucf_field_ensemble_draw", "ucf_debug_ensemble", "ucf_debug_fit_reduce",
+    "ucf_fit_objective", "ucf_ensemble_quantise", "ucf_ensemble_likelihood_weights", "ucf_field_ensemble_weighted",
+    "ucf_debug_ensemble_weighted",
 ]
 
 
@@ -173,6 +175,14 @@ def load() -> C.CDLL:
                                        C.POINTER(UcfEnsembleMaps), C.POINTER(UcfEnsembleMaps), vp, vp, C.POINTER(UcfStats)]
     lib.ucf_field_ensemble_draw.argtypes = [C.c_int, vp, vp, C.c_int, C.c_ulonglong, vp]
     lib.ucf_debug_ensemble.argtypes = [C.c_int, C.c_longlong, vp, C.c_int, vp, C.c_int, vp, C.POINTER(UcfEnsembleMaps), vp, vp]
+    # theta and every output may be NULL: plain addresses
+    lib.ucf_fit_objective.argtypes = [vp, C.c_int] + [vp] * 6
+    lib.ucf_ensemble_quantise.argtypes = [C.c_int, vp, vp, vp]
+    lib.ucf_ensemble_likelihood_weights.argtypes = [C.c_int, vp, vp, C.c_double, vp, vp, vp]
+    # as ucf_field_ensemble, the weights behind thetas, u, ess and nlaunched at the end
+    lib.ucf_field_ensemble_weighted.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp,
+                                                C.POINTER(UcfEnsembleMaps), C.POINTER(UcfEnsembleMaps), vp, vp, C.POINTER(UcfStats), vp, vp, vp]
+    lib.ucf_debug_ensemble_weighted.argtypes = [C.c_int, C.c_longlong, vp, vp, C.c_int, vp, C.c_int, vp, C.POINTER(UcfEnsembleMaps), vp, vp]
     # every array may be NULL for a source or a call that does not read it: plain addresses
     lib.ucf_debug_fit_reduce.argtypes = ([C.c_int] * 4 + [C.c_double, C.c_longlong] + [vp] * 8 + [C.c_longlong, C.c_int] + [vp] * 7 + [vp] * 6)
     _lib = lib
