@@ -251,89 +251,6 @@ int ucf_extraptozero(int n, int R, const double* x, const double* y, double* out
     return UCF_OK;
 }
 
-// The two reduction kernels of ucf_field_ensemble on caller data a [nens][nout]: the same launchers (and through them the
-// same choice of tile), so the kernels are testable at their edges without paying for evaluations.
-int ucf_debug_ensemble(int nens, long long nout, const double* a, int nq, const double* q, int nlim, const double* limit,
-                       const ucf_ensemble_maps* out, double* pexc, long long* nbad)
-{
-    const ucf_ensemble_maps none = {};
-    const ucf_ensemble_maps* w = out ? out : &none;
-    int rc = ensemble_check_levels(nens, nq, q, nlim, limit, w->quant != nullptr, pexc != nullptr);
-    if (rc) return rc;
-    if (!a) return fail(UCF_ERR_BAD_ARGUMENT, "NULL a");
-    if (nout < 1 || nens * nout > 0x7fffffffLL * 256) return fail(UCF_ERR_BAD_ARGUMENT, "nout=%lld: at least one output, at most 2^39 values", nout);
-    if ((rc = require_device())) return rc;
-    const size_t no = (size_t)nout, so = sizeof(double) * no;
-    dev_buf b_a, b_ql, b_mean, b_sd, b_min, b_max, b_quant, b_nfin, b_pexc, b_nbad;
-    if (b_a.alloc(so * nens) || b_ql.alloc(sizeof(double) * 2 * UCF_ENSEMBLE_MAX_Q) || b_nbad.alloc(sizeof(long long)) ||
-        (w->mean && b_mean.alloc(so)) || (w->sd && b_sd.alloc(so)) || (w->min && b_min.alloc(so)) || (w->max && b_max.alloc(so)) ||
-        (w->quant && b_quant.alloc(so * nq)) || (w->nfin && b_nfin.alloc(sizeof(int) * no)) || (pexc && b_pexc.alloc(so * nlim)))
-        return fail(UCF_ERR_NOMEM, "device allocation failed");
-    double ql[2 * UCF_ENSEMBLE_MAX_Q] = {};
-    for (int i = 0; i < nq; i++) ql[i] = q[i];
-    for (int i = 0; i < nlim; i++) ql[UCF_ENSEMBLE_MAX_Q + i] = limit[i];
-    HIP_TRY(hipMemcpy(b_a.p, a, so * nens, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_ql.p, ql, sizeof(ql), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(b_nbad.p, 0, sizeof(long long)));
-    rc = ucf_field_launch_ensemble_moments(nens, nout, (const double*)b_a.p, nlim, (const double*)b_ql.p + UCF_ENSEMBLE_MAX_Q, (double*)b_mean.p,
-                                           (double*)b_sd.p, (double*)b_min.p, (double*)b_max.p, (int*)b_nfin.p, (double*)b_pexc.p,
-                                           (long long*)b_nbad.p, nullptr);
-    if (rc == UCF_OK && w->quant)
-        rc = ucf_field_launch_ensemble_quantile(nens, nout, (const double*)b_a.p, nq, (const double*)b_ql.p, (double*)b_quant.p, nullptr);
-    if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    const struct { void* host; const void* dev; size_t bytes; } back[] = {
-        {w->mean, b_mean.p, so}, {w->sd, b_sd.p, so}, {w->min, b_min.p, so}, {w->max, b_max.p, so}, {w->quant, b_quant.p, so * nq},
-        {w->nfin, b_nfin.p, sizeof(int) * no}, {pexc, b_pexc.p, so * nlim}, {nbad, b_nbad.p, sizeof(long long)}};
-    for (const auto& c : back)
-        if (c.host) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
-    return UCF_OK;
-}
-
-// The two weighted reduction kernels of ucf_field_ensemble_weighted on caller data a [nens][nout] and caller weights: the
-// same quantisation and the same launchers.
-int ucf_debug_ensemble_weighted(int nens, long long nout, const double* a, const double* weight, int nq, const double* q, int nlim,
-                                const double* limit, const ucf_ensemble_maps* out, double* pexc, long long* nbad)
-{
-    const ucf_ensemble_maps none = {};
-    const ucf_ensemble_maps* w = out ? out : &none;
-    int rc = ensemble_check_levels(nens, nq, q, nlim, limit, w->quant != nullptr, pexc != nullptr);
-    if (rc) return rc;
-    if (!a) return fail(UCF_ERR_BAD_ARGUMENT, "NULL a");
-    if (nout < 1 || nens * nout > 0x7fffffffLL * 256) return fail(UCF_ERR_BAD_ARGUMENT, "nout=%lld: at least one output, at most 2^39 values", nout);
-    std::vector<unsigned long long> u((size_t)nens);
-    if ((rc = ucf_ensemble_quantise(nens, weight, u.data(), nullptr))) return rc;
-    if ((rc = require_device())) return rc;
-    const size_t no = (size_t)nout, so = sizeof(double) * no;
-    dev_buf b_a, b_u, b_ql, b_mean, b_sd, b_min, b_max, b_quant, b_nfin, b_pexc, b_nbad;
-    if (b_a.alloc(so * nens) || b_u.alloc(sizeof(unsigned long long) * nens) || b_ql.alloc(sizeof(double) * 2 * UCF_ENSEMBLE_MAX_Q) ||
-        b_nbad.alloc(sizeof(long long)) || (w->mean && b_mean.alloc(so)) || (w->sd && b_sd.alloc(so)) || (w->min && b_min.alloc(so)) ||
-        (w->max && b_max.alloc(so)) || (w->quant && b_quant.alloc(so * nq)) || (w->nfin && b_nfin.alloc(sizeof(int) * no)) ||
-        (pexc && b_pexc.alloc(so * nlim)))
-        return fail(UCF_ERR_NOMEM, "device allocation failed");
-    double ql[2 * UCF_ENSEMBLE_MAX_Q] = {};
-    for (int i = 0; i < nq; i++) ql[i] = q[i];
-    for (int i = 0; i < nlim; i++) ql[UCF_ENSEMBLE_MAX_Q + i] = limit[i];
-    HIP_TRY(hipMemcpy(b_a.p, a, so * nens, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_u.p, u.data(), sizeof(unsigned long long) * nens, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(b_ql.p, ql, sizeof(ql), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(b_nbad.p, 0, sizeof(long long)));
-    rc = ucf_field_launch_ensemble_wmoments(nens, nout, (const double*)b_a.p, (const unsigned long long*)b_u.p, nlim,
-                                            (const double*)b_ql.p + UCF_ENSEMBLE_MAX_Q, (double*)b_mean.p, (double*)b_sd.p, (double*)b_min.p,
-                                            (double*)b_max.p, (int*)b_nfin.p, (double*)b_pexc.p, (long long*)b_nbad.p, nullptr);
-    if (rc == UCF_OK && w->quant)
-        rc = ucf_field_launch_ensemble_wquantile(nens, nout, (const double*)b_a.p, (const unsigned long long*)b_u.p, nq, (const double*)b_ql.p,
-                                                 (double*)b_quant.p, nullptr);
-    if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    const struct { void* host; const void* dev; size_t bytes; } back[] = {
-        {w->mean, b_mean.p, so}, {w->sd, b_sd.p, so}, {w->min, b_min.p, so}, {w->max, b_max.p, so}, {w->quant, b_quant.p, so * nq},
-        {w->nfin, b_nfin.p, sizeof(int) * no}, {pexc, b_pexc.p, so * nlim}, {nbad, b_nbad.p, sizeof(long long)}};
-    for (const auto& c : back)
-        if (c.host) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
-    return UCF_OK;
-}
-
 }  // extern "C"
 
 namespace {
@@ -356,9 +273,61 @@ int pack_refs(const char* what, int n, const long long* prefix, const long long*
     }
     return UCF_OK;
 }
+
+// The reduction of ucf_field_ensemble -- weighted: of ucf_field_ensemble_weighted, on the caller's weights through the same
+// quantisation -- on caller data a [nens][nout]: the same launcher (and through it the same choice of tile), so the kernels
+// are testable at their edges without paying for evaluations.
+int debug_ensemble_core(int nens, long long nout, const double* a, bool weighted, const double* weight, int nq, const double* q, int nlim,
+                        const double* limit, const ucf_ensemble_maps* out, double* pexc, long long* nbad)
+{
+    const ucf_ensemble_maps none = {};
+    const ucf_ensemble_maps* w = out ? out : &none;
+    int rc = ensemble_check_levels(nens, nq, q, nlim, limit, w->quant != nullptr, pexc != nullptr);
+    if (rc) return rc;
+    if (!a) return fail(UCF_ERR_BAD_ARGUMENT, "NULL a");
+    if (nout < 1 || nens * nout > 0x7fffffffLL * 256) return fail(UCF_ERR_BAD_ARGUMENT, "nout=%lld: at least one output, at most 2^39 values", nout);
+    std::vector<unsigned long long> u(weighted ? (size_t)nens : 0);
+    if (weighted && (rc = ucf_ensemble_quantise(nens, weight, u.data(), nullptr))) return rc;
+    if ((rc = require_device())) return rc;
+    const size_t no = (size_t)nout, so = sizeof(double) * no, su = sizeof(unsigned long long) * u.size();
+    dev_buf b_a, b_u, b_ql, b_mean, b_sd, b_min, b_max, b_quant, b_nfin, b_pexc, b_nbad;
+    if (b_a.alloc(so * nens) || (weighted && b_u.alloc(su)) || b_ql.alloc(sizeof(double) * 2 * UCF_ENSEMBLE_MAX_Q) ||
+        b_nbad.alloc(sizeof(long long)) || (w->mean && b_mean.alloc(so)) || (w->sd && b_sd.alloc(so)) || (w->min && b_min.alloc(so)) ||
+        (w->max && b_max.alloc(so)) || (w->quant && b_quant.alloc(so * nq)) || (w->nfin && b_nfin.alloc(sizeof(int) * no)) ||
+        (pexc && b_pexc.alloc(so * nlim)))
+        return fail(UCF_ERR_NOMEM, "device allocation failed");
+    double ql[2 * UCF_ENSEMBLE_MAX_Q];
+    ensemble_pack_levels(nq, q, nlim, limit, ql);
+    HIP_TRY(hipMemcpy(b_a.p, a, so * nens, hipMemcpyHostToDevice));
+    if (weighted) HIP_TRY(hipMemcpy(b_u.p, u.data(), su, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_ql.p, ql, sizeof(ql), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b_nbad.p, 0, sizeof(long long)));
+    ucf_ensemble_reduce_args ra = {};
+    ra.nens = nens; ra.nout = nout; ra.d_a = (const double*)b_a.p; ra.d_u = (const unsigned long long*)b_u.p;
+    ra.nq = nq; ra.d_q = (const double*)b_ql.p; ra.nlim = nlim; ra.d_limit = (const double*)b_ql.p + UCF_ENSEMBLE_MAX_Q;
+    ra.d_mean = (double*)b_mean.p; ra.d_sd = (double*)b_sd.p; ra.d_min = (double*)b_min.p; ra.d_max = (double*)b_max.p;
+    ra.d_nfin = (int*)b_nfin.p; ra.d_quant = (double*)b_quant.p; ra.d_pexc = (double*)b_pexc.p; ra.d_nbad = (long long*)b_nbad.p;
+    rc = ucf_field_launch_ensemble_reduce(&ra, nullptr);
+    if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return copy_back_sync({{w->mean, b_mean.p, so}, {w->sd, b_sd.p, so}, {w->min, b_min.p, so}, {w->max, b_max.p, so}, {w->quant, b_quant.p, so * nq},
+                           {w->nfin, b_nfin.p, sizeof(int) * no}, {pexc, b_pexc.p, so * nlim}, {nbad, b_nbad.p, sizeof(long long)}});
+}
 }  // namespace
 
 extern "C" {
+
+int ucf_debug_ensemble(int nens, long long nout, const double* a, int nq, const double* q, int nlim, const double* limit,
+                       const ucf_ensemble_maps* out, double* pexc, long long* nbad)
+{
+    return debug_ensemble_core(nens, nout, a, false, nullptr, nq, q, nlim, limit, out, pexc, nbad);
+}
+
+int ucf_debug_ensemble_weighted(int nens, long long nout, const double* a, const double* weight, int nq, const double* q, int nlim,
+                                const double* limit, const ucf_ensemble_maps* out, double* pexc, long long* nbad)
+{
+    return debug_ensemble_core(nens, nout, a, true, weight, nq, q, nlim, limit, out, pexc, nbad);
+}
 
 // The fit reduction exactly as ucf_fit_evaluate launches it (ucf_fit_launch_reduce, and through it the same choice of
 // instantiation), on caller data: the kernel is testable at its edges without paying for evaluations.  Everything the
@@ -437,12 +406,8 @@ int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_d
     rc = ucf_fit_launch_reduce(&ra, nullptr);
     if (rc) return fail(rc, "fit reduction kernel launch failed");
     HIP_TRY(hipStreamSynchronize(nullptr));
-    const struct { void* host; const void* dev; size_t bytes; } back[] = {
-        {sums, b_sums.p, sizeof(double) * nsets * nsum}, {nbad, b_nbad.p, sizeof(int) * (size_t)nsets}, {J, b_J.p, npar > 0 ? bJ : 0}, {sim, b_sim.p, bsim},
-        {Jd, b_Jd.p, npar > 0 ? bJ : 0}, {simd, b_simd.p, bsim}};
-    for (const auto& c : back)
-        if (c.host && c.bytes) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
-    return UCF_OK;
+    return copy_back_sync({{sums, b_sums.p, sizeof(double) * nsets * nsum}, {nbad, b_nbad.p, sizeof(int) * (size_t)nsets}, {J, b_J.p, npar > 0 ? bJ : 0},
+                           {sim, b_sim.p, bsim}, {Jd, b_Jd.p, npar > 0 ? bJ : 0}, {simd, b_simd.p, bsim}});
 }
 
 }  // extern "C"

@@ -177,7 +177,7 @@ int field_map_core(ucf_field* f, ucf_plan* pl, const std::vector<field_launch>& 
         (rc = grow_buffer(f->b_stats, sizeof(ucf_stats) * ng, "counters", f->n_alloc))) return rc;
     hipStream_t st = plan_stream(pl);
     if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
-    struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};     // the staging above outlives the copies
+    drain drained{st};                     // the staging above outlives the copies
     if (hipMemcpyAsync(f->b_tD.p, tD.data(), sizeof(double) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(f->b_sv.p, sv.data(), sizeof(int) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(f->b_tfac.p, tfac.data(), sizeof(double) * nT, hipMemcpyHostToDevice, st) != hipSuccess ||
@@ -200,8 +200,7 @@ int field_map_core(ucf_field* f, ucf_plan* pl, const std::vector<field_launch>& 
     if (rc) return fail(rc, "superposition kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     if (!stats) return UCF_OK;
     std::vector<ucf_stats> gst(ng);
-    if (hipMemcpyAsync(gst.data(), f->b_stats.p, sizeof(ucf_stats) * ng, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
+    if ((rc = copy_back({{gst.data(), f->b_stats.p, sizeof(ucf_stats) * ng}}, st, pl->device))) return rc;
     for (int g = 0; g < ng; g++) stats_add(*stats, gst[g]);
     return UCF_OK;
 }
@@ -255,6 +254,21 @@ int field_scratch_plan(ucf_field* f, const ucf_plan* pl, const ucf_params& first
         f->n_alloc++;
     }
     (void)ucf_plan_set_mode(f->scratch, mode);
+    return UCF_OK;
+}
+
+// What every call that launches does between its last check and its first launch: a device there is, the field's buffers
+// live on the plan's device (from here on they do), *stats (NULL ok) starts at zero, and -- where the call runs a sequence
+// of parameter sets, `first` the one that runs first -- the scratch plan holds it.
+int field_begin_launches(ucf_field* f, const ucf_plan* pl, ucf_stats* stats, const ucf_params* first)
+{
+    int rc = require_device();
+    if (rc) return rc;
+    if (f->device >= 0 && f->device != pl->device)
+        return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
+    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if (first && (rc = field_scratch_plan(f, pl, *first))) return rc;
+    f->device = pl->device;
     return UCF_OK;
 }
 
@@ -419,22 +433,13 @@ int ucf_field_drawdown(ucf_field* f, ucf_plan* pl, int nz, const double* z, int 
     std::vector<field_launch> L(ng);
     for (int g = 0; g < ng; g++)
         if ((rc = field_group_core(f, pl->P, pl->D, g, L[g]))) return rc;
-    rc = require_device();
-    if (rc) return rc;
-    if (f->device >= 0 && f->device != pl->device)
-        return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
-    if (stats) std::memset(stats, 0, sizeof(*stats));
+    if ((rc = field_begin_launches(f, pl, stats, nullptr))) return rc;
     device_switch dg(pl->device);
-    f->device = pl->device;
     const size_t so = sizeof(double) * (size_t)nout;
     if ((rc = grow_buffer(f->b_s, so, "superposed drawdown", f->n_alloc)) || (rc = grow_buffer(f->b_ds, so, "superposed derivative", f->n_alloc))) return rc;
     rc = field_map_core(f, pl, L, nz, z, dimensionless, (double*)f->b_s.p, (double*)f->b_ds.p, stats);
     if (rc) return rc;
-    hipStream_t st = plan_stream(pl);
-    if (hipMemcpyAsync(s, f->b_s.p, so, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(ds, f->b_ds.p, so, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
-    return UCF_OK;
+    return copy_back({{s, f->b_s.p, so}, {ds, f->b_ds.p, so}}, plan_stream(pl), pl->device);
 }
 
 int ucf_field_forecast_sets(const ucf_params* base, int npar, const int* ids, const double* theta, double dlog, ucf_params* sets)
@@ -484,15 +489,9 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
         for (int g = 0; g < ng; g++)
             if ((rc = field_group_core(f, sets[k], D, g, L[k][g]))) return forecast_set_failed(rc, k, ids, dlog);
     }
-    rc = require_device();
-    if (rc) return rc;
-    if (f->device >= 0 && f->device != pl->device)
-        return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if ((rc = field_scratch_plan(f, pl, sets[0]))) return rc;
+    if ((rc = field_begin_launches(f, pl, stats, &sets[0]))) return rc;
     ucf_plan* sp = f->scratch;
     device_switch dg(pl->device);
-    f->device = pl->device;
     const size_t so = sizeof(double) * (size_t)nout, sa = so * nset, sj = so * npar;
     if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every set", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every set", f->n_alloc)) ||
         (rc = grow_buffer(f->b_nbad, sizeof(long long) * 2, "counts", f->n_alloc)) ||
@@ -504,7 +503,7 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
     if (rc) return rc;
     hipStream_t st = plan_stream(sp);
     if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
-    struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};
+    drain drained{st};
     if (hipMemsetAsync(f->b_nbad.p, 0, sizeof(long long) * 2, st) != hipSuccess ||
         (cov && hipMemcpyAsync(f->b_cov.p, cov, sizeof(double) * npar * npar, hipMemcpyHostToDevice, st) != hipSuccess))
         return fail(UCF_ERR_HIP, "upload of the forecast's arrays failed: %s", hipGetErrorString(hipGetLastError()));
@@ -516,19 +515,14 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
                                        dsens ? (double*)f->b_dsens.p : nullptr, dse ? (double*)f->b_dse.p : nullptr, (long long*)f->b_nbad.p + 1, st);
     if (rc) return fail(rc, "forecast kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     // s, ds are slot 0 as it stands; everything else only where asked for
-    const struct { void* host; const void* dev; size_t bytes; } back[] = {
-        {s, f->b_sall.p, so}, {ds, f->b_dsall.p, so}, {sens, f->b_sens.p, sj}, {dsens, f->b_dsens.p, sj}, {se, f->b_se.p, so}, {dse, f->b_dse.p, so},
-        {s_all, f->b_sall.p, sa}, {ds_all, f->b_dsall.p, sa}, {nbad, f->b_nbad.p, sizeof(long long) * 2}};
-    for (const auto& c : back)
-        if (c.host && hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
-            return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
-    return UCF_OK;
+    return copy_back({{s, f->b_sall.p, so}, {ds, f->b_dsall.p, so}, {sens, f->b_sens.p, sj}, {dsens, f->b_dsens.p, sj}, {se, f->b_se.p, so},
+                      {dse, f->b_dse.p, so}, {s_all, f->b_sall.p, sa}, {ds_all, f->b_dsall.p, sa}, {nbad, f->b_nbad.p, sizeof(long long) * 2}},
+                     st, pl->device);
 }
 
 // ucf_field_ensemble (weighted == false: weight, u_out, ess, nlaunched are not read) and ucf_field_ensemble_weighted: one
 // sequence.  The weighted call differs in three places: the weights are quantised among the checks; a member with u = 0 is
-// validated but not launched, and its slots are filled with NaN bytes; the reduction kernels are the weighted ones.
+// validated but not launched, and its slots are filled with NaN bytes; the reduction runs with the weights.
 static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, int nz, const double* z,
                                int nq, const double* q, int nlim, const double* limit, const ucf_ensemble_maps* s, const ucf_ensemble_maps* ds,
                                double* pexc, long long* nbad, ucf_stats* stats, bool weighted, const double* weight,
@@ -573,15 +567,9 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
         if ((rc = ucf_fit_perturb(&pl->P, npar, ids, thetas + (size_t)m * npar, &sets[m]))) return m == 0 ? rc : failed(rc, m);
         if ((rc = validate(sets[m])) || (rc = field_launches_of(f, sets[m], L))) return failed(rc, m);
     }
-    rc = require_device();
-    if (rc) return rc;
-    if (f->device >= 0 && f->device != pl->device)
-        return fail(UCF_ERR_BAD_ARGUMENT, "the field's buffers live on device %d, the plan on device %d", f->device, pl->device);
-    if (stats) std::memset(stats, 0, sizeof(*stats));
-    if ((rc = field_scratch_plan(f, pl, sets[first]))) return rc;
+    if ((rc = field_begin_launches(f, pl, stats, &sets[first]))) return rc;
     ucf_plan* sp = f->scratch;
     device_switch dg(pl->device);
-    f->device = pl->device;
     // b_ens: q [MAX_Q], limit [MAX_Q], then per map what is asked for of mean, sd, min, max [nout], quant [nq][nout], nfin
     // [nout] (ints, padded to whole doubles), then pexc [nlim][nout]
     const size_t no = (size_t)nout, so = sizeof(double) * no, sa = so * nens;
@@ -609,18 +597,15 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
     if (rc) return rc;
     hipStream_t st = plan_stream(sp);
     if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
-    struct drain { hipStream_t s; ~drain() { (void)hipStreamSynchronize(s); } } drained{st};
-    double ql[2 * UCF_ENSEMBLE_MAX_Q] = {};
-    for (int i = 0; i < nq; i++) ql[i] = q[i];
-    for (int i = 0; i < nlim; i++) ql[UCF_ENSEMBLE_MAX_Q + i] = limit[i];
+    drain drained{st};
+    double ql[2 * UCF_ENSEMBLE_MAX_Q];
+    ensemble_pack_levels(nq, q, nlim, limit, ql);
     if (hipMemsetAsync(f->b_nbad.p, 0, sizeof(long long) * 2, st) != hipSuccess ||
         hipMemcpyAsync(base, ql, sizeof(ql), hipMemcpyHostToDevice, st) != hipSuccess)
         return fail(UCF_ERR_HIP, "upload of the ensemble's arrays failed: %s", hipGetErrorString(hipGetLastError()));
     const double* slots[2] = {(const double*)f->b_sall.p, (const double*)f->b_dsall.p};
-    const unsigned long long* d_u = nullptr;
     if (weighted) {
         // the weights, and NaN bytes into the slots of the members that were not launched, so that `all` is defined
-        d_u = (const unsigned long long*)f->b_u.p;
         bool ok = hipMemcpyAsync(f->b_u.p, u.data(), sizeof(unsigned long long) * nens, hipMemcpyHostToDevice, st) == hipSuccess;
         for (int m = 0; m < nens && ok; m++)
             if (u[m] == 0)
@@ -629,29 +614,23 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
         if (!ok) return fail(UCF_ERR_HIP, "upload of the ensemble's weights failed: %s", hipGetErrorString(hipGetLastError()));
     }
     for (int i = 0; i < 2 && rc == UCF_OK; i++) {
-        double* pe = i == 0 ? d_pexc : nullptr;
-        long long* nb = (long long*)f->b_nbad.p + i;
-        const double* lim = base + UCF_ENSEMBLE_MAX_Q;
-        rc = d_u ? ucf_field_launch_ensemble_wmoments(nens, nout, slots[i], d_u, nlim, lim, at[i].mean, at[i].sd, at[i].min, at[i].max, at[i].nfin, pe, nb, st)
-                 : ucf_field_launch_ensemble_moments(nens, nout, slots[i], nlim, lim, at[i].mean, at[i].sd, at[i].min, at[i].max, at[i].nfin, pe, nb, st);
-        if (rc == UCF_OK && at[i].quant)
-            rc = d_u ? ucf_field_launch_ensemble_wquantile(nens, nout, slots[i], d_u, nq, base, at[i].quant, st)
-                     : ucf_field_launch_ensemble_quantile(nens, nout, slots[i], nq, base, at[i].quant, st);
+        ucf_ensemble_reduce_args ra = {};
+        ra.nens = nens; ra.nout = nout; ra.d_a = slots[i];
+        ra.d_u = weighted ? (const unsigned long long*)f->b_u.p : nullptr;
+        ra.nq = nq; ra.d_q = base; ra.nlim = nlim; ra.d_limit = base + UCF_ENSEMBLE_MAX_Q;
+        ra.d_mean = at[i].mean; ra.d_sd = at[i].sd; ra.d_min = at[i].min; ra.d_max = at[i].max; ra.d_nfin = at[i].nfin;
+        ra.d_quant = at[i].quant; ra.d_pexc = i == 0 ? d_pexc : nullptr; ra.d_nbad = (long long*)f->b_nbad.p + i;
+        rc = ucf_field_launch_ensemble_reduce(&ra, st);
     }
     if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     // only what is asked for crosses the bus
-    struct copy { void* host; const void* dev; size_t bytes; };
-    std::vector<copy> back = {{pexc, d_pexc, so * nlim}, {nbad, f->b_nbad.p, sizeof(long long) * 2}};
+    std::vector<device_copy> back = {{pexc, d_pexc, so * nlim}, {nbad, f->b_nbad.p, sizeof(long long) * 2}};
     for (int i = 0; i < 2; i++) {
         const ucf_ensemble_maps* w = want[i];
         back.insert(back.end(), {{w->mean, at[i].mean, so}, {w->sd, at[i].sd, so}, {w->min, at[i].min, so}, {w->max, at[i].max, so},
                                  {w->quant, at[i].quant, so * nq}, {w->all, slots[i], sa}, {w->nfin, at[i].nfin, sizeof(int) * no}});
     }
-    for (const copy& c : back)
-        if (c.host && hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
-            return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(UCF_ERR_HIP, "device %d: %s", pl->device, hipGetErrorString(hipGetLastError()));
-    return UCF_OK;
+    return copy_back(back, st, pl->device);
 }
 
 int ucf_field_ensemble(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, int nz, const double* z,

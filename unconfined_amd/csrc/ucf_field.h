@@ -32,30 +32,27 @@ int ucf_field_launch_forecast(int npar, long long nout, double two_dlog, const d
                               double* d_se, long long* d_nbad, void* stream);
 
 // The reduction of an ensemble over its member axis (ucf_field_ensemble.hip), on the member maps d_a [nens][nout]; the
-// arithmetic is stated with ucf_field_ensemble in include/ucf.h.  F(e) = the members m with a[m][e] finite, in member order.
-// field_ensemble_moments_kernel, one thread per output e: d_nfin[e] = n = |F|; d_mean, d_sd, d_min, d_max [nout]; d_pexc
-// [nlim][nout] = the fraction of F above d_limit[l] (not NULL needs nlim >= 1 and d_limit [nlim] in device memory); any of the
-// six may be NULL (not formed).  *d_nbad += the number of outputs with n < nens (the caller zeroes it).
-// UCF_ERR_BAD_ARGUMENT: nens outside 1..UCF_ENSEMBLE_MAX, nlim outside 0..UCF_ENSEMBLE_MAX_Q.
-int ucf_field_launch_ensemble_moments(int nens, long long nout, const double* d_a, int nlim, const double* d_limit, double* d_mean,
-                                      double* d_sd, double* d_min, double* d_max, int* d_nfin, double* d_pexc, long long* d_nbad,
-                                      void* stream);
-// field_ensemble_quantile_kernel<T>: d_quant [nq][nout], the order statistics of F at the levels d_q [nq] (device memory),
-// 1 <= nq <= UCF_ENSEMBLE_MAX_Q.  A workgroup of 256 threads ranks the members of T = ucf_field_ensemble_tile(nens)
-// neighbouring outputs against each other in LDS: (nens + 2 UCF_ENSEMBLE_MAX_Q) T doubles, at most 144 KB.
-int ucf_field_launch_ensemble_quantile(int nens, long long nout, const double* d_a, int nq, const double* d_q, double* d_quant,
-                                       void* stream);
-// outputs per workgroup of the quantile kernel: 64 / 32 / 16 for nens <= 256 / 512 / 1024
+// arithmetic is stated with ucf_field_ensemble and ucf_field_ensemble_weighted in include/ucf.h.  F(e) = the members m with
+// a[m][e] finite, in member order, each of mass 1; with weights d_u only those with u[m] > 0, each of mass u[m].
+// field_ensemble_moments_kernel / _wmoments_kernel, one thread per output e, then, where d_quant is not NULL,
+// field_ensemble_quantile_kernel<T> / _wquantile_kernel<T>: a workgroup of 256 threads ranks the members of T =
+// ucf_field_ensemble_tile(nens) neighbouring outputs against each other in LDS, (nens + 2 UCF_ENSEMBLE_MAX_Q) T doubles, at
+// most 144 KB; weighted (nens + UCF_ENSEMBLE_MAX_Q) T, at most 136 KB.  Device memory throughout.
+struct ucf_ensemble_reduce_args {
+    int nens;                              // 1..UCF_ENSEMBLE_MAX
+    long long nout;
+    const double* d_a;
+    const unsigned long long* d_u;         // [nens] the integers of ucf_ensemble_quantise, each 0 .. 2^32; NULL: unweighted
+    int nq, nlim;                          // 1..UCF_ENSEMBLE_MAX_Q with d_quant, 0..UCF_ENSEMBLE_MAX_Q (>= 1 with d_pexc)
+    const double *d_q, *d_limit;           // [nq] levels, read with d_quant; [nlim] limits, read with d_pexc
+    double *d_mean, *d_sd, *d_min, *d_max; // [nout]; these, d_nfin, d_quant and d_pexc may each be NULL (not formed)
+    int* d_nfin;                           // [nout] |F|
+    double* d_quant;                       // [nq][nout] the order statistics of F at d_q, linearly interpolated; weighted the
+                                           // inverse of the weighted empirical distribution function
+    double* d_pexc;                        // [nlim][nout] the mass of F above d_limit[l] over the mass of F
+    long long* d_nbad;                     // += the outputs with |F| < nens, weighted < the members with u > 0; the caller zeroes it
+};
+// UCF_ERR_BAD_ARGUMENT for what the comments above exclude and for a grid beyond 2^31 - 1 workgroups
+int ucf_field_launch_ensemble_reduce(const ucf_ensemble_reduce_args* a, void* stream);
+// outputs per workgroup of the quantile kernels: 64 / 32 / 16 for nens <= 256 / 512 / 1024
 int ucf_field_ensemble_tile(int nens);
-
-// The weighted reduction (ucf_field_ensemble_weighted in include/ucf.h states the arithmetic): d_u [nens] in device memory are
-// the integer weights of ucf_ensemble_quantise, each 0 .. 2^32; F(e) = the members m with u[m] > 0 and a[m][e] finite.
-// field_ensemble_wmoments_kernel: the outputs of the unweighted launcher; *d_nbad += the number of outputs with |F| < the
-// number of members with u > 0.  field_ensemble_wquantile_kernel<T>: d_quant [nq][nout] = the inverse of the weighted
-// empirical distribution function at the levels d_q; the same tiles; LDS (nens + UCF_ENSEMBLE_MAX_Q) T doubles, at most 136 KB.
-// The checks of the unweighted launchers, and d_u not NULL.
-int ucf_field_launch_ensemble_wmoments(int nens, long long nout, const double* d_a, const unsigned long long* d_u, int nlim,
-                                       const double* d_limit, double* d_mean, double* d_sd, double* d_min, double* d_max, int* d_nfin,
-                                       double* d_pexc, long long* d_nbad, void* stream);
-int ucf_field_launch_ensemble_wquantile(int nens, long long nout, const double* d_a, const unsigned long long* d_u, int nq, const double* d_q,
-                                        double* d_quant, void* stream);

@@ -1,7 +1,7 @@
 // ucf_host.h -- what the host sources of the library share (ucf_api.cpp, ucf_plan.cpp, ucf_drawdown.cpp, ucf_multi.cpp,
 // ucf_debug.cpp, ucf_fit.cpp, ucf_field.cpp).  Internal: everything is in namespace ucf_host with hidden visibility, so
-// the names link between the objects and are not exported from libucf.so.  Declarations only; the comment that explains
-// a function stands at its definition, in the file named here.
+// the names link between the objects and are not exported from libucf.so.  Declarations and a few small inline helpers; the
+// comment that explains a declared function stands at its definition, in the file named here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -68,6 +68,34 @@ struct dev_buf {
 };
 int grow_buffer(ucf_buffer& b, size_t bytes, const char* what, long long& n_alloc);
 void free_buffer(ucf_buffer& b);
+
+// synchronises the stream when the scope ends, however it ends: host staging that asynchronous copies read outlives them
+struct drain {
+    hipStream_t s;
+    ~drain() { (void)hipStreamSynchronize(s); }
+};
+// Results on their way back: only what was asked for (host not NULL, bytes > 0) crosses the bus.  copy_back enqueues the
+// copies on `st` and returns when the stream has drained; copy_back_sync is for callers on the null stream that have
+// synchronised already.
+struct device_copy {
+    void* host;
+    const void* dev;
+    size_t bytes;
+};
+inline int copy_back(const std::vector<device_copy>& list, hipStream_t st, int device)
+{
+    for (const device_copy& c : list)
+        if (c.host && c.bytes && hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, st) != hipSuccess)
+            return fail(UCF_ERR_HIP, "device %d: %s", device, hipGetErrorString(hipGetLastError()));
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(UCF_ERR_HIP, "device %d: %s", device, hipGetErrorString(hipGetLastError()));
+    return UCF_OK;
+}
+inline int copy_back_sync(const std::vector<device_copy>& list)
+{
+    for (const device_copy& c : list)
+        if (c.host && c.bytes) HIP_TRY(hipMemcpy(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost));
+    return UCF_OK;
+}
 
 // ---- ucf_plan.cpp
 int validate(const ucf_params& P);
@@ -138,5 +166,12 @@ int fit_cholesky_factor(int n, double* M);
 int field_check_finite(const char* name, int n, const double* v);
 // what ucf_field_ensemble and ucf_debug_ensemble check on nens, the levels q [nq] and the limits [nlim]
 int ensemble_check_levels(int nens, int nq, const double* q, int nlim, const double* limit, bool want_quant, bool want_pexc);
+// the image of the checked levels and limits that goes to the device: q at [0], limit at [UCF_ENSEMBLE_MAX_Q], the rest 0
+inline void ensemble_pack_levels(int nq, const double* q, int nlim, const double* limit, double (&ql)[2 * UCF_ENSEMBLE_MAX_Q])
+{
+    for (double& v : ql) v = 0.0;
+    for (int i = 0; i < nq; i++) ql[i] = q[i];
+    for (int i = 0; i < nlim; i++) ql[UCF_ENSEMBLE_MAX_Q + i] = limit[i];
+}
 
 }  // namespace ucf_host
