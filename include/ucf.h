@@ -756,6 +756,93 @@ int ucf_field_ensemble_weighted(ucf_field* field, ucf_plan* plan, int npar, cons
 int ucf_debug_ensemble_weighted(int nens, long long nout, const double* a, const double* weight /*[nens]*/,
                                 int nq, const double* q, int nlim, const double* limit,
                                 const ucf_ensemble_maps* out /*all ignored*/, double* pexc, long long* nbad /*[1]*/);
+/* ---- data worth: where the next observation well has to go, and how long it has to be read, so that a forecast becomes sure
+ * (first-order data-worth analysis, the PREDUNC family of PEST).  One call evaluates the slots of ucf_field_forecast and keeps
+ * them on the device; field_worth_kernel conditions the fit's covariance on the readings that a candidate well at (location i,
+ * depth z) would deliver and reports the variance left on up to UCF_WORTH_MAX_TGT forecast targets; a greedy loop picks a
+ * network of up to UCF_WORTH_MAX_PICK wells on the resident slots, one small launch per pick and no evaluation again.
+ *   notation     nout = nt nloc nz, output e = (k nloc + i) nz + z; candidate c = i nz + z, ncand = nloc nz, so e = k ncand + c.
+ *                a_s, a_d [1 + 2 npar][nout]: the slots of s and of ds exactly as ucf_field_forecast forms them (the same sets,
+ *                plan, scratch plan and launch sequence), dimensional.  two_dlog = 2.0 * dlog, formed once on the host.  Every
+ *                operation below is rounded on its own (no FMA contraction), on the device and on the host.
+ *   data         a candidate well records the drawdown at every time k with tsel[k] != 0 (NULL tsel: every time), each reading
+ *                with standard deviation sigma_s: ws = 1.0 / sigma_s; where sigma_d > 0 also the log-time derivative, wd =
+ *                1.0 / sigma_d.  sigma_d == 0: no derivative data, wd = 0, and a_d is read for targets only.
+ *   prior        cov in ln theta as ucf_fit_lm returns it, factorised once on the host: cov = F F', F the lower Cholesky factor
+ *                that ucf_field_ensemble_draw states, its upper triangle +0.0 (UCF_ERR_SINGULAR where a pivot is not positive
+ *                and finite).  After a pick F is a general square matrix: the kernel takes a general F [npar][npar].
+ *   kernel       field_worth_kernel<npar>, one thread per candidate c:
+ *                    B_jj = 1.0, B_ij = +0.0 (i > j; the lower triangle only);  nused = 0
+ *                    for k = 0 .. nt-1 ascending with tsel[k] != 0:
+ *                      for (a, w) = (a_s, ws), then (a_d, wd), only where w > 0:
+ *                        J_j = (a[1+2j][e] - a[2+2j][e]) / two_dlog,  j = 0 .. npar-1
+ *                        if any of these 2 npar slot values is not finite: the datum is skipped
+ *                        nused = nused + 1
+ *                        g_j = +0.0;  g_j = g_j + F[i][j] * J_i,  i = 0 .. npar-1 ascending                      (g = F' J)
+ *                        wg_j = w * g_j;      B_ij = B_ij + wg_i * wg_j,  i >= j
+ *                    B = L D L' without square roots, for j = 0 .. npar-1:
+ *                        v = B_jj;  v = v - (l_jk * l_jk) * d_k, k = 0 .. j-1;   d_j = v
+ *                        for i > j:  v = B_ij;  v = v - (l_ik * l_jk) * d_k, k = 0 .. j-1;   l_ij = v / d_j
+ *                    per target t = 0 .. ntgt-1:
+ *                        v = +0.0;  for j ascending:  y_j = A[t][j];  y_j = y_j - l_jk * y_k, k = 0 .. j-1;  v = v + (y_j * y_j) / d_j
+ *                        post[t][c] = v, NaN where a d_j is not positive and finite (in exact arithmetic every d_j >= 1; overflow
+ *                        breaks that, and rounding where kappa_2(B) exceeds 2^53, as with a Wynn sentinel among the readings)
+ *                    crit[c] = +0.0;  crit[c] = crit[c] + tw[t] * post[t][c],  t ascending;       nused_out[c] = nused
+ *                post[t][c] is the variance of target t after the candidate's data, j_t' (C^-1 + sum w^2 j j')^-1 j_t, formed as
+ *                a_t' B^-1 a_t with B = I + sum (w F'j)(w F'j)': cov is never inverted and B has no eigenvalue below 1.  Slot 0 is
+ *                not read.  The Wynn sentinel is finite and takes part, as everywhere else.  No atomics: a call repeated gives the
+ *                same bits.
+ *   targets      target t is tgt[t] = (kind 0 = s | 1 = ds, k, i, z), an output of the same map.  Per call its 2 npar slot values
+ *                are fetched once (field_gather_kernel, out[n] = a[idx[n]]), J as above; per round on the host
+ *                    A[t][j] = +0.0;  A[t][j] = A[t][j] + F[i][j] * J_i, i ascending;
+ *                    prior[t] = +0.0;  prior[t] = prior[t] + A[t][j] * A[t][j], j ascending.
+ *                A target with a slot value that is not finite: A[t][.] = NaN, so its prior, its post and crit are NaN; the call
+ *                still returns UCF_OK.  tw NULL: every weight 1.
+ *   pick         round r copies crit back; pick[r] = the candidate of least crit among those with cmask[c] != 0 (NULL cmask: all),
+ *                not picked in an earlier round, crit finite; the lowest index on a tie.  None: pick[r] = -1, the later rounds
+ *                are not run, their rows of prior / post / crit are NaN and their pick entries -1.
+ *   conditioning after a pick the column of the picked candidate -- 2 npar nt slot values per map, through the same gather --
+ *                gives the rows (J, w) of its used data in kernel order, F = ucf_worth_condition(F, rows), and the next round
+ *                runs the kernel with that F.  cov_post = F F' of the last factor: after the last pick made (of the prior's factor
+ *                where no pick was made).  nused does not depend on the round.
+ * post, crit, nused and the small arrays are buffers of the field, grown on demand, kept and counted in ucf_field_alloc_count: a
+ * repeated call of the same size allocates nothing.  Every output may be NULL.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything ucf_field_forecast
+ * checks on field, nz, z, npar, ids, theta, dlog and the size of the slots; a NULL cov, and what the forecast checks on cov; a cov
+ * that is not positive definite (UCF_ERR_SINGULAR); sigma_s not positive and finite; sigma_d negative or not finite; ntgt outside
+ * 1..UCF_WORTH_MAX_TGT; a NULL tgt; a target kind, k, i or z out of range; a tw that is negative or not finite; npick outside
+ * 1..UCF_WORTH_MAX_PICK; a tsel that selects no time.  With a NULL plan UCF_ERR_NO_DEVICE comes before "NULL plan". */
+#define UCF_WORTH_MAX_TGT 16
+#define UCF_WORTH_MAX_PICK 16
+int ucf_field_worth(ucf_field* field, ucf_plan* plan, int npar, const int* ids, const double* theta, double dlog,
+                    const double* cov /*[npar][npar], ln theta; required*/, int nz, const double* z,
+                    double sigma_s, double sigma_d, const int* tsel /*[nt], NULL ok*/,
+                    int ntgt, const int* tgt /*[ntgt][4]: kind, k, i, z*/, const double* tw /*[ntgt], NULL = 1*/,
+                    int npick, const int* cmask /*[ncand], NULL ok*/,
+                    double* prior /*[npick][ntgt]*/, double* post /*[npick][ntgt][ncand]*/,
+                    double* crit /*[npick][ncand]*/, int* nused /*[ncand]*/, int* pick /*[npick]*/,
+                    double* cov_post /*[npar][npar]: after the last pick made*/, ucf_stats* stats);
+/* host only, no GPU: the factor of the covariance after nrow readings, row r with sensitivities J[r][.] (in ln theta) and weight
+ * w[r] = 1 / sigma.  B, l and d are formed from the rows, in the order given, by the statements of the kernel above (every row is
+ * used); then per entry
+ *     X[i][j] = F[i][j];  X[i][j] = X[i][j] - X[i][k] * l[j][k], k = 0 .. j-1 ascending     (X L' = F);
+ *     F_out[i][j] = X[i][j] / sqrt(d_j);
+ *     cov_out[i][j] = +0.0;  cov_out[i][j] = cov_out[i][j] + F_out[i][k] * F_out[j][k], k ascending          (cov_out NULL ok)
+ * so that F_out F_out' = F B^-1 F' = (C^-1 + sum w^2 j j')^-1 with C = F F'.  F general [npar][npar]; F_out may be F.  nrow = 0 is
+ * legal and returns F (J, w may then be NULL).  UCF_ERR_BAD_ARGUMENT: npar outside 1..UCF_FIT_MAX_PAR, a NULL array, nrow < 0, a
+ * number that is not finite, a negative w; UCF_ERR_SINGULAR where a d_j is not positive and finite (as in the kernel). */
+int ucf_worth_condition(int npar, const double* F /*[npar][npar]*/, int nrow, const double* J /*[nrow][npar]*/,
+                        const double* w /*[nrow]*/, double* F_out /*[npar][npar]*/, double* cov_out /*[npar][npar]; NULL ok*/);
+/* field_worth_kernel exactly as ucf_field_worth launches it (the same launcher), once, on caller data a_s, a_d
+ * [1 + 2 npar][nt][ncand] (a_d NULL ok where wd == 0), F [npar][npar], A [ntgt][npar], tw [ntgt] (NULL = 1), tsel [nt] (NULL = all):
+ * the twin of ucf_debug_ensemble.  post [ntgt][ncand], crit [ncand], nused [ncand]: each NULL ok.  The slot values and A may hold
+ * anything.  UCF_ERR_BAD_ARGUMENT: npar outside 1..UCF_FIT_MAX_PAR, nt or ncand < 1, (1 + 2 npar) nt ncand beyond 2^31-1 values, a
+ * NULL a_s, F or A, a NULL a_d with wd > 0, two_dlog not positive and finite, an F entry that is not finite, ws not positive and
+ * finite, wd negative or not finite, ntgt outside 1..UCF_WORTH_MAX_TGT, a tw that is negative or not finite, a tsel that selects
+ * no time.  Then UCF_ERR_NO_DEVICE without a device. */
+int ucf_debug_field_worth(int npar, int nt, int ncand, const double* a_s, const double* a_d, double two_dlog, const double* F,
+                          double ws, double wd, const int* tsel, int ntgt, const double* A, const double* tw,
+                          double* post, double* crit, int* nused);
 /* The reduction kernel of ucf_fit_evaluate exactly as a fit launches it (the same launcher, and through it the same choice among the
  * instantiations: npar 0..UCF_FIT_MAX_PAR x source x with / without derivative data), on caller data.  One 256-thread workgroup
  * per parameter set; set s owns the plans s (1 + 2 npar) + (0 base | 1 + 2j: parameter j up | 2 + 2j: parameter j down);

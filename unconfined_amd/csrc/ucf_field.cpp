@@ -38,13 +38,16 @@ struct ucf_field {
     ucf_buffer b_ens;
     // ucf_field_ensemble_weighted: the integer weights u [nens]
     ucf_buffer b_u;
+    // ucf_field_worth: its slots are b_sall / b_dsall; post [ntgt][ncand], crit [ncand], nused [ncand]; F, A, tw in one image
+    // and tsel [nt]; the indices and the values of a gather
+    ucf_buffer b_wpost, b_wcrit, b_wnused, b_wsmall, b_wtsel, b_widx, b_wval;
     ucf_plan* scratch = nullptr;           // the plan that ucf_field_forecast refreshes for every parameter set
     long long n_alloc = 0;
     // every device buffer above: the one list (ucf_field_destroy frees through it)
-    std::array<ucf_buffer*, 21> buffers()
+    std::array<ucf_buffer*, 28> buffers()
     {
         return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats, &b_sall, &b_dsall, &b_sens, &b_dsens,
-                 &b_se, &b_dse, &b_cov, &b_nbad, &b_ens, &b_u}};
+                 &b_se, &b_dse, &b_cov, &b_nbad, &b_ens, &b_u, &b_wpost, &b_wcrit, &b_wnused, &b_wsmall, &b_wtsel, &b_widx, &b_wval}};
     }
 };
 
@@ -309,6 +312,96 @@ int field_launches_of(const ucf_field* f, const ucf_params& P, std::vector<field
     return UCF_OK;
 }
 
+// What ucf_field_forecast and ucf_field_worth share: the 1 + 2 npar parameter sets of a forecast and what every group launches
+// under each of them
+struct forecast_work {
+    ucf_params sets[1 + 2 * UCF_FIT_MAX_PAR];
+    std::vector<std::vector<field_launch>> L;
+};
+
+// all of W under pl's parameters, before any launch
+int forecast_sets_of(const ucf_field* f, const ucf_plan* pl, int npar, const int* ids, const double* theta, double dlog, forecast_work& W)
+{
+    int rc = ucf_field_forecast_sets(&pl->P, npar, ids, theta, dlog, W.sets);
+    if (rc) return rc;
+    const int nset = 1 + 2 * npar, ng = (int)f->groups.size();
+    W.L.assign(nset, std::vector<field_launch>(ng));
+    for (int k = 0; k < nset; k++) {
+        ucf_derived D;
+        nondimensionalise(W.sets[k], D);
+        for (int g = 0; g < ng; g++)
+            if ((rc = field_group_core(f, W.sets[k], D, g, W.L[k][g]))) return forecast_set_failed(rc, k, ids, dlog);
+    }
+    return UCF_OK;
+}
+
+// the slots b_sall / b_dsall [1 + 2 npar][nout], grown and filled by field_map_sets; field_begin_launches has run with W.sets[0]
+// and the plan's device is current
+int forecast_slots(ucf_field* f, int npar, const int* ids, double dlog, const forecast_work& W, int nz, const double* z, long long nout,
+                   ucf_stats* stats)
+{
+    const int nset = 1 + 2 * npar;
+    const size_t sa = sizeof(double) * (size_t)nout * nset;
+    int rc;
+    if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every set", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every set", f->n_alloc)))
+        return rc;
+    return field_map_sets(f, nset, W.sets, [&](int k, const std::vector<field_launch>*& Lk) { Lk = &W.L[k]; return UCF_OK; }, nz, z, nout, stats,
+                          [&](int rc_k, int k) { return forecast_set_failed(rc_k, k, ids, dlog); });
+}
+
+// ---- data worth (ucf_field_worth, ucf_worth_condition, ucf_debug_field_worth): the host arithmetic that include/ucf.h states
+
+// J of one datum from its 2 npar slot values v (v[2j]: slot 1 + 2j, v[2j + 1]: slot 2 + 2j); false where one is not finite
+bool worth_J(int npar, const double* v, double two_dlog, double* J)
+{
+    bool ok = true;
+    for (int j = 0; j < npar; j++) {
+        ok = ok && std::isfinite(v[2 * j]) && std::isfinite(v[2 * j + 1]);
+        J[j] = (v[2 * j] - v[2 * j + 1]) / two_dlog;
+    }
+    return ok;
+}
+
+// g = F' J
+void worth_FtJ(int npar, const double* F, const double* J, double* g)
+{
+    for (int j = 0; j < npar; j++) {
+        double acc = 0.0;
+        for (int i = 0; i < npar; i++) acc = acc + F[i * npar + j] * J[i];
+        g[j] = acc;
+    }
+}
+
+// what ucf_field_worth and ucf_debug_field_worth check on the targets' weights and on the selection of times
+int worth_check_weights(int ntgt, const double* tw, int nt, const int* tsel)
+{
+    if (ntgt < 1 || ntgt > UCF_WORTH_MAX_TGT) return fail(UCF_ERR_BAD_ARGUMENT, "ntgt=%d outside 1..%d", ntgt, UCF_WORTH_MAX_TGT);
+    for (int t = 0; tw && t < ntgt; t++)
+        if (!(tw[t] >= 0.0) || !std::isfinite(tw[t])) return fail(UCF_ERR_BAD_ARGUMENT, "tw[%d]=%g must be finite and not negative", t, tw[t]);
+    bool any = !tsel;
+    for (int k = 0; tsel && k < nt; k++) any = any || tsel[k] != 0;
+    if (!any) return fail(UCF_ERR_BAD_ARGUMENT, "tsel selects none of the %d times: a well that is never read", nt);
+    return UCF_OK;
+}
+
+// The 2 npar perturbed slot values of the outputs e[0 .. ne) of both maps, to the host: hs, hd [ne][2 npar], value v of output q
+// from slot 1 + v.  b_widx and b_wval hold at least 2 npar ne and 4 npar ne entries.  The stream has drained on return.
+int worth_fetch(ucf_field* f, hipStream_t st, int device, int npar, long long nout, int ne, const long long* e, double* hs, double* hd)
+{
+    const int n = 2 * npar * ne;
+    std::vector<long long> idx((size_t)n);
+    for (int q = 0; q < ne; q++)
+        for (int v = 0; v < 2 * npar; v++) idx[(size_t)q * 2 * npar + v] = (long long)(1 + v) * nout + e[q];
+    drain drained{st};                     // idx outlives its copy
+    if (hipMemcpyAsync(f->b_widx.p, idx.data(), sizeof(long long) * n, hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the gather's indices failed: %s", hipGetErrorString(hipGetLastError()));
+    double* d_val = (double*)f->b_wval.p;
+    int rc = ucf_field_launch_gather(n, (const long long*)f->b_widx.p, (const double*)f->b_sall.p, d_val, st);
+    if (rc == UCF_OK) rc = ucf_field_launch_gather(n, (const long long*)f->b_widx.p, (const double*)f->b_dsall.p, d_val + n, st);
+    if (rc) return fail(rc, "gather kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    return copy_back({{hs, d_val, sizeof(double) * n}, {hd, d_val + n, sizeof(double) * n}}, st, device);
+}
+
 // splitmix64 (include/ucf.h states it with ucf_field_ensemble_draw)
 double ensemble_uniform(unsigned long long& state)
 {
@@ -479,28 +572,17 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
         return rc ? rc : fail(UCF_ERR_BAD_ARGUMENT, "NULL plan");
     }
     // the parameter sets and what every group launches under each of them: all of it before any launch
-    ucf_params sets[1 + 2 * UCF_FIT_MAX_PAR];
-    if ((rc = ucf_field_forecast_sets(&pl->P, npar, ids, theta, dlog, sets))) return rc;
-    const int ng = (int)f->groups.size();
-    std::vector<std::vector<field_launch>> L(nset, std::vector<field_launch>(ng));
-    for (int k = 0; k < nset; k++) {
-        ucf_derived D;
-        nondimensionalise(sets[k], D);
-        for (int g = 0; g < ng; g++)
-            if ((rc = field_group_core(f, sets[k], D, g, L[k][g]))) return forecast_set_failed(rc, k, ids, dlog);
-    }
-    if ((rc = field_begin_launches(f, pl, stats, &sets[0]))) return rc;
+    forecast_work W;
+    if ((rc = forecast_sets_of(f, pl, npar, ids, theta, dlog, W))) return rc;
+    if ((rc = field_begin_launches(f, pl, stats, &W.sets[0]))) return rc;
     ucf_plan* sp = f->scratch;
     device_switch dg(pl->device);
     const size_t so = sizeof(double) * (size_t)nout, sa = so * nset, sj = so * npar;
-    if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every set", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every set", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_nbad, sizeof(long long) * 2, "counts", f->n_alloc)) ||
+    if ((rc = grow_buffer(f->b_nbad, sizeof(long long) * 2, "counts", f->n_alloc)) ||
         (sens && (rc = grow_buffer(f->b_sens, sj, "sensitivities", f->n_alloc))) || (dsens && (rc = grow_buffer(f->b_dsens, sj, "derivative sensitivities", f->n_alloc))) ||
         (se && (rc = grow_buffer(f->b_se, so, "standard error", f->n_alloc))) || (dse && (rc = grow_buffer(f->b_dse, so, "derivative standard error", f->n_alloc))) ||
         (cov && (rc = grow_buffer(f->b_cov, sizeof(double) * UCF_FIT_MAX_PAR * UCF_FIT_MAX_PAR, "cov", f->n_alloc)))) return rc;
-    rc = field_map_sets(f, nset, sets, [&](int k, const std::vector<field_launch>*& Lk) { Lk = &L[k]; return UCF_OK; }, nz, z, nout, stats,
-                        [&](int rc_k, int k) { return forecast_set_failed(rc_k, k, ids, dlog); });
-    if (rc) return rc;
+    if ((rc = forecast_slots(f, npar, ids, dlog, W, nz, z, nout, stats))) return rc;
     hipStream_t st = plan_stream(sp);
     if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
     drain drained{st};
@@ -518,6 +600,228 @@ int ucf_field_forecast(ucf_field* f, ucf_plan* pl, int npar, const int* ids, con
     return copy_back({{s, f->b_sall.p, so}, {ds, f->b_dsall.p, so}, {sens, f->b_sens.p, sj}, {dsens, f->b_dsens.p, sj}, {se, f->b_se.p, so},
                       {dse, f->b_dse.p, so}, {s_all, f->b_sall.p, sa}, {ds_all, f->b_dsall.p, sa}, {nbad, f->b_nbad.p, sizeof(long long) * 2}},
                      st, pl->device);
+}
+
+int ucf_worth_condition(int npar, const double* F, int nrow, const double* J, const double* w, double* F_out, double* cov_out)
+{
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (nrow < 0) return fail(UCF_ERR_BAD_ARGUMENT, "nrow=%d is negative", nrow);
+    if (!F || !F_out || (nrow > 0 && (!J || !w))) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !F ? "F" : !F_out ? "F_out" : !J ? "J" : "w");
+    int rc;
+    if ((rc = field_check_finite("F", npar * npar, F))) return rc;
+    if ((long long)nrow * npar > 0x7fffffffLL) return fail(UCF_ERR_BAD_ARGUMENT, "nrow=%d: too many rows", nrow);
+    if ((rc = field_check_finite("J", nrow * npar, J)) || (rc = field_check_finite("w", nrow, w))) return rc;
+    for (int r = 0; r < nrow; r++)
+        if (w[r] < 0.0) return fail(UCF_ERR_BAD_ARGUMENT, "w[%d]=%g is negative", r, w[r]);
+    const int n = npar;
+    double B[UCF_FIT_MAX_PAR][UCF_FIT_MAX_PAR], d[UCF_FIT_MAX_PAR], X[UCF_FIT_MAX_PAR][UCF_FIT_MAX_PAR], g[UCF_FIT_MAX_PAR];
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j <= i; j++) B[i][j] = (i == j) ? 1.0 : 0.0;
+    for (int r = 0; r < nrow; r++) {
+        worth_FtJ(n, F, J + (size_t)r * n, g);
+        for (int j = 0; j < n; j++) g[j] = w[r] * g[j];
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j <= i; j++) B[i][j] = B[i][j] + g[i] * g[j];
+    }
+    // B = L D L': l in the strict lower triangle of B
+    for (int j = 0; j < n; j++) {
+        double v = B[j][j];
+        for (int k = 0; k < j; k++) v = v - (B[j][k] * B[j][k]) * d[k];
+        d[j] = v;
+        if (!(v > 0.0) || !std::isfinite(v)) return fail(UCF_ERR_SINGULAR, "d[%d]=%g of I + sum (w F'j)(w F'j)' is not positive and finite", j, v);
+        for (int i = j + 1; i < n; i++) {
+            double u = B[i][j];
+            for (int k = 0; k < j; k++) u = u - (B[i][k] * B[j][k]) * d[k];
+            B[i][j] = u / d[j];
+        }
+    }
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) {
+            double x = F[i * n + j];
+            for (int k = 0; k < j; k++) x = x - X[i][k] * B[j][k];
+            X[i][j] = x;
+        }
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j < n; j++) F_out[i * n + j] = X[i][j] / std::sqrt(d[j]);
+    if (cov_out)
+        for (int i = 0; i < n; i++)
+            for (int j = 0; j < n; j++) {
+                double acc = 0.0;
+                for (int k = 0; k < n; k++) acc = acc + F_out[i * n + k] * F_out[j * n + k];
+                cov_out[i * n + j] = acc;
+            }
+    return UCF_OK;
+}
+
+int ucf_field_worth(ucf_field* f, ucf_plan* pl, int npar, const int* ids, const double* theta, double dlog, const double* cov, int nz,
+                    const double* z, double sigma_s, double sigma_d, const int* tsel, int ntgt, const int* tgt, const double* tw, int npick,
+                    const int* cmask, double* prior, double* post, double* crit, int* nused, int* pick, double* cov_post, ucf_stats* stats)
+{
+    long long nout = 0;
+    int rc = field_check_call(f, nz, !z ? "NULL z" : !ids ? "NULL ids" : !theta ? "NULL theta" : nullptr, z, nout);
+    if (rc) return rc;
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (!(dlog > 0.0) || !std::isfinite(dlog)) return fail(UCF_ERR_BAD_ARGUMENT, "dlog=%g must be positive and finite", dlog);
+    if (!cov) return fail(UCF_ERR_BAD_ARGUMENT, "NULL cov: the worth of data is measured against the covariance of the fit");
+    if ((rc = field_check_cov(npar, cov))) return rc;
+    if (!(sigma_s > 0.0) || !std::isfinite(sigma_s)) return fail(UCF_ERR_BAD_ARGUMENT, "sigma_s=%g must be positive and finite", sigma_s);
+    if (!(sigma_d >= 0.0) || !std::isfinite(sigma_d)) return fail(UCF_ERR_BAD_ARGUMENT, "sigma_d=%g must be finite and not negative (0: no derivative data)", sigma_d);
+    if ((rc = worth_check_weights(ntgt, tw, f->nt, tsel))) return rc;
+    if (!tgt) return fail(UCF_ERR_BAD_ARGUMENT, "NULL tgt");
+    for (int t = 0; t < ntgt; t++) {
+        const int* g = tgt + 4 * t;
+        if (g[0] < 0 || g[0] > 1 || g[1] < 0 || g[1] >= f->nt || g[2] < 0 || g[2] >= f->nloc || g[3] < 0 || g[3] >= nz)
+            return fail(UCF_ERR_BAD_ARGUMENT, "tgt[%d] = (kind %d, time %d, location %d, depth %d) outside (0..1, 0..%d, 0..%d, 0..%d)", t, g[0], g[1],
+                        g[2], g[3], f->nt - 1, f->nloc - 1, nz - 1);
+    }
+    if (npick < 1 || npick > UCF_WORTH_MAX_PICK) return fail(UCF_ERR_BAD_ARGUMENT, "npick=%d outside 1..%d", npick, UCF_WORTH_MAX_PICK);
+    const int nset = 1 + 2 * npar;
+    if (nset * nout > 0x7fffffffLL * 256)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d parameter sets x %d times x %d locations x %d depths: too many values for one buffer", nset, f->nt, f->nloc, nz);
+    if ((long long)f->nloc * nz > 0x7fffffffLL) return fail(UCF_ERR_BAD_ARGUMENT, "%d locations x %d depths: too many candidates for one call", f->nloc, nz);
+    // cov = F F'
+    double F[UCF_FIT_MAX_PAR * UCF_FIT_MAX_PAR];
+    for (int i = 0; i < npar * npar; i++) F[i] = cov[i];
+    if (fit_cholesky_factor(npar, F) != UCF_OK) return fail(UCF_ERR_SINGULAR, "cov is not positive definite (%d x %d): it has no Cholesky factor", npar, npar);
+    for (int i = 0; i < npar; i++)
+        for (int j = i + 1; j < npar; j++) F[i * npar + j] = 0.0;
+    if (!pl) {
+        rc = require_device();
+        return rc ? rc : fail(UCF_ERR_BAD_ARGUMENT, "NULL plan");
+    }
+    forecast_work W;
+    if ((rc = forecast_sets_of(f, pl, npar, ids, theta, dlog, W))) return rc;
+    if ((rc = field_begin_launches(f, pl, stats, &W.sets[0]))) return rc;
+    ucf_plan* sp = f->scratch;
+    device_switch dg(pl->device);
+    const int nt = f->nt, ncand = f->nloc * nz, nfetch = std::max(ntgt, nt) * 2 * npar;
+    const size_t nc = (size_t)ncand;
+    // b_wsmall: F [MAX_PAR^2], A [MAX_TGT][MAX_PAR], tw [MAX_TGT]
+    constexpr int OFF_A = UCF_FIT_MAX_PAR * UCF_FIT_MAX_PAR, OFF_TW = OFF_A + UCF_WORTH_MAX_TGT * UCF_FIT_MAX_PAR, NSMALL = OFF_TW + UCF_WORTH_MAX_TGT;
+    if ((rc = grow_buffer(f->b_wpost, sizeof(double) * nc * ntgt, "posterior variances", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_wcrit, sizeof(double) * nc, "criterion", f->n_alloc)) || (rc = grow_buffer(f->b_wnused, sizeof(int) * nc, "data counts", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_wsmall, sizeof(double) * NSMALL, "factor and targets", f->n_alloc)) || (rc = grow_buffer(f->b_wtsel, sizeof(int) * nt, "time selection", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_widx, sizeof(long long) * nfetch, "gather indices", f->n_alloc)) || (rc = grow_buffer(f->b_wval, sizeof(double) * 2 * nfetch, "gathered values", f->n_alloc)))
+        return rc;
+    if ((rc = forecast_slots(f, npar, ids, dlog, W, nz, z, nout, stats))) return rc;
+    hipStream_t st = plan_stream(sp);
+    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
+    const double two_dlog = 2.0 * dlog, ws = 1.0 / sigma_s, wd = sigma_d > 0.0 ? 1.0 / sigma_d : 0.0;
+    std::vector<int> sel(nt, 1);
+    for (int k = 0; tsel && k < nt; k++) sel[k] = tsel[k] != 0;
+    double small[NSMALL] = {};
+    for (int t = 0; t < ntgt; t++) small[OFF_TW + t] = tw ? tw[t] : 1.0;
+    drain drained{st};                     // sel and small outlive their copies
+    if (hipMemcpyAsync(f->b_wtsel.p, sel.data(), sizeof(int) * nt, hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the time selection failed: %s", hipGetErrorString(hipGetLastError()));
+    // the targets' sensitivities, once
+    std::vector<long long> e((size_t)std::max(ntgt, nt));
+    std::vector<double> hs((size_t)nfetch), hd((size_t)nfetch);
+    for (int t = 0; t < ntgt; t++) e[t] = ((long long)tgt[4 * t + 1] * f->nloc + tgt[4 * t + 2]) * nz + tgt[4 * t + 3];
+    if ((rc = worth_fetch(f, st, pl->device, npar, nout, ntgt, e.data(), hs.data(), hd.data()))) return rc;
+    double Jt[UCF_WORTH_MAX_TGT][UCF_FIT_MAX_PAR];
+    bool tgt_ok[UCF_WORTH_MAX_TGT];
+    for (int t = 0; t < ntgt; t++) tgt_ok[t] = worth_J(npar, (tgt[4 * t] ? hd.data() : hs.data()) + (size_t)t * 2 * npar, two_dlog, Jt[t]);
+    // what the rounds that do not run leave behind
+    const double nan = std::nan("");
+    if (prior) std::fill(prior, prior + (size_t)npick * ntgt, nan);
+    if (post) std::fill(post, post + (size_t)npick * ntgt * nc, nan);
+    if (crit) std::fill(crit, crit + (size_t)npick * nc, nan);
+    if (pick) std::fill(pick, pick + npick, -1);
+    std::vector<double> hcrit(nc), rows, wrow;
+    std::vector<char> taken(nc, 0);
+    for (int r = 0; r < npick; r++) {
+        for (int t = 0; t < ntgt; t++) {
+            double* A = small + OFF_A + t * npar;
+            worth_FtJ(npar, F, Jt[t], A);
+            double p = 0.0;
+            for (int j = 0; j < npar; j++) {
+                if (!tgt_ok[t]) A[j] = nan;
+                p = p + A[j] * A[j];
+            }
+            if (prior) prior[(size_t)r * ntgt + t] = p;
+        }
+        for (int i = 0; i < npar * npar; i++) small[i] = F[i];
+        if (hipMemcpyAsync(f->b_wsmall.p, small, sizeof(small), hipMemcpyHostToDevice, st) != hipSuccess)
+            return fail(UCF_ERR_HIP, "upload of the factor and the targets failed: %s", hipGetErrorString(hipGetLastError()));
+        const double* d_small = (const double*)f->b_wsmall.p;
+        rc = ucf_field_launch_worth(npar, nt, ncand, (const double*)f->b_sall.p, (const double*)f->b_dsall.p, two_dlog, d_small, ws, wd,
+                                    (const int*)f->b_wtsel.p, ntgt, d_small + OFF_A, d_small + OFF_TW, (double*)f->b_wpost.p, (double*)f->b_wcrit.p,
+                                    (int*)f->b_wnused.p, st);
+        if (rc) return fail(rc, "worth kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        if ((rc = copy_back({{post ? post + (size_t)r * ntgt * nc : nullptr, f->b_wpost.p, sizeof(double) * nc * ntgt}, {hcrit.data(), f->b_wcrit.p, sizeof(double) * nc},
+                             {r == 0 ? nused : nullptr, f->b_wnused.p, sizeof(int) * nc}}, st, pl->device))) return rc;
+        if (crit) std::copy(hcrit.begin(), hcrit.end(), crit + (size_t)r * nc);
+        // the allowed, unpicked candidate of least finite crit; the lowest index on a tie
+        int best = -1;
+        for (int c = 0; c < ncand; c++)
+            if ((!cmask || cmask[c] != 0) && !taken[c] && std::isfinite(hcrit[c]) && (best < 0 || hcrit[c] < hcrit[best])) best = c;
+        if (best < 0) break;
+        if (pick) pick[r] = best;
+        taken[best] = 1;
+        if (r + 1 == npick && !cov_post) break;
+        // the used data of the picked candidate in kernel order, and the factor after them
+        int ne = 0;
+        for (int k = 0; k < nt; k++)
+            if (sel[k]) e[ne++] = (long long)k * ncand + best;
+        if ((rc = worth_fetch(f, st, pl->device, npar, nout, ne, e.data(), hs.data(), hd.data()))) return rc;
+        rows.clear(); wrow.clear();
+        double J[UCF_FIT_MAX_PAR];
+        for (int q = 0; q < ne; q++)
+            for (int kind = 0; kind < 2; kind++) {
+                const double wk = kind ? wd : ws;
+                if (!(wk > 0.0) || !worth_J(npar, (kind ? hd.data() : hs.data()) + (size_t)q * 2 * npar, two_dlog, J)) continue;
+                rows.insert(rows.end(), J, J + npar);
+                wrow.push_back(wk);
+            }
+        if ((rc = ucf_worth_condition(npar, F, (int)wrow.size(), rows.data(), wrow.data(), F, nullptr))) return rc;
+    }
+    if (cov_post) {
+        double same[UCF_FIT_MAX_PAR * UCF_FIT_MAX_PAR];
+        if ((rc = ucf_worth_condition(npar, F, 0, nullptr, nullptr, same, cov_post))) return rc;
+    }
+    return UCF_OK;
+}
+
+int ucf_debug_field_worth(int npar, int nt, int ncand, const double* a_s, const double* a_d, double two_dlog, const double* F, double ws,
+                          double wd, const int* tsel, int ntgt, const double* A, const double* tw, double* post, double* crit, int* nused)
+{
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (nt < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nt=%d: at least one time", nt);
+    if (ncand < 1) return fail(UCF_ERR_BAD_ARGUMENT, "ncand=%d: at least one candidate", ncand);
+    const long long nval = (long long)(1 + 2 * npar) * nt * ncand;
+    if (nval > 0x7fffffffLL) return fail(UCF_ERR_BAD_ARGUMENT, "%d slots x %d times x %d candidates: more than 2^31-1 values", 1 + 2 * npar, nt, ncand);
+    if (!a_s || !F || !A) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !a_s ? "a_s" : !F ? "F" : "A");
+    if (!(two_dlog > 0.0) || !std::isfinite(two_dlog)) return fail(UCF_ERR_BAD_ARGUMENT, "two_dlog=%g must be positive and finite", two_dlog);
+    int rc = field_check_finite("F", npar * npar, F);
+    if (rc) return rc;
+    if (!(ws > 0.0) || !std::isfinite(ws)) return fail(UCF_ERR_BAD_ARGUMENT, "ws=%g must be positive and finite", ws);
+    if (!(wd >= 0.0) || !std::isfinite(wd)) return fail(UCF_ERR_BAD_ARGUMENT, "wd=%g must be finite and not negative (0: no derivative data)", wd);
+    if (wd > 0.0 && !a_d) return fail(UCF_ERR_BAD_ARGUMENT, "NULL a_d with wd=%g", wd);
+    if ((rc = worth_check_weights(ntgt, tw, nt, tsel))) return rc;
+    if ((rc = require_device())) return rc;
+    const size_t sa = sizeof(double) * (size_t)nval, nc = (size_t)ncand;
+    std::vector<int> sel(nt, 1);
+    for (int k = 0; tsel && k < nt; k++) sel[k] = tsel[k] != 0;
+    double w1[UCF_WORTH_MAX_TGT];
+    for (int t = 0; t < ntgt; t++) w1[t] = tw ? tw[t] : 1.0;
+    dev_buf b_as, b_ad, b_F, b_sel, b_A, b_tw, b_post, b_crit, b_nused;
+    if (b_as.alloc(sa) || (wd > 0.0 && b_ad.alloc(sa)) || b_F.alloc(sizeof(double) * npar * npar) || b_sel.alloc(sizeof(int) * nt) ||
+        b_A.alloc(sizeof(double) * ntgt * npar) || b_tw.alloc(sizeof(double) * ntgt) || b_post.alloc(sizeof(double) * nc * ntgt) ||
+        b_crit.alloc(sizeof(double) * nc) || b_nused.alloc(sizeof(int) * nc))
+        return fail(UCF_ERR_NOMEM, "device allocation failed");
+    HIP_TRY(hipMemcpy(b_as.p, a_s, sa, hipMemcpyHostToDevice));
+    if (wd > 0.0) HIP_TRY(hipMemcpy(b_ad.p, a_d, sa, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_F.p, F, sizeof(double) * npar * npar, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_sel.p, sel.data(), sizeof(int) * nt, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_A.p, A, sizeof(double) * ntgt * npar, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_tw.p, w1, sizeof(double) * ntgt, hipMemcpyHostToDevice));
+    rc = ucf_field_launch_worth(npar, nt, ncand, (const double*)b_as.p, (const double*)b_ad.p, two_dlog, (const double*)b_F.p, ws, wd,
+                                (const int*)b_sel.p, ntgt, (const double*)b_A.p, (const double*)b_tw.p, (double*)b_post.p, (double*)b_crit.p,
+                                (int*)b_nused.p, nullptr);
+    if (rc) return fail(rc, "worth kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return copy_back_sync({{post, b_post.p, sizeof(double) * nc * ntgt}, {crit, b_crit.p, sizeof(double) * nc}, {nused, b_nused.p, sizeof(int) * nc}});
 }
 
 // ucf_field_ensemble (weighted == false: weight, u_out, ess, nlaunched are not read) and ucf_field_ensemble_weighted: one

@@ -1,6 +1,6 @@
 // ucf_field.h -- launchers of the well-field kernels: the superposition, called by ucf_field_drawdown, ucf_field_forecast and
-// ucf_field_ensemble (ucf_field.cpp), the combination of a forecast (both ucf_field.hip) and the reduction of an ensemble
-// (ucf_field_ensemble.hip).
+// ucf_field_ensemble (ucf_field.cpp), the combination of a forecast (both ucf_field.hip), the reduction of an ensemble
+// (ucf_field_ensemble.hip) and the data worth of candidate wells (ucf_field_worth.hip).
 #pragma once
 #include <cstddef>
 
@@ -56,3 +56,16 @@ struct ucf_ensemble_reduce_args {
 int ucf_field_launch_ensemble_reduce(const ucf_ensemble_reduce_args* a, void* stream);
 // outputs per workgroup of the quantile kernels: 64 / 32 / 16 for nens <= 256 / 512 / 1024
 int ucf_field_ensemble_tile(int nens);
+
+// Data worth (ucf_field_worth.hip), field_worth_kernel<npar>: one thread per candidate c of the slots d_as, d_ad
+// [1 + 2 npar][nt][ncand], one wave per workgroup; the arithmetic is stated with ucf_field_worth in include/ucf.h.  d_F
+// [npar][npar] (general, row-major), d_tsel [nt] (never NULL here: all ones where the caller selects every time), d_A
+// [ntgt][npar], d_tw [ntgt]; d_post [ntgt][ncand], d_crit [ncand], d_nused [ncand].  d_ad is read only where wd > 0 (NULL ok
+// otherwise).  Device memory throughout.  UCF_ERR_BAD_ARGUMENT for npar outside 1..UCF_FIT_MAX_PAR, ntgt outside
+// 1..UCF_WORTH_MAX_TGT, nt or ncand < 1, a NULL array that the kernel would read or write.
+int ucf_field_launch_worth(int npar, int nt, int ncand, const double* d_as, const double* d_ad, double two_dlog, const double* d_F,
+                           double ws, double wd, const int* d_tsel, int ntgt, const double* d_A, const double* d_tw, double* d_post,
+                           double* d_crit, int* d_nused, void* stream);
+// field_gather_kernel: d_out[i] = d_a[d_idx[i]], i = 0 .. n-1 -- the few slot values that the host needs (targets, the column
+// of a picked candidate) of maps that stay on the device.  The caller has checked every index against the length of d_a.
+int ucf_field_launch_gather(int n, const long long* d_idx, const double* d_a, double* d_out, void* stream);

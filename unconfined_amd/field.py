@@ -28,6 +28,12 @@ Members that are a design and not a sample -- a Latin hypercube, the rows of a m
     lw = likelihood_weights(fit.objective(thetas)["phi"])
     out = field.ensemble(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], limits=[0.5], weights=lw["weight"])
     out["quant"], out["ess"], out["nlaunched"]                                                # weighted inverse CDF, effective sample size
+
+Where the next observation wells have to go so that a forecast becomes sure -- every (location, depth) of the map is a candidate,
+the maps stay on the GPU and the picks cost one small launch each (ucf_field_worth):
+
+    out = field.worth(plan, ["Kr", "Ss"], res["theta"][0], res["cov"][0], z=[145.7, 100.0], targets=[("s", 2, 1, 0)], sigma=0.01, picks=3)
+    out["pick"], out["reduction"], out["cov_post"]                                            # [(i, z)] * 3, [3, ntgt, nloc, nz], [npar, npar]
 """
 from __future__ import annotations
 
@@ -73,6 +79,24 @@ def ensemble_draw(theta, cov, n: int, seed: int = 0):
     out = np.zeros((max(int(n), 0), len(theta)))
     _libmod.check(_libmod.load().ucf_field_ensemble_draw(len(theta), _addr(theta), _addr(cov), int(n), int(seed) & (2 ** 64 - 1), _addr(out)))
     return out
+
+
+def worth_condition(F, J, w):
+    """the factor of the covariance after the readings (J [nrow, npar] their sensitivities in ln theta, w [nrow] = 1 / sigma):
+    F_out and cov_out = F_out F_out' = (C^-1 + sum w^2 j j')^-1 with C = F F' (ucf_worth_condition; no GPU).  F is any square
+    factor of C; no rows returns F itself."""
+    F = np.atleast_2d(_f64(F))
+    n = len(F)
+    if F.shape != (n, n):
+        raise ValueError("F: [npar, npar]")
+    J = _f64(J).reshape(-1, n) if np.size(J) else np.zeros((0, n))
+    w = np.atleast_1d(_f64(w)) if np.size(w) else np.zeros(0)
+    if len(w) != len(J):
+        raise ValueError("w: one weight per row of J")
+    F_out, cov_out = np.zeros((n, n)), np.zeros((n, n))
+    _libmod.check(_libmod.load().ucf_worth_condition(n, _addr(F), len(J), _addr(J) if len(J) else None, _addr(w) if len(J) else None,
+                                                     _addr(F_out), _addr(cov_out)))
+    return F_out, cov_out
 
 
 def _wells(wells):
@@ -244,6 +268,56 @@ class WellField:
             _libmod.check(self._lib.ucf_field_ensemble_weighted(self._h, plan._h, len(ids), _addr(ids), nens, _addr(thetas), _addr(w), *levels,
                                                                 _addr(out["u"]), C.addressof(ess), C.addressof(nl)))
             out["ess"], out["nlaunched"] = float(ess.value), int(nl.value)
+        if with_stats:
+            out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
+        return out
+
+    def worth(self, plan, free, theta, cov, z, targets, sigma, sigma_d: float = 0.0, times=None, picks: int = 1, weights=None,
+              allowed=None, dlog: float = 1e-3, with_stats: bool = False) -> dict:
+        """where the next observation wells have to go (ucf_field_worth): every (location, depth) of the map is a candidate well
+        that records the drawdown with standard deviation ``sigma`` (and, with ``sigma_d`` > 0, its log-time derivative) at the
+        times selected by ``times`` (a mask [nt]; None: all).  ``targets`` are forecasts of the same map, (kind, k, i, z) each
+        with kind 's' or 'ds' and the indices of time, location and depth; ``weights`` [ntgt] weigh them in the criterion
+        (None: 1).  ``theta`` and ``cov`` are those of ``Fit.lm``.  Greedily ``picks`` wells are chosen among the candidates
+        that ``allowed`` [nloc, nz] admits (None: all), each conditioning the covariance for the next round.  Returns prior
+        [picks, ntgt], the variance of every target before a round; post [picks, ntgt, nloc, nz], what a candidate would leave
+        of it; reduction = 1 - post / prior; crit [picks, nloc, nz], the weighted sum of post; nused [nloc, nz] (int32), the
+        readings of a candidate that are finite; pick, per round (location, depth) or None; cov_post [npar, npar], the
+        covariance after the last pick made.  ``plan`` is not modified."""
+        ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
+        theta = np.atleast_1d(_f64(theta))
+        if len(theta) != len(ids):
+            raise ValueError("theta: one value per free parameter")
+        npar = len(ids)
+        cov = _f64(cov)
+        if cov.shape != (npar, npar):
+            raise ValueError("cov: [npar, npar]")
+        z = np.atleast_1d(_f64(z))
+        nz, picks = len(z), int(picks)
+        kinds = {"s": 0, "ds": 1, 0: 0, 1: 1}
+        tgt = np.ascontiguousarray([(kinds[t[0]], int(t[1]), int(t[2]), int(t[3])) for t in targets], dtype=np.int32).reshape(-1, 4)
+        ntgt = len(tgt)
+        tw = None if weights is None else np.atleast_1d(_f64(weights))
+        if tw is not None and len(tw) != ntgt:
+            raise ValueError("weights: one value per target")
+        tsel = None if times is None else np.ascontiguousarray(np.asarray(times) != 0, dtype=np.int32)
+        if tsel is not None and tsel.shape != (self.nt,):
+            raise ValueError("times: a mask [nt]")
+        cmask = None if allowed is None else np.ascontiguousarray(np.asarray(allowed) != 0, dtype=np.int32)
+        if cmask is not None and cmask.size != self.nloc * nz:
+            raise ValueError("allowed: a mask [nloc, nz]")
+        n = max(picks, 0)
+        out = {"prior": np.zeros((n, ntgt)), "post": np.zeros((n, ntgt, self.nloc, nz)), "crit": np.zeros((n, self.nloc, nz)),
+               "nused": np.zeros((self.nloc, nz), np.int32), "cov_post": np.zeros((npar, npar))}
+        pick = np.zeros(n, np.int32)
+        st = UcfStats()
+        _libmod.check(self._lib.ucf_field_worth(
+            self._h, plan._h, npar, _addr(ids), _addr(theta), float(dlog), _addr(cov), nz, _addr(z), float(sigma), float(sigma_d), _addr(tsel),
+            ntgt, _addr(tgt), _addr(tw), picks, _addr(cmask), *(_addr(out[k]) for k in ("prior", "post", "crit", "nused")), _addr(pick),
+            _addr(out["cov_post"]), C.byref(st) if with_stats else None))
+        out["pick"] = [None if c < 0 else (int(c) // nz, int(c) % nz) for c in pick]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["reduction"] = 1.0 - out["post"] / out["prior"][:, :, None, None]
         if with_stats:
             out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
         return out

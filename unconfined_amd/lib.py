@@ -46,6 +46,7 @@ EXPORTS = [
     "ucf_field_ensemble", "ucf_field_ensemble_draw", "ucf_debug_ensemble", "ucf_debug_fit_reduce",
     "ucf_fit_objective", "ucf_ensemble_quantise", "ucf_ensemble_likelihood_weights", "ucf_field_ensemble_weighted",
     "ucf_debug_ensemble_weighted",
+    "ucf_field_worth", "ucf_worth_condition", "ucf_debug_field_worth",
 ]
 
 
@@ -183,6 +184,13 @@ def load() -> C.CDLL:
     lib.ucf_field_ensemble_weighted.argtypes = [vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp,
                                                 C.POINTER(UcfEnsembleMaps), C.POINTER(UcfEnsembleMaps), vp, vp, C.POINTER(UcfStats), vp, vp, vp]
     lib.ucf_debug_ensemble_weighted.argtypes = [C.c_int, C.c_longlong, vp, vp, C.c_int, vp, C.c_int, vp, C.POINTER(UcfEnsembleMaps), vp, vp]
+    # every array may be NULL: plain addresses.  field, plan, npar, ids, theta, dlog, cov, nz, z | sigma_s, sigma_d, tsel | ntgt,
+    # tgt, tw | npick, cmask | prior, post, crit, nused, pick, cov_post | stats
+    lib.ucf_field_worth.argtypes = ([vp, vp, C.c_int, vp, vp, C.c_double, vp, C.c_int, vp] + [C.c_double, C.c_double, vp] + [C.c_int, vp, vp] +
+                                    [C.c_int, vp] + [vp] * 6 + [C.POINTER(UcfStats)])
+    lib.ucf_worth_condition.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    # npar, nt, ncand, a_s, a_d, two_dlog, F, ws, wd, tsel, ntgt, A, tw, post, crit, nused
+    lib.ucf_debug_field_worth.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, vp, C.c_double, C.c_double, vp, C.c_int, vp, vp, vp, vp, vp]
     # every array may be NULL for a source or a call that does not read it: plain addresses
     lib.ucf_debug_fit_reduce.argtypes = ([C.c_int] * 4 + [C.c_double, C.c_longlong] + [vp] * 8 + [C.c_longlong, C.c_int] + [vp] * 7 + [vp] * 6)
     _lib = lib
