@@ -843,6 +843,88 @@ int ucf_worth_condition(int npar, const double* F /*[npar][npar]*/, int nrow, co
 int ucf_debug_field_worth(int npar, int nt, int ncand, const double* a_s, const double* a_d, double two_dlog, const double* F,
                           double ws, double wd, const int* tsel, int ntgt, const double* A, const double* tw,
                           double* post, double* crit, int* nused);
+/* ---- well-field yield: how much may these wells pump before a permitted drawdown is exceeded somewhere, and how sure is that
+ * under the posterior.  Drawdown is linear in the rates: with the group results of a member on the device its map is an affine
+ * function of any rate multipliers, and the largest admissible multiplier is a ratio test over the constrained outputs.  One
+ * ensemble's worth of evaluator launches answers every rate pattern at once.
+ *   controls     a control is a set of wells whose rates move together (a real well with its images).  ctl[j], one per well of the
+ *                field, in -1 .. nctl-1: -1 = the well is fixed and is not scaled; every control 0 .. nctl-1 owns at least one well;
+ *                nctl in 1..UCF_YIELD_MAX_CTL.
+ *   patterns     x [npat][nctl]: multipliers on the wells' qw, every entry finite (negative and zero are legal), npat in
+ *                1..UCF_YIELD_MAX_PAT.  Pattern p at scale lam pumps well j of control c at lam * x[p][c] * qw[j] (in units of the
+ *                plan's Q); a fixed well pumps qw[j].
+ *   limits       limit [nt][nloc][nz]: dimensional drawdowns; +inf = the output is unconstrained; NaN and -inf are refused.  con =
+ *                the ascending list of the output indices e = (k nloc + iloc) nz + z with a finite limit, ncon >= 1 of them.
+ *   smax         the largest scale of interest (the pump capacity), positive and finite: it keeps every result finite.
+ *   members      those of ucf_field_ensemble; with weight != NULL u = ucf_ensemble_quantise(weight) as in
+ *                ucf_field_ensemble_weighted: a member with u[m] = 0 is validated but not launched, its rows of R are NaN bytes
+ *                (0xff) and through R its rows of y, fe, hi, lo are NaN; u, *ess, *nlaunched are written with or without a device.
+ *   response     per member m exactly what ucf_field_ensemble runs per member up to the superposition -- the same launch arrays,
+ *                group calls, scratch plan and order -- then, in place of field_superpose_kernel, field_response_kernel: one thread
+ *                per (slot c = 0 .. nctl, constrained output i), e = con[i] = (k, iloc, z):
+ *                    acc = +0.0
+ *                    for j = 0 .. nwell-1 in the caller's order, only the wells with ctl[j] == c (slot nctl: ctl[j] == -1) and
+ *                        k >= k0_j:   acc = acc + q_j * h[at]                     (the index `at` of field_superpose_kernel)
+ *                    R[m][c][i] = acc * Hc_m
+ *                every operation rounded on its own; the drawdown only (dh is not read).  With one control that holds every well
+ *                R[m][0][i] has the bits of the member map of ucf_field_ensemble at con[i].
+ *   ratio test   field_yield_kernel<nctl>, for member m and pattern p over i = 0 .. ncon-1, with b = R[m][nctl][i], r_c = R[m][c][i]:
+ *                    hi = smax;  lo = +0.0;  dead = 0;  bind = -1
+ *                    room = limit[con[i]] - b
+ *                    D = +0.0;  D = D + x[p][c] * r_c,  c ascending                  (one product, one sum, each rounded)
+ *                    D > 0:   cand = room / D;  if cand < hi, or (cand == hi and bind == -1):  hi = cand, bind = con[i]
+ *                    D < 0:   cand = room / D;  if cand > lo:  lo = cand
+ *                    D == 0:  if room < 0:  dead = 1
+ *                  after the loop:
+ *                    feas = (dead == 0 && lo <= hi);    y[m][p] = feas ? hi : +0.0;    fe[m][p] = feas ? 1.0 : 0.0
+ *                The result is defined without order: hi is the least candidate (smax where none is below it), lo the greatest, bind
+ *                the lowest con[i] among the outputs whose candidate equals hi under ==, -1 where no candidate is <= smax.  A
+ *                candidate or a D that is NaN passes no comparison and changes nothing.  The sign of a zero in hi, lo and y is not
+ *                part of the contract.  A negative hi (room < 0 with D > 0) is below lo: not feasible.  Member m is valid when
+ *                every one of its (nctl + 1) ncon slot values is finite (the Wynn sentinel is finite and takes part, as everywhere);
+ *                for an invalid member y, fe, hi, lo are NaN, bind is -1 and dead is 0 for every pattern.  *nbad = the launched
+ *                members that are invalid, each counted once (one integer atomic per member).  No floating-point atomics: a call
+ *                repeated gives the same bits.
+ *   reduction    no kernel of its own: the reduction of ucf_field_ensemble (of ucf_field_ensemble_weighted with weights) with
+ *                nout = npat, on y for ystat (mean, sd, min, max, quant at q, nfin; all = y) and for pexc [nlev][npat], the share
+ *                of members whose admissible scale exceeds level[l]; on fe with the single limit 0.5 for pfeas [npat], the share of
+ *                valid members that admit any scale.  Reading a quantile: quant at level q is the scale that a share 1 - q of the
+ *                ensemble admits -- the yield at reliability 1 - q; the 5 % map is the scale that 95 % of the members admit.
+ *   outputs      hi, lo (double), bind, dead (int) [nens][npat]; resp [nens][nctl + 1][ncon] = R; con [nout] with its first *ncon
+ *                entries filled, and *ncon: written by the checks, with or without a device; stats summed over the launched
+ *                members and groups.  Every output may be NULL.
+ * R, y, fe, hi, lo, bind, dead, con, ctl, x and the limits are buffers of the field, grown on demand, kept and counted in
+ * ucf_field_alloc_count: a repeated call of the same or a smaller size allocates nothing.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything
+ * ucf_field_ensemble_weighted checks on field, nz, z, npar, ids, nens, thetas, nq, q, nlev, level (as its nlim, limit), quant and
+ * pexc, and on weight where it is not NULL; nctl outside 1..UCF_YIELD_MAX_CTL; a NULL ctl, x or limit; a ctl outside -1 .. nctl-1;
+ * a control without a well; npat outside 1..UCF_YIELD_MAX_PAT; an x that is not finite; a limit that is NaN or -inf; no finite
+ * limit at all; nt nloc nz beyond 2^31-1 (con and bind are ints); smax not positive and finite; nens (nctl + 1) ncon beyond what
+ * one buffer may hold.  With a NULL plan UCF_ERR_NO_DEVICE comes before "NULL plan". */
+#define UCF_YIELD_MAX_CTL 8        /* controls of one ucf_field_yield */
+#define UCF_YIELD_MAX_PAT 4096     /* rate patterns of one ucf_field_yield */
+#define UCF_YIELD_PAT_TILE 8       /* patterns per workgroup of field_yield_kernel */
+int ucf_field_yield(ucf_field* field, ucf_plan* plan, int npar, const int* ids,
+                    int nens, const double* thetas /*[nens][npar]*/, const double* weight /*[nens]; NULL ok: unweighted*/,
+                    int nz, const double* z,
+                    int nctl, const int* ctl /*[nwell]*/, int npat, const double* x /*[npat][nctl]*/,
+                    const double* limit /*[nt][nloc][nz]*/, double smax,
+                    int nq, const double* q /*[nq]*/, int nlev, const double* level /*[nlev], scales*/,
+                    const ucf_ensemble_maps* ystat /*of y, nout = npat*/, double* pexc /*[nlev][npat]*/, double* pfeas /*[npat]*/,
+                    double* hi, double* lo, int* bind, int* dead /*[nens][npat] each*/,
+                    double* resp /*[nens][nctl+1][ncon]*/, int* con /*[nout], first *ncon filled*/, int* ncon,
+                    long long* nbad /*[1]*/, ucf_stats* stats,
+                    unsigned long long* u /*[nens]*/, double* ess, int* nlaunched);
+/* field_yield_kernel exactly as ucf_field_yield launches it (the same launcher), once, on caller data R [nens][nctl + 1][ncon], x
+ * [npat][nctl], limit_con [ncon] (the limit of constrained output i) and con [ncon]: the twin of ucf_debug_field_worth.  y, fe,
+ * hi, lo, bind, dead [nens][npat] and nbad [1] (every invalid member): each NULL ok.  R may hold anything.
+ * UCF_ERR_BAD_ARGUMENT: nctl outside 1..UCF_YIELD_MAX_CTL, nens outside 1..UCF_ENSEMBLE_MAX, ncon < 1, npat outside
+ * 1..UCF_YIELD_MAX_PAT, nens (nctl + 1) ncon beyond 2^31-1 values, a NULL R, x, limit_con or con, an x or a limit_con that is not
+ * finite, a con that is negative or does not ascend strictly, smax not positive and finite.  Then UCF_ERR_NO_DEVICE without a
+ * device. */
+int ucf_debug_field_yield(int nctl, int nens, int ncon, int npat, const double* R, const double* x, const double* limit_con,
+                          const int* con, double smax, double* y, double* fe, double* hi, double* lo, int* bind, int* dead,
+                          long long* nbad /*[1]*/);
 /* The reduction kernel of ucf_fit_evaluate exactly as a fit launches it (the same launcher, and through it the same choice among the
  * instantiations: npar 0..UCF_FIT_MAX_PAR x source x with / without derivative data), on caller data.  One 256-thread workgroup
  * per parameter set; set s owns the plans s (1 + 2 npar) + (0 base | 1 + 2j: parameter j up | 2 + 2j: parameter j down);

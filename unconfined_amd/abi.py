@@ -13,6 +13,9 @@ UCF_ENSEMBLE_MAX = 1024       # members of one ucf_field_ensemble
 UCF_ENSEMBLE_MAX_Q = 16       # quantile levels, and drawdown limits, per call
 UCF_WORTH_MAX_TGT = 16        # forecast targets of one ucf_field_worth
 UCF_WORTH_MAX_PICK = 16       # wells that one ucf_field_worth picks
+UCF_YIELD_MAX_CTL = 8         # controls of one ucf_field_yield
+UCF_YIELD_MAX_PAT = 4096      # rate patterns of one ucf_field_yield
+UCF_YIELD_PAT_TILE = 8        # patterns per workgroup of field_yield_kernel
 # parameter ids of a fit (enum UCF_PAR_* of include/ucf.h); a Moench alpha is PAR_MOENCH_ALPHA0 + i
 PAR_KR, PAR_KAPPA, PAR_SS, PAR_SY, PAR_AC, PAR_AK, PAR_USL, PAR_MOENCH_ALPHA0 = range(8)
 PAR_IDS = {"Kr": PAR_KR, "kappa": PAR_KAPPA, "Ss": PAR_SS, "Sy": PAR_SY, "ac": PAR_AC, "ak": PAR_AK, "usL": PAR_USL}

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <new>
 #include <string>
 #include <vector>
@@ -41,13 +42,17 @@ struct ucf_field {
     // ucf_field_worth: its slots are b_sall / b_dsall; post [ntgt][ncand], crit [ncand], nused [ncand]; F, A, tw in one image
     // and tsel [nt]; the indices and the values of a gather
     ucf_buffer b_wpost, b_wcrit, b_wnused, b_wsmall, b_wtsel, b_widx, b_wval;
+    // ucf_field_yield: the response slots R [nens][nctl + 1][ncon]; con [ncon] and ctl [nwell]; x [npat][nctl] and the limits
+    // [ncon]; y, fe, hi, lo [4][nens][npat]; bind, dead [2][nens][npat].  Its statistics are staged in b_ens.
+    ucf_buffer b_yR, b_yint, b_ysmall, b_yval, b_yidx;
     ucf_plan* scratch = nullptr;           // the plan that ucf_field_forecast refreshes for every parameter set
     long long n_alloc = 0;
     // every device buffer above: the one list (ucf_field_destroy frees through it)
-    std::array<ucf_buffer*, 28> buffers()
+    std::array<ucf_buffer*, 33> buffers()
     {
         return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats, &b_sall, &b_dsall, &b_sens, &b_dsens,
-                 &b_se, &b_dse, &b_cov, &b_nbad, &b_ens, &b_u, &b_wpost, &b_wcrit, &b_wnused, &b_wsmall, &b_wtsel, &b_widx, &b_wval}};
+                 &b_se, &b_dse, &b_cov, &b_nbad, &b_ens, &b_u, &b_wpost, &b_wcrit, &b_wnused, &b_wsmall, &b_wtsel, &b_widx, &b_wval,
+                 &b_yR, &b_yint, &b_ysmall, &b_yval, &b_yidx}};
     }
 };
 
@@ -137,12 +142,29 @@ int field_check_call(const ucf_field* f, int nz, const char* null_what, const do
     return UCF_OK;
 }
 
+// The kernel that finishes a map once the group results lie in b_h / b_dh and the wells, columns and time factors in their
+// buffers: `launch` enqueues it on the stream of the plan that ran the groups and returns a launcher's status.
+struct field_finish {
+    const char* what;
+    std::function<int(const ucf_plan*, hipStream_t)> launch;
+};
+
+// field_superpose_kernel into s, ds [nt][nloc][nz] at d_s, d_ds -- device memory of the caller on the plan's device
+field_finish field_superpose_into(ucf_field* f, int nz, int dimensionless, double* d_s, double* d_ds)
+{
+    return {"superposition", [=](const ucf_plan* pl, hipStream_t st) {
+                return ucf_field_launch_superpose(f->nt, f->nloc, nz, f->nwell, (const ucf_field_well*)f->b_wells.p, (const int*)f->b_col.p,
+                                                  (const double*)f->b_tfac.p, (const double*)f->b_h.p, (const double*)f->b_dh.p,
+                                                  dimensionless ? 0 : 1, pl->D.Hc, d_s, d_ds, st);
+            }};
+}
+
 // One map of the field under plan pl, whose launch arrays are L (field_group_core under pl's parameters): the arrays go to the
-// device, every group takes one call of the grid path, and field_superpose_kernel leaves s, ds [nt][nloc][nz] at d_s, d_ds --
-// device memory of the caller on pl's device, which is current.  The counters of the groups are ADDED to *stats (NULL ok).
-// The plan's stream has drained when the call returns.
-int field_map_core(ucf_field* f, ucf_plan* pl, const std::vector<field_launch>& L, int nz, const double* z, int dimensionless, double* d_s,
-                   double* d_ds, ucf_stats* stats)
+// device, every group takes one call of the grid path, and `finish` (field_superpose_kernel for a map, field_response_kernel
+// for the slots of ucf_field_yield) forms its outputs from the group results; pl's device is current.  The counters of the
+// groups are ADDED to *stats (NULL ok).  The plan's stream has drained when the call returns.
+int field_map_core(ucf_field* f, ucf_plan* pl, const std::vector<field_launch>& L, int nz, const double* z, const field_finish& finish,
+                   ucf_stats* stats)
 {
     const int ng = (int)f->groups.size();
     // zD, zLay as in ucf_drawdown_multi
@@ -197,10 +219,8 @@ int field_map_core(ucf_field* f, ucf_plan* pl, const std::vector<field_launch>& 
                                       (double*)f->b_dh.p + hoff[g], stats ? (ucf_stats*)f->b_stats.p + g : nullptr, st);
         if (rc) return rc;
     }
-    rc = ucf_field_launch_superpose(f->nt, f->nloc, nz, f->nwell, (const ucf_field_well*)f->b_wells.p, (const int*)f->b_col.p,
-                                    (const double*)f->b_tfac.p, (const double*)f->b_h.p, (const double*)f->b_dh.p, dimensionless ? 0 : 1,
-                                    pl->D.Hc, d_s, d_ds, st);
-    if (rc) return fail(rc, "superposition kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    rc = finish.launch(pl, st);
+    if (rc) return fail(rc, "%s kernel launch failed: %s", finish.what, hipGetErrorString(hipGetLastError()));
     if (!stats) return UCF_OK;
     std::vector<ucf_stats> gst(ng);
     if ((rc = copy_back({{gst.data(), f->b_stats.p, sizeof(ucf_stats) * ng}}, st, pl->device))) return rc;
@@ -277,11 +297,12 @@ int field_begin_launches(ucf_field* f, const ucf_plan* pl, ucf_stats* stats, con
 
 // What ucf_field_forecast and ucf_field_ensemble run per parameter set, for k = 0 .. nset-1 in this order: the scratch plan
 // (which holds the first set that runs) refreshed to sets[k], then field_map_core under the launch arrays that launch_of(k, L) hands out --
-// kept from the checks (forecast) or formed again (ensemble) -- into slot k of b_sall / b_dsall [nset][nout], dimensional.
+// kept from the checks (forecast) or formed again (ensemble) -- finished by finish_of(k): field_slot_superpose, into slot k of
+// b_sall / b_dsall [nset][nout], dimensional; for ucf_field_yield the response slots of member k.
 // A set that anything refuses: failed(rc, k).  With u (ucf_field_ensemble_weighted) a set with u[k] == 0 is left out, its slot
 // untouched; the scratch plan then holds the first set that is not.
-template <class Launch, class Failed>
-int field_map_sets(ucf_field* f, int nset, const ucf_params* sets, Launch launch_of, int nz, const double* z, long long nout,
+template <class Launch, class Finish, class Failed>
+int field_map_sets(ucf_field* f, int nset, const ucf_params* sets, Launch launch_of, int nz, const double* z, Finish finish_of,
                    ucf_stats* stats, Failed failed, const unsigned long long* u = nullptr)
 {
     ucf_plan* sp = f->scratch;
@@ -293,10 +314,16 @@ int field_map_sets(ucf_field* f, int nset, const ucf_params* sets, Launch launch
         held = false;
         const std::vector<field_launch>* L = nullptr;
         if ((rc = launch_of(k, L))) return failed(rc, k);
-        rc = field_map_core(f, sp, *L, nz, z, 0, (double*)f->b_sall.p + (size_t)k * nout, (double*)f->b_dsall.p + (size_t)k * nout, stats);
+        rc = field_map_core(f, sp, *L, nz, z, finish_of(k), stats);
         if (rc) return failed(rc, k);
     }
     return UCF_OK;
+}
+
+// finish_of for the maps of a forecast or an ensemble: slot k of b_sall / b_dsall [nset][nout] (grown before the call), dimensional
+auto field_slot_superpose(ucf_field* f, int nz, long long nout)
+{
+    return [=](int k) { return field_superpose_into(f, nz, 0, (double*)f->b_sall.p + (size_t)k * nout, (double*)f->b_dsall.p + (size_t)k * nout); };
 }
 
 // the launch arrays of every group of the field under P
@@ -345,7 +372,8 @@ int forecast_slots(ucf_field* f, int npar, const int* ids, double dlog, const fo
     int rc;
     if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every set", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every set", f->n_alloc)))
         return rc;
-    return field_map_sets(f, nset, W.sets, [&](int k, const std::vector<field_launch>*& Lk) { Lk = &W.L[k]; return UCF_OK; }, nz, z, nout, stats,
+    return field_map_sets(f, nset, W.sets, [&](int k, const std::vector<field_launch>*& Lk) { Lk = &W.L[k]; return UCF_OK; }, nz, z,
+                          field_slot_superpose(f, nz, nout), stats,
                           [&](int rc_k, int k) { return forecast_set_failed(rc_k, k, ids, dlog); });
 }
 
@@ -414,19 +442,20 @@ double ensemble_uniform(unsigned long long& state)
 }
 }  // namespace
 
-int ucf_host::ensemble_check_levels(int nens, int nq, const double* q, int nlim, const double* limit, bool want_quant, bool want_pexc)
+int ucf_host::ensemble_check_levels(int nens, int nq, const double* q, int nlim, const double* limit, bool want_quant, bool want_pexc,
+                                    const char* nlim_name, const char* limit_name)
 {
     if (nens < 1 || nens > UCF_ENSEMBLE_MAX) return fail(UCF_ERR_BAD_ARGUMENT, "nens=%d outside 1..%d", nens, UCF_ENSEMBLE_MAX);
     if (nq < 0 || nq > UCF_ENSEMBLE_MAX_Q) return fail(UCF_ERR_BAD_ARGUMENT, "nq=%d outside 0..%d", nq, UCF_ENSEMBLE_MAX_Q);
-    if (nlim < 0 || nlim > UCF_ENSEMBLE_MAX_Q) return fail(UCF_ERR_BAD_ARGUMENT, "nlim=%d outside 0..%d", nlim, UCF_ENSEMBLE_MAX_Q);
+    if (nlim < 0 || nlim > UCF_ENSEMBLE_MAX_Q) return fail(UCF_ERR_BAD_ARGUMENT, "%s=%d outside 0..%d", nlim_name, nlim, UCF_ENSEMBLE_MAX_Q);
     if (nq > 0 && !q) return fail(UCF_ERR_BAD_ARGUMENT, "NULL q with nq=%d", nq);
-    if (nlim > 0 && !limit) return fail(UCF_ERR_BAD_ARGUMENT, "NULL limit with nlim=%d", nlim);
+    if (nlim > 0 && !limit) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s with %s=%d", limit_name, nlim_name, nlim);
     for (int i = 0; i < nq; i++)
         if (!std::isfinite(q[i]) || q[i] < 0.0 || q[i] > 1.0) return fail(UCF_ERR_BAD_ARGUMENT, "q[%d]=%g is not a level in [0,1]", i, q[i]);
-    int rc = field_check_finite("limit", nlim, limit);
+    int rc = field_check_finite(limit_name, nlim, limit);
     if (rc) return rc;
     if (want_quant && nq == 0) return fail(UCF_ERR_BAD_ARGUMENT, "quant is asked for with nq=0: no level to form it at");
-    if (want_pexc && nlim == 0) return fail(UCF_ERR_BAD_ARGUMENT, "pexc is asked for with nlim=0: no limit to exceed");
+    if (want_pexc && nlim == 0) return fail(UCF_ERR_BAD_ARGUMENT, "pexc is asked for with %s=0: no %s to exceed", nlim_name, limit_name);
     return UCF_OK;
 }
 
@@ -530,7 +559,7 @@ int ucf_field_drawdown(ucf_field* f, ucf_plan* pl, int nz, const double* z, int 
     device_switch dg(pl->device);
     const size_t so = sizeof(double) * (size_t)nout;
     if ((rc = grow_buffer(f->b_s, so, "superposed drawdown", f->n_alloc)) || (rc = grow_buffer(f->b_ds, so, "superposed derivative", f->n_alloc))) return rc;
-    rc = field_map_core(f, pl, L, nz, z, dimensionless, (double*)f->b_s.p, (double*)f->b_ds.p, stats);
+    rc = field_map_core(f, pl, L, nz, z, field_superpose_into(f, nz, dimensionless, (double*)f->b_s.p, (double*)f->b_ds.p), stats);
     if (rc) return rc;
     return copy_back({{s, f->b_s.p, so}, {ds, f->b_ds.p, so}}, plan_stream(pl), pl->device);
 }
@@ -824,6 +853,63 @@ int ucf_debug_field_worth(int npar, int nt, int ncand, const double* a_s, const 
     return copy_back_sync({{post, b_post.p, sizeof(double) * nc * ntgt}, {crit, b_crit.p, sizeof(double) * nc}, {nused, b_nused.p, sizeof(int) * nc}});
 }
 
+// What ucf_field_ensemble, ucf_field_ensemble_weighted and ucf_field_yield share on their members, in the order of their checks
+struct ensemble_members {
+    std::vector<ucf_params> sets;          // member m = ucf_fit_perturb(plan, thetas[m])
+    std::vector<unsigned long long> u;     // the integer weights; empty: unweighted
+    int first = 0, nrun = 0;               // the first member that is launched, and how many are
+};
+
+static int ensemble_check_thetas(int npar, const int* ids, int nens, const double* thetas)
+{
+    char nb[32];
+    for (int m = 0; m < nens; m++)
+        for (int j = 0; j < npar; j++) {
+            const double v = thetas[(size_t)m * npar + j];
+            if (!(v > 0.0) || !std::isfinite(v))
+                return fail(UCF_ERR_BAD_ARGUMENT, "member %d: %s=%g must be positive and finite", m, fit_par_name(ids[j], nb, sizeof(nb)), v);
+        }
+    return UCF_OK;
+}
+
+// the weights quantised (weighted == false: every member runs, nothing is written); u_out, ess, nlaunched: NULL ok
+static int ensemble_weights_of(int nens, const double* weight, bool weighted, unsigned long long* u_out, double* ess, int* nlaunched,
+                               ensemble_members& E)
+{
+    E.first = 0;
+    E.nrun = nens;
+    if (!weighted) return UCF_OK;
+    E.u.resize(nens);
+    double e = 0.0;
+    int rc = ucf_ensemble_quantise(nens, weight, E.u.data(), &e);
+    if (rc) return rc;
+    E.nrun = 0;
+    for (int m = nens - 1; m >= 0; m--)
+        if (E.u[m] != 0) { E.first = m; E.nrun++; }
+    if (u_out) std::copy(E.u.begin(), E.u.end(), u_out);
+    if (ess) *ess = e;
+    if (nlaunched) *nlaunched = E.nrun;
+    return UCF_OK;
+}
+
+// a plan there must be; then every member and what every group launches under it: checked before any launch, the arrays not kept
+static int ensemble_sets_of(const ucf_field* f, const ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, ensemble_members& E)
+{
+    int rc;
+    if (!pl) {
+        rc = require_device();
+        return rc ? rc : fail(UCF_ERR_BAD_ARGUMENT, "NULL plan");
+    }
+    E.sets.resize(nens);
+    std::vector<field_launch> L;
+    for (int m = 0; m < nens; m++) {
+        const double* theta = thetas + (size_t)m * npar;
+        if ((rc = ucf_fit_perturb(&pl->P, npar, ids, theta, &E.sets[m]))) return m == 0 ? rc : ensemble_member_failed(rc, m, npar, ids, theta);
+        if ((rc = validate(E.sets[m])) || (rc = field_launches_of(f, E.sets[m], L))) return ensemble_member_failed(rc, m, npar, ids, theta);
+    }
+    return UCF_OK;
+}
+
 // ucf_field_ensemble (weighted == false: weight, u_out, ess, nlaunched are not read) and ucf_field_ensemble_weighted: one
 // sequence.  The weighted call differs in three places: the weights are quantised among the checks; a member with u = 0 is
 // validated but not launched, and its slots are filled with NaN bytes; the reduction runs with the weights.
@@ -837,41 +923,17 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
     if (rc) return rc;
     if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
     if ((rc = ensemble_check_levels(nens, nq, q, nlim, limit, (s && s->quant) || (ds && ds->quant), pexc != nullptr))) return rc;
-    char nb[32];
-    for (int m = 0; m < nens; m++)
-        for (int j = 0; j < npar; j++) {
-            const double v = thetas[(size_t)m * npar + j];
-            if (!(v > 0.0) || !std::isfinite(v))
-                return fail(UCF_ERR_BAD_ARGUMENT, "member %d: %s=%g must be positive and finite", m, fit_par_name(ids[j], nb, sizeof(nb)), v);
-        }
+    if ((rc = ensemble_check_thetas(npar, ids, nens, thetas))) return rc;
     if (nens * nout > 0x7fffffffLL * 256)
         return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d times x %d locations x %d depths: too many values for one buffer", nens, f->nt, f->nloc, nz);
-    std::vector<unsigned long long> u;
-    int first = 0, nrun = nens;            // the first member that is launched, and how many are
-    if (weighted) {
-        u.resize(nens);
-        double e = 0.0;
-        if ((rc = ucf_ensemble_quantise(nens, weight, u.data(), &e))) return rc;
-        nrun = 0;
-        for (int m = nens - 1; m >= 0; m--)
-            if (u[m] != 0) { first = m; nrun++; }
-        if (u_out) std::copy(u.begin(), u.end(), u_out);
-        if (ess) *ess = e;
-        if (nlaunched) *nlaunched = nrun;
-    }
-    if (!pl) {
-        rc = require_device();
-        return rc ? rc : fail(UCF_ERR_BAD_ARGUMENT, "NULL plan");
-    }
-    // every member and what every group launches under it: checked before any launch, the arrays not kept
-    std::vector<ucf_params> sets(nens);
+    ensemble_members E;
+    if ((rc = ensemble_weights_of(nens, weighted ? weight : nullptr, weighted, u_out, ess, nlaunched, E)) ||
+        (rc = ensemble_sets_of(f, pl, npar, ids, nens, thetas, E))) return rc;
+    std::vector<ucf_params>& sets = E.sets;
+    std::vector<unsigned long long>& u = E.u;
     std::vector<field_launch> L;
     auto failed = [&](int rc_m, int m) { return ensemble_member_failed(rc_m, m, npar, ids, thetas + (size_t)m * npar); };
-    for (int m = 0; m < nens; m++) {
-        if ((rc = ucf_fit_perturb(&pl->P, npar, ids, thetas + (size_t)m * npar, &sets[m]))) return m == 0 ? rc : failed(rc, m);
-        if ((rc = validate(sets[m])) || (rc = field_launches_of(f, sets[m], L))) return failed(rc, m);
-    }
-    if ((rc = field_begin_launches(f, pl, stats, &sets[first]))) return rc;
+    if ((rc = field_begin_launches(f, pl, stats, &sets[E.first]))) return rc;
     ucf_plan* sp = f->scratch;
     device_switch dg(pl->device);
     // b_ens: q [MAX_Q], limit [MAX_Q], then per map what is asked for of mean, sd, min, max [nout], quant [nq][nout], nfin
@@ -897,7 +959,7 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
     for (int i = 0; i < 2; i++) at[i] = map_at{dev(off[i][0]), dev(off[i][1]), dev(off[i][2]), dev(off[i][3]), dev(off[i][4]), (int*)dev(off[i][5])};
     double* d_pexc = dev(off_pexc);
     rc = field_map_sets(f, nens, sets.data(), [&](int m, const std::vector<field_launch>*& Lm) { Lm = &L; return field_launches_of(f, sets[m], L); },
-                        nz, z, nout, stats, failed, weighted ? u.data() : nullptr);
+                        nz, z, field_slot_superpose(f, nz, nout), stats, failed, weighted ? u.data() : nullptr);
     if (rc) return rc;
     hipStream_t st = plan_stream(sp);
     if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
@@ -952,6 +1014,191 @@ int ucf_field_ensemble_weighted(ucf_field* f, ucf_plan* pl, int npar, const int*
 {
     return field_ensemble_core(f, pl, npar, ids, nens, thetas, nz, z, nq, q, nlim, limit, s, ds, pexc, nbad, stats, true, weight, u, ess,
                                nlaunched);
+}
+
+// what ucf_field_yield and ucf_debug_field_yield check on the controls' count, the patterns and smax
+static int yield_check_patterns(int nctl, int npat, const double* x, double smax)
+{
+    if (nctl < 1 || nctl > UCF_YIELD_MAX_CTL) return fail(UCF_ERR_BAD_ARGUMENT, "nctl=%d outside 1..%d", nctl, UCF_YIELD_MAX_CTL);
+    if (npat < 1 || npat > UCF_YIELD_MAX_PAT) return fail(UCF_ERR_BAD_ARGUMENT, "npat=%d outside 1..%d", npat, UCF_YIELD_MAX_PAT);
+    if (!x) return fail(UCF_ERR_BAD_ARGUMENT, "NULL x");
+    int rc = field_check_finite("x", npat * nctl, x);
+    if (rc) return rc;
+    if (!(smax > 0.0) || !std::isfinite(smax)) return fail(UCF_ERR_BAD_ARGUMENT, "smax=%g must be positive and finite", smax);
+    return UCF_OK;
+}
+
+int ucf_field_yield(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, const double* weight, int nz,
+                    const double* z, int nctl, const int* ctl, int npat, const double* x, const double* limit, double smax, int nq,
+                    const double* q, int nlev, const double* level, const ucf_ensemble_maps* ystat, double* pexc, double* pfeas, double* hi,
+                    double* lo, int* bind, int* dead, double* resp, int* con, int* ncon, long long* nbad, ucf_stats* stats,
+                    unsigned long long* u_out, double* ess, int* nlaunched)
+{
+    long long nout = 0;
+    int rc = field_check_call(f, nz, !z ? "NULL z" : !ids ? "NULL ids" : !thetas ? "NULL thetas" : nullptr, z, nout);
+    if (rc) return rc;
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if ((rc = ensemble_check_levels(nens, nq, q, nlev, level, ystat && ystat->quant, pexc != nullptr, "nlev", "level")) ||
+        (rc = ensemble_check_thetas(npar, ids, nens, thetas))) return rc;
+    if (!ctl || !limit) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !ctl ? "ctl" : "limit");
+    if ((rc = yield_check_patterns(nctl, npat, x, smax))) return rc;
+    int owned[UCF_YIELD_MAX_CTL] = {};
+    for (int j = 0; j < f->nwell; j++) {
+        if (ctl[j] < -1 || ctl[j] >= nctl) return fail(UCF_ERR_BAD_ARGUMENT, "ctl[%d]=%d outside -1..%d", j, ctl[j], nctl - 1);
+        if (ctl[j] >= 0) owned[ctl[j]]++;
+    }
+    for (int c = 0; c < nctl; c++)
+        if (!owned[c]) return fail(UCF_ERR_BAD_ARGUMENT, "control %d owns no well", c);
+    if (nout > 0x7fffffffLL)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d times x %d locations x %d depths: more than 2^31-1 outputs (con and bind are ints)", f->nt, f->nloc, nz);
+    // con: the outputs with a finite limit, ascending, and their limits
+    std::vector<int> hcon;
+    std::vector<double> hlim;
+    for (long long e = 0; e < nout; e++) {
+        const double v = limit[e];
+        if (std::isnan(v) || (std::isinf(v) && v < 0.0))
+            return fail(UCF_ERR_BAD_ARGUMENT, "limit[%lld]=%g: a limit is finite, or +inf where the output is not constrained", e, v);
+        if (std::isfinite(v)) { hcon.push_back((int)e); hlim.push_back(v); }
+    }
+    if (hcon.empty()) return fail(UCF_ERR_BAD_ARGUMENT, "no finite limit among the %lld outputs: nothing is constrained", nout);
+    const int nc = (int)hcon.size();
+    if ((long long)nens * (nctl + 1) * nc > 0x7fffffffLL * 256)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d slots x %d constrained outputs: too many values for one buffer", nens, nctl + 1, nc);
+    if (con) std::copy(hcon.begin(), hcon.end(), con);
+    if (ncon) *ncon = nc;
+    const bool weighted = weight != nullptr;
+    ensemble_members E;
+    if ((rc = ensemble_weights_of(nens, weight, weighted, u_out, ess, nlaunched, E)) || (rc = ensemble_sets_of(f, pl, npar, ids, nens, thetas, E)))
+        return rc;
+    auto failed = [&](int rc_m, int m) { return ensemble_member_failed(rc_m, m, npar, ids, thetas + (size_t)m * npar); };
+    if ((rc = field_begin_launches(f, pl, stats, &E.sets[E.first]))) return rc;
+    ucf_plan* sp = f->scratch;
+    device_switch dg(pl->device);
+    // b_ens: q [MAX_Q], level [MAX_Q], the limit 0.5 of pfeas, then what is asked for of mean, sd, min, max [npat], quant
+    // [nq][npat], nfin [npat] (ints, padded to whole doubles), pexc [nlev][npat], pfeas [npat]
+    const size_t np = (size_t)npat, nmp = (size_t)nens * np, nslot = (size_t)(nctl + 1) * nc, so = sizeof(double) * np;
+    const ucf_ensemble_maps none = {};
+    const ucf_ensemble_maps* want = ystat ? ystat : &none;
+    constexpr size_t OFF_HALF = 2 * UCF_ENSEMBLE_MAX_Q;
+    size_t used = OFF_HALF + 1;                           // in doubles
+    auto take = [&](bool asked, size_t n) { const size_t o = used; if (asked) used += n; return asked ? o : (size_t)-1; };
+    const size_t o_mean = take(want->mean, np), o_sd = take(want->sd, np), o_min = take(want->min, np), o_max = take(want->max, np),
+                 o_quant = take(want->quant, np * nq), o_nfin = take(want->nfin, (np + 1) / 2), o_pexc = take(pexc, np * nlev),
+                 o_pfeas = take(pfeas, np);
+    if ((rc = grow_buffer(f->b_yR, sizeof(double) * nens * nslot, "response slots", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_yint, sizeof(int) * ((size_t)nc + f->nwell), "constrained outputs and controls", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_ysmall, sizeof(double) * (np * nctl + nc), "patterns and limits", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_yval, sizeof(double) * 4 * nmp, "admissible scales", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_yidx, sizeof(int) * 2 * nmp, "binding outputs", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_nbad, sizeof(long long) * 3, "counts", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_ens, sizeof(double) * used, "ensemble statistics", f->n_alloc)) ||
+        (weighted && (rc = grow_buffer(f->b_u, sizeof(unsigned long long) * nens, "ensemble weights", f->n_alloc)))) return rc;
+    double* base = (double*)f->b_ens.p;
+    auto dev = [&](size_t o) { return o == (size_t)-1 ? nullptr : base + o; };
+    double *d_R = (double*)f->b_yR.p, *d_x = (double*)f->b_ysmall.p, *d_lim = d_x + np * nctl;
+    double *d_y = (double*)f->b_yval.p, *d_fe = d_y + nmp, *d_hi = d_fe + nmp, *d_lo = d_hi + nmp;
+    int *d_con = (int*)f->b_yint.p, *d_ctl = d_con + nc, *d_bind = (int*)f->b_yidx.p, *d_dead = d_bind + nmp;
+    hipStream_t st = plan_stream(sp);
+    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
+    drain drained{st};                     // the staging outlives its copies
+    if (hipMemcpyAsync(d_con, hcon.data(), sizeof(int) * nc, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_ctl, ctl, sizeof(int) * f->nwell, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_x, x, sizeof(double) * np * nctl, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_lim, hlim.data(), sizeof(double) * nc, hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the controls, patterns and limits failed: %s", hipGetErrorString(hipGetLastError()));
+    // per member the groups as in ucf_field_ensemble, finished by field_response_kernel into the member's slots (the buffers
+    // of the groups may grow from member to member: their addresses are read at the launch)
+    auto response_of = [=](int m) {
+        return field_finish{"response", [=](const ucf_plan* p, hipStream_t s) {
+                                return ucf_field_launch_response(nc, nctl, f->nloc, nz, f->nwell, (const ucf_field_well*)f->b_wells.p,
+                                                                 (const int*)f->b_col.p, d_ctl, d_con, (const double*)f->b_h.p, p->D.Hc,
+                                                                 d_R + (size_t)m * nslot, s);
+                            }};
+    };
+    std::vector<field_launch> L;
+    rc = field_map_sets(f, nens, E.sets.data(), [&](int m, const std::vector<field_launch>*& Lm) { Lm = &L; return field_launches_of(f, E.sets[m], L); },
+                        nz, z, response_of, stats, failed, weighted ? E.u.data() : nullptr);
+    if (rc) return rc;
+    double ql[2 * UCF_ENSEMBLE_MAX_Q];
+    ensemble_pack_levels(nq, q, nlev, level, ql);
+    const double half = 0.5;
+    if (hipMemsetAsync(f->b_nbad.p, 0, sizeof(long long) * 3, st) != hipSuccess ||
+        hipMemcpyAsync(base, ql, sizeof(ql), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(base + OFF_HALF, &half, sizeof(half), hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the ensemble's arrays failed: %s", hipGetErrorString(hipGetLastError()));
+    if (weighted) {
+        // the weights, and NaN bytes into the slots of the members that were not launched
+        bool ok = hipMemcpyAsync(f->b_u.p, E.u.data(), sizeof(unsigned long long) * nens, hipMemcpyHostToDevice, st) == hipSuccess;
+        for (int m = 0; m < nens && ok; m++)
+            if (E.u[m] == 0) ok = hipMemsetAsync(d_R + (size_t)m * nslot, 0xff, sizeof(double) * nslot, st) == hipSuccess;
+        if (!ok) return fail(UCF_ERR_HIP, "upload of the ensemble's weights failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    long long* d_nbad = (long long*)f->b_nbad.p;
+    ucf_yield_args ya = {};
+    ya.nctl = nctl; ya.nens = nens; ya.ncon = nc; ya.npat = npat; ya.d_R = d_R; ya.d_x = d_x; ya.d_lim = d_lim; ya.d_con = d_con; ya.smax = smax;
+    ya.d_y = d_y; ya.d_fe = d_fe; ya.d_hi = d_hi; ya.d_lo = d_lo; ya.d_bind = d_bind; ya.d_dead = d_dead; ya.d_nbad = d_nbad + 2;
+    if ((rc = ucf_field_launch_yield(&ya, st))) return fail(rc, "yield kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    // the member reduction of ucf_field_ensemble with nout = npat: on y, then on fe against 0.5
+    ucf_ensemble_reduce_args ra = {};
+    ra.nens = nens; ra.nout = npat; ra.d_a = d_y;
+    ra.d_u = weighted ? (const unsigned long long*)f->b_u.p : nullptr;
+    ra.nq = nq; ra.d_q = base; ra.nlim = nlev; ra.d_limit = base + UCF_ENSEMBLE_MAX_Q;
+    ra.d_mean = dev(o_mean); ra.d_sd = dev(o_sd); ra.d_min = dev(o_min); ra.d_max = dev(o_max); ra.d_nfin = (int*)dev(o_nfin);
+    ra.d_quant = dev(o_quant); ra.d_pexc = dev(o_pexc); ra.d_nbad = d_nbad;
+    rc = ucf_field_launch_ensemble_reduce(&ra, st);
+    if (rc == UCF_OK && pfeas) {
+        ucf_ensemble_reduce_args rf = {};
+        rf.nens = nens; rf.nout = npat; rf.d_a = d_fe; rf.d_u = ra.d_u;
+        rf.nlim = 1; rf.d_limit = base + OFF_HALF; rf.d_pexc = dev(o_pfeas); rf.d_nbad = d_nbad + 1;
+        rc = ucf_field_launch_ensemble_reduce(&rf, st);
+    }
+    if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    long long invalid = 0;
+    const size_t sm = sizeof(double) * nmp;
+    rc = copy_back({{want->mean, dev(o_mean), so}, {want->sd, dev(o_sd), so}, {want->min, dev(o_min), so}, {want->max, dev(o_max), so},
+                    {want->quant, dev(o_quant), so * nq}, {want->nfin, dev(o_nfin), sizeof(int) * np}, {want->all, d_y, sm},
+                    {pexc, dev(o_pexc), so * nlev}, {pfeas, dev(o_pfeas), so}, {hi, d_hi, sm}, {lo, d_lo, sm}, {bind, d_bind, sizeof(int) * nmp},
+                    {dead, d_dead, sizeof(int) * nmp}, {resp, d_R, sizeof(double) * nens * nslot}, {&invalid, d_nbad + 2, sizeof(long long)}},
+                   st, pl->device);
+    if (rc) return rc;
+    if (nbad) *nbad = invalid - (nens - E.nrun);          // a member that was not launched is not counted
+    return UCF_OK;
+}
+
+int ucf_debug_field_yield(int nctl, int nens, int ncon, int npat, const double* R, const double* x, const double* limit_con, const int* con,
+                          double smax, double* y, double* fe, double* hi, double* lo, int* bind, int* dead, long long* nbad)
+{
+    if (nens < 1 || nens > UCF_ENSEMBLE_MAX) return fail(UCF_ERR_BAD_ARGUMENT, "nens=%d outside 1..%d", nens, UCF_ENSEMBLE_MAX);
+    if (ncon < 1) return fail(UCF_ERR_BAD_ARGUMENT, "ncon=%d: at least one constrained output", ncon);
+    int rc = yield_check_patterns(nctl, npat, x, smax);
+    if (rc) return rc;
+    const long long nval = (long long)nens * (nctl + 1) * ncon;
+    if (nval > 0x7fffffffLL) return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d slots x %d constrained outputs: more than 2^31-1 values", nens, nctl + 1, ncon);
+    if (!R || !limit_con || !con) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !R ? "R" : !limit_con ? "limit_con" : "con");
+    if ((rc = field_check_finite("limit_con", ncon, limit_con))) return rc;
+    for (int i = 0; i < ncon; i++)
+        if (con[i] < 0 || (i > 0 && con[i] <= con[i - 1]))
+            return fail(UCF_ERR_BAD_ARGUMENT, "con[%d]=%d: the constrained outputs are not negative and ascend strictly", i, con[i]);
+    if ((rc = require_device())) return rc;
+    const size_t nmp = (size_t)nens * npat, sR = sizeof(double) * (size_t)nval, sx = sizeof(double) * npat * nctl, sm = sizeof(double) * nmp;
+    dev_buf b_R, b_x, b_lim, b_con, b_val, b_idx, b_nbad;
+    if (b_R.alloc(sR) || b_x.alloc(sx) || b_lim.alloc(sizeof(double) * ncon) || b_con.alloc(sizeof(int) * ncon) || b_val.alloc(4 * sm) ||
+        b_idx.alloc(sizeof(int) * 2 * nmp) || b_nbad.alloc(sizeof(long long)))
+        return fail(UCF_ERR_NOMEM, "device allocation failed");
+    HIP_TRY(hipMemcpy(b_R.p, R, sR, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_x.p, x, sx, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_lim.p, limit_con, sizeof(double) * ncon, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_con.p, con, sizeof(int) * ncon, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b_nbad.p, 0, sizeof(long long)));
+    ucf_yield_args ya = {};
+    ya.nctl = nctl; ya.nens = nens; ya.ncon = ncon; ya.npat = npat; ya.smax = smax;
+    ya.d_R = (const double*)b_R.p; ya.d_x = (const double*)b_x.p; ya.d_lim = (const double*)b_lim.p; ya.d_con = (const int*)b_con.p;
+    ya.d_y = (double*)b_val.p; ya.d_fe = ya.d_y + nmp; ya.d_hi = ya.d_fe + nmp; ya.d_lo = ya.d_hi + nmp;
+    ya.d_bind = (int*)b_idx.p; ya.d_dead = ya.d_bind + nmp; ya.d_nbad = (long long*)b_nbad.p;
+    if ((rc = ucf_field_launch_yield(&ya, nullptr))) return fail(rc, "yield kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return copy_back_sync({{y, ya.d_y, sm}, {fe, ya.d_fe, sm}, {hi, ya.d_hi, sm}, {lo, ya.d_lo, sm}, {bind, ya.d_bind, sizeof(int) * nmp},
+                           {dead, ya.d_dead, sizeof(int) * nmp}, {nbad, b_nbad.p, sizeof(long long)}});
 }
 
 int ucf_ensemble_quantise(int nens, const double* weight, unsigned long long* u, double* ess)

@@ -1,6 +1,7 @@
 // ucf_field.h -- launchers of the well-field kernels: the superposition, called by ucf_field_drawdown, ucf_field_forecast and
-// ucf_field_ensemble (ucf_field.cpp), the combination of a forecast (both ucf_field.hip), the reduction of an ensemble
-// (ucf_field_ensemble.hip) and the data worth of candidate wells (ucf_field_worth.hip).
+// ucf_field_ensemble (ucf_field.cpp), the response slots of ucf_field_yield, the combination of a forecast (all three
+// ucf_field.hip), the reduction of an ensemble (ucf_field_ensemble.hip), the data worth of candidate wells
+// (ucf_field_worth.hip) and the ratio test of ucf_field_yield (ucf_field_yield.hip).
 #pragma once
 #include <cstddef>
 
@@ -20,6 +21,30 @@ struct ucf_field_well {
 int ucf_field_launch_superpose(int nt, int nloc, int nz, int nwell, const ucf_field_well* d_wells, const int* d_col,
                                const double* d_tfac, const double* d_h, const double* d_dh, int scaled, double scale,
                                double* d_s, double* d_ds, void* stream);
+
+// The response slots of ucf_field_yield, field_response_kernel, in place of the superposition: one thread per (slot c,
+// constrained output i) of d_R [nctl + 1][ncon], output e = d_con[i] = (k, iloc, z) of the map:
+//   acc = +0.0;  for j = 0..nwell-1 with d_ctl[j] == c (slot nctl: d_ctl[j] == -1) and k >= k0_j:  acc = acc + q_j * h[at]
+//   d_R[c][i] = acc * scale                                       (`at` as in the superposition; dh is not read)
+// d_ctl [nwell] in -1 .. nctl-1, d_con [ncon] each in 0 .. nt nloc nz - 1 (the caller has checked both).
+int ucf_field_launch_response(int ncon, int nctl, int nloc, int nz, int nwell, const ucf_field_well* d_wells, const int* d_col,
+                              const int* d_ctl, const int* d_con, const double* d_h, double scale, double* d_R, void* stream);
+
+// The ratio test of ucf_field_yield (ucf_field_yield.hip), field_yield_kernel<nctl>: a workgroup of 256 threads per (member,
+// tile of UCF_YIELD_PAT_TILE patterns); the arithmetic is stated with ucf_field_yield in include/ucf.h.  Device memory throughout.
+struct ucf_yield_args {
+    int nctl, nens, ncon, npat;            // 1..UCF_YIELD_MAX_CTL, 1..UCF_ENSEMBLE_MAX, >= 1, 1..UCF_YIELD_MAX_PAT
+    const double* d_R;                     // [nens][nctl + 1][ncon]
+    const double* d_x;                     // [npat][nctl]
+    const double* d_lim;                   // [ncon] the limit of constrained output i
+    const int* d_con;                      // [ncon] ascending, not negative
+    double smax;
+    double *d_y, *d_fe, *d_hi, *d_lo;      // [nens][npat]
+    int *d_bind, *d_dead;                  // [nens][npat]
+    long long* d_nbad;                     // += the members with a slot value that is not finite; the caller zeroes it
+};
+// UCF_ERR_BAD_ARGUMENT for what the comments above exclude and for a NULL array
+int ucf_field_launch_yield(const ucf_yield_args* a, void* stream);
 
 // The combination of a forecast, field_forecast_kernel<npar>: one thread per output e of the slots d_a [1 + 2 npar][nout]
 // (slot 0 the base set, slot 1 + 2j / 2 + 2j parameter j up / down), every operation rounded on its own:

@@ -5,7 +5,8 @@
 // group results) read neighbours.  Built with -ffp-contract=off: every product and sum below is rounded on its own, so the
 // result is the arithmetic written here.  One thread owns one output and adds the wells in the caller's order: no atomics,
 // a repeated call gives the same bits.  Nothing is scrubbed: non-finite values and the Wynn sentinel propagate.
-// field_forecast_kernel (ucf_field_forecast) combines the 1 + 2 npar superposed maps of a forecast under the same rules.
+// field_forecast_kernel (ucf_field_forecast) combines the 1 + 2 npar superposed maps of a forecast under the same rules;
+// field_response_kernel (ucf_field_yield) forms the same sums control by control at the constrained outputs.
 #include <hip/hip_runtime.h>
 #include "../../include/ucf.h"
 #include "ucf_field.h"
@@ -37,6 +38,34 @@ __global__ __launch_bounds__(FIELD_THREADS) void field_superpose_kernel(long lon
     if (scaled) { acc = acc * scale; dacc = dacc * scale; }
     s[e] = acc;
     ds[e] = dacc;
+}
+
+// The response slots of ucf_field_yield, in place of the superposition: one thread per (slot c, constrained output i).  Slot c
+// sums the wells of control c, slot nctl the fixed wells (ctl == -1), in the caller's order and with the statements of
+// field_superpose_kernel, so that the slots of a member add up to its map; the drawdown only, dh is not read.  Neighbouring
+// threads are neighbouring constrained outputs of one slot: the stores are coalesced, the gathers as near as con allows.
+__global__ __launch_bounds__(FIELD_THREADS) void field_response_kernel(int ncon, int nctl, int nloc, int nz, int nwell,
+                                                                       const ucf_field_well* __restrict__ wells,
+                                                                       const int* __restrict__ col, const int* __restrict__ ctl,
+                                                                       const int* __restrict__ con, const double* __restrict__ h,
+                                                                       double scale, double* __restrict__ R)
+{
+    const long long q = (long long)blockIdx.x * FIELD_THREADS + threadIdx.x;
+    if (q >= (long long)(nctl + 1) * ncon) return;
+    const int c = (int)(q / ncon), i = (int)(q % ncon);
+    const int mine = (c == nctl) ? -1 : c;
+    const long long e = con[i];
+    const int z = (int)(e % nz);
+    const long long p = e / nz;
+    const int iloc = (int)(p % nloc), k = (int)(p / nloc);
+    double acc = 0.0;
+    for (int j = 0; j < nwell; j++) {
+        const ucf_field_well w = wells[j];
+        if (ctl[j] != mine || k < w.k0) continue;
+        const size_t at = (size_t)w.off + ((size_t)(k - w.k0) * w.nr + col[(size_t)iloc * nwell + j]) * nz + z;
+        acc = acc + w.q * h[at];
+    }
+    R[q] = acc * scale;
 }
 
 // The combination of a forecast (ucf_field_forecast): one thread per output e of the slots a [1 + 2 NPAR][nout], launched once
@@ -101,6 +130,17 @@ int ucf_field_launch_superpose(int nt, int nloc, int nz, int nwell, const ucf_fi
     if (nout < 1 || blocks > 0x7fffffffLL) return UCF_ERR_BAD_ARGUMENT;
     hipLaunchKernelGGL(field_superpose_kernel, dim3((unsigned)blocks), dim3(FIELD_THREADS), 0, (hipStream_t)stream, nout, nloc, nz,
                        nwell, d_wells, d_col, d_tfac, d_h, d_dh, scaled, scale, d_s, d_ds);
+    return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
+}
+
+int ucf_field_launch_response(int ncon, int nctl, int nloc, int nz, int nwell, const ucf_field_well* d_wells, const int* d_col,
+                              const int* d_ctl, const int* d_con, const double* d_h, double scale, double* d_R, void* stream)
+{
+    const long long n = (long long)(nctl + 1) * ncon, blocks = (n + FIELD_THREADS - 1) / FIELD_THREADS;
+    if (ncon < 1 || nctl < 1 || nctl > UCF_YIELD_MAX_CTL || blocks > 0x7fffffffLL || !d_wells || !d_col || !d_ctl || !d_con || !d_h || !d_R)
+        return UCF_ERR_BAD_ARGUMENT;
+    hipLaunchKernelGGL(field_response_kernel, dim3((unsigned)blocks), dim3(FIELD_THREADS), 0, (hipStream_t)stream, ncon, nctl, nloc, nz,
+                       nwell, d_wells, d_col, d_ctl, d_con, d_h, scale, d_R);
     return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
 }
 

@@ -165,7 +165,9 @@ int fit_cholesky_factor(int n, double* M);
 // UCF_ERR_BAD_ARGUMENT naming name[i] for the first v[i] that is not finite
 int field_check_finite(const char* name, int n, const double* v);
 // what ucf_field_ensemble and ucf_debug_ensemble check on nens, the levels q [nq] and the limits [nlim]
-int ensemble_check_levels(int nens, int nq, const double* q, int nlim, const double* limit, bool want_quant, bool want_pexc);
+// (ucf_field_yield calls its limits `level`, nlev of them, and has them named so)
+int ensemble_check_levels(int nens, int nq, const double* q, int nlim, const double* limit, bool want_quant, bool want_pexc,
+                          const char* nlim_name = "nlim", const char* limit_name = "limit");
 // the image of the checked levels and limits that goes to the device: q at [0], limit at [UCF_ENSEMBLE_MAX_Q], the rest 0
 inline void ensemble_pack_levels(int nq, const double* q, int nlim, const double* limit, double (&ql)[2 * UCF_ENSEMBLE_MAX_Q])
 {

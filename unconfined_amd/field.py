@@ -34,6 +34,15 @@ the maps stay on the GPU and the picks cost one small launch each (ucf_field_wor
 
     out = field.worth(plan, ["Kr", "Ss"], res["theta"][0], res["cov"][0], z=[145.7, 100.0], targets=[("s", 2, 1, 0)], sigma=0.01, picks=3)
     out["pick"], out["reduction"], out["cov_post"]                                            # [(i, z)] * 3, [3, ntgt, nloc, nz], [npar, npar]
+
+How much the wells may pump before a permitted drawdown is exceeded somewhere, and how sure that is -- drawdown is linear in the
+rates, so one ensemble's worth of evaluations answers every rate pattern (ucf_field_yield); here the real well and its image are
+one control and 64 splits between two such pairs are tried, up to three times today's rates:
+
+    patterns = [(a, 1.0 - a) for a in np.linspace(0.0, 1.0, 64)]
+    out = field.sustainable_yield(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], controls=[0, 1, 0, 1], patterns=patterns,
+                                  limit=2.0, smax=3.0, levels=[1.0])
+    out["quant"][0], out["pexc"], out["bind"]                                                 # the scale that 95 % admit, P(scale > 1), where it binds
 """
 from __future__ import annotations
 
@@ -318,6 +327,74 @@ class WellField:
         out["pick"] = [None if c < 0 else (int(c) // nz, int(c) % nz) for c in pick]
         with np.errstate(invalid="ignore", divide="ignore"):
             out["reduction"] = 1.0 - out["post"] / out["prior"][:, :, None, None]
+        if with_stats:
+            out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
+        return out
+
+    def sustainable_yield(self, plan, free, thetas, z, controls, patterns, limit, smax, weights=None, q=(0.05, 0.5, 0.95), levels=(),
+                          with_stats: bool = False) -> dict:
+        """how much the wells may pump before a permitted drawdown is exceeded somewhere, under the ensemble ``thetas`` [nens,
+        npar] (ucf_field_yield).  ``controls`` [nwell] gives every well its control 0 .. nctl-1 (wells of one control are
+        scaled together; -1: the well is fixed), ``patterns`` [npat, nctl] the multipliers on the wells' q that are tried,
+        ``limit`` [nt, nloc, nz] (or a scalar) the permitted dimensional drawdown (inf: not constrained) and ``smax`` the
+        largest scale of interest.  Pattern p at scale lam pumps well j of control c at lam * patterns[p, c] * q_j.  Returns
+        y [nens, npat], the largest admissible scale per member and pattern (0 where none is; NaN for a member with a value
+        that is not finite); over the members mean, sd, min, max, nfin [npat], quant [nq, npat] at the levels ``q`` -- the
+        level-q quantile is the scale that a share 1 - q of the ensemble admits, the yield at reliability 1 - q --, with
+        ``levels`` pexc [nlev, npat], the share of members that admit more than a level, and pfeas [npat], the share that
+        admit any scale; hi, lo, bind, dead [nens, npat], the two ends of the admissible interval, the output (an index into
+        the flattened map) that binds hi (-1: smax does) and whether an output is over its limit at every scale; resp [nens,
+        nctl + 1, ncon], the response slots, con [ncon], the constrained outputs, and nbad, the members that are not finite.
+        With ``weights`` the members count by their weight as in ``ensemble`` and the result gains u, ess and nlaunched.
+        ``plan`` is not modified."""
+        ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
+        thetas = np.atleast_2d(_f64(thetas))
+        if thetas.ndim != 2 or thetas.shape[1] != len(ids):
+            raise ValueError("thetas: [nens, npar], one value per free parameter")
+        nens = len(thetas)
+        z = np.atleast_1d(_f64(z))
+        ctl = np.ascontiguousarray(np.atleast_1d(controls), dtype=np.int32)
+        if ctl.shape != (self.nwell,):
+            raise ValueError("controls: one control (or -1) per well")
+        x = np.atleast_2d(_f64(patterns))
+        if x.ndim != 2 or x.shape[1] < 1:
+            raise ValueError("patterns: [npat, nctl]")
+        npat, nctl = x.shape
+        if ctl.max() >= nctl:
+            raise ValueError("patterns: one column per control")
+        shape = (self.nt, self.nloc, len(z))
+        try:
+            lim = np.ascontiguousarray(np.broadcast_to(_f64(limit), shape))
+        except ValueError:
+            raise ValueError("limit: [nt, nloc, nz] or a scalar") from None
+        qs = np.atleast_1d(_f64(q if q is not None else []))
+        lev = np.atleast_1d(_f64(levels if levels is not None else []))
+        w = None if weights is None else np.atleast_1d(_f64(weights))
+        if w is not None and len(w) != nens:
+            raise ValueError("weights: one value per member")
+        nslot = max(int(np.isfinite(lim).sum()), 1)
+        out = {"y": np.zeros((nens, npat)), "pfeas": np.zeros(npat), "nfin": np.zeros(npat, np.int32)}
+        for key in ("mean", "sd", "min", "max"):
+            out[key] = np.zeros(npat)
+        if len(qs):
+            out["quant"] = np.zeros((len(qs), npat))
+        if len(lev):
+            out["pexc"] = np.zeros((len(lev), npat))
+        out["hi"], out["lo"] = np.zeros((nens, npat)), np.zeros((nens, npat))
+        out["bind"], out["dead"] = np.zeros((nens, npat), np.int32), np.zeros((nens, npat), np.int32)
+        out["resp"] = np.zeros((nens, nctl + 1, nslot))
+        con, ncon, nbad = np.zeros(lim.size, np.int32), C.c_int(), C.c_longlong()
+        maps = UcfEnsembleMaps(*(_addr(out.get(key)) for key in ("mean", "sd", "min", "max", "quant", "y", "nfin")))
+        st = UcfStats()
+        u, ess, nl = np.zeros(nens, np.uint64), C.c_double(), C.c_int()
+        _libmod.check(self._lib.ucf_field_yield(
+            self._h, plan._h, len(ids), _addr(ids), nens, _addr(thetas), _addr(w), len(z), _addr(z), nctl, _addr(ctl), npat, _addr(x),
+            _addr(lim), float(smax), len(qs), _addr(qs) if len(qs) else None, len(lev), _addr(lev) if len(lev) else None, C.byref(maps),
+            _addr(out.get("pexc")), _addr(out["pfeas"]), *(_addr(out[k]) for k in ("hi", "lo", "bind", "dead", "resp")), _addr(con),
+            C.addressof(ncon), C.addressof(nbad), C.byref(st) if with_stats else None, _addr(u), C.addressof(ess), C.addressof(nl)))
+        out["con"], out["nbad"] = con[:ncon.value].copy(), int(nbad.value)
+        if w is not None:
+            out["u"], out["ess"], out["nlaunched"] = u, float(ess.value), int(nl.value)
         if with_stats:
             out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
         return out

@@ -47,6 +47,7 @@ EXPORTS = [
     "ucf_fit_objective", "ucf_ensemble_quantise", "ucf_ensemble_likelihood_weights", "ucf_field_ensemble_weighted",
     "ucf_debug_ensemble_weighted",
     "ucf_field_worth", "ucf_worth_condition", "ucf_debug_field_worth",
+    "ucf_field_yield", "ucf_debug_field_yield",
 ]
 
 
@@ -191,6 +192,13 @@ def load() -> C.CDLL:
     lib.ucf_worth_condition.argtypes = [C.c_int, vp, C.c_int, vp, vp, vp, vp]
     # npar, nt, ncand, a_s, a_d, two_dlog, F, ws, wd, tsel, ntgt, A, tw, post, crit, nused
     lib.ucf_debug_field_worth.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_double, vp, C.c_double, C.c_double, vp, C.c_int, vp, vp, vp, vp, vp]
+    # every array may be NULL: plain addresses.  field, plan, npar, ids, nens, thetas, weight, nz, z | nctl, ctl, npat, x, limit,
+    # smax | nq, q, nlev, level | ystat, pexc, pfeas | hi, lo, bind, dead | resp, con, ncon, nbad | stats | u, ess, nlaunched
+    lib.ucf_field_yield.argtypes = ([vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp] + [C.c_int, vp, C.c_int, vp, vp, C.c_double] +
+                                    [C.c_int, vp, C.c_int, vp] + [C.POINTER(UcfEnsembleMaps), vp, vp] + [vp] * 4 + [vp] * 4 +
+                                    [C.POINTER(UcfStats)] + [vp] * 3)
+    # nctl, nens, ncon, npat, R, x, limit_con, con, smax, y, fe, hi, lo, bind, dead, nbad
+    lib.ucf_debug_field_yield.argtypes = [C.c_int] * 4 + [vp] * 4 + [C.c_double] + [vp] * 7
     # every array may be NULL for a source or a call that does not read it: plain addresses
     lib.ucf_debug_fit_reduce.argtypes = ([C.c_int] * 4 + [C.c_double, C.c_longlong] + [vp] * 8 + [C.c_longlong, C.c_int] + [vp] * 7 + [vp] * 6)
     _lib = lib
