@@ -495,6 +495,59 @@ int ucf_fit_debug_dh(ucf_fit* fit, int plan, int i, int cap, double* dh, int* n)
 int ucf_fit_objective(ucf_fit* fit, int nsets, const double* theta /*[nsets][npar]*/,
                       double* phi, int* nbad, double* sim /*NULL ok*/, double* phi_d /*NULL ok*/, double* simd /*NULL ok*/);
 
+/* Robust losses.  A loss is a property of a fit, like derivative data: once set, every entry that reduces residuals uses it.
+ * The residuals exist only inside fit_reduce_kernel, so the loss is applied there: no evaluator launch and no traffic is added.
+ *   kinds        UCF_LOSS_L2 (plain least squares, the default), UCF_LOSS_HUBER, UCF_LOSS_TUKEY (the biweight);
+ *   c            the tuning constant, positive and finite, in units of the WEIGHTED residual: sigmas where weight = 1 / sigma.
+ * A weighted residual x -- the drawdown term wr with its weighted derivatives wd_j, or the derivative term wrd with wdd_j; the
+ * same rule and the same c for both -- gives rho(x) and the factor b(x), every operation rounded on its own:
+ *     a = fabs(x)
+ *     HUBER:  a <= c :  b = 1.0;            rho = x * x
+ *             else   :  b = c / a;          rho = c * (2.0 * a - c)
+ *     TUKEY:  c2 = c * c;  u = x / c
+ *             a <  c :  v = 1.0 - u * u;  b = v * v;  rho = (c2 * (1.0 - b * v)) / 3.0
+ *             else   :  b = 0.0;            rho = c2 / 3.0
+ * and the sums, in place of the least-squares ones, in the same order and over the same counted observations:
+ *     phi   = phi   + rho            (derivative term: also phi_d = phi_d + rho)
+ *     phi_w = phi_w + b * (x * x)    (new, the last entry of a set's sums: phi | g | A | [phi_d] | phi_w)
+ *     bw_j  = b * wd_j;   g_j = g_j + bw_j * x;   A_jk = A_jk + bw_j * wd_k   (j <= k)
+ *     ndown[set] = number of counted residual terms (drawdown and derivative) with b < 1.0
+ * This is the IRLS / Gauss-Newton form: the term of the loss's second derivative is dropped, so A stays positive
+ * semidefinite.  Unchanged: the rule that decides whether an observation counts, nbad, "the derivative term is skipped where
+ * dweight == 0", the lane / butterfly / wave order of the sums, the absence of floating-point atomics.  Consequences:
+ *   - Huber with c >= every |x| gives the bits of least squares in phi, g, A, phi_d and nbad, and phi_w has the bits of phi;
+ *   - at a == c both branches of Tukey give the same rho (b = 0 * 0, rho = (c2 * 1.0) / 3.0 = c2 / 3.0);
+ *   - an infinite x gives b = 0 and rho = +inf under Huber. */
+enum { UCF_LOSS_L2 = 0, UCF_LOSS_HUBER = 1, UCF_LOSS_TUKEY = 2 };
+/* host only, no GPU, compiled without contraction: the arithmetic above on x[n] -> rho[n], b[n]; UCF_LOSS_L2 gives rho = x * x,
+ * b = 1.0 and does not read c.  UCF_ERR_BAD_ARGUMENT: a kind outside the enum, a c that is not positive and finite (Huber,
+ * Tukey), n < 0, a NULL array. */
+int ucf_fit_loss_terms(int kind, double c, int n, const double* x, double* rho, double* b);
+/* host only, no GPU: *scale = 1.4826 * m, m the median of fabs(x[i]) over the finite x[i]: the k of them sorted ascending
+ * into a[0..k), m = a[k / 2] for odd k and (a[k / 2 - 1] + a[k / 2]) / 2.0 for even k (the textbook median); one product.  The
+ * usual estimate of sigma from residuals that hold outliers; a multiple of it (4.685 for 95 % efficiency under Tukey, 1.345
+ * under Huber) is the usual c.  UCF_ERR_BAD_ARGUMENT: n < 1, a NULL argument, no finite entry. */
+int ucf_fit_robust_scale(int n, const double* x, double* scale);
+/* sets the loss of a fit made by any of the three constructors; UCF_LOSS_L2 detaches it (c is then not read).  The argument
+ * checks come before anything else (NULL fit, a kind outside the enum, c not positive and finite); the call allocates nothing.
+ * From here on ucf_fit_evaluate, ucf_fit_evaluate_joint, ucf_fit_objective and ucf_fit_lm reduce with the loss: their phi and
+ * phi_d are the robust sums, g and A the reweighted ones above, and ucf_fit_lm accepts and rejects on the robust phi.
+ *   cov          of ucf_fit_lm = phi_w / (nobs + nd - npar) A^-1 with the IRLS A at the final point: the covariance of the
+ *                WEIGHTED LEAST-SQUARES problem that the final factors define.  It is NOT a sandwich estimator: it ignores
+ *                that the factors depend on the data, and understates the variance when many observations are down-weighted.
+ * On a fit whose loss is UCF_LOSS_L2 every one of these entries returns the bits it returned before a loss existed. */
+int ucf_fit_set_loss(ucf_fit* fit, int kind, double c);
+int ucf_fit_get_loss(const ucf_fit* fit, int* kind, double* c /*0.0 under UCF_LOSS_L2*/);
+/* The factors at given parameter sets: how a caller flags outliers at a fitted theta.  Evaluates the base plans only, through the
+ * npar = 0 reduction, as ucf_fit_objective does, on every kind of fit, with the fit's loss.  phi, phi_w [nsets], nbad, ndown
+ * [nsets], b, bd [nsets][nobs] in the caller's observation order: the factor of observation i's drawdown residual and of its
+ * derivative residual, NaN where the observation does not count (bd: or has dweight == 0).  Any output may be NULL; bd on a fit
+ * without derivative data is UCF_ERR_BAD_ARGUMENT.  On a fit whose loss is UCF_LOSS_L2 b is 1.0 where the observation counts,
+ * phi_w has the bits of phi and ndown is 0.  The checks of ucf_fit_objective.  A repeated call of the same size allocates
+ * nothing (ucf_fit_alloc_count). */
+int ucf_fit_loss_report(ucf_fit* fit, int nsets, const double* theta /*[nsets][npar]*/,
+                        double* phi, double* phi_w, int* nbad, int* ndown, double* b, double* bd);
+
 /* ---- well fields: the drawdown of several pumping wells -- wells that start at different times, image wells for a river or an
  * outcrop -- is the sum over wells of q_j h(t - t0_j, |x - x_j|, z).  All wells share the plan's aquifer, well geometry and
  * time behaviour; they differ in position (xw, yw), rate factor qw (times the plan's Q; negative: injection or a constant-head
@@ -964,6 +1017,21 @@ int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_d
                          int nref, const long long* prefix, const long long* stride, const int* at, const int* count /*[nref]*/,
                          const double* q, const double* tfac /*[nref]*/, const int* first /*[nobs + 1]*/,
                          double* sums, int* nbad, double* J, double* sim, double* Jd, double* simd);
+/* ucf_debug_fit_reduce under a robust loss (ucf_fit_set_loss states the arithmetic): the production launcher on caller data with
+ * kind = UCF_LOSS_HUBER or UCF_LOSS_TUKEY and the constant c, through the ROBUST instantiations of the kernel.  sums is one entry
+ * longer per set, phi | g | upper A | [phi_d] | phi_w.  ndown [nsets] = counted residual terms with a factor below 1.0; b, bd
+ * [nsets][nobs] = the factor of observation i's drawdown residual and of its derivative residual under the set's base plan, NaN
+ * where the observation does not count (bd: or has wd[i] == 0); each of the three may be NULL, bd needs dh.  The validation of
+ * ucf_debug_fit_reduce, which needs no GPU, and: kind outside 1..2 (least squares is ucf_debug_fit_reduce), c not positive and
+ * finite, bd without dh.  Then UCF_ERR_NO_DEVICE without a device. */
+int ucf_debug_fit_reduce_loss(int kind, double c, int source, int npar, int nsets, int nobs, double two_dlog,
+                              long long nh, const double* h, const double* dh /*NULL ok*/, const double* Hc /*[nplans]*/,
+                              const double* obs, const double* w, const double* dobs, const double* wd /*[nobs]*/,
+                              const int* slot /*[nobs]*/, long long plan_stride,
+                              int nref, const long long* prefix, const long long* stride, const int* at, const int* count /*[nref]*/,
+                              const double* q, const double* tfac /*[nref]*/, const int* first /*[nobs + 1]*/,
+                              double* sums, int* nbad, double* J, double* sim, double* Jd, double* simd,
+                              int* ndown, double* b, double* bd);
 /* Host only: the nwell real wells followed by their mirror images in the straight line a x + b y = c (xo, yo, qo, t0o
  * [2 nwell]).  An image has q = +q for a no-flow boundary (kind 0), -q for a constant-head boundary (kind 1), and the t0 of its
  * real well.  One boundary only (two parallel boundaries need an infinite image series).  UCF_ERR_BAD_ARGUMENT: a = b = 0, a

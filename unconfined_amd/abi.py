@@ -25,6 +25,9 @@ FIT_CONVERGED, FIT_MAX_ITER, FIT_SINGULAR, FIT_NONFINITE_START = range(4)
 FIT_SCREEN = -1
 # source of ucf_debug_fit_reduce: how an observation finds its simulated value in h
 FIT_SLOTS, FIT_NETWORK, FIT_FIELD = range(3)
+# loss of a fit (enum UCF_LOSS_* of include/ucf.h: ucf_fit_set_loss)
+LOSS_L2, LOSS_HUBER, LOSS_TUKEY = range(3)
+LOSS_KINDS = {"l2": LOSS_L2, "huber": LOSS_HUBER, "tukey": LOSS_TUKEY}
 UCF_ERR_BAD_ARGUMENT, UCF_ERR_NO_DEVICE, UCF_ERR_SINGULAR = -11, -12, -16
 
 

@@ -329,15 +329,24 @@ int ucf_debug_ensemble_weighted(int nens, long long nout, const double* a, const
     return debug_ensemble_core(nens, nout, a, true, weight, nq, q, nlim, limit, out, pexc, nbad);
 }
 
-// The fit reduction exactly as ucf_fit_evaluate launches it (ucf_fit_launch_reduce, and through it the same choice of
-// instantiation), on caller data: the kernel is testable at its edges without paying for evaluations.  Everything the
-// kernel could read is checked against the lengths the caller gave before anything is allocated or launched.
-int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_dlog, long long nh, const double* h, const double* dh,
-                         const double* Hc, const double* obs, const double* w, const double* dobs, const double* wd, const int* slot,
-                         long long plan_stride, int nref, const long long* prefix, const long long* stride, const int* at,
-                         const int* count, const double* q, const double* tfac, const int* first, double* sums, int* nbad, double* J,
-                         double* sim, double* Jd, double* simd)
+}  // extern "C"
+
+namespace {
+// ucf_debug_fit_reduce (loss = UCF_LOSS_L2: c, ndown, b, bd are not read) and ucf_debug_fit_reduce_loss: one validation and one
+// launch through ucf_fit_launch_reduce.  Everything the kernel could read is checked against the lengths the caller gave
+// before anything is allocated or launched.
+int debug_fit_reduce_core(int loss, double c, int source, int npar, int nsets, int nobs, double two_dlog, long long nh, const double* h,
+                          const double* dh, const double* Hc, const double* obs, const double* w, const double* dobs, const double* wd,
+                          const int* slot, long long plan_stride, int nref, const long long* prefix, const long long* stride, const int* at,
+                          const int* count, const double* q, const double* tfac, const int* first, double* sums, int* nbad, double* J,
+                          double* sim, double* Jd, double* simd, int* ndown, double* b, double* bd)
 {
+    if (loss != UCF_LOSS_L2) {
+        if (loss != UCF_LOSS_HUBER && loss != UCF_LOSS_TUKEY)
+            return fail(UCF_ERR_BAD_ARGUMENT, "kind=%d: UCF_LOSS_HUBER (1) or UCF_LOSS_TUKEY (2); least squares is ucf_debug_fit_reduce", loss);
+        if (!(c > 0.0) || !std::isfinite(c)) return fail(UCF_ERR_BAD_ARGUMENT, "c=%g must be positive and finite", c);
+        if (!dh && bd) return fail(UCF_ERR_BAD_ARGUMENT, "bd asked for without dh");
+    }
     if (source != UCF_FIT_SLOTS && source != UCF_FIT_NETWORK && source != UCF_FIT_FIELD) return fail(UCF_ERR_BAD_ARGUMENT, "source=%d outside 0..2", source);
     if (npar < 0 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 0..%d", npar, UCF_FIT_MAX_PAR);
     if (nsets < 1 || nsets > (1 << 16)) return fail(UCF_ERR_BAD_ARGUMENT, "nsets=%d outside 1..65536", nsets);
@@ -375,16 +384,18 @@ int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_d
     if ((rc = require_device())) return rc;
     const bool joint = dh != nullptr;
     const size_t so = sizeof(double) * (size_t)nobs, sh = sizeof(double) * (size_t)nh, nt = (size_t)(nref > 0 ? nref : 1);
-    const size_t nsum = (size_t)(joint ? ucf_fit_joint_nsums(npar) : ucf_fit_nsums(npar));
+    const size_t nsum = (size_t)(joint ? ucf_fit_joint_nsums(npar) : ucf_fit_nsums(npar)) + (loss != UCF_LOSS_L2 ? 1 : 0);
+    const size_t bfac = so * (size_t)nsets;
     const size_t bJ = so * nsets * (npar > 0 ? npar : 1), bsim = so * (size_t)nplans;
-    dev_buf b_h, b_dh, b_hc, b_obs, b_w, b_dobs, b_wd, b_slot, b_ref, b_term, b_first, b_tfac, b_sums, b_nbad, b_J, b_sim, b_Jd, b_simd;
+    dev_buf b_h, b_dh, b_hc, b_obs, b_w, b_dobs, b_wd, b_slot, b_ref, b_term, b_first, b_tfac, b_sums, b_nbad, b_J, b_sim, b_Jd, b_simd, b_ndown, b_b, b_bd;
     if (b_h.alloc(sh) || (joint && b_dh.alloc(sh)) || b_hc.alloc(sizeof(double) * (size_t)nplans) || b_obs.alloc(so) || b_w.alloc(so) ||
         (joint && (b_dobs.alloc(so) || b_wd.alloc(so))) || (source == UCF_FIT_SLOTS && b_slot.alloc(sizeof(int) * (size_t)nobs)) ||
         (source == UCF_FIT_NETWORK && b_ref.alloc(sizeof(ucf_fit_obs_ref) * nt)) ||
         (source == UCF_FIT_FIELD && (b_term.alloc(sizeof(ucf_fit_term) * nt) || b_first.alloc(sizeof(int) * ((size_t)nobs + 1)) ||
                                      (joint && b_tfac.alloc(sizeof(double) * nt)))) ||
         b_sums.alloc(sizeof(double) * nsets * nsum) || b_nbad.alloc(sizeof(int) * (size_t)nsets) || (J && b_J.alloc(bJ)) || (sim && b_sim.alloc(bsim)) ||
-        (Jd && b_Jd.alloc(bJ)) || (simd && b_simd.alloc(bsim)))
+        (Jd && b_Jd.alloc(bJ)) || (simd && b_simd.alloc(bsim)) || (ndown && b_ndown.alloc(sizeof(int) * (size_t)nsets)) || (b && b_b.alloc(bfac)) ||
+        (bd && b_bd.alloc(bfac)))
         return fail(UCF_ERR_NOMEM, "device allocation failed");
     const struct { void* dev; const void* host; size_t bytes; } up[] = {
         {b_h.p, h, sh}, {b_dh.p, dh, sh}, {b_hc.p, Hc, sizeof(double) * (size_t)nplans}, {b_obs.p, obs, so}, {b_w.p, w, so}, {b_dobs.p, dobs, so},
@@ -403,11 +414,41 @@ int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_d
     ra.d_obs = (const double*)b_obs.p; ra.d_w = (const double*)b_w.p; ra.d_dobs = (const double*)b_dobs.p; ra.d_wd = (const double*)b_wd.p;
     ra.d_sums = (double*)b_sums.p; ra.d_nbad = (int*)b_nbad.p;
     ra.d_J = (double*)b_J.p; ra.d_sim = (double*)b_sim.p; ra.d_Jd = (double*)b_Jd.p; ra.d_simd = (double*)b_simd.p;
+    ra.loss = loss; ra.loss_c = c; ra.d_ndown = (int*)b_ndown.p; ra.d_b = (double*)b_b.p; ra.d_bd = (double*)b_bd.p;
     rc = ucf_fit_launch_reduce(&ra, nullptr);
     if (rc) return fail(rc, "fit reduction kernel launch failed");
     HIP_TRY(hipStreamSynchronize(nullptr));
     return copy_back_sync({{sums, b_sums.p, sizeof(double) * nsets * nsum}, {nbad, b_nbad.p, sizeof(int) * (size_t)nsets}, {J, b_J.p, npar > 0 ? bJ : 0},
-                           {sim, b_sim.p, bsim}, {Jd, b_Jd.p, npar > 0 ? bJ : 0}, {simd, b_simd.p, bsim}});
+                           {sim, b_sim.p, bsim}, {Jd, b_Jd.p, npar > 0 ? bJ : 0}, {simd, b_simd.p, bsim}, {ndown, b_ndown.p, sizeof(int) * (size_t)nsets},
+                           {b, b_b.p, bfac}, {bd, b_bd.p, bfac}});
+}
+}  // namespace
+
+extern "C" {
+
+// The fit reduction exactly as ucf_fit_evaluate launches it (ucf_fit_launch_reduce, and through it the same choice of
+// instantiation), on caller data: the kernel is testable at its edges without paying for evaluations.
+int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_dlog, long long nh, const double* h, const double* dh,
+                         const double* Hc, const double* obs, const double* w, const double* dobs, const double* wd, const int* slot,
+                         long long plan_stride, int nref, const long long* prefix, const long long* stride, const int* at,
+                         const int* count, const double* q, const double* tfac, const int* first, double* sums, int* nbad, double* J,
+                         double* sim, double* Jd, double* simd)
+{
+    return debug_fit_reduce_core(UCF_LOSS_L2, 0.0, source, npar, nsets, nobs, two_dlog, nh, h, dh, Hc, obs, w, dobs, wd, slot, plan_stride, nref,
+                                 prefix, stride, at, count, q, tfac, first, sums, nbad, J, sim, Jd, simd, nullptr, nullptr, nullptr);
+}
+
+// the same under a robust loss: kind and c are checked first, with the rest before any device is touched
+int ucf_debug_fit_reduce_loss(int kind, double c, int source, int npar, int nsets, int nobs, double two_dlog, long long nh, const double* h,
+                              const double* dh, const double* Hc, const double* obs, const double* w, const double* dobs, const double* wd,
+                              const int* slot, long long plan_stride, int nref, const long long* prefix, const long long* stride,
+                              const int* at, const int* count, const double* q, const double* tfac, const int* first, double* sums, int* nbad,
+                              double* J, double* sim, double* Jd, double* simd, int* ndown, double* b, double* bd)
+{
+    if (kind != UCF_LOSS_HUBER && kind != UCF_LOSS_TUKEY)
+        return fail(UCF_ERR_BAD_ARGUMENT, "kind=%d: UCF_LOSS_HUBER (1) or UCF_LOSS_TUKEY (2); least squares is ucf_debug_fit_reduce", kind);
+    return debug_fit_reduce_core(kind, c, source, npar, nsets, nobs, two_dlog, nh, h, dh, Hc, obs, w, dobs, wd, slot, plan_stride, nref, prefix,
+                                 stride, at, count, q, tfac, first, sums, nbad, J, sim, Jd, simd, ndown, b, bd);
 }
 
 }  // extern "C"

@@ -69,11 +69,16 @@ struct ucf_fit {
     int nd = 0;
     ucf_buffer b_dobs, b_wd, b_tfac;
     ucf_buffer b_Jd, b_simd;               // grown on demand, as b_J and b_sim
+    // the loss (ucf_fit_set_loss): a kind and its constant, nothing on the device.  The factors that ucf_fit_loss_report asks
+    // for are grown on demand.
+    int loss = UCF_LOSS_L2;
+    double loss_c = 0.0;
+    ucf_buffer b_ndown, b_bfac, b_bdfac;
     // every device buffer above: the one list (ucf_fit_destroy frees through it)
-    std::array<ucf_buffer*, 21> buffers()
+    std::array<ucf_buffer*, 24> buffers()
     {
         return {{&b_slot, &b_obs, &b_w, &b_t, &b_r, &b_s, &b_h, &b_d, &b_hc, &b_sums, &b_nbad, &b_J, &b_sim, &b_ref, &b_term, &b_first,
-                 &b_dobs, &b_wd, &b_tfac, &b_Jd, &b_simd}};
+                 &b_dobs, &b_wd, &b_tfac, &b_Jd, &b_simd, &b_ndown, &b_bfac, &b_bdfac}};
     }
     std::vector<double> st_t;              // staging of one plan: its tD over all groups ...
     std::vector<int> st_s;                 // ... and their split vector
@@ -409,10 +414,20 @@ int network_core(ucf_fit* f, int nplans)
     return rc;
 }
 
+// what the robust reduction adds to the outputs of fit_evaluate: phi_w, ndown [nsets], b, bd [nsets][nobs]; each may be NULL.
+// ndown, b or bd asked for on a least-squares fit run the robust instantiation with every factor 1.0 (ucf_fit.h).
+struct fit_loss_out {
+    double* phi_w = nullptr;
+    int* ndown = nullptr;
+    double *b = nullptr, *bd = nullptr;
+};
+
 // jac != 0: base and perturbed plans, everything; jac == 0: the base plans only, phi and nbad (the trial points of ucf_fit_lm).
 // On a fit with derivative data the sums are the joint ones and phi_d, Jd, simd_all may be asked for; without, they are NULL.
+// The fit's loss decides the instantiation; on a least-squares fit with lo == NULL nothing differs from a fit without one.
 int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int jac, double* phi, double* g, double* A, int* nbad,
-                 double* J, double* sim_all, double* phi_d = nullptr, double* Jd = nullptr, double* simd_all = nullptr)
+                 double* J, double* sim_all, double* phi_d = nullptr, double* Jd = nullptr, double* simd_all = nullptr,
+                 const fit_loss_out* lo = nullptr)
 {
     if (!f || !theta) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (nsets < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nsets=%d: at least one parameter set", nsets);
@@ -453,7 +468,11 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
         }
     }
     const bool joint = f->deriv;
-    const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_, nsum = (size_t)(joint ? ucf_fit_joint_nsums(jac ? npar : 0) : ucf_fit_nsums(jac ? npar : 0));
+    const fit_loss_out none;
+    const fit_loss_out& L = lo ? *lo : none;
+    const bool robust = f->loss != UCF_LOSS_L2 || L.ndown || L.b || L.bd;
+    const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_;
+    const size_t nsum = (size_t)(joint ? ucf_fit_joint_nsums(jac ? npar : 0) : ucf_fit_nsums(jac ? npar : 0)) + (robust ? 1 : 0);
     // points and (point, depth) values that are launched: every depth at every observation, or the network's blocks
     const size_t ptot = (size_t)nplans * (f->is_network() ? f->net_pts : np_), vtot = (size_t)nplans * (f->is_network() ? f->net_vals : np_ * nz);
     int rc;
@@ -466,6 +485,9 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     if (sim_all && (rc = grow_buffer(f->b_sim, sizeof(double) * tot, "sim_all", f->n_alloc))) return rc;
     if (Jd && jac && (rc = grow_buffer(f->b_Jd, sizeof(double) * nsets * np_ * npar, "Jd", f->n_alloc))) return rc;
     if (simd_all && (rc = grow_buffer(f->b_simd, sizeof(double) * tot, "simd_all", f->n_alloc))) return rc;
+    if (L.ndown && (rc = grow_buffer(f->b_ndown, sizeof(int) * nsets, "ndown", f->n_alloc))) return rc;
+    if (L.b && (rc = grow_buffer(f->b_bfac, sizeof(double) * nsets * np_, "b", f->n_alloc))) return rc;
+    if (L.bd && (rc = grow_buffer(f->b_bdfac, sizeof(double) * nsets * np_, "bd", f->n_alloc))) return rc;
     f->io.d_t = (double*)f->b_t.p; f->io.d_r = (double*)f->b_r.p; f->io.d_s = (int*)f->b_s.p;
     f->io.d_h = (double*)f->b_h.p; f->io.d_d = (double*)f->b_d.p;
     f->last_nplans = 0;
@@ -487,6 +509,8 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     ra.d_sums = (double*)f->b_sums.p; ra.d_nbad = (int*)f->b_nbad.p;
     ra.d_J = (J && jac) ? (double*)f->b_J.p : nullptr; ra.d_sim = sim_all ? (double*)f->b_sim.p : nullptr;
     ra.d_Jd = (Jd && jac) ? (double*)f->b_Jd.p : nullptr; ra.d_simd = simd_all ? (double*)f->b_simd.p : nullptr;
+    ra.loss = f->loss; ra.loss_c = f->loss_c;
+    ra.d_ndown = L.ndown ? (int*)f->b_ndown.p : nullptr; ra.d_b = L.b ? (double*)f->b_bfac.p : nullptr; ra.d_bd = L.bd ? (double*)f->b_bdfac.p : nullptr;
     rc = ucf_fit_launch_reduce(&ra, nullptr);
     if (rc) return fail(rc, "fit reduction kernel launch failed");
     HIP_TRY(hipStreamSynchronize(nullptr));
@@ -497,10 +521,14 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     if (sim_all) HIP_TRY(hipMemcpy(sim_all, f->b_sim.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
     if (Jd && jac) HIP_TRY(hipMemcpy(Jd, f->b_Jd.p, sizeof(double) * nsets * np_ * npar, hipMemcpyDeviceToHost));
     if (simd_all) HIP_TRY(hipMemcpy(simd_all, f->b_simd.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
+    if (L.ndown) HIP_TRY(hipMemcpy(L.ndown, f->b_ndown.p, sizeof(int) * nsets, hipMemcpyDeviceToHost));
+    if (L.b) HIP_TRY(hipMemcpy(L.b, f->b_bfac.p, sizeof(double) * nsets * np_, hipMemcpyDeviceToHost));
+    if (L.bd) HIP_TRY(hipMemcpy(L.bd, f->b_bdfac.p, sizeof(double) * nsets * np_, hipMemcpyDeviceToHost));
     for (int s = 0; s < nsets; s++) {
         const double* v = &f->h_sums[s * nsum];
         if (phi) phi[s] = v[0];
-        if (phi_d) phi_d[s] = v[nsum - 1];
+        if (phi_d) phi_d[s] = v[nsum - 1 - (robust ? 1 : 0)];
+        if (L.phi_w) L.phi_w[s] = robust ? v[nsum - 1] : v[0];      // least squares: every factor is 1.0
         if (!jac) continue;
         if (g) for (int j = 0; j < npar; j++) g[(size_t)s * npar + j] = v[1 + j];
         if (A) {
@@ -880,6 +908,81 @@ int ucf_fit_objective(ucf_fit* f, int nsets, const double* theta, double* phi, i
     return fit_evaluate(f, nsets, theta, 0.0, 0, phi, nullptr, nullptr, nbad, nullptr, sim, phi_d, nullptr, simd);
 }
 
+// ---- robust losses (include/ucf.h states the arithmetic; this file is compiled without contraction)
+static int loss_check(int kind, double c)
+{
+    if (kind != UCF_LOSS_L2 && kind != UCF_LOSS_HUBER && kind != UCF_LOSS_TUKEY)
+        return fail(UCF_ERR_BAD_ARGUMENT, "kind=%d is no loss (UCF_LOSS_L2 0, UCF_LOSS_HUBER 1, UCF_LOSS_TUKEY 2)", kind);
+    if (kind != UCF_LOSS_L2 && (!(c > 0.0) || !std::isfinite(c))) return fail(UCF_ERR_BAD_ARGUMENT, "c=%g must be positive and finite", c);
+    return UCF_OK;
+}
+
+int ucf_fit_loss_terms(int kind, double c, int n, const double* x, double* rho, double* b)
+{
+    int rc = loss_check(kind, c);
+    if (rc) return rc;
+    if (n < 0) return fail(UCF_ERR_BAD_ARGUMENT, "n=%d is negative", n);
+    if (!x || !rho || !b) return fail(UCF_ERR_BAD_ARGUMENT, "NULL x, rho or b");
+    const double c2 = c * c;
+    for (int i = 0; i < n; i++) {
+        const double xi = x[i], a = std::fabs(xi);
+        if (kind == UCF_LOSS_L2) { b[i] = 1.0; rho[i] = xi * xi; }
+        else if (kind == UCF_LOSS_HUBER) {
+            if (a <= c) { b[i] = 1.0; rho[i] = xi * xi; }
+            else { b[i] = c / a; rho[i] = c * (2.0 * a - c); }
+        } else {
+            const double u = xi / c;
+            if (a < c) { const double v = 1.0 - u * u; b[i] = v * v; rho[i] = (c2 * (1.0 - b[i] * v)) / 3.0; }
+            else { b[i] = 0.0; rho[i] = c2 / 3.0; }
+        }
+    }
+    return UCF_OK;
+}
+
+int ucf_fit_robust_scale(int n, const double* x, double* scale)
+{
+    if (n < 1) return fail(UCF_ERR_BAD_ARGUMENT, "n=%d: at least one residual", n);
+    if (!x || !scale) return fail(UCF_ERR_BAD_ARGUMENT, "NULL x or scale");
+    std::vector<double> a;
+    a.reserve((size_t)n);
+    for (int i = 0; i < n; i++)
+        if (std::isfinite(x[i])) a.push_back(std::fabs(x[i]));
+    if (a.empty()) return fail(UCF_ERR_BAD_ARGUMENT, "none of the %d residuals is finite", n);
+    std::sort(a.begin(), a.end());
+    const size_t k = a.size();
+    const double m = (k & 1) ? a[k / 2] : (a[k / 2 - 1] + a[k / 2]) / 2.0;
+    *scale = 1.4826 * m;
+    return UCF_OK;
+}
+
+int ucf_fit_set_loss(ucf_fit* f, int kind, double c)
+{
+    int rc = loss_check(kind, c);
+    if (rc) return rc;
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL fit");
+    f->loss = kind;
+    f->loss_c = kind == UCF_LOSS_L2 ? 0.0 : c;
+    return UCF_OK;
+}
+
+int ucf_fit_get_loss(const ucf_fit* f, int* kind, double* c)
+{
+    if (!f || !kind || !c) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    *kind = f->loss;
+    *c = f->loss_c;
+    return UCF_OK;
+}
+
+// base plans only, the npar = 0 reduction in its robust instantiation (on a least-squares fit with every factor 1.0)
+int ucf_fit_loss_report(ucf_fit* f, int nsets, const double* theta, double* phi, double* phi_w, int* nbad, int* ndown, double* b, double* bd)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (bd && !f->deriv) return fail(UCF_ERR_BAD_ARGUMENT, "bd is asked for, but the fit has no derivative data (ucf_fit_set_derivative)");
+    fit_loss_out lo;
+    lo.phi_w = phi_w; lo.ndown = ndown; lo.b = b; lo.bd = bd;
+    return fit_evaluate(f, nsets, theta, 0.0, 0, phi, nullptr, nullptr, nbad, nullptr, nullptr, nullptr, nullptr, nullptr, &lo);
+}
+
 int ucf_fit_default_options(ucf_fit_options* opt)
 {
     if (!opt) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
@@ -993,7 +1096,14 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
             const int n = (int)idx.size();
             th.resize((size_t)n * P); ph.resize(n); AA.resize(n * PP); nb.resize(n);
             for (int q = 0; q < n; q++) for (int j = 0; j < P; j++) th[(size_t)q * P + j] = theta[(size_t)idx[q] * P + j];
-            rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), nullptr, AA.data(), nb.data(), nullptr, nullptr);
+            // under a robust loss the variance factor is phi_w of this evaluation: the weighted least-squares problem that the
+            // final factors define (include/ucf.h); under least squares it stays the phi the iteration ended with
+            const bool robust = f->loss != UCF_LOSS_L2;
+            std::vector<double> pw(robust ? n : 0);
+            fit_loss_out lo;
+            lo.phi_w = robust ? pw.data() : nullptr;
+            rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), nullptr, AA.data(), nb.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                              robust ? &lo : nullptr);
             if (rc) return rc;
             for (int q = 0; q < n; q++) {
                 const int s = idx[q];
@@ -1002,7 +1112,7 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
                 for (int j = 0; j < P && good; j++) {
                     for (int k = 0; k < P; k++) e[k] = (k == j) ? 1.0 : 0.0;
                     good = ucf_fit_solve_step(P, &AA[q * PP], e, 0.0, col) == UCF_OK;
-                    for (int k = 0; k < P && good; k++) cov[s * PP + (size_t)k * P + j] = phi[s] / (double)dof * col[k];
+                    for (int k = 0; k < P && good; k++) cov[s * PP + (size_t)k * P + j] = (robust ? pw[q] : phi[s]) / (double)dof * col[k];
                 }
                 if (!good) for (size_t i = 0; i < PP; i++) cov[s * PP + i] = NAN;
             }

@@ -2,7 +2,7 @@
 #pragma once
 
 // sums per parameter set: phi | g[npar] | upper triangle of A, row by row (j <= k); with derivative data: ... | phi_d, the
-// derivative terms' share of phi
+// derivative terms' share of phi; a robust reduction (ucf_fit_reduce_is_robust) ends with one more: ... | phi_w
 static inline int ucf_fit_nsums(int npar) { return 1 + npar + npar * (npar + 1) / 2; }
 static inline int ucf_fit_joint_nsums(int npar) { return ucf_fit_nsums(npar) + 1; }
 
@@ -54,6 +54,22 @@ struct ucf_fit_reduce_args {
     int* d_nbad;                           // [nsets]
     double *d_J, *d_sim;                   // [nsets][nobs][npar], [nsets][1+2 npar][nobs]; each may be NULL
     double *d_Jd, *d_simd;                 // the same of the derivative; each may be NULL
+    // The loss (include/ucf.h, ucf_fit_set_loss).  All zero: least squares, the reduction and the sums as above.  Otherwise
+    // -- a loss other than UCF_LOSS_L2, or one of the three outputs asked for -- the robust instantiation runs and every set
+    // of d_sums is one entry longer (phi_w).  Least squares with an output asked for runs as Huber with c = +inf: every factor
+    // is 1.0 and phi, g, A, phi_d, nbad have the bits of the plain reduction.
+    int loss;                              // UCF_LOSS_*
+    double loss_c;                         // positive and finite; not read under UCF_LOSS_L2
+    int* d_ndown;                          // [nsets] counted residual terms with a factor below 1.0; may be NULL
+    double *d_b, *d_bd;                    // [nsets][nobs] factor of the drawdown / derivative residual under the base plan, NaN
+                                           // where the observation does not count (d_bd: or has wd == 0); each may be NULL;
+                                           // d_bd needs d_dh
 };
+static inline int ucf_fit_reduce_is_robust(const ucf_fit_reduce_args* a) { return a->loss != 0 || a->d_ndown || a->d_b || a->d_bd; }
+// doubles per set of d_sums that the launch of `a` writes
+static inline int ucf_fit_reduce_nsums(const ucf_fit_reduce_args* a)
+{
+    return (a->d_dh ? ucf_fit_joint_nsums(a->npar) : ucf_fit_nsums(a->npar)) + (ucf_fit_reduce_is_robust(a) ? 1 : 0);
+}
 
 int ucf_fit_launch_reduce(const ucf_fit_reduce_args* a, void* stream);

@@ -1,12 +1,16 @@
 // ucf_fit.hip -- residuals, objective, central-difference Jacobian and normal equations of a least-squares fit, from the
 // drawdowns that the evaluators left in device memory (ucf_fit_evaluate, include/ucf.h).  One kernel template over one
-// body, fit_reduce_kernel<NPAR, SOURCE, DERIV>, behind one launcher (ucf_fit_launch_reduce, ucf_fit.h):
+// body, fit_reduce_kernel<NPAR, SOURCE, DERIV, ROBUST>, behind one launcher (ucf_fit_launch_reduce, ucf_fit.h):
 //   SOURCE  how observation i finds its simulated value in h and its log-time derivative in dh: slot_source
 //           (ucf_fit_create: one double per observation and plan), network_source (ucf_fit_create_network: ragged per-group
 //           h, point observations and screen averages) or field_source (ucf_fit_create_field: an observation is the sum
 //           over pumping wells of rate factor x such a value);
 //   DERIV   whether the fit has derivative data (ucf_fit_set_derivative).  It is a template parameter so that a fit
-//           without them has no load of dh, no phi_d and no register for either.
+//           without them has no load of dh, no phi_d and no register for either;
+//   ROBUST  whether a robust loss (ucf_fit_set_loss: Huber or Tukey, the kind a wave-uniform argument) reweights the terms.
+//           It is a template parameter so that a plain least-squares fit has the arithmetic, the registers and the sums it
+//           had before a loss existed; the kind is an argument because the two losses differ by one short branch that every
+//           lane of a launch takes alike, and a third template axis would double the robust instantiations for nothing.
 //
 // Tiny and HBM-bound: (1 + 2 NPAR) x nobs doubles per parameter set are read once (twice with derivative data).  Built with
 // -ffp-contract=off: every product and sum below is rounded on its own, so that the result is the arithmetic written here.
@@ -28,6 +32,29 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;
 }
 
+// The robust loss of a launch and where its per-observation factors go (ROBUST instantiations only; passed by value)
+struct fit_loss {
+    int kind;                              // UCF_LOSS_HUBER or UCF_LOSS_TUKEY: the same in every lane
+    double c;                              // > 0; +inf under Huber: every factor 1.0, the bits of least squares
+    int* __restrict__ ndown;               // [nsets] counted residual terms with b < 1.0, or NULL
+    double* __restrict__ b;                // [nsets][nobs] factor of the drawdown residual, NaN where not counted, or NULL
+    double* __restrict__ bd;               // [nsets][nobs] the same of the derivative residual (NaN also where wd == 0), or NULL
+};
+
+// rho(x) and the IRLS factor b(x) of include/ucf.h (ucf_fit_loss_terms), every operation rounded on its own
+__device__ __forceinline__ void loss_terms(int kind, double c, double x, double& rho, double& b)
+{
+    const double a = fabs(x);
+    if (kind == UCF_LOSS_HUBER) {
+        if (a <= c) { b = 1.0; rho = x * x; }
+        else { b = c / a; rho = c * (2.0 * a - c); }
+    } else {
+        const double c2 = c * c, u = x / c;
+        if (a < c) { const double v = 1.0 - u * u; b = v * v; rho = (c2 * (1.0 - b * v)) / 3.0; }
+        else { b = 0.0; rho = c2 / 3.0; }
+    }
+}
+
 // Everything after the simulated values.  src.value(h, i, plan) is the dimensionless simulated value of observation i
 // under plan `plan`, src.dvalue(dh, i, plan) its log-time derivative; the kernels differ only in them.  Either is scaled
 // by Hc[plan] here, as ucf_drawdown_multi scales it.  First the drawdown term; then, with DERIV and where the derivative
@@ -36,28 +63,32 @@ __device__ __forceinline__ double wave_sum(double v)
 // wd_i == 0 OR every sd[k] finite); with all wd = 0 the sums have the bits of the reduction without DERIV.  sums per set:
 // phi | g | upper A, with DERIV ... | phi_d.  The weighted drawdown residual and derivatives are formed before sd is read,
 // so that s[] is dead by then.
-template <int NPAR, class SOURCE, bool DERIV>
+// With ROBUST a residual term x (wr, wrd) with weighted derivatives wd_j adds rho(x) to phi (phi_d), b (x x) to phi_w,
+// (b wd_j) x to g_j and (b wd_j) wd_k to A_jk: the Gauss-Newton / IRLS form, A stays positive semidefinite.  Same counting
+// rule, same order; sums per set: phi | g | upper A | [phi_d] | phi_w.
+template <int NPAR, class SOURCE, bool DERIV, bool ROBUST>
 __device__ __forceinline__ void fit_reduce_body(int nobs, double two_dlog, const SOURCE& src, const double* __restrict__ h,
                                                 const double* __restrict__ dh, const double* __restrict__ Hc,
                                                 const double* __restrict__ obs, const double* __restrict__ w,
                                                 const double* __restrict__ dobs, const double* __restrict__ wdv,
                                                 double* __restrict__ sums, int* __restrict__ nbad, double* __restrict__ J,
-                                                double* __restrict__ sim, double* __restrict__ Jd, double* __restrict__ simd)
+                                                double* __restrict__ sim, double* __restrict__ Jd, double* __restrict__ simd,
+                                                const fit_loss& loss)
 {
     constexpr int NP = NPAR > 0 ? NPAR : 1;                  // array extents (NPAR = 0: objective only)
     constexpr int NPLANS = 1 + 2 * NPAR;
     constexpr int NA = NPAR * (NPAR + 1) / 2;
-    constexpr int NSUMS = 1 + NPAR + NA + (DERIV ? 1 : 0);
+    constexpr int NSUMS = 1 + NPAR + NA + (DERIV ? 1 : 0) + (ROBUST ? 1 : 0);
     __shared__ double part[FIT_WAVES][NSUMS];
-    __shared__ int part_bad[FIT_WAVES];
+    __shared__ int part_bad[FIT_WAVES], part_down[FIT_WAVES];
     const int set = blockIdx.x, lane = threadIdx.x;
     const size_t plan0 = (size_t)set * NPLANS;
-    double phi = 0.0, phi_d = 0.0, g[NP], A[NP * (NP + 1) / 2];
+    double phi = 0.0, phi_d = 0.0, phi_w = 0.0, g[NP], A[NP * (NP + 1) / 2];
 #pragma unroll
     for (int j = 0; j < NP; j++) g[j] = 0.0;
 #pragma unroll
     for (int j = 0; j < NP * (NP + 1) / 2; j++) A[j] = 0.0;
-    int bad = 0;
+    int bad = 0, down = 0;
     for (int i = lane; i < nobs; i += FIT_THREADS) {
         bool ok = true;
         double wr, wd[NP];
@@ -107,44 +138,93 @@ __device__ __forceinline__ void fit_reduce_body(int nobs, double two_dlog, const
             sd0 = sd[0];
             ok = ok && (wdi == 0.0 || okd);
         }
-        if (!ok) { bad++; continue; }
+        if (!ok) {
+            bad++;
+            if constexpr (ROBUST) {
+                if (loss.b) loss.b[(size_t)set * nobs + i] = __builtin_nan("");
+                if (loss.bd) loss.bd[(size_t)set * nobs + i] = __builtin_nan("");
+            }
+            continue;
+        }
         // Without DERIV the compiler sinks the loads of w[i] and obs[i] to here and, left alone, asks for one after the other
         // has arrived: both first (2 VMEM reads), then the arithmetic.  One memory round trip of a pass that has three.
         if constexpr (!DERIV) { __builtin_amdgcn_sched_group_barrier(0x20, 2, 0); __builtin_amdgcn_sched_group_barrier(0x2, 256, 0); }
         // the drawdown term
-        phi = phi + wr * wr;
-#pragma unroll
-        for (int j = 0; j < NPAR; j++) g[j] = g[j] + wd[j] * wr;
         int q = 0;
+        if constexpr (ROBUST) {
+            double rho, b;
+            loss_terms(loss.kind, loss.c, wr, rho, b);
+            phi = phi + rho;
+            phi_w = phi_w + b * (wr * wr);
+            if (b < 1.0) down++;
+            if (loss.b) loss.b[(size_t)set * nobs + i] = b;
 #pragma unroll
-        for (int j = 0; j < NPAR; j++)
+            for (int j = 0; j < NPAR; j++) {
+                const double bw = b * wd[j];
+                g[j] = g[j] + bw * wr;
 #pragma unroll
-            for (int k = j; k < NPAR; k++) { A[q] = A[q] + wd[j] * wd[k]; q++; }
-        // the derivative term: skipped, not added as zero, where it has no weight
-        if (DERIV && wdi > 0.0) {
-            const double wrd = wdi * (dobs[i] - sd0);
-            phi = phi + wrd * wrd;
-            phi_d = phi_d + wrd * wrd;
-            double wdd[NP];
+                for (int k = j; k < NPAR; k++) { A[q] = A[q] + bw * wd[k]; q++; }
+            }
+        } else {
+            phi = phi + wr * wr;
 #pragma unroll
-            for (int j = 0; j < NPAR; j++) { wdd[j] = wdi * dd[j]; g[j] = g[j] + wdd[j] * wrd; }
-            q = 0;
+            for (int j = 0; j < NPAR; j++) g[j] = g[j] + wd[j] * wr;
 #pragma unroll
             for (int j = 0; j < NPAR; j++)
 #pragma unroll
-                for (int k = j; k < NPAR; k++) { A[q] = A[q] + wdd[j] * wdd[k]; q++; }
+                for (int k = j; k < NPAR; k++) { A[q] = A[q] + wd[j] * wd[k]; q++; }
+        }
+        // the derivative term: skipped, not added as zero, where it has no weight
+        if (DERIV && wdi > 0.0) {
+            const double wrd = wdi * (dobs[i] - sd0);
+            double wdd[NP];
+            q = 0;
+            if constexpr (ROBUST) {
+                double rho, b;
+                loss_terms(loss.kind, loss.c, wrd, rho, b);
+                phi = phi + rho;
+                phi_d = phi_d + rho;
+                phi_w = phi_w + b * (wrd * wrd);
+                if (b < 1.0) down++;
+                if (loss.bd) loss.bd[(size_t)set * nobs + i] = b;
+#pragma unroll
+                for (int j = 0; j < NPAR; j++) wdd[j] = wdi * dd[j];
+#pragma unroll
+                for (int j = 0; j < NPAR; j++) {
+                    const double bw = b * wdd[j];
+                    g[j] = g[j] + bw * wrd;
+#pragma unroll
+                    for (int k = j; k < NPAR; k++) { A[q] = A[q] + bw * wdd[k]; q++; }
+                }
+            } else {
+                phi = phi + wrd * wrd;
+                phi_d = phi_d + wrd * wrd;
+#pragma unroll
+                for (int j = 0; j < NPAR; j++) { wdd[j] = wdi * dd[j]; g[j] = g[j] + wdd[j] * wrd; }
+#pragma unroll
+                for (int j = 0; j < NPAR; j++)
+#pragma unroll
+                    for (int k = j; k < NPAR; k++) { A[q] = A[q] + wdd[j] * wdd[k]; q++; }
+            }
+        } else if constexpr (ROBUST) {
+            if (loss.bd) loss.bd[(size_t)set * nobs + i] = __builtin_nan("");
         }
     }
     // wave butterfly, then the waves in order
     const int wave = lane >> 6;
     phi = wave_sum(phi);
     if constexpr (DERIV) phi_d = wave_sum(phi_d);
+    if constexpr (ROBUST) phi_w = wave_sum(phi_w);
 #pragma unroll
     for (int j = 0; j < NPAR; j++) g[j] = wave_sum(g[j]);
 #pragma unroll
     for (int j = 0; j < NA; j++) A[j] = wave_sum(A[j]);
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) bad += __shfl_xor(bad, m, 64);
+    if constexpr (ROBUST) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) down += __shfl_xor(down, m, 64);
+    }
     if ((lane & 63) == 0) {
         part[wave][0] = phi;
 #pragma unroll
@@ -152,6 +232,7 @@ __device__ __forceinline__ void fit_reduce_body(int nobs, double two_dlog, const
 #pragma unroll
         for (int j = 0; j < NA; j++) part[wave][1 + NPAR + j] = A[j];
         if constexpr (DERIV) part[wave][1 + NPAR + NA] = phi_d;
+        if constexpr (ROBUST) { part[wave][NSUMS - 1] = phi_w; part_down[wave] = down; }
         part_bad[wave] = bad;
     }
     __syncthreads();
@@ -164,6 +245,13 @@ __device__ __forceinline__ void fit_reduce_body(int nobs, double two_dlog, const
         int b = 0;
         for (int k = 0; k < FIT_WAVES; k++) b += part_bad[k];
         nbad[set] = b;
+        if constexpr (ROBUST) {
+            if (loss.ndown) {
+                int d = 0;
+                for (int k = 0; k < FIT_WAVES; k++) d += part_down[k];
+                loss.ndown[set] = d;
+            }
+        }
     }
 }
 
@@ -224,30 +312,33 @@ struct field_source {
     }
 };
 
-template <int NPAR, class SOURCE, bool DERIV>
+template <int NPAR, class SOURCE, bool DERIV, bool ROBUST>
 __global__ void __launch_bounds__(FIT_THREADS) fit_reduce_kernel(int nobs, double two_dlog, SOURCE src, const double* __restrict__ h,
                                                                  const double* __restrict__ dh, const double* __restrict__ Hc,
                                                                  const double* __restrict__ obs, const double* __restrict__ w,
                                                                  const double* __restrict__ dobs,
                                                                  const double* __restrict__ wd, double* __restrict__ sums,
                                                                  int* __restrict__ nbad, double* __restrict__ J, double* __restrict__ sim,
-                                                                 double* __restrict__ Jd, double* __restrict__ simd)
+                                                                 double* __restrict__ Jd, double* __restrict__ simd, fit_loss loss)
 {
-    fit_reduce_body<NPAR, SOURCE, DERIV>(nobs, two_dlog, src, h, dh, Hc, obs, w, dobs, wd, sums, nbad, J, sim, Jd, simd);
+    fit_reduce_body<NPAR, SOURCE, DERIV, ROBUST>(nobs, two_dlog, src, h, dh, Hc, obs, w, dobs, wd, sums, nbad, J, sim, Jd, simd, loss);
 }
 
-template <int NPAR, class SOURCE, bool DERIV>
+template <int NPAR, class SOURCE, bool DERIV, bool ROBUST>
 int launch(const ucf_fit_reduce_args& a, const SOURCE& src, hipStream_t stream)
 {
-    hipLaunchKernelGGL((fit_reduce_kernel<NPAR, SOURCE, DERIV>), dim3(a.nsets), dim3(FIT_THREADS), 0, stream, a.nobs, a.two_dlog, src, a.d_h, a.d_dh,
-                       a.d_Hc, a.d_obs, a.d_w, a.d_dobs, a.d_wd, a.d_sums, a.d_nbad, a.d_J, a.d_sim, a.d_Jd, a.d_simd);
+    // least squares with a factor asked for: Huber with c = +inf, whose every factor is 1.0 and whose sums have the bits of L2
+    const fit_loss loss = {a.loss == UCF_LOSS_L2 ? (int)UCF_LOSS_HUBER : a.loss, a.loss == UCF_LOSS_L2 ? (double)INFINITY : a.loss_c, a.d_ndown,
+                           a.d_b, a.d_bd};
+    hipLaunchKernelGGL((fit_reduce_kernel<NPAR, SOURCE, DERIV, ROBUST>), dim3(a.nsets), dim3(FIT_THREADS), 0, stream, a.nobs, a.two_dlog, src, a.d_h,
+                       a.d_dh, a.d_Hc, a.d_obs, a.d_w, a.d_dobs, a.d_wd, a.d_sums, a.d_nbad, a.d_J, a.d_sim, a.d_Jd, a.d_simd, loss);
     return hipGetLastError() == hipSuccess ? UCF_OK : UCF_ERR_HIP;
 }
 
-template <class SOURCE, bool DERIV>
+template <class SOURCE, bool DERIV, bool ROBUST>
 int launch_npar(const ucf_fit_reduce_args& a, const SOURCE& src, hipStream_t stream)
 {
-#define UCF_FIT_CASE(N) case N: return launch<N, SOURCE, DERIV>(a, src, stream)
+#define UCF_FIT_CASE(N) case N: return launch<N, SOURCE, DERIV, ROBUST>(a, src, stream)
     switch (a.npar) {
         UCF_FIT_CASE(0); UCF_FIT_CASE(1); UCF_FIT_CASE(2); UCF_FIT_CASE(3); UCF_FIT_CASE(4);
         UCF_FIT_CASE(5); UCF_FIT_CASE(6); UCF_FIT_CASE(7); UCF_FIT_CASE(8);
@@ -259,13 +350,17 @@ int launch_npar(const ucf_fit_reduce_args& a, const SOURCE& src, hipStream_t str
 template <class SOURCE>
 int launch_source(const ucf_fit_reduce_args& a, const SOURCE& src, hipStream_t stream)
 {
-    return a.d_dh ? launch_npar<SOURCE, true>(a, src, stream) : launch_npar<SOURCE, false>(a, src, stream);
+    if (ucf_fit_reduce_is_robust(&a)) return a.d_dh ? launch_npar<SOURCE, true, true>(a, src, stream) : launch_npar<SOURCE, false, true>(a, src, stream);
+    return a.d_dh ? launch_npar<SOURCE, true, false>(a, src, stream) : launch_npar<SOURCE, false, false>(a, src, stream);
 }
 }  // namespace
 
 int ucf_fit_launch_reduce(const ucf_fit_reduce_args* a, void* stream)
 {
     if (!a || a->nsets < 1 || a->nobs < 1) return UCF_ERR_BAD_ARGUMENT;
+    if (a->loss != UCF_LOSS_L2 && a->loss != UCF_LOSS_HUBER && a->loss != UCF_LOSS_TUKEY) return UCF_ERR_BAD_ARGUMENT;
+    if (a->loss != UCF_LOSS_L2 && !(a->loss_c > 0.0 && a->loss_c < (double)INFINITY)) return UCF_ERR_BAD_ARGUMENT;
+    if (a->d_bd && !a->d_dh) return UCF_ERR_BAD_ARGUMENT;
     hipStream_t s = (hipStream_t)stream;
     switch (a->source) {
     case UCF_FIT_SLOTS: return launch_source(*a, slot_source{a->d_slot, a->plan_stride}, s);

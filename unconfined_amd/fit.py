@@ -13,6 +13,8 @@ equations are formed on the device; this module only marshals arrays.
                                                   # an interference test: pumping wells (x, y, q, t0) as WellField / images take them
     obj = fit.objective(thetas)                   # phi, nbad of many parameter sets without a Jacobian: one plan per set
     lw = likelihood_weights(obj["phi"], obj["nbad"])          # weights for WellField.ensemble(..., weights=lw["weight"])
+    fit.set_loss("huber", 1.345)                  # a robust loss: evaluate, objective and lm reduce with it from here on
+    rep = fit.loss_report(res["theta"], factors=True)         # b (and bd): the factor of every residual; b == 0: an outlier
 
 Parameters are positive and fitted in their logarithm; ``theta`` arrays hold the parameters themselves.
 """
@@ -24,7 +26,7 @@ from typing import Sequence, Union
 import numpy as np
 
 from . import lib as _libmod
-from .abi import FIT_SCREEN, PAR_IDS, PAR_MOENCH_ALPHA0, UcfFitOptions, UcfParams
+from .abi import FIT_SCREEN, LOSS_KINDS, LOSS_L2, PAR_IDS, PAR_MOENCH_ALPHA0, UcfFitOptions, UcfParams
 
 
 def _f64(a):
@@ -161,6 +163,33 @@ def likelihood_weights(phi, nbad=None, s2: float = 1.0) -> dict:
     return {"weight": w, "best": int(best.value), "nadmissible": int(nadm.value)}
 
 
+def loss_kind(kind: Union[str, int]) -> int:
+    """'l2', 'huber', 'tukey' (or the number itself) -> UCF_LOSS_*"""
+    if isinstance(kind, (int, np.integer)):
+        return int(kind)
+    if str(kind).lower() in LOSS_KINDS:
+        return LOSS_KINDS[str(kind).lower()]
+    raise ValueError(f"unknown loss {kind!r}")
+
+
+def loss_terms(kind, c: float, x) -> tuple:
+    """(rho, b) of the weighted residuals ``x`` under a loss (ucf_fit_loss_terms; no GPU): the arithmetic of the device
+    reduction, operation for operation.  ``c`` is not read for 'l2'."""
+    x = np.atleast_1d(_f64(x))
+    rho, b = np.zeros(x.shape), np.zeros(x.shape)
+    _libmod.check(_libmod.load().ucf_fit_loss_terms(loss_kind(kind), float(c), x.size, x.ctypes.data, rho.ctypes.data, b.ctypes.data))
+    return rho, b
+
+
+def robust_scale(x) -> float:
+    """1.4826 x the median of |x| over the finite entries (ucf_fit_robust_scale; no GPU): sigma of weighted residuals that
+    hold outliers.  A multiple of it is the usual ``c`` of ``Fit.set_loss``."""
+    x = np.atleast_1d(_f64(x)).ravel()
+    s = C.c_double()
+    _libmod.check(_libmod.load().ucf_fit_robust_scale(len(x), x.ctypes.data if len(x) else None, C.addressof(s)))
+    return float(s.value)
+
+
 def quantise_weights(w) -> tuple:
     """(u, ess): the integer weights u [nens] (uint64, 0 .. 2^32, the largest weight 2^32) that a weighted ensemble reduces
     with, and Kish's effective sample size of them (ucf_ensemble_quantise; no GPU).  A member with u = 0 is not in the ensemble."""
@@ -282,6 +311,41 @@ class Fit:
         _libmod.check(self._lib.ucf_fit_set_derivative(self._h, None, None))
         self._deriv = False
 
+    def set_loss(self, kind, c: float = 0.0):
+        """the loss of the fit (ucf_fit_set_loss): 'l2' (least squares, the default; detaches a loss), 'huber' or 'tukey' with
+        the constant ``c`` in units of the weighted residual.  ``evaluate``, ``objective`` and ``lm`` reduce with it from here
+        on; cov of ``lm`` is then that of the weighted least-squares problem of the final factors (no sandwich estimator)."""
+        _libmod.check(self._lib.ucf_fit_set_loss(self._h, loss_kind(kind), float(c)))
+
+    def clear_loss(self):
+        """back to least squares"""
+        _libmod.check(self._lib.ucf_fit_set_loss(self._h, LOSS_L2, 0.0))
+
+    def get_loss(self) -> tuple:
+        """(kind, c) as ucf_fit_get_loss returns them; c = 0.0 under least squares"""
+        k, c = C.c_int(), C.c_double()
+        _libmod.check(self._lib.ucf_fit_get_loss(self._h, C.byref(k), C.byref(c)))
+        return int(k.value), float(c.value)
+
+    def loss_report(self, thetas, factors: bool = False) -> dict:
+        """thetas [nsets][npar] -> phi, phi_w, nbad, ndown [nsets] under the fit's loss (ucf_fit_loss_report: base plans only);
+        with ``factors`` b [nsets][nobs], the factor of every drawdown residual (NaN where the observation does not count),
+        and on a fit with derivative data bd, that of the derivative residual (NaN also where its weight is 0).  A factor
+        of 0 under Tukey, or below 1 under Huber, flags an outlier."""
+        thetas = np.atleast_2d(_f64(thetas))
+        n, P = thetas.shape
+        if P != self.npar:
+            raise ValueError(f"thetas has {P} columns, the fit has {self.npar} free parameters")
+        out = {"phi": np.zeros(n), "phi_w": np.zeros(n), "nbad": np.zeros(n, np.int32), "ndown": np.zeros(n, np.int32)}
+        if factors:
+            out["b"] = np.zeros((n, self.nobs))
+            if getattr(self, "_deriv", False):
+                out["bd"] = np.zeros((n, self.nobs))
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        _libmod.check(self._lib.ucf_fit_loss_report(self._h, n, thetas.ctypes.data, ptr("phi"), ptr("phi_w"), ptr("nbad"), ptr("ndown"),
+                                                    ptr("b"), ptr("bd")))
+        return out
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.ucf_fit_destroy(self._h)
@@ -346,10 +410,19 @@ class Fit:
                                                   ptr("simd")))
         return out
 
-    def lm(self, theta0, cov: bool = True, **opt) -> dict:
+    def lm(self, theta0, cov: bool = True, loss=None, **opt) -> dict:
         """Levenberg-Marquardt from the starting points theta0 [nstarts][npar], all in one call; options as the fields of
         ucf_fit_options (max_iter, dlog, lambda0, lambda_up, lambda_down, tol_step, tol_phi).  Returns theta, phi, iters,
-        status (abi.FIT_*) per start and, unless cov=False, the covariance in ln(theta)."""
+        status (abi.FIT_*) per start and, unless cov=False, the covariance in ln(theta).  ``loss`` = (kind, c) applies for
+        this call only: the fit's own loss is put back afterwards, also when the call raises."""
+        if loss is not None:
+            kind, c = (loss, 0.0) if isinstance(loss, (str, int, np.integer)) else loss
+            before = self.get_loss()
+            self.set_loss(kind, c)
+            try:
+                return self.lm(theta0, cov=cov, **opt)
+            finally:
+                self.set_loss(*before)
         theta0 = np.atleast_2d(_f64(theta0))
         n, P = theta0.shape
         if P != self.npar:

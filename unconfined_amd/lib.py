@@ -48,6 +48,7 @@ EXPORTS = [
     "ucf_debug_ensemble_weighted",
     "ucf_field_worth", "ucf_worth_condition", "ucf_debug_field_worth",
     "ucf_field_yield", "ucf_debug_field_yield",
+    "ucf_fit_loss_terms", "ucf_fit_robust_scale", "ucf_fit_set_loss", "ucf_fit_get_loss", "ucf_fit_loss_report", "ucf_debug_fit_reduce_loss",
 ]
 
 
@@ -201,6 +202,14 @@ def load() -> C.CDLL:
     lib.ucf_debug_field_yield.argtypes = [C.c_int] * 4 + [vp] * 4 + [C.c_double] + [vp] * 7
     # every array may be NULL for a source or a call that does not read it: plain addresses
     lib.ucf_debug_fit_reduce.argtypes = ([C.c_int] * 4 + [C.c_double, C.c_longlong] + [vp] * 8 + [C.c_longlong, C.c_int] + [vp] * 7 + [vp] * 6)
+    # x, rho, b, scale and every output may be NULL: plain addresses
+    lib.ucf_fit_loss_terms.argtypes = [C.c_int, C.c_double, C.c_int, vp, vp, vp]
+    lib.ucf_fit_robust_scale.argtypes = [C.c_int, vp, vp]
+    lib.ucf_fit_set_loss.argtypes = [vp, C.c_int, C.c_double]
+    lib.ucf_fit_get_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double)]
+    lib.ucf_fit_loss_report.argtypes = [vp, C.c_int] + [vp] * 7
+    # kind, c, then the arguments of ucf_debug_fit_reduce, then ndown, b, bd
+    lib.ucf_debug_fit_reduce_loss.argtypes = [C.c_int, C.c_double] + lib.ucf_debug_fit_reduce.argtypes + [vp] * 3
     _lib = lib
     return lib
 
