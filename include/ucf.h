@@ -548,6 +548,86 @@ int ucf_fit_get_loss(const ucf_fit* fit, int* kind, double* c /*0.0 under UCF_LO
 int ucf_fit_loss_report(ucf_fit* fit, int nsets, const double* theta /*[nsets][npar]*/,
                         double* phi, double* phi_w, int* nbad, int* ndown, double* b, double* bd);
 
+/* Resampled fits.  cov of ucf_fit_lm is linearised and model-based; the honest spread of a fit comes from refitting on bootstrap or
+ * jackknife replicates of the data.  A replicate is a vector of integer multiplicities on the observations, and like a loss it is
+ * applied where the residuals are, inside fit_reduce_kernel: no evaluator launch is added per replicate, and several replicates
+ * reduced at the same parameter set read one evaluation.
+ *   mult         [nrep][nobs] unsigned short, in the caller's observation order; m = mult[rep][i] copies of observation i;
+ *   reduction r  one workgroup: the plans of parameter set set_of[r] (set_of NULL: r) under the multiplicities of replicate rep[r];
+ *                rep[r] == -1 (or rep NULL): every m = 1.  Every output is indexed by r.
+ * Per observation i, on top of the arithmetic of ucf_fit_set_loss (least squares runs as Huber with c = +inf, every factor 1.0),
+ * every operation rounded on its own, in the lane / butterfly / wave order of ucf_debug_fit_reduce, no floating-point atomics;
+ * `ok` is the counting rule stated there:
+ *     m == 0 (held out) and ok:  phi_out = phi_out + wr * wr;  where dweight_i > 0 also  phi_out = phi_out + wrd * wrd;  nheld++.
+ *              A held-out observation adds nothing else and is never counted in nbad; one that is not ok is in no count at all.
+ *     m > 0 and not ok:          nbad++          (once, not m times)
+ *     m > 0 and ok:              fm = (double)m;  (rho, b) of x = wr;  fb = fm * b;
+ *              phi = phi + fm * rho;  phi_w = phi_w + fb * (x * x);  bw_j = fb * wd_j;  g_j = g_j + bw_j * x;
+ *              A_jk = A_jk + bw_j * wd_k (j <= k);  ndown++ where b < 1.0 (once);  nuse += m;
+ *              then, where dweight_i > 0, the derivative term x = wrd with its own b by the same rules, also
+ *              phi_d = phi_d + fm * rho, and nuse_d += m.
+ *     sums per reduction:  phi | g | upper A | [phi_d] | phi_w | phi_out;   counts per reduction: nuse, nuse_d, nheld, ndown.
+ * Consequence: with every m = 1, fm * x == x exactly, so phi, g, A, phi_d, phi_w, nbad and ndown have the bits of the reduction
+ * under the fit's loss (ucf_fit_set_loss), and under least squares the bits of the plain one.
+ *
+ * ucf_fit_set_resample attaches mult to a fit made by any of the three constructors; NULL detaches (nrep is then not read).  The
+ * device buffer stays with the fit and is counted in ucf_fit_alloc_count when it grows.  A row with no positive entry is legal.
+ * Every existing entry (ucf_fit_evaluate, _joint, _objective, _lm, _loss_report) ignores the multiplicities and returns the bits it
+ * returns without them.  UCF_ERR_BAD_ARGUMENT before any GPU work: a NULL fit, nrep outside 1..65536, a row whose entries sum
+ * beyond 2^31 - 1 (the counts are int; the row is named). */
+int ucf_fit_set_resample(ucf_fit* fit, int nrep, const unsigned short* mult /*[nrep][nobs]; NULL: detach*/);
+/* One evaluation of the nsets (1 + 2 npar) plans that ucf_fit_evaluate makes of theta, then ONE reduction launch of nred workgroups.
+ * phi, phi_d, phi_w, phi_out [nred], g [nred][npar], A [nred][npar][npar] (full, symmetric), nbad [nred], counts [nred][4] = nuse,
+ * nuse_d, nheld, ndown.  Any output may be NULL.  On a fit without derivative data nuse_d is 0 and phi_d is refused.  A repeated
+ * call of the same size allocates nothing (ucf_fit_alloc_count).  UCF_ERR_BAD_ARGUMENT before any GPU work: the checks of
+ * ucf_fit_evaluate; nred outside 1..2^20; set_of NULL with nred > nsets; a set_of[r] outside 0..nsets-1; a rep[r] outside
+ * -1..nrep-1; a rep[r] != -1 on a fit without attached multiplicities; phi_d on a fit without derivative data. */
+int ucf_fit_evaluate_resampled(ucf_fit* fit, int nsets, const double* theta /*[nsets][npar]*/, double dlog,
+                               int nred, const int* set_of /*[nred]; NULL: r*/, const int* rep /*[nred]; NULL: all -1*/,
+                               double* phi, double* g, double* A, int* nbad, double* phi_d, double* phi_w, double* phi_out,
+                               int* counts /*[nred][4]*/);
+/* the same on the base plans only, through the npar = 0 instantiations (no dlog, g or A): what ucf_fit_lm_resampled runs at its
+ * trial points, and the cross-validation score phi_out of many replicates at one theta.  The same checks. */
+int ucf_fit_objective_resampled(ucf_fit* fit, int nsets, const double* theta /*[nsets][npar]*/,
+                                int nred, const int* set_of, const int* rep,
+                                double* phi, int* nbad, double* phi_d, double* phi_w, double* phi_out, int* counts);
+/* ucf_fit_lm with start s reduced under replicate rep[s] (set_of the identity): the same loop, not a copy -- the same steps,
+ * damping, stopping rules and status; accept and reject decisions use the replicate's phi; a start is UCF_FIT_NONFINITE_START
+ * where an observation with m > 0 is not finite at theta0.  From one more evaluation at the final point:
+ *   cov          = phi_w / (nuse + nuse_d - npar) A^-1 per start, NaN where the denominator is <= 0, A is singular, nbad > 0 or
+ *                the start was not finite: ucf_fit_lm's cov of the replicate's own weighted problem.  The spread that resampling
+ *                is for comes from the thetas over the replicates (ucf_fit_resample_cov), not from this matrix;
+ *   phi_out      [nstarts] the held-out sum of squares (the cross-validation score of a jackknife replicate), NaN for a start
+ *                that was not finite;  counts [nstarts][4], 0 there.
+ * cov, phi_out, counts: NULL ok.  With rep all -1 (or NULL) theta, phi, iters, status and cov have the bytes of ucf_fit_lm.  The
+ * checks of ucf_fit_lm, and a rep[s] outside -1..nrep-1 or != -1 without attached multiplicities, before any GPU work. */
+int ucf_fit_lm_resampled(ucf_fit* fit, int nstarts, const double* theta0, const int* rep /*[nstarts]; NULL: all -1*/,
+                         const ucf_fit_options* opt /*NULL = defaults*/,
+                         double* theta, double* phi, int* iters, int* status, double* cov, double* phi_out, int* counts);
+/* host only, no GPU, compiled without contraction: the block bootstrap.  block[i] is the block (well, time window) of observation i,
+ * in 0..nb-1 with every id used, nb = the largest id + 1; block NULL: block i = i (nb = nobs), the iid bootstrap.  Replicates in
+ * ascending order, each with nb draws; a draw is one step of the splitmix64 stream stated at ucf_field_ensemble_draw (state = seed,
+ * one stream for the whole call), then  k = (x * nb) >> 64  as a 128-bit unsigned product, and every observation of block k gains
+ * 1.  mult [nrep][nobs] (NULL: only *nblock is set);  *nblock = nb (NULL ok).  UCF_ERR_BAD_ARGUMENT: nobs outside 1..2^24, nrep
+ * outside 1..65536, a block id that is negative or >= nobs, an id below the largest that no observation has, a count beyond 65535
+ * (the replicate is named). */
+int ucf_fit_resample_blocks(int nobs, const int* block /*[nobs]; NULL: iid*/, int nrep, unsigned long long seed,
+                            unsigned short* mult /*[nrep][nobs]*/, int* nblock);
+/* host only, no GPU: delete-one-block.  Row b of mult [nb][nobs] is 0 on the observations of block b and 1 elsewhere: leave one
+ * well out, or k-fold cross-validation with fold ids as blocks.  block NULL: block i = i.  The checks of ucf_fit_resample_blocks on
+ * nobs and block; a NULL mult. */
+int ucf_fit_resample_jackknife(int nobs, const int* block /*[nobs]; NULL: i*/, unsigned short* mult /*[nb][nobs]*/);
+/* host only, no GPU, compiled without contraction: mean and covariance in ln theta over the n replicates r with use[r] != 0 (use
+ * NULL: all), every operation rounded on its own, every sum from +0.0 in ascending r:
+ *     x_rj = log(theta[r][j]);   s_j = s_j + x_rj;   mean_j = s_j / (double)n;
+ *     c_jk = c_jk + (x_rj - mean_j) * (x_rk - mean_k)   for j <= k, mirrored;
+ *     UCF_RESAMPLE_BOOTSTRAP:  cov_jk = c_jk / (double)(n - 1);     UCF_RESAMPLE_JACKKNIFE:  cov_jk = c_jk * ((double)(n - 1) / (double)n)
+ * mean [npar], cov [npar][npar], *nused = n; each NULL ok.  UCF_ERR_BAD_ARGUMENT: a kind outside the enum, nrep < 1, npar outside
+ * 1..UCF_FIT_MAX_PAR, a NULL theta, n < 2, a used theta that is not positive and finite (replicate and parameter named). */
+enum { UCF_RESAMPLE_BOOTSTRAP = 0, UCF_RESAMPLE_JACKKNIFE = 1 };
+int ucf_fit_resample_cov(int kind, int nrep, int npar, const double* theta /*[nrep][npar]*/, const int* use /*[nrep]; NULL: all*/,
+                         double* mean, double* cov, int* nused);
+
 /* ---- well fields: the drawdown of several pumping wells -- wells that start at different times, image wells for a river or an
  * outcrop -- is the sum over wells of q_j h(t - t0_j, |x - x_j|, z).  All wells share the plan's aquifer, well geometry and
  * time behaviour; they differ in position (xw, yw), rate factor qw (times the plan's Q; negative: injection or a constant-head
@@ -1032,6 +1112,23 @@ int ucf_debug_fit_reduce_loss(int kind, double c, int source, int npar, int nset
                               const double* q, const double* tfac /*[nref]*/, const int* first /*[nobs + 1]*/,
                               double* sums, int* nbad, double* J, double* sim, double* Jd, double* simd,
                               int* ndown, double* b, double* bd);
+/* The RESAMPLE instantiations of the kernel (ucf_fit_set_resample states the arithmetic) through the production launcher on caller
+ * data: the arguments of ucf_debug_fit_reduce_loss -- kind 0 (UCF_LOSS_L2) is allowed here and runs as Huber with c = +inf, c is
+ * then not read -- without J, sim, Jd, simd, b and bd, which belong to a parameter set and not to a reduction, plus mult
+ * [nrep][nobs], nred, set_of [nred] (NULL: r) and rep [nred] (NULL: all -1).  One workgroup per reduction.  sums
+ * [nred][1 + npar + npar (npar+1) / 2 (+ 1 with dh) + 2] = phi | g | upper A | [phi_d] | phi_w | phi_out;  nbad [nred];  counts
+ * [nred][4] = nuse, nuse_d, nheld, ndown.  The validation of ucf_debug_fit_reduce, which needs no GPU, and: kind outside 0..2, c not
+ * positive and finite under kinds 1 and 2, nrep outside 0..65536 (0: no mult), a NULL mult with nrep > 0, a row of mult that sums
+ * beyond 2^31 - 1, nred outside 1..2^16, set_of NULL with nred > nsets, a set_of[r] outside 0..nsets-1, a rep[r] outside
+ * -1..nrep-1, a NULL sums, nbad or counts.  Then UCF_ERR_NO_DEVICE without a device. */
+int ucf_debug_fit_reduce_resampled(int kind, double c, int source, int npar, int nsets, int nobs, double two_dlog,
+                                   long long nh, const double* h, const double* dh /*NULL ok*/, const double* Hc /*[nplans]*/,
+                                   const double* obs, const double* w, const double* dobs, const double* wd /*[nobs]*/,
+                                   const int* slot /*[nobs]*/, long long plan_stride,
+                                   int nref, const long long* prefix, const long long* stride, const int* at, const int* count /*[nref]*/,
+                                   const double* q, const double* tfac /*[nref]*/, const int* first /*[nobs + 1]*/,
+                                   int nrep, const unsigned short* mult, int nred, const int* set_of, const int* rep,
+                                   double* sums, int* nbad, int* counts);
 /* Host only: the nwell real wells followed by their mirror images in the straight line a x + b y = c (xo, yo, qo, t0o
  * [2 nwell]).  An image has q = +q for a no-flow boundary (kind 0), -q for a constant-head boundary (kind 1), and the t0 of its
  * real well.  One boundary only (two parallel boundaries need an infinite image series).  UCF_ERR_BAD_ARGUMENT: a = b = 0, a

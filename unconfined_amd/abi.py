@@ -28,6 +28,9 @@ FIT_SLOTS, FIT_NETWORK, FIT_FIELD = range(3)
 # loss of a fit (enum UCF_LOSS_* of include/ucf.h: ucf_fit_set_loss)
 LOSS_L2, LOSS_HUBER, LOSS_TUKEY = range(3)
 LOSS_KINDS = {"l2": LOSS_L2, "huber": LOSS_HUBER, "tukey": LOSS_TUKEY}
+# kind of ucf_fit_resample_cov (enum UCF_RESAMPLE_*)
+RESAMPLE_BOOTSTRAP, RESAMPLE_JACKKNIFE = range(2)
+RESAMPLE_KINDS = {"bootstrap": RESAMPLE_BOOTSTRAP, "jackknife": RESAMPLE_JACKKNIFE}
 UCF_ERR_BAD_ARGUMENT, UCF_ERR_NO_DEVICE, UCF_ERR_SINGULAR = -11, -12, -16
 
 

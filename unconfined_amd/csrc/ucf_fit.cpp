@@ -74,11 +74,15 @@ struct ucf_fit {
     int loss = UCF_LOSS_L2;
     double loss_c = 0.0;
     ucf_buffer b_ndown, b_bfac, b_bdfac;
+    // resampling (ucf_fit_set_resample): nrep rows of nobs multiplicities on the device, 0 when detached (the buffer stays); what
+    // a resampled reduction reads and writes per reduction is grown on demand
+    int nrep = 0;
+    ucf_buffer b_mult, b_setof, b_rep, b_counts;
     // every device buffer above: the one list (ucf_fit_destroy frees through it)
-    std::array<ucf_buffer*, 24> buffers()
+    std::array<ucf_buffer*, 28> buffers()
     {
         return {{&b_slot, &b_obs, &b_w, &b_t, &b_r, &b_s, &b_h, &b_d, &b_hc, &b_sums, &b_nbad, &b_J, &b_sim, &b_ref, &b_term, &b_first,
-                 &b_dobs, &b_wd, &b_tfac, &b_Jd, &b_simd, &b_ndown, &b_bfac, &b_bdfac}};
+                 &b_dobs, &b_wd, &b_tfac, &b_Jd, &b_simd, &b_ndown, &b_bfac, &b_bdfac, &b_mult, &b_setof, &b_rep, &b_counts}};
     }
     std::vector<double> st_t;              // staging of one plan: its tD over all groups ...
     std::vector<int> st_s;                 // ... and their split vector
@@ -422,15 +426,43 @@ struct fit_loss_out {
     double *b = nullptr, *bd = nullptr;
 };
 
+// A resampled reduction (ucf_fit_set_resample): nred reductions in place of one per set.  set_of NULL: the identity (nred <=
+// nsets), rep NULL: all -1; both have been checked by fit_resample_check.  phi, g, A, nbad, phi_d of fit_evaluate are then per
+// reduction, as are phi_w, phi_out [nred] and counts [nred][4] here; each may be NULL.
+struct fit_resample_io {
+    int nred = 0;
+    const int *set_of = nullptr, *rep = nullptr;
+    double *phi_w = nullptr, *phi_out = nullptr;
+    int* counts = nullptr;
+};
+
+// the checks of a resampled call that need the fit only: before any GPU work
+int fit_resample_check(const ucf_fit* f, int nsets, int nred, const int* set_of, const int* rep)
+{
+    if (nred < 1 || nred > (1 << 20)) return fail(UCF_ERR_BAD_ARGUMENT, "nred=%d outside 1..2^20", nred);
+    if (!set_of && nred > nsets) return fail(UCF_ERR_BAD_ARGUMENT, "set_of is NULL (reduction r reads set r), but nred=%d exceeds nsets=%d", nred, nsets);
+    for (int r = 0; r < nred; r++) {
+        if (set_of && (set_of[r] < 0 || set_of[r] >= nsets)) return fail(UCF_ERR_BAD_ARGUMENT, "set_of[%d]=%d outside 0..%d", r, set_of[r], nsets - 1);
+        if (!rep || rep[r] == -1) continue;
+        if (f->nrep < 1) return fail(UCF_ERR_BAD_ARGUMENT, "rep[%d]=%d, but the fit has no multiplicities attached (ucf_fit_set_resample)", r, rep[r]);
+        if (rep[r] < -1 || rep[r] >= f->nrep) return fail(UCF_ERR_BAD_ARGUMENT, "rep[%d]=%d outside -1..%d", r, rep[r], f->nrep - 1);
+    }
+    return UCF_OK;
+}
+
 // jac != 0: base and perturbed plans, everything; jac == 0: the base plans only, phi and nbad (the trial points of ucf_fit_lm).
 // On a fit with derivative data the sums are the joint ones and phi_d, Jd, simd_all may be asked for; without, they are NULL.
 // The fit's loss decides the instantiation; on a least-squares fit with lo == NULL nothing differs from a fit without one.
 int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int jac, double* phi, double* g, double* A, int* nbad,
                  double* J, double* sim_all, double* phi_d = nullptr, double* Jd = nullptr, double* simd_all = nullptr,
-                 const fit_loss_out* lo = nullptr)
+                 const fit_loss_out* lo = nullptr, const fit_resample_io* rs = nullptr)
 {
     if (!f || !theta) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (nsets < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nsets=%d: at least one parameter set", nsets);
+    if (rs) {
+        int rc = fit_resample_check(f, nsets, rs->nred, rs->set_of, rs->rep);
+        if (rc) return rc;
+    }
     if (jac && (!(dlog > 0.0) || !std::isfinite(dlog))) return fail(UCF_ERR_BAD_ARGUMENT, "dlog=%g must be positive and finite", dlog);
     const int npar = f->npar, per = jac ? 1 + 2 * npar : 1, nobs = f->nobs, nz = f->nz;
     if ((long long)nsets * per > (1 << 20)) return fail(UCF_ERR_BAD_ARGUMENT, "%d sets x %d plans: too many plans for one call", nsets, per);
@@ -470,16 +502,22 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     const bool joint = f->deriv;
     const fit_loss_out none;
     const fit_loss_out& L = lo ? *lo : none;
-    const bool robust = f->loss != UCF_LOSS_L2 || L.ndown || L.b || L.bd;
+    // a resampled reduction always carries phi_w (least squares runs as Huber with c = +inf) and one more sum, phi_out
+    const bool robust = rs || f->loss != UCF_LOSS_L2 || L.ndown || L.b || L.bd;
     const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_;
-    const size_t nsum = (size_t)(joint ? ucf_fit_joint_nsums(jac ? npar : 0) : ucf_fit_nsums(jac ? npar : 0)) + (robust ? 1 : 0);
+    const size_t nsum = (size_t)(joint ? ucf_fit_joint_nsums(jac ? npar : 0) : ucf_fit_nsums(jac ? npar : 0)) + (robust ? 1 : 0) + (rs ? 1 : 0);
+    const int nout = rs ? rs->nred : nsets;        // workgroups of the reduction: what sums and nbad are indexed by
     // points and (point, depth) values that are launched: every depth at every observation, or the network's blocks
     const size_t ptot = (size_t)nplans * (f->is_network() ? f->net_pts : np_), vtot = (size_t)nplans * (f->is_network() ? f->net_vals : np_ * nz);
     int rc;
     if ((rc = grow_buffer(f->b_t, sizeof(double) * ptot, "tD", f->n_alloc)) || (rc = grow_buffer(f->b_r, sizeof(double) * ptot, "rD", f->n_alloc)) ||
         (rc = grow_buffer(f->b_s, sizeof(int) * ptot, "sv", f->n_alloc)) || (rc = grow_buffer(f->b_h, sizeof(double) * vtot, "h", f->n_alloc)) ||
         (rc = grow_buffer(f->b_d, sizeof(double) * vtot, "dh", f->n_alloc)) || (rc = grow_buffer(f->b_hc, sizeof(double) * nplans, "Hc", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_sums, sizeof(double) * nsets * nsum, "sums", f->n_alloc)) || (rc = grow_buffer(f->b_nbad, sizeof(int) * nsets, "nbad", f->n_alloc)))
+        (rc = grow_buffer(f->b_sums, sizeof(double) * nout * nsum, "sums", f->n_alloc)) || (rc = grow_buffer(f->b_nbad, sizeof(int) * nout, "nbad", f->n_alloc)))
+        return rc;
+    if (rs && ((rc = grow_buffer(f->b_counts, sizeof(int) * 4 * nout, "counts", f->n_alloc)) ||
+               (rs->set_of && (rc = grow_buffer(f->b_setof, sizeof(int) * nout, "set_of", f->n_alloc))) ||
+               (rs->rep && (rc = grow_buffer(f->b_rep, sizeof(int) * nout, "rep", f->n_alloc)))))
         return rc;
     if (J && jac && (rc = grow_buffer(f->b_J, sizeof(double) * nsets * np_ * npar, "J", f->n_alloc))) return rc;
     if (sim_all && (rc = grow_buffer(f->b_sim, sizeof(double) * tot, "sim_all", f->n_alloc))) return rc;
@@ -511,12 +549,20 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     ra.d_Jd = (Jd && jac) ? (double*)f->b_Jd.p : nullptr; ra.d_simd = simd_all ? (double*)f->b_simd.p : nullptr;
     ra.loss = f->loss; ra.loss_c = f->loss_c;
     ra.d_ndown = L.ndown ? (int*)f->b_ndown.p : nullptr; ra.d_b = L.b ? (double*)f->b_bfac.p : nullptr; ra.d_bd = L.bd ? (double*)f->b_bdfac.p : nullptr;
+    if (rs) {
+        if (rs->set_of) HIP_TRY(hipMemcpy(f->b_setof.p, rs->set_of, sizeof(int) * nout, hipMemcpyHostToDevice));
+        if (rs->rep) HIP_TRY(hipMemcpy(f->b_rep.p, rs->rep, sizeof(int) * nout, hipMemcpyHostToDevice));
+        ra.nred = nout; ra.d_mult = f->nrep > 0 ? (const unsigned short*)f->b_mult.p : nullptr;
+        ra.d_set_of = rs->set_of ? (const int*)f->b_setof.p : nullptr; ra.d_rep = rs->rep ? (const int*)f->b_rep.p : nullptr;
+        ra.d_counts = (int*)f->b_counts.p;
+    }
     rc = ucf_fit_launch_reduce(&ra, nullptr);
     if (rc) return fail(rc, "fit reduction kernel launch failed");
     HIP_TRY(hipStreamSynchronize(nullptr));
-    f->h_sums.resize(nsets * nsum);
-    HIP_TRY(hipMemcpy(f->h_sums.data(), f->b_sums.p, sizeof(double) * nsets * nsum, hipMemcpyDeviceToHost));
-    if (nbad) HIP_TRY(hipMemcpy(nbad, f->b_nbad.p, sizeof(int) * nsets, hipMemcpyDeviceToHost));
+    f->h_sums.resize(nout * nsum);
+    HIP_TRY(hipMemcpy(f->h_sums.data(), f->b_sums.p, sizeof(double) * nout * nsum, hipMemcpyDeviceToHost));
+    if (nbad) HIP_TRY(hipMemcpy(nbad, f->b_nbad.p, sizeof(int) * nout, hipMemcpyDeviceToHost));
+    if (rs && rs->counts) HIP_TRY(hipMemcpy(rs->counts, f->b_counts.p, sizeof(int) * 4 * nout, hipMemcpyDeviceToHost));
     if (J && jac) HIP_TRY(hipMemcpy(J, f->b_J.p, sizeof(double) * nsets * np_ * npar, hipMemcpyDeviceToHost));
     if (sim_all) HIP_TRY(hipMemcpy(sim_all, f->b_sim.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
     if (Jd && jac) HIP_TRY(hipMemcpy(Jd, f->b_Jd.p, sizeof(double) * nsets * np_ * npar, hipMemcpyDeviceToHost));
@@ -524,11 +570,15 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
     if (L.ndown) HIP_TRY(hipMemcpy(L.ndown, f->b_ndown.p, sizeof(int) * nsets, hipMemcpyDeviceToHost));
     if (L.b) HIP_TRY(hipMemcpy(L.b, f->b_bfac.p, sizeof(double) * nsets * np_, hipMemcpyDeviceToHost));
     if (L.bd) HIP_TRY(hipMemcpy(L.bd, f->b_bdfac.p, sizeof(double) * nsets * np_, hipMemcpyDeviceToHost));
-    for (int s = 0; s < nsets; s++) {
+    for (int s = 0; s < nout; s++) {
         const double* v = &f->h_sums[s * nsum];
         if (phi) phi[s] = v[0];
-        if (phi_d) phi_d[s] = v[nsum - 1 - (robust ? 1 : 0)];
-        if (L.phi_w) L.phi_w[s] = robust ? v[nsum - 1] : v[0];      // least squares: every factor is 1.0
+        if (phi_d) phi_d[s] = v[nsum - 1 - (robust ? 1 : 0) - (rs ? 1 : 0)];
+        if (rs) {
+            if (rs->phi_w) rs->phi_w[s] = v[nsum - 2];
+            if (rs->phi_out) rs->phi_out[s] = v[nsum - 1];
+        }
+        if (L.phi_w && !rs) L.phi_w[s] = robust ? v[nsum - 1] : v[0];      // least squares: every factor is 1.0
         if (!jac) continue;
         if (g) for (int j = 0; j < npar; j++) g[(size_t)s * npar + j] = v[1 + j];
         if (A) {
@@ -991,11 +1041,21 @@ int ucf_fit_default_options(ucf_fit_options* opt)
     return UCF_OK;
 }
 
-int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_options* opt_in, double* theta, double* phi, int* iters,
-               int* status, double* cov)
+}  // extern "C"
+
+// ucf_fit_lm and ucf_fit_lm_resampled: one loop.  resampled == false: every evaluation is the plain fit_evaluate (rep, phi_out,
+// counts are not read).  resampled == true: start s is reduced under replicate rep[s] (NULL: -1) with set_of the identity, in
+// every evaluation of the loop and in the final one, whose phi_w and counts give cov.
+static int fit_lm_core(ucf_fit* f, int nstarts, const double* theta0, bool resampled, const int* rep, const ucf_fit_options* opt_in, double* theta,
+                       double* phi, int* iters, int* status, double* cov, double* phi_out, int* counts)
 {
     if (!f || !theta0 || !theta || !phi || !iters || !status) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (nstarts < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nstarts=%d: at least one start", nstarts);
+    if (resampled) {
+        if (nstarts > (1 << 20)) return fail(UCF_ERR_BAD_ARGUMENT, "nstarts=%d: at most 2^20 resampled starts", nstarts);
+        int rc0 = fit_resample_check(f, nstarts, nstarts, nullptr, rep);
+        if (rc0) return rc0;
+    }
     ucf_fit_options opt;
     (void)ucf_fit_default_options(&opt);
     if (opt_in) opt = *opt_in;
@@ -1017,8 +1077,17 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
     }
     std::vector<int> idx;
     std::vector<double> th, ph, gg, AA;
-    std::vector<int> nb;
+    std::vector<int> nb, rp;
     int rc = UCF_OK;
+    // the replicates of the starts in idx, in its order (resampled only; set_of is the identity over the sets of one evaluation)
+    fit_resample_io rs;
+    auto replicates = [&]() -> const fit_resample_io* {
+        if (!resampled) return nullptr;
+        rp.resize(idx.size());
+        for (size_t q = 0; q < idx.size(); q++) rp[q] = rep ? rep[idx[q]] : -1;
+        rs.nred = (int)idx.size(); rs.rep = rp.data();
+        return &rs;
+    };
     for (;;) {
         // 1. objective, gradient and normal equations where the point has moved (one call for all of them)
         idx.clear();
@@ -1027,7 +1096,8 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
             const int n = (int)idx.size();
             th.resize((size_t)n * P); ph.resize(n); gg.resize((size_t)n * P); AA.resize(n * PP); nb.resize(n);
             for (int q = 0; q < n; q++) for (int j = 0; j < P; j++) th[(size_t)q * P + j] = theta[(size_t)idx[q] * P + j];
-            rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), gg.data(), AA.data(), nb.data(), nullptr, nullptr);
+            rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), gg.data(), AA.data(), nb.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, replicates());
             if (rc) return rc;
             for (int q = 0; q < n; q++) {
                 const int s = idx[q];
@@ -1059,7 +1129,8 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
         bool finite_trial = true;
         for (double v : th) finite_trial = finite_trial && std::isfinite(v) && v > 0.0;
         if (finite_trial) {
-            rc = fit_evaluate(f, n, th.data(), opt.dlog, 0, ph.data(), nullptr, nullptr, nb.data(), nullptr, nullptr);
+            rc = fit_evaluate(f, n, th.data(), opt.dlog, 0, ph.data(), nullptr, nullptr, nb.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, replicates());
             if (rc != UCF_OK && rc != UCF_ERR_BAD_ARGUMENT && rc != UCF_ERR_HIP && rc != UCF_ERR_NOMEM && rc != UCF_ERR_NO_DEVICE) finite_trial = false;   // a trial outside the model's range: rejected below
             else if (rc) return rc;
         }
@@ -1085,28 +1156,43 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
             else if (iters[s] >= opt.max_iter) { status[s] = UCF_FIT_MAX_ITER; active[s] = 0; }
         }
     }
-    if (cov) {
+    if (resampled) {
+        if (phi_out) for (int s = 0; s < nstarts; s++) phi_out[s] = NAN;
+        if (counts) for (int i = 0; i < 4 * nstarts; i++) counts[i] = 0;
+    }
+    if (cov || (resampled && (phi_out || counts))) {
         // cov = phi / (nobs + nd - npar) A^-1 at the final point (NaN where A is singular, the start was not finite or no degree
-        // of freedom is left); nd = derivative data with a positive weight, 0 on a fit without
-        for (size_t i = 0; i < nstarts * PP; i++) cov[i] = NAN;
+        // of freedom is left); nd = derivative data with a positive weight, 0 on a fit without.  Resampled: phi_w / (nuse + nuse_d -
+        // npar) A^-1 with the sums and counts of the start's replicate, from this evaluation, which also gives phi_out and counts
+        if (cov) for (size_t i = 0; i < nstarts * PP; i++) cov[i] = NAN;
         idx.clear();
         for (int s = 0; s < nstarts; s++) if (status[s] != UCF_FIT_NONFINITE_START) idx.push_back(s);
-        const int dof = f->nobs + (f->deriv ? f->nd : 0) - P;
-        if (!idx.empty() && dof > 0) {
+        const int dof_all = f->nobs + (f->deriv ? f->nd : 0) - P;
+        if (!idx.empty() && (resampled || dof_all > 0)) {
             const int n = (int)idx.size();
             th.resize((size_t)n * P); ph.resize(n); AA.resize(n * PP); nb.resize(n);
             for (int q = 0; q < n; q++) for (int j = 0; j < P; j++) th[(size_t)q * P + j] = theta[(size_t)idx[q] * P + j];
             // under a robust loss the variance factor is phi_w of this evaluation: the weighted least-squares problem that the
             // final factors define (include/ucf.h); under least squares it stays the phi the iteration ended with
-            const bool robust = f->loss != UCF_LOSS_L2;
-            std::vector<double> pw(robust ? n : 0);
+            const bool robust = resampled || f->loss != UCF_LOSS_L2;
+            std::vector<double> pw(robust ? n : 0), po(resampled ? n : 0);
+            std::vector<int> cnt(resampled ? 4 * (size_t)n : 0);
             fit_loss_out lo;
             lo.phi_w = robust ? pw.data() : nullptr;
+            const fit_resample_io* fin = replicates();
+            if (fin) { rs.phi_w = pw.data(); rs.phi_out = po.data(); rs.counts = cnt.data(); }
             rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), nullptr, AA.data(), nb.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                              robust ? &lo : nullptr);
+                              robust && !resampled ? &lo : nullptr, fin);
             if (rc) return rc;
             for (int q = 0; q < n; q++) {
                 const int s = idx[q];
+                if (resampled) {
+                    if (phi_out) phi_out[s] = po[q];
+                    if (counts) std::memcpy(&counts[4 * (size_t)s], &cnt[4 * (size_t)q], sizeof(int) * 4);
+                }
+                if (!cov) continue;
+                const int dof = resampled ? cnt[4 * (size_t)q] + cnt[4 * (size_t)q + 1] - P : dof_all;
+                if (dof <= 0) continue;
                 double e[UCF_FIT_MAX_PAR], col[UCF_FIT_MAX_PAR];
                 bool good = nb[q] == 0;
                 for (int j = 0; j < P && good; j++) {
@@ -1118,6 +1204,171 @@ int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_opti
             }
         }
     }
+    return UCF_OK;
+}
+
+// ---- the host side of resampling (include/ucf.h states the arithmetic; this file is compiled without contraction)
+namespace {
+// nobs and the block ids of ucf_fit_resample_blocks / _jackknife; *nb = the number of blocks
+int resample_check_blocks(int nobs, const int* block, int* nb)
+{
+    if (nobs < 1 || nobs > (1 << 24)) return fail(UCF_ERR_BAD_ARGUMENT, "nobs=%d outside 1..2^24", nobs);
+    if (!block) { *nb = nobs; return UCF_OK; }
+    int top = -1;
+    for (int i = 0; i < nobs; i++) {
+        if (block[i] < 0 || block[i] >= nobs) return fail(UCF_ERR_BAD_ARGUMENT, "block[%d]=%d outside 0..%d", i, block[i], nobs - 1);
+        top = std::max(top, block[i]);
+    }
+    std::vector<char> seen((size_t)top + 1, 0);
+    for (int i = 0; i < nobs; i++) seen[block[i]] = 1;
+    for (int b = 0; b <= top; b++)
+        if (!seen[b]) return fail(UCF_ERR_BAD_ARGUMENT, "block id %d is used by no observation (the ids are 0..%d)", b, top);
+    *nb = top + 1;
+    return UCF_OK;
+}
+}  // namespace
+
+// a row of multiplicities must sum within an int: nuse and nuse_d of the reduction are int
+int ucf_host::fit_resample_check_rows(int nrep, int nobs, const unsigned short* mult)
+{
+    for (int r = 0; r < nrep; r++) {
+        long long sum = 0;
+        for (int i = 0; i < nobs; i++) sum += mult[(size_t)r * nobs + i];
+        if (sum > 0x7fffffffLL) return fail(UCF_ERR_BAD_ARGUMENT, "replicate %d: its multiplicities sum to %lld, beyond 2^31 - 1", r, sum);
+    }
+    return UCF_OK;
+}
+
+extern "C" {
+
+int ucf_fit_lm(ucf_fit* f, int nstarts, const double* theta0, const ucf_fit_options* opt_in, double* theta, double* phi, int* iters,
+               int* status, double* cov)
+{
+    return fit_lm_core(f, nstarts, theta0, false, nullptr, opt_in, theta, phi, iters, status, cov, nullptr, nullptr);
+}
+
+int ucf_fit_lm_resampled(ucf_fit* f, int nstarts, const double* theta0, const int* rep, const ucf_fit_options* opt_in, double* theta, double* phi,
+                         int* iters, int* status, double* cov, double* phi_out, int* counts)
+{
+    return fit_lm_core(f, nstarts, theta0, true, rep, opt_in, theta, phi, iters, status, cov, phi_out, counts);
+}
+
+int ucf_fit_set_resample(ucf_fit* f, int nrep, const unsigned short* mult)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL fit");
+    if (!mult) { f->nrep = 0; return UCF_OK; }
+    if (nrep < 1 || nrep > 65536) return fail(UCF_ERR_BAD_ARGUMENT, "nrep=%d outside 1..65536", nrep);
+    int rc = fit_resample_check_rows(nrep, f->nobs, mult);
+    if (rc) return rc;
+    device_switch dg(f->device);
+    const size_t bytes = sizeof(unsigned short) * (size_t)nrep * (size_t)f->nobs;
+    if ((rc = grow_buffer(f->b_mult, bytes, "multiplicities", f->n_alloc))) return rc;
+    f->nrep = 0;                           // until everything is in place
+    HIP_TRY(hipMemcpy(f->b_mult.p, mult, bytes, hipMemcpyHostToDevice));
+    f->nrep = nrep;
+    return UCF_OK;
+}
+
+int ucf_fit_evaluate_resampled(ucf_fit* f, int nsets, const double* theta, double dlog, int nred, const int* set_of, const int* rep, double* phi,
+                               double* g, double* A, int* nbad, double* phi_d, double* phi_w, double* phi_out, int* counts)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (phi_d && !f->deriv) return fail(UCF_ERR_BAD_ARGUMENT, "phi_d is asked for, but the fit has no derivative data (ucf_fit_set_derivative)");
+    fit_resample_io rs;
+    rs.nred = nred; rs.set_of = set_of; rs.rep = rep; rs.phi_w = phi_w; rs.phi_out = phi_out; rs.counts = counts;
+    return fit_evaluate(f, nsets, theta, dlog, 1, phi, g, A, nbad, nullptr, nullptr, phi_d, nullptr, nullptr, nullptr, &rs);
+}
+
+int ucf_fit_objective_resampled(ucf_fit* f, int nsets, const double* theta, int nred, const int* set_of, const int* rep, double* phi, int* nbad,
+                                double* phi_d, double* phi_w, double* phi_out, int* counts)
+{
+    if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
+    if (phi_d && !f->deriv) return fail(UCF_ERR_BAD_ARGUMENT, "phi_d is asked for, but the fit has no derivative data (ucf_fit_set_derivative)");
+    fit_resample_io rs;
+    rs.nred = nred; rs.set_of = set_of; rs.rep = rep; rs.phi_w = phi_w; rs.phi_out = phi_out; rs.counts = counts;
+    return fit_evaluate(f, nsets, theta, 0.0, 0, phi, nullptr, nullptr, nbad, nullptr, nullptr, phi_d, nullptr, nullptr, nullptr, &rs);
+}
+
+int ucf_fit_resample_blocks(int nobs, const int* block, int nrep, unsigned long long seed, unsigned short* mult, int* nblock)
+{
+    int nb = 0;
+    int rc = resample_check_blocks(nobs, block, &nb);
+    if (rc) return rc;
+    if (nblock) *nblock = nb;
+    if (!mult) return UCF_OK;
+    if (nrep < 1 || nrep > 65536) return fail(UCF_ERR_BAD_ARGUMENT, "nrep=%d outside 1..65536", nrep);
+    std::vector<int> drawn((size_t)nb);
+    unsigned long long state = seed;
+    for (int r = 0; r < nrep; r++) {
+        std::fill(drawn.begin(), drawn.end(), 0);
+        for (int d = 0; d < nb; d++) {
+            state += 0x9E3779B97F4A7C15ULL;
+            unsigned long long x = state;
+            x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+            x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+            x = x ^ (x >> 31);
+            drawn[(size_t)(((unsigned __int128)x * (unsigned __int128)(unsigned long long)nb) >> 64)]++;
+        }
+        for (int b = 0; b < nb; b++)
+            if (drawn[b] > 65535) return fail(UCF_ERR_BAD_ARGUMENT, "replicate %d: block %d was drawn %d times, beyond 65535", r, b, drawn[b]);
+        for (int i = 0; i < nobs; i++) mult[(size_t)r * nobs + i] = (unsigned short)drawn[block ? block[i] : i];
+    }
+    return UCF_OK;
+}
+
+int ucf_fit_resample_jackknife(int nobs, const int* block, unsigned short* mult)
+{
+    int nb = 0;
+    int rc = resample_check_blocks(nobs, block, &nb);
+    if (rc) return rc;
+    if (!mult) return fail(UCF_ERR_BAD_ARGUMENT, "NULL mult");
+    for (int b = 0; b < nb; b++)
+        for (int i = 0; i < nobs; i++) mult[(size_t)b * nobs + i] = (block ? block[i] : i) == b ? 0 : 1;
+    return UCF_OK;
+}
+
+int ucf_fit_resample_cov(int kind, int nrep, int npar, const double* theta, const int* use, double* mean, double* cov, int* nused)
+{
+    if (nused) *nused = 0;
+    if (kind != UCF_RESAMPLE_BOOTSTRAP && kind != UCF_RESAMPLE_JACKKNIFE)
+        return fail(UCF_ERR_BAD_ARGUMENT, "kind=%d is no kind of resampling (UCF_RESAMPLE_BOOTSTRAP 0, UCF_RESAMPLE_JACKKNIFE 1)", kind);
+    if (nrep < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nrep=%d: at least one replicate", nrep);
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (!theta) return fail(UCF_ERR_BAD_ARGUMENT, "NULL theta");
+    int n = 0;
+    for (int r = 0; r < nrep; r++) {
+        if (use && !use[r]) continue;
+        n++;
+        for (int j = 0; j < npar; j++) {
+            const double v = theta[(size_t)r * npar + j];
+            if (!(v > 0.0) || !std::isfinite(v)) return fail(UCF_ERR_BAD_ARGUMENT, "replicate %d: parameter %d = %g must be positive and finite", r, j, v);
+        }
+    }
+    if (n < 2) return fail(UCF_ERR_BAD_ARGUMENT, "%d replicates in use: at least two", n);
+    if (nused) *nused = n;
+    std::vector<double> x((size_t)nrep * npar);
+    double m[UCF_FIT_MAX_PAR];
+    for (int j = 0; j < npar; j++) {
+        double s = 0.0;
+        for (int r = 0; r < nrep; r++) {
+            if (use && !use[r]) continue;
+            x[(size_t)r * npar + j] = std::log(theta[(size_t)r * npar + j]);
+            s = s + x[(size_t)r * npar + j];
+        }
+        m[j] = s / (double)n;
+        if (mean) mean[j] = m[j];
+    }
+    if (!cov) return UCF_OK;
+    for (int j = 0; j < npar; j++)
+        for (int k = j; k < npar; k++) {
+            double c = 0.0;
+            for (int r = 0; r < nrep; r++) {
+                if (use && !use[r]) continue;
+                c = c + (x[(size_t)r * npar + j] - m[j]) * (x[(size_t)r * npar + k] - m[k]);
+            }
+            const double v = kind == UCF_RESAMPLE_BOOTSTRAP ? c / (double)(n - 1) : c * ((double)(n - 1) / (double)n);
+            cov[(size_t)j * npar + k] = cov[(size_t)k * npar + j] = v;
+        }
     return UCF_OK;
 }
 

@@ -64,12 +64,23 @@ struct ucf_fit_reduce_args {
     double *d_b, *d_bd;                    // [nsets][nobs] factor of the drawdown / derivative residual under the base plan, NaN
                                            // where the observation does not count (d_bd: or has wd == 0); each may be NULL;
                                            // d_bd needs d_dh
+    // Resampling (include/ucf.h, ucf_fit_set_resample).  nred == 0: none, everything as above.  nred >= 1: the RESAMPLE
+    // instantiation runs, one workgroup per REDUCTION r = 0 .. nred-1, which reads the plans of set d_set_of[r] (NULL: r, then
+    // nred <= nsets) under the multiplicities d_mult[d_rep[r]][.] (d_rep NULL or d_rep[r] == -1: every m = 1), with the loss above
+    // (least squares: Huber with c = +inf).  d_sums [nred][.. | phi_w | phi_out] is two entries longer than the plain one, d_nbad
+    // is [nred].  d_J, d_sim, d_Jd, d_simd, d_ndown, d_b, d_bd belong to the set, not to the reduction: the launcher refuses them.
+    int nred;
+    const unsigned short* d_mult;          // [nrep][nobs]; NULL where every d_rep[r] is -1
+    const int *d_set_of, *d_rep;           // [nred]; each may be NULL
+    int* d_counts;                         // [nred][4]: nuse, nuse_d, nheld, ndown
 };
+static inline int ucf_fit_reduce_is_resampled(const ucf_fit_reduce_args* a) { return a->nred > 0; }
 static inline int ucf_fit_reduce_is_robust(const ucf_fit_reduce_args* a) { return a->loss != 0 || a->d_ndown || a->d_b || a->d_bd; }
-// doubles per set of d_sums that the launch of `a` writes
+// doubles per set (per reduction) of d_sums that the launch of `a` writes
 static inline int ucf_fit_reduce_nsums(const ucf_fit_reduce_args* a)
 {
-    return (a->d_dh ? ucf_fit_joint_nsums(a->npar) : ucf_fit_nsums(a->npar)) + (ucf_fit_reduce_is_robust(a) ? 1 : 0);
+    return (a->d_dh ? ucf_fit_joint_nsums(a->npar) : ucf_fit_nsums(a->npar)) +
+           (ucf_fit_reduce_is_resampled(a) ? 2 : (ucf_fit_reduce_is_robust(a) ? 1 : 0));
 }
 
 int ucf_fit_launch_reduce(const ucf_fit_reduce_args* a, void* stream);

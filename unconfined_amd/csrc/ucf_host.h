@@ -160,6 +160,9 @@ int fit_theta_sets(const ucf_params& base, int npar, const int* ids, const doubl
 // the lower Cholesky factor of M [n][n] (symmetric, row-major) in its lower triangle, as ucf_fit_solve_step forms it;
 // UCF_ERR_SINGULAR (no message) where a pivot is not positive and finite
 int fit_cholesky_factor(int n, double* M);
+// UCF_ERR_BAD_ARGUMENT naming the first row of mult [nrep][nobs] whose entries sum beyond 2^31 - 1 (the counts of a resampled
+// reduction are int)
+int fit_resample_check_rows(int nrep, int nobs, const unsigned short* mult);
 
 // ---- ucf_field.cpp
 // UCF_ERR_BAD_ARGUMENT naming name[i] for the first v[i] that is not finite

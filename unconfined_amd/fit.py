@@ -15,6 +15,9 @@ equations are formed on the device; this module only marshals arrays.
     lw = likelihood_weights(obj["phi"], obj["nbad"])          # weights for WellField.ensemble(..., weights=lw["weight"])
     fit.set_loss("huber", 1.345)                  # a robust loss: evaluate, objective and lm reduce with it from here on
     rep = fit.loss_report(res["theta"], factors=True)         # b (and bd): the factor of every residual; b == 0: an outlier
+    bs = fit.bootstrap(res["theta"][0], 1024, block=well)     # one-step block bootstrap: one evaluation, 1024 reductions;
+                                                              # bs["thetas"] feed WellField.ensemble, bs["cov"] replaces cov
+    jk = fit.lm_resampled(np.tile(th, (nwell, 1)), rep=np.arange(nwell))   # after set_resample(resample_jackknife(nobs, well))
 
 Parameters are positive and fitted in their logarithm; ``theta`` arrays hold the parameters themselves.
 """
@@ -26,7 +29,7 @@ from typing import Sequence, Union
 import numpy as np
 
 from . import lib as _libmod
-from .abi import FIT_SCREEN, LOSS_KINDS, LOSS_L2, PAR_IDS, PAR_MOENCH_ALPHA0, UcfFitOptions, UcfParams
+from .abi import FIT_CONVERGED, FIT_MAX_ITER, FIT_SCREEN, LOSS_KINDS, LOSS_L2, PAR_IDS, PAR_MOENCH_ALPHA0, RESAMPLE_KINDS, UcfFitOptions, UcfParams
 
 
 def _f64(a):
@@ -190,6 +193,60 @@ def robust_scale(x) -> float:
     return float(s.value)
 
 
+def _u16(a):
+    return np.ascontiguousarray(a, dtype=np.uint16)
+
+
+def _blocks(block, nobs):
+    if block is None:
+        return None, int(nobs)
+    block = _i32(block)
+    if nobs is not None and len(block) != nobs:
+        raise ValueError("block must have one entry per observation")
+    return block, len(block)
+
+
+def resample_blocks(nobs: int, nrep: int, block=None, seed: int = 0) -> np.ndarray:
+    """mult [nrep][nobs] (uint16) of a block bootstrap (ucf_fit_resample_blocks; no GPU): per replicate as many draws as there
+    are blocks, every observation of a drawn block gains 1.  ``block`` [nobs] holds block ids 0..nb-1 (wells, time windows);
+    None: every observation is its own block, the iid bootstrap."""
+    block, nobs = _blocks(block, nobs)
+    mult = np.zeros((max(int(nrep), 1), max(nobs, 1)), np.uint16)          # (the call refuses an nrep or nobs below 1)
+    _libmod.check(_libmod.load().ucf_fit_resample_blocks(nobs, None if block is None else block.ctypes.data, int(nrep),
+                                                         int(seed) & 0xFFFFFFFFFFFFFFFF, mult.ctypes.data, None))
+    return mult
+
+
+def resample_jackknife(nobs: int, block=None) -> np.ndarray:
+    """mult [nb][nobs] (uint16) of the delete-one-block jackknife (ucf_fit_resample_jackknife; no GPU): row b is 0 on block b
+    and 1 elsewhere.  Leave one well out with the well index as ``block``; k-fold cross-validation with fold ids."""
+    block, nobs = _blocks(block, nobs)
+    nb = C.c_int()
+    lib = _libmod.load()
+    _libmod.check(lib.ucf_fit_resample_blocks(nobs, None if block is None else block.ctypes.data, 1, 0, None, C.addressof(nb)))
+    mult = np.zeros((nb.value, nobs), np.uint16)
+    _libmod.check(lib.ucf_fit_resample_jackknife(nobs, None if block is None else block.ctypes.data, mult.ctypes.data))
+    return mult
+
+
+def resample_cov(kind, thetas, use=None) -> dict:
+    """mean [npar] and cov [npar][npar] in ln(theta) over the replicates ``thetas`` [nrep][npar] with use[r] != 0
+    (ucf_fit_resample_cov; no GPU); kind 'bootstrap' divides the sum of products by n - 1, 'jackknife' multiplies it by
+    (n - 1) / n.  Also nused = n."""
+    k = kind if isinstance(kind, (int, np.integer)) else RESAMPLE_KINDS[str(kind).lower()]
+    thetas = np.atleast_2d(_f64(thetas))
+    n, P = thetas.shape
+    use = None if use is None else _i32(use)
+    if use is not None and len(use) != n:
+        raise ValueError("use must have one entry per replicate")
+    out = {"mean": np.zeros(P), "cov": np.zeros((P, P))}
+    nused = C.c_int()
+    _libmod.check(_libmod.load().ucf_fit_resample_cov(int(k), n, P, thetas.ctypes.data, None if use is None else use.ctypes.data,
+                                                      out["mean"].ctypes.data, out["cov"].ctypes.data, C.addressof(nused)))
+    out["nused"] = int(nused.value)
+    return out
+
+
 def quantise_weights(w) -> tuple:
     """(u, ess): the integer weights u [nens] (uint64, 0 .. 2^32, the largest weight 2^32) that a weighted ensemble reduces
     with, and Kish's effective sample size of them (ucf_ensemble_quantise; no GPU).  A member with u = 0 is not in the ensemble."""
@@ -344,6 +401,126 @@ class Fit:
         ptr = lambda k: out[k].ctypes.data if k in out else None
         _libmod.check(self._lib.ucf_fit_loss_report(self._h, n, thetas.ctypes.data, ptr("phi"), ptr("phi_w"), ptr("nbad"), ptr("ndown"),
                                                     ptr("b"), ptr("bd")))
+        return out
+
+    def set_resample(self, mult):
+        """attach the multiplicities mult [nrep][nobs] (uint16, caller's observation order) of bootstrap or jackknife
+        replicates (ucf_fit_set_resample; ``resample_blocks``, ``resample_jackknife``); None detaches them.  Only the
+        ``*_resampled`` entries read them; ``evaluate``, ``objective``, ``lm`` and ``loss_report`` are unchanged."""
+        if mult is None:
+            _libmod.check(self._lib.ucf_fit_set_resample(self._h, 0, None))
+            self.nrep = 0
+            return
+        mult = np.atleast_2d(_u16(mult))
+        if mult.shape[1] != self.nobs:
+            raise ValueError(f"mult has {mult.shape[1]} columns, the fit has {self.nobs} observations")
+        _libmod.check(self._lib.ucf_fit_set_resample(self._h, mult.shape[0], mult.ctypes.data))
+        self.nrep = mult.shape[0]
+
+    def _reductions(self, nsets, set_of, rep):
+        set_of = None if set_of is None else np.atleast_1d(_i32(set_of))
+        rep = None if rep is None else np.atleast_1d(_i32(rep))
+        if set_of is not None and rep is not None and len(set_of) != len(rep):
+            raise ValueError("set_of and rep must have one entry per reduction")
+        nred = len(set_of) if set_of is not None else (len(rep) if rep is not None else nsets)
+        return nred, set_of, rep
+
+    def evaluate_resampled(self, theta, dlog: float, set_of=None, rep=None) -> dict:
+        """theta [nsets][npar] evaluated once, then nred reductions in one launch (ucf_fit_evaluate_resampled): reduction r
+        reads the plans of set set_of[r] (None: r) under replicate rep[r] of the attached multiplicities (-1, or None: every
+        multiplicity 1).  Per reduction phi, g, A, nbad, phi_w, phi_out (the held-out sum of squares), counts [nred][4] =
+        nuse, nuse_d, nheld, ndown, and on a fit with derivative data phi_d."""
+        theta = np.atleast_2d(_f64(theta))
+        n, P = theta.shape
+        if P != self.npar:
+            raise ValueError(f"theta has {P} columns, the fit has {self.npar} free parameters")
+        nred, set_of, rep = self._reductions(n, set_of, rep)
+        out = {"phi": np.zeros(nred), "g": np.zeros((nred, P)), "A": np.zeros((nred, P, P)), "nbad": np.zeros(nred, np.int32),
+               "phi_w": np.zeros(nred), "phi_out": np.zeros(nred), "counts": np.zeros((nred, 4), np.int32)}
+        if getattr(self, "_deriv", False):
+            out["phi_d"] = np.zeros(nred)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        _libmod.check(self._lib.ucf_fit_evaluate_resampled(self._h, n, theta.ctypes.data, float(dlog), nred,
+                                                           None if set_of is None else set_of.ctypes.data,
+                                                           None if rep is None else rep.ctypes.data, ptr("phi"), ptr("g"), ptr("A"),
+                                                           ptr("nbad"), ptr("phi_d"), ptr("phi_w"), ptr("phi_out"), ptr("counts")))
+        return out
+
+    def objective_resampled(self, thetas, set_of=None, rep=None) -> dict:
+        """``evaluate_resampled`` on the base plans only (ucf_fit_objective_resampled): phi, nbad, phi_w, phi_out, counts (and
+        phi_d) per reduction, no g or A.  phi_out of jackknife replicates at one theta is the cross-validation score."""
+        thetas = np.atleast_2d(_f64(thetas))
+        n, P = thetas.shape
+        if P != self.npar:
+            raise ValueError(f"thetas has {P} columns, the fit has {self.npar} free parameters")
+        nred, set_of, rep = self._reductions(n, set_of, rep)
+        out = {"phi": np.zeros(nred), "nbad": np.zeros(nred, np.int32), "phi_w": np.zeros(nred), "phi_out": np.zeros(nred),
+               "counts": np.zeros((nred, 4), np.int32)}
+        if getattr(self, "_deriv", False):
+            out["phi_d"] = np.zeros(nred)
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        _libmod.check(self._lib.ucf_fit_objective_resampled(self._h, n, thetas.ctypes.data, nred,
+                                                            None if set_of is None else set_of.ctypes.data,
+                                                            None if rep is None else rep.ctypes.data, ptr("phi"), ptr("nbad"),
+                                                            ptr("phi_d"), ptr("phi_w"), ptr("phi_out"), ptr("counts")))
+        return out
+
+    def lm_resampled(self, theta0, rep=None, cov: bool = True, **opt) -> dict:
+        """``lm`` with start s reduced under replicate rep[s] of the attached multiplicities (ucf_fit_lm_resampled; None: all
+        -1, the bytes of ``lm``).  Adds phi_out [nstarts] and counts [nstarts][4] at the final point; cov of a start is
+        phi_w / (nuse + nuse_d - npar) A^-1 of its own replicate."""
+        theta0 = np.atleast_2d(_f64(theta0))
+        n, P = theta0.shape
+        if P != self.npar:
+            raise ValueError(f"theta0 has {P} columns, the fit has {self.npar} free parameters")
+        rep = None if rep is None else np.atleast_1d(_i32(rep))
+        if rep is not None and len(rep) != n:
+            raise ValueError("rep must have one entry per start")
+        o = default_options()
+        for k, v in opt.items():
+            if not hasattr(o, k):
+                raise TypeError(f"unknown option {k!r}")
+            setattr(o, k, v)
+        out = {"theta": np.zeros((n, P)), "phi": np.zeros(n), "iters": np.zeros(n, np.int32), "status": np.zeros(n, np.int32),
+               "phi_out": np.zeros(n), "counts": np.zeros((n, 4), np.int32)}
+        if cov:
+            out["cov"] = np.zeros((n, P, P))
+        _libmod.check(self._lib.ucf_fit_lm_resampled(self._h, n, theta0.ctypes.data, None if rep is None else rep.ctypes.data, C.byref(o),
+                                                     out["theta"].ctypes.data, out["phi"].ctypes.data, out["iters"].ctypes.data,
+                                                     out["status"].ctypes.data, out["cov"].ctypes.data if cov else None,
+                                                     out["phi_out"].ctypes.data, out["counts"].ctypes.data))
+        return out
+
+    def bootstrap(self, theta_hat, nrep: int, block=None, seed: int = 0, refit: bool = False, dlog: float = 1.0e-3, **opt) -> dict:
+        """``nrep`` block-bootstrap replicates of the fit around theta_hat [npar] (``resample_blocks`` with ``block`` and
+        ``seed``; the multiplicities stay attached).  refit=False: the one-step (linearised) bootstrap -- ONE evaluation at
+        theta_hat, every replicate a reduction of it, then step_r = solve_step(A_r, g_r, 0) and theta_r = theta_hat exp(step_r);
+        refit=True: ``lm_resampled`` from theta_hat (options as ``lm``).  Returns thetas [nrep][npar], ready for
+        ``WellField.ensemble`` or ``sustainable_yield``; used [nrep] (bool: the step could be solved and no counted
+        observation was non-finite, or the refit did not end in a non-finite start or a singular matrix); mean, cov, nused of
+        ``resample_cov('bootstrap', thetas, used)``; mult."""
+        theta_hat = _f64(theta_hat).ravel()
+        if len(theta_hat) != self.npar:
+            raise ValueError(f"theta_hat has {len(theta_hat)} entries, the fit has {self.npar} free parameters")
+        mult = resample_blocks(self.nobs, nrep, block=block, seed=seed)
+        self.set_resample(mult)
+        rep = np.arange(nrep, dtype=np.int32)
+        thetas = np.tile(theta_hat, (nrep, 1))
+        if refit:
+            res = self.lm_resampled(thetas, rep=rep, cov=False, dlog=dlog, **opt)
+            thetas = res["theta"]
+            used = (res["status"] == FIT_CONVERGED) | (res["status"] == FIT_MAX_ITER)
+        else:
+            ev = self.evaluate_resampled(theta_hat, dlog, set_of=np.zeros(nrep, np.int32), rep=rep)
+            used = ev["nbad"] == 0
+            for r in np.flatnonzero(used):
+                try:
+                    thetas[r] = theta_hat * np.exp(solve_step(ev["A"][r], ev["g"][r], 0.0))
+                except _libmod.UcfError:
+                    used[r] = False
+        used &= np.isfinite(thetas).all(axis=1) & (thetas > 0.0).all(axis=1)
+        out = {"thetas": thetas, "used": used, "mult": mult}
+        out.update(resample_cov("bootstrap", np.where(used[:, None], thetas, 1.0), used.astype(np.int32)))
         return out
 
     def close(self):

@@ -49,6 +49,8 @@ EXPORTS = [
     "ucf_field_worth", "ucf_worth_condition", "ucf_debug_field_worth",
     "ucf_field_yield", "ucf_debug_field_yield",
     "ucf_fit_loss_terms", "ucf_fit_robust_scale", "ucf_fit_set_loss", "ucf_fit_get_loss", "ucf_fit_loss_report", "ucf_debug_fit_reduce_loss",
+    "ucf_fit_set_resample", "ucf_fit_evaluate_resampled", "ucf_fit_objective_resampled", "ucf_fit_lm_resampled",
+    "ucf_fit_resample_blocks", "ucf_fit_resample_jackknife", "ucf_fit_resample_cov", "ucf_debug_fit_reduce_resampled",
 ]
 
 
@@ -210,6 +212,17 @@ def load() -> C.CDLL:
     lib.ucf_fit_loss_report.argtypes = [vp, C.c_int] + [vp] * 7
     # kind, c, then the arguments of ucf_debug_fit_reduce, then ndown, b, bd
     lib.ucf_debug_fit_reduce_loss.argtypes = [C.c_int, C.c_double] + lib.ucf_debug_fit_reduce.argtypes + [vp] * 3
+    # resampling: mult, set_of, rep and every output may be NULL: plain addresses
+    lib.ucf_fit_set_resample.argtypes = [vp, C.c_int, vp]
+    lib.ucf_fit_evaluate_resampled.argtypes = [vp, C.c_int, vp, C.c_double, C.c_int] + [vp] * 10
+    lib.ucf_fit_objective_resampled.argtypes = [vp, C.c_int, vp, C.c_int] + [vp] * 8
+    lib.ucf_fit_lm_resampled.argtypes = [vp, C.c_int, vp, vp, C.POINTER(UcfFitOptions)] + [vp] * 7
+    lib.ucf_fit_resample_blocks.argtypes = [C.c_int, vp, C.c_int, C.c_ulonglong, vp, vp]
+    lib.ucf_fit_resample_jackknife.argtypes = [C.c_int, vp, vp]
+    lib.ucf_fit_resample_cov.argtypes = [C.c_int, C.c_int, C.c_int] + [vp] * 5
+    # kind, c, then the arguments of ucf_debug_fit_reduce up to `first`, then nrep, mult, nred, set_of, rep, sums, nbad, counts
+    lib.ucf_debug_fit_reduce_resampled.argtypes = ([C.c_int, C.c_double] + lib.ucf_debug_fit_reduce.argtypes[:-6] +
+                                                   [C.c_int, vp, C.c_int, vp, vp, vp, vp, vp])
     _lib = lib
     return lib
 
