@@ -334,20 +334,33 @@ int ucf_debug_ensemble_weighted(int nens, long long nout, const double* a, const
 namespace {
 // ucf_debug_fit_reduce (loss = UCF_LOSS_L2: c, ndown, b, bd are not read) and ucf_debug_fit_reduce_loss: one validation and one
 // launch through ucf_fit_launch_reduce.  Everything the kernel could read is checked against the lengths the caller gave
-// before anything is allocated or launched.  rsm != NULL: ucf_debug_fit_reduce_resampled -- nred reductions in place of one per
-// set; sums, nbad and rsm->counts are per reduction, and none of J .. bd may be asked for.
-struct debug_resample {
-    int nrep;
+// before anything is allocated or launched.  resampled: ucf_debug_fit_reduce_resampled -- nred reductions in place of one per
+// set; sums, nbad and counts are per reduction, and none of J .. bd may be asked for.
+// The members are the arguments of the three entries under their names of include/ucf.h, zero where an entry has none.
+struct debug_fit_reduce {
+    int loss;
+    double c;
+    int source, npar, nsets, nobs;
+    double two_dlog;
+    long long nh, plan_stride;
+    const double *h, *dh, *Hc, *obs, *w, *dobs, *wd, *q, *tfac;
+    const long long *prefix, *stride;
+    const int *slot, *at, *count, *first, *set_of, *rep;
     const unsigned short* mult;
-    int nred;
-    const int *set_of, *rep;
-    int* counts;
+    int nref, nrep, nred;
+    bool resampled;
+    double *sums, *J, *sim, *Jd, *simd, *b, *bd;
+    int *nbad, *ndown, *counts;
+    int run() const;
 };
-int debug_fit_reduce_core(int loss, double c, int source, int npar, int nsets, int nobs, double two_dlog, long long nh, const double* h,
-                          const double* dh, const double* Hc, const double* obs, const double* w, const double* dobs, const double* wd,
-                          const int* slot, long long plan_stride, int nref, const long long* prefix, const long long* stride, const int* at,
-                          const int* count, const double* q, const double* tfac, const int* first, double* sums, int* nbad, double* J,
-                          double* sim, double* Jd, double* simd, int* ndown, double* b, double* bd, const debug_resample* rsm = nullptr)
+// what the three entries have in common, from their parameters of the same names
+#define UCF_DEBUG_FIT_REDUCE_IN(in)                                                                                              \
+    in.source = source; in.npar = npar; in.nsets = nsets; in.nobs = nobs; in.two_dlog = two_dlog; in.nh = nh;                    \
+    in.h = h; in.dh = dh; in.Hc = Hc; in.obs = obs; in.w = w; in.dobs = dobs; in.wd = wd; in.slot = slot;                        \
+    in.plan_stride = plan_stride; in.nref = nref; in.prefix = prefix; in.stride = stride; in.at = at; in.count = count; in.q = q; \
+    in.tfac = tfac; in.first = first; in.sums = sums; in.nbad = nbad
+
+int debug_fit_reduce::run() const
 {
     if (loss != UCF_LOSS_L2) {
         if (loss != UCF_LOSS_HUBER && loss != UCF_LOSS_TUKEY)
@@ -367,19 +380,19 @@ int debug_fit_reduce_core(int loss, double c, int source, int npar, int nsets, i
     std::vector<ucf_fit_obs_ref> refs;
     std::vector<ucf_fit_term> terms;
     int rc;
-    if (rsm) {
-        if (!rsm->counts) return fail(UCF_ERR_BAD_ARGUMENT, "NULL counts");
-        if (rsm->nrep < 0 || rsm->nrep > 65536) return fail(UCF_ERR_BAD_ARGUMENT, "nrep=%d outside 0..65536", rsm->nrep);
-        if (rsm->nrep > 0 && !rsm->mult) return fail(UCF_ERR_BAD_ARGUMENT, "NULL mult with nrep=%d", rsm->nrep);
-        if (rsm->nrep > 0 && (rc = fit_resample_check_rows(rsm->nrep, nobs, rsm->mult))) return rc;
-        if (rsm->nred < 1 || rsm->nred > (1 << 16)) return fail(UCF_ERR_BAD_ARGUMENT, "nred=%d outside 1..65536", rsm->nred);
-        if (!rsm->set_of && rsm->nred > nsets)
-            return fail(UCF_ERR_BAD_ARGUMENT, "set_of is NULL (reduction r reads set r), but nred=%d exceeds nsets=%d", rsm->nred, nsets);
-        for (int r = 0; r < rsm->nred; r++) {
-            if (rsm->set_of && (rsm->set_of[r] < 0 || rsm->set_of[r] >= nsets))
-                return fail(UCF_ERR_BAD_ARGUMENT, "set_of[%d]=%d outside 0..%d", r, rsm->set_of[r], nsets - 1);
-            if (rsm->rep && (rsm->rep[r] < -1 || rsm->rep[r] >= rsm->nrep))
-                return fail(UCF_ERR_BAD_ARGUMENT, "rep[%d]=%d outside -1..%d", r, rsm->rep[r], rsm->nrep - 1);
+    if (resampled) {
+        if (!counts) return fail(UCF_ERR_BAD_ARGUMENT, "NULL counts");
+        if (nrep < 0 || nrep > 65536) return fail(UCF_ERR_BAD_ARGUMENT, "nrep=%d outside 0..65536", nrep);
+        if (nrep > 0 && !mult) return fail(UCF_ERR_BAD_ARGUMENT, "NULL mult with nrep=%d", nrep);
+        if (nrep > 0 && (rc = fit_resample_check_rows(nrep, nobs, mult))) return rc;
+        if (nred < 1 || nred > (1 << 16)) return fail(UCF_ERR_BAD_ARGUMENT, "nred=%d outside 1..65536", nred);
+        if (!set_of && nred > nsets)
+            return fail(UCF_ERR_BAD_ARGUMENT, "set_of is NULL (reduction r reads set r), but nred=%d exceeds nsets=%d", nred, nsets);
+        for (int r = 0; r < nred; r++) {
+            if (set_of && (set_of[r] < 0 || set_of[r] >= nsets))
+                return fail(UCF_ERR_BAD_ARGUMENT, "set_of[%d]=%d outside 0..%d", r, set_of[r], nsets - 1);
+            if (rep && (rep[r] < -1 || rep[r] >= nrep))
+                return fail(UCF_ERR_BAD_ARGUMENT, "rep[%d]=%d outside -1..%d", r, rep[r], nrep - 1);
         }
     }
     if (source == UCF_FIT_SLOTS) {
@@ -407,14 +420,13 @@ int debug_fit_reduce_core(int loss, double c, int source, int npar, int nsets, i
     if ((rc = require_device())) return rc;
     const bool joint = dh != nullptr;
     const size_t so = sizeof(double) * (size_t)nobs, sh = sizeof(double) * (size_t)nh, nt = (size_t)(nref > 0 ? nref : 1);
-    const size_t nsum = (size_t)(joint ? ucf_fit_joint_nsums(npar) : ucf_fit_nsums(npar)) + (rsm ? 2 : (loss != UCF_LOSS_L2 ? 1 : 0));
-    const size_t nout = (size_t)(rsm ? rsm->nred : nsets);      // workgroups: what sums and nbad are indexed by
-    const size_t smult = rsm ? sizeof(unsigned short) * (size_t)rsm->nrep * (size_t)nobs : 0;
+    const size_t nout = (size_t)(resampled ? nred : nsets);      // workgroups: what sums and nbad are indexed by
+    const size_t smult = resampled ? sizeof(unsigned short) * (size_t)nrep * (size_t)nobs : 0;
     const size_t bfac = so * (size_t)nsets;
     const size_t bJ = so * nsets * (npar > 0 ? npar : 1), bsim = so * (size_t)nplans;
     dev_buf b_h, b_dh, b_hc, b_obs, b_w, b_dobs, b_wd, b_slot, b_ref, b_term, b_first, b_tfac, b_sums, b_nbad, b_J, b_sim, b_Jd, b_simd, b_ndown, b_b, b_bd;
     dev_buf b_mult, b_setof, b_rep, b_counts;
-    if (rsm && ((smult && b_mult.alloc(smult)) || (rsm->set_of && b_setof.alloc(sizeof(int) * nout)) || (rsm->rep && b_rep.alloc(sizeof(int) * nout)) ||
+    if (resampled && ((smult && b_mult.alloc(smult)) || (set_of && b_setof.alloc(sizeof(int) * nout)) || (rep && b_rep.alloc(sizeof(int) * nout)) ||
                 b_counts.alloc(sizeof(int) * 4 * nout)))
         return fail(UCF_ERR_NOMEM, "device allocation failed");
     if (b_h.alloc(sh) || (joint && b_dh.alloc(sh)) || b_hc.alloc(sizeof(double) * (size_t)nplans) || b_obs.alloc(so) || b_w.alloc(so) ||
@@ -422,18 +434,10 @@ int debug_fit_reduce_core(int loss, double c, int source, int npar, int nsets, i
         (source == UCF_FIT_NETWORK && b_ref.alloc(sizeof(ucf_fit_obs_ref) * nt)) ||
         (source == UCF_FIT_FIELD && (b_term.alloc(sizeof(ucf_fit_term) * nt) || b_first.alloc(sizeof(int) * ((size_t)nobs + 1)) ||
                                      (joint && b_tfac.alloc(sizeof(double) * nt)))) ||
-        b_sums.alloc(sizeof(double) * nout * nsum) || b_nbad.alloc(sizeof(int) * nout) || (J && b_J.alloc(bJ)) || (sim && b_sim.alloc(bsim)) ||
+        b_nbad.alloc(sizeof(int) * nout) || (J && b_J.alloc(bJ)) || (sim && b_sim.alloc(bsim)) ||
         (Jd && b_Jd.alloc(bJ)) || (simd && b_simd.alloc(bsim)) || (ndown && b_ndown.alloc(sizeof(int) * (size_t)nsets)) || (b && b_b.alloc(bfac)) ||
         (bd && b_bd.alloc(bfac)))
         return fail(UCF_ERR_NOMEM, "device allocation failed");
-    const struct { void* dev; const void* host; size_t bytes; } up[] = {
-        {b_h.p, h, sh}, {b_dh.p, dh, sh}, {b_hc.p, Hc, sizeof(double) * (size_t)nplans}, {b_obs.p, obs, so}, {b_w.p, w, so}, {b_dobs.p, dobs, so},
-        {b_wd.p, wd, so}, {b_slot.p, slot, sizeof(int) * (size_t)nobs}, {b_ref.p, refs.data(), sizeof(ucf_fit_obs_ref) * refs.size()},
-        {b_term.p, terms.data(), sizeof(ucf_fit_term) * terms.size()}, {b_first.p, first, sizeof(int) * ((size_t)nobs + 1)},
-        {b_tfac.p, tfac, sizeof(double) * terms.size()}, {b_mult.p, rsm ? rsm->mult : nullptr, smult},
-        {b_setof.p, rsm ? rsm->set_of : nullptr, sizeof(int) * nout}, {b_rep.p, rsm ? rsm->rep : nullptr, sizeof(int) * nout}};
-    for (const auto& c : up)
-        if (c.dev && c.bytes) HIP_TRY(hipMemcpy(c.dev, c.host, c.bytes, hipMemcpyHostToDevice));
     ucf_fit_reduce_args ra = {};
     ra.npar = npar; ra.nsets = nsets; ra.nobs = nobs;
     ra.nplans = (size_t)nplans; ra.plan_stride = (size_t)plan_stride; ra.two_dlog = two_dlog;
@@ -442,20 +446,29 @@ int debug_fit_reduce_core(int loss, double c, int source, int npar, int nsets, i
     ra.d_slot = (const int*)b_slot.p; ra.d_ref = (const ucf_fit_obs_ref*)b_ref.p;
     ra.d_term = (const ucf_fit_term*)b_term.p; ra.d_first = (const int*)b_first.p; ra.d_tfac = (const double*)b_tfac.p;
     ra.d_obs = (const double*)b_obs.p; ra.d_w = (const double*)b_w.p; ra.d_dobs = (const double*)b_dobs.p; ra.d_wd = (const double*)b_wd.p;
-    ra.d_sums = (double*)b_sums.p; ra.d_nbad = (int*)b_nbad.p;
+    ra.d_nbad = (int*)b_nbad.p;
     ra.d_J = (double*)b_J.p; ra.d_sim = (double*)b_sim.p; ra.d_Jd = (double*)b_Jd.p; ra.d_simd = (double*)b_simd.p;
     ra.loss = loss; ra.loss_c = c; ra.d_ndown = (int*)b_ndown.p; ra.d_b = (double*)b_b.p; ra.d_bd = (double*)b_bd.p;
-    if (rsm) {
-        ra.nred = rsm->nred; ra.d_mult = (const unsigned short*)b_mult.p; ra.d_set_of = (const int*)b_setof.p; ra.d_rep = (const int*)b_rep.p;
-        ra.d_counts = (int*)b_counts.p;
-    }
+    ra.nred = resampled ? nred : 0; ra.d_mult = (const unsigned short*)b_mult.p; ra.d_set_of = (const int*)b_setof.p;
+    ra.d_rep = (const int*)b_rep.p; ra.d_counts = (int*)b_counts.p;
+    // the sums last: their number per workgroup follows from the launch that `ra` now describes
+    const size_t nsum = (size_t)ucf_fit_sums_of(&ra).count;
+    if (b_sums.alloc(sizeof(double) * nout * nsum)) return fail(UCF_ERR_NOMEM, "device allocation failed");
+    ra.d_sums = (double*)b_sums.p;
+    const struct { void* dev; const void* host; size_t bytes; } up[] = {
+        {b_h.p, h, sh}, {b_dh.p, dh, sh}, {b_hc.p, Hc, sizeof(double) * (size_t)nplans}, {b_obs.p, obs, so}, {b_w.p, w, so}, {b_dobs.p, dobs, so},
+        {b_wd.p, wd, so}, {b_slot.p, slot, sizeof(int) * (size_t)nobs}, {b_ref.p, refs.data(), sizeof(ucf_fit_obs_ref) * refs.size()},
+        {b_term.p, terms.data(), sizeof(ucf_fit_term) * terms.size()}, {b_first.p, first, sizeof(int) * ((size_t)nobs + 1)},
+        {b_tfac.p, tfac, sizeof(double) * terms.size()}, {b_mult.p, mult, smult},
+        {b_setof.p, set_of, sizeof(int) * nout}, {b_rep.p, rep, sizeof(int) * nout}};
+    for (const auto& c : up)
+        if (c.dev && c.bytes) HIP_TRY(hipMemcpy(c.dev, c.host, c.bytes, hipMemcpyHostToDevice));
     rc = ucf_fit_launch_reduce(&ra, nullptr);
     if (rc) return fail(rc, "fit reduction kernel launch failed");
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if (rsm) HIP_TRY(hipMemcpy(rsm->counts, b_counts.p, sizeof(int) * 4 * nout, hipMemcpyDeviceToHost));
-    return copy_back_sync({{sums, b_sums.p, sizeof(double) * nout * nsum}, {nbad, b_nbad.p, sizeof(int) * nout}, {J, b_J.p, npar > 0 ? bJ : 0},
-                           {sim, b_sim.p, bsim}, {Jd, b_Jd.p, npar > 0 ? bJ : 0}, {simd, b_simd.p, bsim}, {ndown, b_ndown.p, sizeof(int) * (size_t)nsets},
-                           {b, b_b.p, bfac}, {bd, b_bd.p, bfac}});
+    return copy_back_sync({{counts, b_counts.p, sizeof(int) * 4 * nout}, {sums, b_sums.p, sizeof(double) * nout * nsum}, {nbad, b_nbad.p, sizeof(int) * nout},
+                           {J, b_J.p, npar > 0 ? bJ : 0}, {sim, b_sim.p, bsim}, {Jd, b_Jd.p, npar > 0 ? bJ : 0}, {simd, b_simd.p, bsim},
+                           {ndown, b_ndown.p, sizeof(int) * (size_t)nsets}, {b, b_b.p, bfac}, {bd, b_bd.p, bfac}});
 }
 }  // namespace
 
@@ -469,8 +482,10 @@ int ucf_debug_fit_reduce(int source, int npar, int nsets, int nobs, double two_d
                          const int* count, const double* q, const double* tfac, const int* first, double* sums, int* nbad, double* J,
                          double* sim, double* Jd, double* simd)
 {
-    return debug_fit_reduce_core(UCF_LOSS_L2, 0.0, source, npar, nsets, nobs, two_dlog, nh, h, dh, Hc, obs, w, dobs, wd, slot, plan_stride, nref,
-                                 prefix, stride, at, count, q, tfac, first, sums, nbad, J, sim, Jd, simd, nullptr, nullptr, nullptr);
+    debug_fit_reduce in = {};
+    UCF_DEBUG_FIT_REDUCE_IN(in);
+    in.J = J; in.sim = sim; in.Jd = Jd; in.simd = simd;
+    return in.run();
 }
 
 // the same under a robust loss: kind and c are checked first, with the rest before any device is touched
@@ -482,8 +497,10 @@ int ucf_debug_fit_reduce_loss(int kind, double c, int source, int npar, int nset
 {
     if (kind != UCF_LOSS_HUBER && kind != UCF_LOSS_TUKEY)
         return fail(UCF_ERR_BAD_ARGUMENT, "kind=%d: UCF_LOSS_HUBER (1) or UCF_LOSS_TUKEY (2); least squares is ucf_debug_fit_reduce", kind);
-    return debug_fit_reduce_core(kind, c, source, npar, nsets, nobs, two_dlog, nh, h, dh, Hc, obs, w, dobs, wd, slot, plan_stride, nref, prefix,
-                                 stride, at, count, q, tfac, first, sums, nbad, J, sim, Jd, simd, ndown, b, bd);
+    debug_fit_reduce in = {};
+    UCF_DEBUG_FIT_REDUCE_IN(in);
+    in.loss = kind; in.c = c; in.J = J; in.sim = sim; in.Jd = Jd; in.simd = simd; in.ndown = ndown; in.b = b; in.bd = bd;
+    return in.run();
 }
 
 // the same per reduction under multiplicities: kind, c and the resampling arguments are checked with the rest before any device
@@ -495,9 +512,13 @@ int ucf_debug_fit_reduce_resampled(int kind, double c, int source, int npar, int
 {
     if (kind != UCF_LOSS_L2 && kind != UCF_LOSS_HUBER && kind != UCF_LOSS_TUKEY)
         return fail(UCF_ERR_BAD_ARGUMENT, "kind=%d is no loss (UCF_LOSS_L2 0, UCF_LOSS_HUBER 1, UCF_LOSS_TUKEY 2)", kind);
-    const debug_resample rsm = {nrep, mult, nred, set_of, rep, counts};
-    return debug_fit_reduce_core(kind, c, source, npar, nsets, nobs, two_dlog, nh, h, dh, Hc, obs, w, dobs, wd, slot, plan_stride, nref, prefix,
-                                 stride, at, count, q, tfac, first, sums, nbad, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &rsm);
+    debug_fit_reduce in = {};
+    UCF_DEBUG_FIT_REDUCE_IN(in);
+    in.loss = kind; in.c = c;
+    in.resampled = true; in.nrep = nrep; in.mult = mult; in.nred = nred; in.set_of = set_of; in.rep = rep; in.counts = counts;
+    return in.run();
 }
 
 }  // extern "C"
+
+#undef UCF_DEBUG_FIT_REDUCE_IN

@@ -418,24 +418,6 @@ int network_core(ucf_fit* f, int nplans)
     return rc;
 }
 
-// what the robust reduction adds to the outputs of fit_evaluate: phi_w, ndown [nsets], b, bd [nsets][nobs]; each may be NULL.
-// ndown, b or bd asked for on a least-squares fit run the robust instantiation with every factor 1.0 (ucf_fit.h).
-struct fit_loss_out {
-    double* phi_w = nullptr;
-    int* ndown = nullptr;
-    double *b = nullptr, *bd = nullptr;
-};
-
-// A resampled reduction (ucf_fit_set_resample): nred reductions in place of one per set.  set_of NULL: the identity (nred <=
-// nsets), rep NULL: all -1; both have been checked by fit_resample_check.  phi, g, A, nbad, phi_d of fit_evaluate are then per
-// reduction, as are phi_w, phi_out [nred] and counts [nred][4] here; each may be NULL.
-struct fit_resample_io {
-    int nred = 0;
-    const int *set_of = nullptr, *rep = nullptr;
-    double *phi_w = nullptr, *phi_out = nullptr;
-    int* counts = nullptr;
-};
-
 // the checks of a resampled call that need the fit only: before any GPU work
 int fit_resample_check(const ucf_fit* f, int nsets, int nred, const int* set_of, const int* rep)
 {
@@ -450,23 +432,42 @@ int fit_resample_check(const ucf_fit* f, int nsets, int nred, const int* set_of,
     return UCF_OK;
 }
 
-// jac != 0: base and perturbed plans, everything; jac == 0: the base plans only, phi and nbad (the trial points of ucf_fit_lm).
-// On a fit with derivative data the sums are the joint ones and phi_d, Jd, simd_all may be asked for; without, they are NULL.
-// The fit's loss decides the instantiation; on a least-squares fit with lo == NULL nothing differs from a fit without one.
-int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int jac, double* phi, double* g, double* A, int* nbad,
-                 double* J, double* sim_all, double* phi_d = nullptr, double* Jd = nullptr, double* simd_all = nullptr,
-                 const fit_loss_out* lo = nullptr, const fit_resample_io* rs = nullptr)
+// What one call of fit_evaluate asks for; an output that stays NULL is neither computed nor copied.
+//   jac != 0: base and perturbed plans (dlog: the step of the central difference), everything.  jac == 0: the base plans only, the
+//   npar = 0 reduction (the trial points of ucf_fit_lm); g, A, J, Jd are not read.
+//   phi, g, A, nbad, phi_d (a fit with derivative data only) and phi_w are per set, per reduction when resampled.  phi_w is phi of
+//   the weighted problem that the final factors define; a launch without factors (least squares, no ndown, b, bd) gives phi.
+//   J, Jd [nsets][nobs][npar], sim_all, simd_all [nsets][plans][nobs], ndown [nsets], b, bd [nsets][nobs] are per set only.  One of
+//   the last three on a least-squares fit runs the robust instantiation with every factor 1.0 (ucf_fit.h).
+//   resampled (ucf_fit_set_resample): nred reductions in place of one per set; set_of NULL: the identity (nred <= nsets), rep
+//   NULL: all -1 (fit_resample_check).  phi_out [nred] and counts [nred][4] are its own.
+struct fit_request {
+    int jac = 0;
+    double dlog = 0.0;
+    double *phi = nullptr, *g = nullptr, *A = nullptr, *phi_d = nullptr, *phi_w = nullptr, *phi_out = nullptr;
+    double *J = nullptr, *sim_all = nullptr, *Jd = nullptr, *simd_all = nullptr, *b = nullptr, *bd = nullptr;
+    int *nbad = nullptr, *ndown = nullptr, *counts = nullptr;
+    bool resampled = false;
+    int nred = 0;
+    const int *set_of = nullptr, *rep = nullptr;
+};
+// the sizes of one call: plans per set and in all; workgroups of the reduction, what sums, nbad and counts are indexed by; bytes
+// of J (Jd), sim_all (simd_all), b (bd)
+struct fit_shape {
+    int nsets, per, nplans, nout;
+    size_t bJ, bsim, bfac;
+};
+
+// 1. the arguments, before any GPU work
+int fit_check_request(const ucf_fit* f, int nsets, const double* theta, const fit_request& q, fit_shape& sh)
 {
     if (!f || !theta) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (nsets < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nsets=%d: at least one parameter set", nsets);
-    if (rs) {
-        int rc = fit_resample_check(f, nsets, rs->nred, rs->set_of, rs->rep);
-        if (rc) return rc;
-    }
-    if (jac && (!(dlog > 0.0) || !std::isfinite(dlog))) return fail(UCF_ERR_BAD_ARGUMENT, "dlog=%g must be positive and finite", dlog);
-    const int npar = f->npar, per = jac ? 1 + 2 * npar : 1, nobs = f->nobs, nz = f->nz;
+    int rc = q.resampled ? fit_resample_check(f, nsets, q.nred, q.set_of, q.rep) : UCF_OK;
+    if (rc) return rc;
+    if (q.jac && (!(q.dlog > 0.0) || !std::isfinite(q.dlog))) return fail(UCF_ERR_BAD_ARGUMENT, "dlog=%g must be positive and finite", q.dlog);
+    const int npar = f->npar, per = q.jac ? 1 + 2 * npar : 1;
     if ((long long)nsets * per > (1 << 20)) return fail(UCF_ERR_BAD_ARGUMENT, "%d sets x %d plans: too many plans for one call", nsets, per);
-    const int nplans = nsets * per;
     char nb[32];
     for (int s = 0; s < nsets; s++)
         for (int j = 0; j < npar; j++) {
@@ -475,118 +476,157 @@ int fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, int ja
                 return fail(UCF_ERR_BAD_ARGUMENT, "set %d: %s=%g must be positive and finite (parameters are fitted in their logarithm)", s,
                             fit_par_name(f->ids[j], nb, sizeof(nb)), v);
         }
-    device_switch dg(f->device);
-    // the plans: refreshed in place, made on first use
+    const size_t so = sizeof(double) * (size_t)f->nobs;
+    sh = fit_shape{nsets, per, nsets * per, q.resampled ? q.nred : nsets, so * nsets * npar, so * nsets * per, so * nsets};
+    return UCF_OK;
+}
+
+// 2. the plans of the pool: refreshed in place, made on first use
+int fit_refresh_plans(ucf_fit* f, const double* theta, double dlog, const fit_shape& sh)
+{
+    const int npar = f->npar, per = sh.per;
+    char nb[32];
     std::vector<ucf_params> sets(per);
-    for (int s = 0; s < nsets; s++) {
+    for (int s = 0; s < sh.nsets; s++) {
         int rc = fit_theta_sets(f->base, npar, f->ids, theta + (size_t)s * npar, dlog, per, sets.data());
         if (rc) return rc;
         for (int v = 0; v < per; v++) {
-            const int j = (v - 1) / 2;
-            const ucf_params& P = sets[v];
             const size_t k = (size_t)s * per + v;
             if (k < f->plans.size()) {
-                rc = ucf_plan_update(f->plans[k], &P);
+                rc = ucf_plan_update(f->plans[k], &sets[v]);
             } else {
                 ucf_plan* pl = nullptr;
-                rc = ucf_plan_create(&P, &pl);
+                rc = ucf_plan_create(&sets[v], &pl);
                 if (rc == UCF_OK) { (void)ucf_plan_set_mode(pl, 1); f->plans.push_back(pl); f->n_alloc++; }
             }
-            if (rc) {
-                std::string why = ucf_last_error();
-                if (v == 0) return fail(rc, "set %d: %s", s, why.c_str());
-                return fail(rc, "set %d, %s moved by %+g in its logarithm: %s", s, fit_par_name(f->ids[j], nb, sizeof(nb)), (v & 1) ? dlog : -dlog, why.c_str());
-            }
+            if (rc == UCF_OK) continue;
+            std::string why = ucf_last_error();
+            if (v == 0) return fail(rc, "set %d: %s", s, why.c_str());
+            return fail(rc, "set %d, %s moved by %+g in its logarithm: %s", s, fit_par_name(f->ids[(v - 1) / 2], nb, sizeof(nb)), (v & 1) ? dlog : -dlog, why.c_str());
         }
     }
-    const bool joint = f->deriv;
-    const fit_loss_out none;
-    const fit_loss_out& L = lo ? *lo : none;
-    // a resampled reduction always carries phi_w (least squares runs as Huber with c = +inf) and one more sum, phi_out
-    const bool robust = rs || f->loss != UCF_LOSS_L2 || L.ndown || L.b || L.bd;
-    const size_t np_ = (size_t)nobs, tot = (size_t)nplans * np_;
-    const size_t nsum = (size_t)(joint ? ucf_fit_joint_nsums(jac ? npar : 0) : ucf_fit_nsums(jac ? npar : 0)) + (robust ? 1 : 0) + (rs ? 1 : 0);
-    const int nout = rs ? rs->nred : nsets;        // workgroups of the reduction: what sums and nbad are indexed by
-    // points and (point, depth) values that are launched: every depth at every observation, or the network's blocks
-    const size_t ptot = (size_t)nplans * (f->is_network() ? f->net_pts : np_), vtot = (size_t)nplans * (f->is_network() ? f->net_vals : np_ * nz);
-    int rc;
-    if ((rc = grow_buffer(f->b_t, sizeof(double) * ptot, "tD", f->n_alloc)) || (rc = grow_buffer(f->b_r, sizeof(double) * ptot, "rD", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_s, sizeof(int) * ptot, "sv", f->n_alloc)) || (rc = grow_buffer(f->b_h, sizeof(double) * vtot, "h", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_d, sizeof(double) * vtot, "dh", f->n_alloc)) || (rc = grow_buffer(f->b_hc, sizeof(double) * nplans, "Hc", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_sums, sizeof(double) * nout * nsum, "sums", f->n_alloc)) || (rc = grow_buffer(f->b_nbad, sizeof(int) * nout, "nbad", f->n_alloc)))
-        return rc;
-    if (rs && ((rc = grow_buffer(f->b_counts, sizeof(int) * 4 * nout, "counts", f->n_alloc)) ||
-               (rs->set_of && (rc = grow_buffer(f->b_setof, sizeof(int) * nout, "set_of", f->n_alloc))) ||
-               (rs->rep && (rc = grow_buffer(f->b_rep, sizeof(int) * nout, "rep", f->n_alloc)))))
-        return rc;
-    if (J && jac && (rc = grow_buffer(f->b_J, sizeof(double) * nsets * np_ * npar, "J", f->n_alloc))) return rc;
-    if (sim_all && (rc = grow_buffer(f->b_sim, sizeof(double) * tot, "sim_all", f->n_alloc))) return rc;
-    if (Jd && jac && (rc = grow_buffer(f->b_Jd, sizeof(double) * nsets * np_ * npar, "Jd", f->n_alloc))) return rc;
-    if (simd_all && (rc = grow_buffer(f->b_simd, sizeof(double) * tot, "simd_all", f->n_alloc))) return rc;
-    if (L.ndown && (rc = grow_buffer(f->b_ndown, sizeof(int) * nsets, "ndown", f->n_alloc))) return rc;
-    if (L.b && (rc = grow_buffer(f->b_bfac, sizeof(double) * nsets * np_, "b", f->n_alloc))) return rc;
-    if (L.bd && (rc = grow_buffer(f->b_bdfac, sizeof(double) * nsets * np_, "bd", f->n_alloc))) return rc;
-    f->io.d_t = (double*)f->b_t.p; f->io.d_r = (double*)f->b_r.p; f->io.d_s = (int*)f->b_s.p;
-    f->io.d_h = (double*)f->b_h.p; f->io.d_d = (double*)f->b_d.p;
-    f->last_nplans = 0;
-    rc = f->is_network() ? network_core(f, nplans) : multi_core(f->plans.data(), nplans, nobs, f->t_s.data(), f->r_s.data(), nz, f->z.data(), f->io);
-    if (rc) return rc;
-    f->last_nplans = nplans;
-    f->h_hc.resize(nplans);
-    for (int k = 0; k < nplans; k++) f->h_hc[k] = f->plans[k]->D.Hc;
-    HIP_TRY(hipMemcpy(f->b_hc.p, f->h_hc.data(), sizeof(double) * nplans, hipMemcpyHostToDevice));
+    return UCF_OK;
+}
+
+// 3. The reduction as its launcher sees it (ucf_fit.h), before the buffers grow: which arrays a launch has decides its
+// instantiation and so the layout of its sums, and that layout sizes b_sums.  Everything is filled in but the addresses that
+// growth may move.  In their place an array that a launch may go without -- d_dh, the outputs and index lists of the request --
+// is non-NULL where this one will have it (a host address that nothing reads through); fit_grow puts the buffer's there.
+ucf_fit_reduce_args fit_reduce_asked(const ucf_fit* f, const double* theta, const fit_request& q, const fit_shape& sh)
+{
     ucf_fit_reduce_args ra = {};
-    ra.npar = jac ? npar : 0; ra.nsets = nsets; ra.nobs = nobs;
-    ra.nplans = (size_t)nplans; ra.plan_stride = np_ * nz; ra.two_dlog = 2.0 * dlog;
-    ra.d_h = (const double*)f->b_h.p; ra.d_dh = joint ? (const double*)f->b_d.p : nullptr; ra.d_Hc = (const double*)f->b_hc.p;
+    ra.npar = q.jac ? f->npar : 0; ra.nsets = sh.nsets; ra.nobs = f->nobs;
+    ra.nplans = (size_t)sh.nplans; ra.plan_stride = (size_t)f->nobs * f->nz; ra.two_dlog = 2.0 * q.dlog;
     ra.source = f->kind;
     ra.d_slot = (const int*)f->b_slot.p; ra.d_ref = (const ucf_fit_obs_ref*)f->b_ref.p;
     ra.d_term = (const ucf_fit_term*)f->b_term.p; ra.d_first = (const int*)f->b_first.p; ra.d_tfac = (const double*)f->b_tfac.p;
     ra.d_obs = (const double*)f->b_obs.p; ra.d_w = (const double*)f->b_w.p;
     ra.d_dobs = (const double*)f->b_dobs.p; ra.d_wd = (const double*)f->b_wd.p;
-    ra.d_sums = (double*)f->b_sums.p; ra.d_nbad = (int*)f->b_nbad.p;
-    ra.d_J = (J && jac) ? (double*)f->b_J.p : nullptr; ra.d_sim = sim_all ? (double*)f->b_sim.p : nullptr;
-    ra.d_Jd = (Jd && jac) ? (double*)f->b_Jd.p : nullptr; ra.d_simd = simd_all ? (double*)f->b_simd.p : nullptr;
     ra.loss = f->loss; ra.loss_c = f->loss_c;
-    ra.d_ndown = L.ndown ? (int*)f->b_ndown.p : nullptr; ra.d_b = L.b ? (double*)f->b_bfac.p : nullptr; ra.d_bd = L.bd ? (double*)f->b_bdfac.p : nullptr;
-    if (rs) {
-        if (rs->set_of) HIP_TRY(hipMemcpy(f->b_setof.p, rs->set_of, sizeof(int) * nout, hipMemcpyHostToDevice));
-        if (rs->rep) HIP_TRY(hipMemcpy(f->b_rep.p, rs->rep, sizeof(int) * nout, hipMemcpyHostToDevice));
-        ra.nred = nout; ra.d_mult = f->nrep > 0 ? (const unsigned short*)f->b_mult.p : nullptr;
-        ra.d_set_of = rs->set_of ? (const int*)f->b_setof.p : nullptr; ra.d_rep = rs->rep ? (const int*)f->b_rep.p : nullptr;
-        ra.d_counts = (int*)f->b_counts.p;
+    ra.d_dh = f->deriv ? theta : nullptr;
+    ra.d_J = q.J; ra.d_sim = q.sim_all; ra.d_Jd = q.Jd; ra.d_simd = q.simd_all; ra.d_ndown = q.ndown; ra.d_b = q.b; ra.d_bd = q.bd;
+    if (q.resampled) {
+        ra.nred = sh.nout; ra.d_mult = f->nrep > 0 ? (const unsigned short*)f->b_mult.p : nullptr;
+        ra.d_set_of = q.set_of; ra.d_rep = q.rep;
     }
-    rc = ucf_fit_launch_reduce(&ra, nullptr);
+    return ra;
+}
+
+// 4. the buffers, grown on demand, and their addresses to where the evaluators (f->io) and the reduction (ra) read them: what
+// every evaluation has, then what this one will have; nsum doubles of sums per workgroup
+template <class T>
+int fit_grow_to(ucf_fit* f, T*& at, ucf_buffer& b, size_t bytes, const char* what)
+{
+    int rc = grow_buffer(b, bytes, what, f->n_alloc);
+    at = (T*)b.p;
+    return rc;
+}
+int fit_grow(ucf_fit* f, ucf_fit_reduce_args& ra, const fit_shape& sh, size_t nsum)
+{
+    // points and (point, depth) values that are launched: every depth at every observation, or the network's blocks
+    const size_t np_ = (size_t)f->nobs, nplans = (size_t)sh.nplans, nout = (size_t)sh.nout;
+    const size_t ptot = nplans * (f->is_network() ? f->net_pts : np_), vtot = nplans * (f->is_network() ? f->net_vals : np_ * f->nz);
+    multi_io& io = f->io;
+    int rc;
+    if ((rc = fit_grow_to(f, io.d_t, f->b_t, sizeof(double) * ptot, "tD")) || (rc = fit_grow_to(f, io.d_r, f->b_r, sizeof(double) * ptot, "rD")) ||
+        (rc = fit_grow_to(f, io.d_s, f->b_s, sizeof(int) * ptot, "sv")) || (rc = fit_grow_to(f, io.d_h, f->b_h, sizeof(double) * vtot, "h")) ||
+        (rc = fit_grow_to(f, io.d_d, f->b_d, sizeof(double) * vtot, "dh")) || (rc = fit_grow_to(f, ra.d_Hc, f->b_hc, sizeof(double) * nplans, "Hc")) ||
+        (rc = fit_grow_to(f, ra.d_sums, f->b_sums, sizeof(double) * nout * nsum, "sums")) || (rc = fit_grow_to(f, ra.d_nbad, f->b_nbad, sizeof(int) * nout, "nbad")))
+        return rc;
+    ra.d_h = io.d_h;
+    if (ra.d_dh) ra.d_dh = io.d_d;
+    if (ucf_fit_reduce_is_resampled(&ra) && ((rc = fit_grow_to(f, ra.d_counts, f->b_counts, sizeof(int) * 4 * nout, "counts")) ||
+                                             (ra.d_set_of && (rc = fit_grow_to(f, ra.d_set_of, f->b_setof, sizeof(int) * nout, "set_of"))) ||
+                                             (ra.d_rep && (rc = fit_grow_to(f, ra.d_rep, f->b_rep, sizeof(int) * nout, "rep")))))
+        return rc;
+    if ((ra.d_J && (rc = fit_grow_to(f, ra.d_J, f->b_J, sh.bJ, "J"))) || (ra.d_sim && (rc = fit_grow_to(f, ra.d_sim, f->b_sim, sh.bsim, "sim_all"))) ||
+        (ra.d_Jd && (rc = fit_grow_to(f, ra.d_Jd, f->b_Jd, sh.bJ, "Jd"))) || (ra.d_simd && (rc = fit_grow_to(f, ra.d_simd, f->b_simd, sh.bsim, "simd_all"))) ||
+        (ra.d_ndown && (rc = fit_grow_to(f, ra.d_ndown, f->b_ndown, sizeof(int) * sh.nsets, "ndown"))) ||
+        (ra.d_b && (rc = fit_grow_to(f, ra.d_b, f->b_bfac, sh.bfac, "b"))) || (ra.d_bd && (rc = fit_grow_to(f, ra.d_bd, f->b_bdfac, sh.bfac, "bd"))))
+        return rc;
+    return UCF_OK;
+}
+
+// 5. the evaluations: the dimensionless h and dh of every plan stay in b_h and b_d, their scales go to b_hc
+int fit_simulate(ucf_fit* f, int nplans)
+{
+    f->last_nplans = 0;
+    int rc = f->is_network() ? network_core(f, nplans) : multi_core(f->plans.data(), nplans, f->nobs, f->t_s.data(), f->r_s.data(), f->nz, f->z.data(), f->io);
+    if (rc) return rc;
+    f->last_nplans = nplans;
+    f->h_hc.resize(nplans);
+    for (int k = 0; k < nplans; k++) f->h_hc[k] = f->plans[k]->D.Hc;
+    HIP_TRY(hipMemcpy(f->b_hc.p, f->h_hc.data(), sizeof(double) * nplans, hipMemcpyHostToDevice));
+    return UCF_OK;
+}
+
+// 6. the launch, and what was asked for on its way back (the sums to f->h_sums, nsum doubles per workgroup)
+int fit_reduce(ucf_fit* f, const fit_request& q, const ucf_fit_reduce_args& ra, const fit_shape& sh, size_t nsum)
+{
+    const size_t nout = (size_t)sh.nout;
+    if (ra.d_set_of) HIP_TRY(hipMemcpy(f->b_setof.p, q.set_of, sizeof(int) * nout, hipMemcpyHostToDevice));
+    if (ra.d_rep) HIP_TRY(hipMemcpy(f->b_rep.p, q.rep, sizeof(int) * nout, hipMemcpyHostToDevice));
+    int rc = ucf_fit_launch_reduce(&ra, nullptr);
     if (rc) return fail(rc, "fit reduction kernel launch failed");
     HIP_TRY(hipStreamSynchronize(nullptr));
     f->h_sums.resize(nout * nsum);
-    HIP_TRY(hipMemcpy(f->h_sums.data(), f->b_sums.p, sizeof(double) * nout * nsum, hipMemcpyDeviceToHost));
-    if (nbad) HIP_TRY(hipMemcpy(nbad, f->b_nbad.p, sizeof(int) * nout, hipMemcpyDeviceToHost));
-    if (rs && rs->counts) HIP_TRY(hipMemcpy(rs->counts, f->b_counts.p, sizeof(int) * 4 * nout, hipMemcpyDeviceToHost));
-    if (J && jac) HIP_TRY(hipMemcpy(J, f->b_J.p, sizeof(double) * nsets * np_ * npar, hipMemcpyDeviceToHost));
-    if (sim_all) HIP_TRY(hipMemcpy(sim_all, f->b_sim.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
-    if (Jd && jac) HIP_TRY(hipMemcpy(Jd, f->b_Jd.p, sizeof(double) * nsets * np_ * npar, hipMemcpyDeviceToHost));
-    if (simd_all) HIP_TRY(hipMemcpy(simd_all, f->b_simd.p, sizeof(double) * tot, hipMemcpyDeviceToHost));
-    if (L.ndown) HIP_TRY(hipMemcpy(L.ndown, f->b_ndown.p, sizeof(int) * nsets, hipMemcpyDeviceToHost));
-    if (L.b) HIP_TRY(hipMemcpy(L.b, f->b_bfac.p, sizeof(double) * nsets * np_, hipMemcpyDeviceToHost));
-    if (L.bd) HIP_TRY(hipMemcpy(L.bd, f->b_bdfac.p, sizeof(double) * nsets * np_, hipMemcpyDeviceToHost));
+    return copy_back_sync({{f->h_sums.data(), ra.d_sums, sizeof(double) * nout * nsum}, {q.nbad, ra.d_nbad, sizeof(int) * nout},
+                           {q.counts, ra.d_counts, sizeof(int) * 4 * nout}, {q.J, ra.d_J, sh.bJ}, {q.sim_all, ra.d_sim, sh.bsim}, {q.Jd, ra.d_Jd, sh.bJ},
+                           {q.simd_all, ra.d_simd, sh.bsim}, {q.ndown, ra.d_ndown, sizeof(int) * sh.nsets}, {q.b, ra.d_b, sh.bfac}, {q.bd, ra.d_bd, sh.bfac}});
+}
+
+// 7. f->h_sums to the outputs of the request, through the layout that the launch wrote them in
+void fit_unpack(const ucf_fit* f, const fit_request& q, const ucf_fit_sums_layout& at, int nout, int npar)
+{
     for (int s = 0; s < nout; s++) {
-        const double* v = &f->h_sums[s * nsum];
-        if (phi) phi[s] = v[0];
-        if (phi_d) phi_d[s] = v[nsum - 1 - (robust ? 1 : 0) - (rs ? 1 : 0)];
-        if (rs) {
-            if (rs->phi_w) rs->phi_w[s] = v[nsum - 2];
-            if (rs->phi_out) rs->phi_out[s] = v[nsum - 1];
-        }
-        if (L.phi_w && !rs) L.phi_w[s] = robust ? v[nsum - 1] : v[0];      // least squares: every factor is 1.0
-        if (!jac) continue;
-        if (g) for (int j = 0; j < npar; j++) g[(size_t)s * npar + j] = v[1 + j];
-        if (A) {
-            int q = 1 + npar;
-            for (int j = 0; j < npar; j++)
-                for (int k = j; k < npar; k++, q++) A[((size_t)s * npar + j) * npar + k] = A[((size_t)s * npar + k) * npar + j] = v[q];
-        }
+        const double* v = &f->h_sums[(size_t)s * at.count];
+        if (q.phi) q.phi[s] = v[at.phi];
+        if (q.phi_d && at.phi_d >= 0) q.phi_d[s] = v[at.phi_d];
+        if (q.phi_w) q.phi_w[s] = v[at.phi_w >= 0 ? at.phi_w : at.phi];      // least squares: every factor is 1.0
+        if (q.phi_out) q.phi_out[s] = v[at.phi_out];
+        if (q.g) for (int j = 0; j < npar; j++) q.g[(size_t)s * npar + j] = v[at.g + j];
+        if (!q.A) continue;
+        const double* a = v + at.A;
+        for (int j = 0; j < npar; j++)
+            for (int k = j; k < npar; k++) q.A[((size_t)s * npar + j) * npar + k] = q.A[((size_t)s * npar + k) * npar + j] = *a++;
     }
+}
+
+// On a fit with derivative data the sums are the joint ones and phi_d, Jd, simd_all may be asked for.  The fit's loss and what is
+// asked for decide the instantiation; a least-squares fit asked for none of ndown, b, bd runs as a fit without a loss.
+int fit_evaluate(ucf_fit* f, int nsets, const double* theta, fit_request q)
+{
+    if (!q.jac) q.g = q.A = q.J = q.Jd = nullptr;
+    if (!q.resampled) { q.phi_out = nullptr; q.counts = nullptr; }
+    fit_shape sh;
+    int rc = fit_check_request(f, nsets, theta, q, sh);
+    if (rc) return rc;
+    device_switch dg(f->device);
+    if ((rc = fit_refresh_plans(f, theta, q.dlog, sh))) return rc;
+    ucf_fit_reduce_args ra = fit_reduce_asked(f, theta, q, sh);
+    const ucf_fit_sums_layout at = ucf_fit_sums_of(&ra);
+    if ((rc = fit_grow(f, ra, sh, (size_t)at.count)) || (rc = fit_simulate(f, sh.nplans)) || (rc = fit_reduce(f, q, ra, sh, (size_t)at.count))) return rc;
+    fit_unpack(f, q, at, sh.nout, ra.npar);
     return UCF_OK;
 }
 
@@ -938,7 +978,9 @@ long long ucf_fit_alloc_count(const ucf_fit* f)
 int ucf_fit_evaluate(ucf_fit* f, int nsets, const double* theta, double dlog, double* phi, double* g, double* A, int* nbad, double* J,
                      double* sim_all)
 {
-    return fit_evaluate(f, nsets, theta, dlog, 1, phi, g, A, nbad, J, sim_all);
+    fit_request q;
+    q.jac = 1; q.dlog = dlog; q.phi = phi; q.g = g; q.A = A; q.nbad = nbad; q.J = J; q.sim_all = sim_all;
+    return fit_evaluate(f, nsets, theta, q);
 }
 
 int ucf_fit_evaluate_joint(ucf_fit* f, int nsets, const double* theta, double dlog, double* phi, double* g, double* A, int* nbad, double* J,
@@ -946,7 +988,10 @@ int ucf_fit_evaluate_joint(ucf_fit* f, int nsets, const double* theta, double dl
 {
     if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (!f->deriv) return fail(UCF_ERR_BAD_ARGUMENT, "the fit has no derivative data (ucf_fit_set_derivative)");
-    return fit_evaluate(f, nsets, theta, dlog, 1, phi, g, A, nbad, J, sim_all, phi_d, Jd, simd_all);
+    fit_request q;
+    q.jac = 1; q.dlog = dlog; q.phi = phi; q.g = g; q.A = A; q.nbad = nbad; q.J = J; q.sim_all = sim_all;
+    q.phi_d = phi_d; q.Jd = Jd; q.simd_all = simd_all;
+    return fit_evaluate(f, nsets, theta, q);
 }
 
 // the trial-point evaluation of ucf_fit_lm with an entry of its own: base plans only, the npar = 0 reduction; dlog is not read
@@ -955,7 +1000,9 @@ int ucf_fit_objective(ucf_fit* f, int nsets, const double* theta, double* phi, i
     if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if ((phi_d || simd) && !f->deriv)
         return fail(UCF_ERR_BAD_ARGUMENT, "%s is asked for, but the fit has no derivative data (ucf_fit_set_derivative)", phi_d ? "phi_d" : "simd");
-    return fit_evaluate(f, nsets, theta, 0.0, 0, phi, nullptr, nullptr, nbad, nullptr, sim, phi_d, nullptr, simd);
+    fit_request q;
+    q.phi = phi; q.nbad = nbad; q.sim_all = sim; q.phi_d = phi_d; q.simd_all = simd;
+    return fit_evaluate(f, nsets, theta, q);
 }
 
 // ---- robust losses (include/ucf.h states the arithmetic; this file is compiled without contraction)
@@ -1028,9 +1075,9 @@ int ucf_fit_loss_report(ucf_fit* f, int nsets, const double* theta, double* phi,
 {
     if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (bd && !f->deriv) return fail(UCF_ERR_BAD_ARGUMENT, "bd is asked for, but the fit has no derivative data (ucf_fit_set_derivative)");
-    fit_loss_out lo;
-    lo.phi_w = phi_w; lo.ndown = ndown; lo.b = b; lo.bd = bd;
-    return fit_evaluate(f, nsets, theta, 0.0, 0, phi, nullptr, nullptr, nbad, nullptr, nullptr, nullptr, nullptr, nullptr, &lo);
+    fit_request q;
+    q.phi = phi; q.nbad = nbad; q.phi_w = phi_w; q.ndown = ndown; q.b = b; q.bd = bd;
+    return fit_evaluate(f, nsets, theta, q);
 }
 
 int ucf_fit_default_options(ucf_fit_options* opt)
@@ -1079,14 +1126,23 @@ static int fit_lm_core(ucf_fit* f, int nstarts, const double* theta0, bool resam
     std::vector<double> th, ph, gg, AA;
     std::vector<int> nb, rp;
     int rc = UCF_OK;
-    // the replicates of the starts in idx, in its order (resampled only; set_of is the identity over the sets of one evaluation)
-    fit_resample_io rs;
-    auto replicates = [&]() -> const fit_resample_io* {
-        if (!resampled) return nullptr;
-        rp.resize(idx.size());
-        for (size_t q = 0; q < idx.size(); q++) rp[q] = rep ? rep[idx[q]] : -1;
-        rs.nred = (int)idx.size(); rs.rep = rp.data();
-        return &rs;
+    // th = the rows of `from` that idx names, in its order
+    auto gather = [&](const double* from) {
+        th.resize(idx.size() * P);
+        for (size_t q = 0; q < idx.size(); q++) for (int j = 0; j < P; j++) th[q * P + j] = from[(size_t)idx[q] * P + j];
+    };
+    // phi and nbad of the starts in idx, in its order; resampled: each under its replicate (set_of is the identity over the sets
+    // of one evaluation)
+    auto request = [&](int jac) {
+        ph.resize(idx.size()); nb.resize(idx.size());
+        fit_request q;
+        q.jac = jac; q.dlog = opt.dlog; q.phi = ph.data(); q.nbad = nb.data();
+        if (resampled) {
+            rp.resize(idx.size());
+            for (size_t k = 0; k < idx.size(); k++) rp[k] = rep ? rep[idx[k]] : -1;
+            q.resampled = true; q.nred = (int)idx.size(); q.rep = rp.data();
+        }
+        return q;
     };
     for (;;) {
         // 1. objective, gradient and normal equations where the point has moved (one call for all of them)
@@ -1094,10 +1150,11 @@ static int fit_lm_core(ucf_fit* f, int nstarts, const double* theta0, bool resam
         for (int s = 0; s < nstarts; s++) if (active[s] && needJ[s]) idx.push_back(s);
         if (!idx.empty()) {
             const int n = (int)idx.size();
-            th.resize((size_t)n * P); ph.resize(n); gg.resize((size_t)n * P); AA.resize(n * PP); nb.resize(n);
-            for (int q = 0; q < n; q++) for (int j = 0; j < P; j++) th[(size_t)q * P + j] = theta[(size_t)idx[q] * P + j];
-            rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), gg.data(), AA.data(), nb.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, replicates());
+            gather(theta);
+            gg.resize((size_t)n * P); AA.resize(n * PP);
+            fit_request ask = request(1);
+            ask.g = gg.data(); ask.A = AA.data();
+            rc = fit_evaluate(f, n, th.data(), ask);
             if (rc) return rc;
             for (int q = 0; q < n; q++) {
                 const int s = idx[q];
@@ -1123,14 +1180,14 @@ static int fit_lm_core(ucf_fit* f, int nstarts, const double* theta0, bool resam
         }
         if (idx.empty()) break;
         const int n = (int)idx.size();
-        th.resize((size_t)n * P); ph.resize(n); nb.resize(n);
+        th.resize((size_t)n * P);
         for (int q = 0; q < n; q++)
             for (int j = 0; j < P; j++) th[(size_t)q * P + j] = std::exp(x[(size_t)idx[q] * P + j] + step[(size_t)idx[q] * P + j]);
+        const fit_request trial = request(0);
         bool finite_trial = true;
         for (double v : th) finite_trial = finite_trial && std::isfinite(v) && v > 0.0;
         if (finite_trial) {
-            rc = fit_evaluate(f, n, th.data(), opt.dlog, 0, ph.data(), nullptr, nullptr, nb.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, replicates());
+            rc = fit_evaluate(f, n, th.data(), trial);
             if (rc != UCF_OK && rc != UCF_ERR_BAD_ARGUMENT && rc != UCF_ERR_HIP && rc != UCF_ERR_NOMEM && rc != UCF_ERR_NO_DEVICE) finite_trial = false;   // a trial outside the model's range: rejected below
             else if (rc) return rc;
         }
@@ -1170,19 +1227,18 @@ static int fit_lm_core(ucf_fit* f, int nstarts, const double* theta0, bool resam
         const int dof_all = f->nobs + (f->deriv ? f->nd : 0) - P;
         if (!idx.empty() && (resampled || dof_all > 0)) {
             const int n = (int)idx.size();
-            th.resize((size_t)n * P); ph.resize(n); AA.resize(n * PP); nb.resize(n);
-            for (int q = 0; q < n; q++) for (int j = 0; j < P; j++) th[(size_t)q * P + j] = theta[(size_t)idx[q] * P + j];
+            gather(theta);
+            AA.resize(n * PP);
             // under a robust loss the variance factor is phi_w of this evaluation: the weighted least-squares problem that the
             // final factors define (include/ucf.h); under least squares it stays the phi the iteration ended with
             const bool robust = resampled || f->loss != UCF_LOSS_L2;
             std::vector<double> pw(robust ? n : 0), po(resampled ? n : 0);
             std::vector<int> cnt(resampled ? 4 * (size_t)n : 0);
-            fit_loss_out lo;
-            lo.phi_w = robust ? pw.data() : nullptr;
-            const fit_resample_io* fin = replicates();
-            if (fin) { rs.phi_w = pw.data(); rs.phi_out = po.data(); rs.counts = cnt.data(); }
-            rc = fit_evaluate(f, n, th.data(), opt.dlog, 1, ph.data(), nullptr, AA.data(), nb.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                              robust && !resampled ? &lo : nullptr, fin);
+            fit_request ask = request(1);
+            ask.A = AA.data();
+            if (robust) ask.phi_w = pw.data();
+            if (resampled) { ask.phi_out = po.data(); ask.counts = cnt.data(); }
+            rc = fit_evaluate(f, n, th.data(), ask);
             if (rc) return rc;
             for (int q = 0; q < n; q++) {
                 const int s = idx[q];
@@ -1274,9 +1330,10 @@ int ucf_fit_evaluate_resampled(ucf_fit* f, int nsets, const double* theta, doubl
 {
     if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (phi_d && !f->deriv) return fail(UCF_ERR_BAD_ARGUMENT, "phi_d is asked for, but the fit has no derivative data (ucf_fit_set_derivative)");
-    fit_resample_io rs;
-    rs.nred = nred; rs.set_of = set_of; rs.rep = rep; rs.phi_w = phi_w; rs.phi_out = phi_out; rs.counts = counts;
-    return fit_evaluate(f, nsets, theta, dlog, 1, phi, g, A, nbad, nullptr, nullptr, phi_d, nullptr, nullptr, nullptr, &rs);
+    fit_request q;
+    q.jac = 1; q.dlog = dlog; q.phi = phi; q.g = g; q.A = A; q.nbad = nbad; q.phi_d = phi_d; q.phi_w = phi_w;
+    q.resampled = true; q.nred = nred; q.set_of = set_of; q.rep = rep; q.phi_out = phi_out; q.counts = counts;
+    return fit_evaluate(f, nsets, theta, q);
 }
 
 int ucf_fit_objective_resampled(ucf_fit* f, int nsets, const double* theta, int nred, const int* set_of, const int* rep, double* phi, int* nbad,
@@ -1284,9 +1341,10 @@ int ucf_fit_objective_resampled(ucf_fit* f, int nsets, const double* theta, int 
 {
     if (!f) return fail(UCF_ERR_BAD_ARGUMENT, "NULL argument");
     if (phi_d && !f->deriv) return fail(UCF_ERR_BAD_ARGUMENT, "phi_d is asked for, but the fit has no derivative data (ucf_fit_set_derivative)");
-    fit_resample_io rs;
-    rs.nred = nred; rs.set_of = set_of; rs.rep = rep; rs.phi_w = phi_w; rs.phi_out = phi_out; rs.counts = counts;
-    return fit_evaluate(f, nsets, theta, 0.0, 0, phi, nullptr, nullptr, nbad, nullptr, nullptr, phi_d, nullptr, nullptr, nullptr, &rs);
+    fit_request q;
+    q.phi = phi; q.nbad = nbad; q.phi_d = phi_d; q.phi_w = phi_w;
+    q.resampled = true; q.nred = nred; q.set_of = set_of; q.rep = rep; q.phi_out = phi_out; q.counts = counts;
+    return fit_evaluate(f, nsets, theta, q);
 }
 
 int ucf_fit_resample_blocks(int nobs, const int* block, int nrep, unsigned long long seed, unsigned short* mult, int* nblock)

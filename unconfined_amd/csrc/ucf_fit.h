@@ -1,10 +1,20 @@
 // ucf_fit.h -- launcher of the fit reduction (ucf_fit.hip), called by ucf_fit_evaluate (ucf_fit.cpp).
 #pragma once
 
-// sums per parameter set: phi | g[npar] | upper triangle of A, row by row (j <= k); with derivative data: ... | phi_d, the
-// derivative terms' share of phi; a robust reduction (ucf_fit_reduce_is_robust) ends with one more: ... | phi_w
-static inline int ucf_fit_nsums(int npar) { return 1 + npar + npar * (npar + 1) / 2; }
-static inline int ucf_fit_joint_nsums(int npar) { return ucf_fit_nsums(npar) + 1; }
+#include <cstddef>
+
+// The sums of one parameter set (of one reduction, when resampled) in d_sums, stated once: the kernel places them, the host
+// sizes its buffers and reads them through this.  phi | g[npar] | upper triangle of A, row by row (j <= k) | [phi_d] the
+// derivative terms' share of phi, with derivative data | [phi_w] under a robust or resampled reduction | [phi_out] the held-out
+// observations' squares, resampled only.  -1: the launch has no such sum; count = doubles per set.
+struct ucf_fit_sums_layout {
+    int phi, g, A, phi_d, phi_w, phi_out, count;
+};
+constexpr ucf_fit_sums_layout ucf_fit_sums(int npar, bool deriv, bool robust, bool resampled)
+{
+    const int nA = npar * (npar + 1) / 2, tail = 1 + npar + nA, d = deriv ? 1 : 0, w = (robust || resampled) ? 1 : 0;
+    return {0, 1, 1 + npar, deriv ? tail : -1, w ? tail + d : -1, resampled ? tail + d + w : -1, tail + d + w + (resampled ? 1 : 0)};
+}
 
 // Where an observation of a network fit (ucf_fit_create_network) finds its simulated value.  The h of a network is ragged:
 // one region per group of wells with the same number of depths, group g at nplans * prefix_g doubles, plan k of it at
@@ -50,7 +60,7 @@ struct ucf_fit_reduce_args {
     const double* d_tfac;                  // [terms] t_i / (t_i - t0) of each term; read with derivative data only
     const double *d_obs, *d_w;             // [nobs]
     const double *d_dobs, *d_wd;           // [nobs], with derivative data; d_dobs[i] is read only where d_wd[i] > 0
-    double* d_sums;                        // [nsets][ucf_fit_nsums(npar)], with derivative data ucf_fit_joint_nsums(npar)
+    double* d_sums;                        // [nsets][ucf_fit_sums_of(this).count], resampled [nred][..]: ucf_fit_sums_layout
     int* d_nbad;                           // [nsets]
     double *d_J, *d_sim;                   // [nsets][nobs][npar], [nsets][1+2 npar][nobs]; each may be NULL
     double *d_Jd, *d_simd;                 // the same of the derivative; each may be NULL
@@ -76,11 +86,10 @@ struct ucf_fit_reduce_args {
 };
 static inline int ucf_fit_reduce_is_resampled(const ucf_fit_reduce_args* a) { return a->nred > 0; }
 static inline int ucf_fit_reduce_is_robust(const ucf_fit_reduce_args* a) { return a->loss != 0 || a->d_ndown || a->d_b || a->d_bd; }
-// doubles per set (per reduction) of d_sums that the launch of `a` writes
-static inline int ucf_fit_reduce_nsums(const ucf_fit_reduce_args* a)
+// where the launch of `a` writes its sums: by the predicates that choose its instantiation (launch_source, ucf_fit.hip)
+static inline ucf_fit_sums_layout ucf_fit_sums_of(const ucf_fit_reduce_args* a)
 {
-    return (a->d_dh ? ucf_fit_joint_nsums(a->npar) : ucf_fit_nsums(a->npar)) +
-           (ucf_fit_reduce_is_resampled(a) ? 2 : (ucf_fit_reduce_is_robust(a) ? 1 : 0));
+    return ucf_fit_sums(a->npar, a->d_dh != NULL, ucf_fit_reduce_is_robust(a) != 0, ucf_fit_reduce_is_resampled(a) != 0);
 }
 
 int ucf_fit_launch_reduce(const ucf_fit_reduce_args* a, void* stream);

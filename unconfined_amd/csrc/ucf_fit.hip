@@ -98,7 +98,8 @@ __device__ __forceinline__ void fit_reduce_body(int nobs, double two_dlog, const
     constexpr int NP = NPAR > 0 ? NPAR : 1;                  // array extents (NPAR = 0: objective only)
     constexpr int NPLANS = 1 + 2 * NPAR;
     constexpr int NA = NPAR * (NPAR + 1) / 2;
-    constexpr int NSUMS = 1 + NPAR + NA + (DERIV ? 1 : 0) + (ROBUST ? 1 : 0) + (RESAMPLE ? 1 : 0);
+    constexpr ucf_fit_sums_layout AT = ucf_fit_sums(NPAR, DERIV, ROBUST, RESAMPLE);      // where the sums of a set go
+    constexpr int NSUMS = AT.count;
     __shared__ double part[FIT_WAVES][NSUMS];
     __shared__ int part_bad[FIT_WAVES], part_down[FIT_WAVES];
     const int lane = threadIdx.x;
@@ -284,15 +285,15 @@ __device__ __forceinline__ void fit_reduce_body(int nobs, double two_dlog, const
     }
     [[maybe_unused]] __shared__ int part_cnt[RESAMPLE ? FIT_WAVES : 1][3];
     if ((lane & 63) == 0) {
-        part[wave][0] = phi;
+        part[wave][AT.phi] = phi;
 #pragma unroll
-        for (int j = 0; j < NPAR; j++) part[wave][1 + j] = g[j];
+        for (int j = 0; j < NPAR; j++) part[wave][AT.g + j] = g[j];
 #pragma unroll
-        for (int j = 0; j < NA; j++) part[wave][1 + NPAR + j] = A[j];
-        if constexpr (DERIV) part[wave][1 + NPAR + NA] = phi_d;
-        if constexpr (ROBUST) { part[wave][NSUMS - 1 - (RESAMPLE ? 1 : 0)] = phi_w; part_down[wave] = down; }
+        for (int j = 0; j < NA; j++) part[wave][AT.A + j] = A[j];
+        if constexpr (DERIV) part[wave][AT.phi_d] = phi_d;
+        if constexpr (ROBUST) { part[wave][AT.phi_w] = phi_w; part_down[wave] = down; }
         if constexpr (RESAMPLE) {
-            part[wave][NSUMS - 1] = phi_out;
+            part[wave][AT.phi_out] = phi_out;
             part_cnt[wave][0] = nuse; part_cnt[wave][1] = nuse_d; part_cnt[wave][2] = nheld;
         }
         part_bad[wave] = bad;
