@@ -14,7 +14,11 @@ usage: tools/folded_loop_phase_shares.py            the grids of tests/test_gpu_
        tools/folded_loop_phase_shares.py units
             the bench sweep's quadrature units (J0 intervals, the tanh-sinh part in 1 / 2 / 4 runs, 12-node runs of unproven
             intervals) by what the bounds alone decide (zpair_unit_bounds; bound_class_v() below) and what the exact
-            classifier behind them still proves"""
+            classifier behind them still proves
+       tools/folded_loop_phase_shares.py sh [bench]
+            UCF_PH_SH (Re eta zD >= 0.35 in every lane from here on: sinh without its series test): the share of the proven
+            cosh/sinh Gauss-Lobatto pairs that run with the bit, and where in a part it is set -- the grids of
+            tests/test_gpu_folded_loop_drops.py, or the bench sweep"""
 import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -256,6 +260,131 @@ def unit_shares(tD, radii, zD):
     return cnt, cls_pairs, stronger
 
 
+# ---- UCF_PH_SH: "Re eta zD >= 0.35 in every lane from here on", so that sinh(eta zD) and sinh(eta) never take their series
+# again (prim_from_e).  Set by the units' classifiers, from the lower end of a unit proven on the cosh/sinh form: by the
+# bounds (kappa (Re eta)^2 >= Re p + lob^2 against zb[UCF_ZB_SH]) or, where they did not decide the unit, from Re eta at lob.
+# A proven cosh/sinh J0 interval of a part that has the bit runs the loop without the series test.
+SINH_SERIES = 0.35
+
+
+def sh_limit(zD, kappa=None):
+    kappa = P.kappa if kappa is None else kappa
+    with np.errstate(divide="ignore"):
+        s = np.float64(SINH_SERIES) / np.float64(zD)
+        return float(kappa * (s * s) / (1.0 - 2.0 ** -19))
+
+
+def sh_bound_v(p, lob, zD, kappa=None):
+    """the bounds' test for waves p[lane, ...]: a bool array over the trailing indices"""
+    with np.errstate(all="ignore"):
+        return np.all(lob * lob + p.real > sh_limit(zD, kappa), axis=0)
+
+
+def sh_exact_v(p, lob, zD, kappa=None):
+    """the exact classifier's test"""
+    kappa = P.kappa if kappa is None else kappa
+    with np.errstate(all="ignore"):
+        re_lo = np.sqrt((p + lob * lob) / kappa).real
+        return np.all(re_lo * (1.0 - 2.0 ** -20) * zD >= SINH_SERIES, axis=0)
+
+
+def interval_class_v(p, lob, hib, zD, kappa=None):
+    """interval_class for waves p[lane][m]: the index into CLASSES per m"""
+    kappa = P.kappa if kappa is None else kappa
+    with np.errstate(all="ignore"):
+        eta_hi, eta_lo = np.sqrt((p + hib * hib) / kappa), np.sqrt((p + lob * lob) / kappa)
+        re_hi, re_lo, im_lo = eta_hi.real, eta_lo.real, np.abs(eta_lo.imag)
+        ok = np.all((p.real > 0.0) & (re_hi * 1.01 <= FAST_ETA_MAX) & (im_lo * 2.0 < FAST_IM_MAX), axis=0)
+        ys = np.all(im_lo < SMALL, axis=0)
+        yl = ys | np.all(im_lo * (1.0 - zD) < SMALL, axis=0)
+        cs = np.all(re_hi * (1.0 + 2.0 ** -20) < maxexp, axis=0)
+        ex = ~cs & np.all(re_lo * (1.0 - 2.0 ** -20) > maxexp, axis=0)
+    out = np.full(ok.shape, CLASSES.index("unproven"))
+    out[ok & cs & ys] = CLASSES.index("cs_short")
+    out[ok & cs & ~ys] = CLASSES.index("cs_tab")
+    out[ok & ex & yl] = CLASSES.index("ex_short")
+    out[ok & ex & ~yl] = CLASSES.index("ex_tab")
+    return out
+
+
+def part_cuts(nsplit):
+    """the abscissae at which integrate_kernel cuts an item into nsplit parts (part_bound)"""
+    nabs = N + nacc * ngl
+    cuts = [0]
+    for k in range(1, nsplit):
+        j = (k * nabs // nsplit - N + ngl // 2) // ngl
+        cuts.append(N + min(max(j, 0), nacc) * ngl)
+    return cuts + [nabs]
+
+
+def sh_walk(p, a, s, rD, zD, nsplit=1, ts_runs_n=2):
+    """One wave's items (p[lane][m], every m an item) through the units as the kernel classifies them, part by part (the bits
+    are cleared at the start of a part).  Returns a list of (kind, first node, end node, class index [m], the unit's own
+    classification set the bit [m], the part has the bit when the unit runs [m], part index, lob, hib)."""
+    cuts = part_cuts(nsplit)
+    units = [("ts", b, e, 0.0 if b == 0 else a[b], a[e - 1]) for b, e in ts_runs(ts_runs_n)]
+    units += [("interval", N + jj * ngl, N + (jj + 1) * ngl, j0z[s + jj - 1] / rD, j0z[s + jj] / rD) for jj in range(nacc)]
+    out = []
+    nm = p.shape[1]
+    CS = (CLASSES.index("cs_tab"), CLASSES.index("cs_short"))
+    for ip, (c0, c1) in enumerate(zip(cuts, cuts[1:])):
+        have = np.zeros(nm, bool)
+        for kind, b, e, lob, hib in units:
+            if not (c0 <= b < c1):
+                continue
+            bc = bound_class_v(p, lob, hib, zD)
+            ec = interval_class_v(p, lob, hib, zD)
+            cls = np.where(bc != UNDECIDED, bc, ec)
+            is_cs = (cls == CS[0]) | (cls == CS[1])
+            sets = is_cs & np.where(bc != UNDECIDED, sh_bound_v(p, lob, zD), sh_exact_v(p, lob, zD))
+            have = have | sets
+            out.append((kind, b, e, cls, sets, have.copy(), ip, lob, hib))
+    return out
+
+
+def sh_shares(tD, radii, zD, nsplit=1):
+    """(wave, abscissa) pairs of proven cosh/sinh J0 intervals with and without the bit; parts by what happens to the bit"""
+    cnt = dict(cs_sh=0, cs_plain=0, ts_cs=0, other=0)
+    ev = dict(parts=0, never=0, from_start=0, inside=0, lanes_split=0, ts_sets=0, first_of_part_after_none=0)
+    CS = (CLASSES.index("cs_tab"), CLASSES.index("cs_short"))
+    for s, p in waves(tD):
+        for rD in radii:
+            a = row(rD, s)
+            walk = sh_walk(p, a, s, rD, zD, nsplit)
+            nparts = walk[-1][6] + 1
+            prev_had = None
+            for ip in range(nparts):
+                us = [u for u in walk if u[6] == ip]
+                had_end = us[-1][5]
+                iv = [u for u in us if u[0] == "interval"]
+                ev["parts"] += had_end.size
+                ev["never"] += int((~had_end).sum())
+                ev["from_start"] += int(us[0][4].sum())
+                for i, u in enumerate(us):
+                    new = u[4] & ~(us[i - 1][5] if i else np.zeros(had_end.size, bool))
+                    if i:
+                        ev["inside"] += int(new.sum())
+                    if u[0] == "ts":
+                        ev["ts_sets"] += int(new.sum())
+                    # some lanes past the limit at the unit's lower end, others not: the wave waits for the last of them
+                    is_cs = (u[3] == CS[0]) | (u[3] == CS[1])
+                    with np.errstate(all="ignore"):
+                        past = np.sqrt((p + u[7] * u[7]) / P.kappa).real * zD >= SINH_SERIES
+                    ev["lanes_split"] += int((is_cs & past.any(0) & ~past.all(0)).sum())
+                if prev_had is not None:
+                    ev["first_of_part_after_none"] += int((us[0][4] & ~prev_had).sum())
+                prev_had = had_end
+                for u in iv:
+                    is_cs = (u[3] == CS[0]) | (u[3] == CS[1])
+                    cnt["cs_sh"] += ngl * int((is_cs & u[5]).sum())
+                    cnt["cs_plain"] += ngl * int((is_cs & ~u[5]).sum())
+                    cnt["other"] += ngl * int((~is_cs).sum())
+                for u in us:
+                    if u[0] == "ts":
+                        cnt["ts_cs"] += (u[2] - u[1]) * int(((u[3] == CS[0]) | (u[3] == CS[1])).sum())
+    return cnt, ev
+
+
 def bench_grid():
     return O.logspace(-1, 8, 1024) / D.Tc, np.logspace(-1, 1, 256)[::8], 145.7 / D.Lc      # (bench.py's radii span rD = 0.1 ... 10)
 
@@ -279,6 +408,22 @@ if __name__ == "__main__":
         n = sum(cls_pairs.values())
         print("Gauss-Lobatto pairs by class, bounds first:", {k: round(100.0 * v / n, 1) for k, v in cls_pairs.items()},
               "; intervals where the bounds decide another class than the exact classifier:", stronger)
+    elif args[:1] == ["sh"]:
+        def sh_line(tag, cnt, ev):
+            cs = cnt["cs_sh"] + cnt["cs_plain"]
+            print(f"{tag:22s} proven cosh/sinh Gauss-Lobatto pairs {cs:9d} ({100.0 * cs / max(cs + cnt['other'], 1):5.1f} % of all), "
+                  f"with UCF_PH_SH {100.0 * cnt['cs_sh'] / max(cs, 1):5.1f} %; cosh/sinh tanh-sinh pairs {cnt['ts_cs']}")
+            print(f"{'':22s} parts {ev['parts']}: never set {ev['never']}, set by the part's first unit {ev['from_start']} "
+                  f"(the part before ended without it: {ev['first_of_part_after_none']}), set by a later unit {ev['inside']}, "
+                  f"by a tanh-sinh run {ev['ts_sets']}; cosh/sinh units with lanes on both sides of the limit at their lower end {ev['lanes_split']}")
+        if args[1:2] == ["bench"]:
+            tD, rD, zD = bench_grid()
+            sh_line("bench C2", *sh_shares(tD, rD, zD))
+        else:
+            import test_gpu_folded_loop_drops as TD
+            for tag, beta, zD, cut, clusters, radii in TD.CALLS:
+                tD = np.concatenate([np.logspace(c, c + 0.5, 64) for c in clusters])
+                sh_line(tag, *sh_shares(tD, np.array(radii), zD, int(cut.get("UCF_NSPLIT", 1))))
     elif args[:1] == ["bench"]:
         tD, rD, zD = bench_grid()
         line("bench C2", *shares(tD, rD, zD))

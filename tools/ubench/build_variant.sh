@@ -18,5 +18,5 @@ for l in 0 1 2 3; do
   esac
 done
 wait
-hipcc --offload-arch=gfx950 -shared -fPIC -o $here/libucf_$tag.so $src/build/kernels_faithful.o $objs $src/build/peak.o $src/build/fit.o $src/build/field.o $src/build/host_*.o
+hipcc --offload-arch=gfx950 -shared -fPIC -o $here/libucf_$tag.so $src/build/kernels_faithful.o $objs $src/build/peak.o $src/build/fit.o $src/build/field.o $src/build/field_ensemble.o $src/build/field_worth.o $src/build/field_yield.o $src/build/host_*.o
 echo "built $here/libucf_$tag.so"

@@ -66,6 +66,8 @@ UCF_DEV void stat_add(long long* ctr, bool pred)
 #define UCF_TU_HAS(L) (UCF_TU < 0 || UCF_TU == (L))
 
 typedef double2 lds_c;   // one complex per lane per slot
+// a double in memory that no kernel writes (the constant address space): a load at a wave-uniform address is a scalar load
+typedef __attribute__((address_space(4))) double ucf_const_double;
 UCF_DEV cplx lds_ld(const lds_c* base, int slot, int lane) { lds_c v = base[slot * UCF_WAVE + lane]; return cmake(v.x, v.y); }
 UCF_DEV void lds_st(lds_c* base, int slot, int lane, cplx z) { base[slot * UCF_WAVE + lane] = make_double2(z.re, z.im); }
 // scratch columns hold UCF_PART lanes per slot (ucf_launch_plan.h)
@@ -1889,6 +1891,10 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
             const double* __restrict__ ends = (const double*)tab + abscissa_ends_offset((size_t)nr * nsv, nabs) + (size_t)(W.ir * nsv + (sv - svmin)) * (nacc + 1);
             const double* __restrict__ zb = (const double*)tab + abscissa_limits_offset((size_t)nr * nsv, nabs, nacc);
             int settled = 0;
+            // The level weights, taken once per item as a pointer to constant memory (the plan's tables are written before any
+            // launch and never by a kernel): the index is wave-uniform, so the weight of a level update comes by scalar load
+            // like every other table of the loops, not by a vector load that the update then waits for
+            const ucf_const_double* const tsw = (const ucf_const_double*)P.ts_w;
             if (nlim > n0) zph = zpair_part_phase(P, LC, ends[nlim > N ? (nlim - N + ngl - 1) / ngl : 0]);
             const int nts = nlim < N ? nlim : N;
             // The tanh-sinh part in TS_RUNS runs of nodes (they ascend: a run lies between its own first and last
@@ -1905,7 +1911,7 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                     if (tz > R - 1) tz = R - 1;
                     for (int sh = 0; sh <= tz; sh++) {                                       // (driver.f90:129-157)
                         const int j = R - sh;
-                        const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
+                        const double wl = tsw[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
                         lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
                     }
                     aa = nxt;
@@ -1942,7 +1948,7 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                         if (tz > R - 1) tz = R - 1;
                         for (int sh = 0; sh <= tz; sh++) {                                   // (driver.f90:129-157)
                             const int j = R - sh;
-                            const double wl = P.ts_w[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
+                            const double wl = tsw[(size_t)(j - 1) * N + ((n1 >> sh) - 1)];
                             lds_st(accTS, j - 1, lane, cadd(lds_ld(accTS, j - 1, lane), rscale(wl, val)));
                         }
                         aa = nxt;
@@ -1985,8 +1991,13 @@ integrate_kernel(const ucf_dev_params P0, int npts, int per_point, int nr, int n
                     zph |= known;
                     if (cls == UCF_IV_EX_SHORT && (zph & UCF_PH_RANGE)) settled = 1;
                 }
+                // (a proven cosh/sinh interval of a part that has UCF_PH_SH: the loop without the series test of sinh.  The
+                //  tanh-sinh runs keep the plain loops: four more would not fit the 64 KB instruction cache)
+                if ((zph & UCF_PH_SH) && (cls == UCF_IV_CS_TAB || cls == UCF_IV_CS_SHORT)) cls += UCF_IV_CS_TAB_SH - UCF_IV_CS_TAB;
                 if (cls == UCF_IV_CS_TAB) proven_class(std::integral_constant<int, UCF_IV_CS_TAB>());
                 else if (cls == UCF_IV_CS_SHORT) proven_class(std::integral_constant<int, UCF_IV_CS_SHORT>());
+                else if (cls == UCF_IV_CS_TAB_SH) proven_class(std::integral_constant<int, UCF_IV_CS_TAB_SH>());
+                else if (cls == UCF_IV_CS_SHORT_SH) proven_class(std::integral_constant<int, UCF_IV_CS_SHORT_SH>());
                 else if (cls == UCF_IV_EX_TAB) proven_class(std::integral_constant<int, UCF_IV_EX_TAB>());
                 else if (cls == UCF_IV_EX_SHORT) proven_class(std::integral_constant<int, UCF_IV_EX_SHORT>());
                 else {

@@ -34,7 +34,8 @@ struct fprim {
 
 // (the part of prim after e = exp(ax) and ei = 1/e)
 // SMALLY: the caller knows 0 <= y < UCF_SC_SMALL (sincos_small_)
-template <bool POS, bool SMALLY = false>
+// NOSERIES: the caller knows ax >= UCF_ZB_SINH_SERIES in every lane (UCF_PH_SH): the difference form alone, no test
+template <bool POS, bool SMALLY = false, bool NOSERIES = false>
 UCF_DEV fprim prim_from_e(double x, double ax, double e, double ei, double y, const sc_ctx& sc)
 {
     const int salt = sc.salt;
@@ -43,7 +44,9 @@ UCF_DEV fprim prim_from_e(double x, double ax, double e, double ei, double y, co
     const double he = 0.5 * e;
     f.ch = __builtin_fma(0.5, ei, he);
     double s;
-    if (ax < 0.35) {
+    if (NOSERIES) {
+        s = __builtin_fma(-0.5, ei, he);
+    } else if (ax < UCF_ZB_SINH_SERIES) {
         const double x2 = ax * ax;
         double pl = addk(mulk(x2, UCF_KHERE(1.0 / 6227020800.0, salt)), UCF_KHERE(1.0 / 39916800.0, salt));
         pl = fmak(pl, x2, UCF_KHERE(1.0 / 362880.0, salt));
@@ -75,15 +78,18 @@ UCF_DEV fprim prim(double x, double y, const sc_ctx& sc)
 // canonicalises both operands (v_max_f64 of a value with itself, for the sake of signalling NaNs), one of them the
 // loop-invariant cap.  x has passed fast_eta_wave's range test, so it is a number, and v_min_f64 returns the same bits.
 // xcap is wave-uniform (one plan per launch) and is read from its SGPR pair
+// CLAMP = false: the caller knows x < xcap in every lane (a unit proven on the cosh/sinh form): v_min_f64 would return x
+// bit for bit and is not issued.  NOSERIES: x zD >= UCF_ZB_SINH_SERIES in every lane, and so is x (zD <= 1): prim_from_e
+template <bool CLAMP = true, bool NOSERIES = false>
 UCF_DEV void prim_pair_min(double x, double y, double zD, double xcap, const sc_ctx& sc, fprim* f, fprim* fz)
 {
-    double xc;
-    asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(xcap));
+    double xc = x;
+    if (CLAMP) asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(xcap));
     const double xz = xc * zD;
     const double e = exp_tab_(xc, sc), ez = exp_tab_(xz, sc);
     const double r = fast_rcp(e * ez);
-    *f = prim_from_e<true>(xc, xc, e, r * ez, y, sc);
-    *fz = prim_from_e<true>(xz, xz, ez, r * e, y * zD, sc);
+    *f = prim_from_e<true, false, NOSERIES>(xc, xc, e, r * ez, y, sc);
+    *fz = prim_from_e<true, false, NOSERIES>(xz, xz, ez, r * e, y * zD, sc);
 }
 // primitive of x1 - x2, y1 - y2 from the primitives of (x1, y1) and (x2, y2), 0 <= x2 <= x1: the real
 // exponentials divide, the angles subtract (no cancellation in either; sinh of a small difference loses
@@ -123,16 +129,17 @@ UCF_DEV cplx expneg_small(double x, double y, const sc_ctx& sc)
     return cmake(ei * cs, -(ei * sn));
 }
 // prim_pair_min for 0 <= y < UCF_SC_SMALL (and so 0 <= y zD < UCF_SC_SMALL): prim_from_e<true> with both sin/cos in
-// the short form, operation for operation
+// the short form, operation for operation (CLAMP, NOSERIES: as there)
+template <bool CLAMP = true, bool NOSERIES = false>
 UCF_DEV void prim_pair_small(double x, double y, double zD, double xcap, const sc_ctx& sc, fprim* f, fprim* fz)
 {
-    double xc;
-    asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(xcap));
+    double xc = x;
+    if (CLAMP) asm("v_min_f64 %0, %1, %2" : "=v"(xc) : "v"(x), "s"(xcap));
     const double xz = xc * zD;
     const double e = exp_tab_(xc, sc), ez = exp_tab_(xz, sc);
     const double r = fast_rcp(e * ez);
-    *f = prim_from_e<true, true>(xc, xc, e, r * ez, y, sc);
-    *fz = prim_from_e<true, true>(xz, xz, ez, r * e, y * zD, sc);
+    *f = prim_from_e<true, true, NOSERIES>(xc, xc, e, r * ez, y, sc);
+    *fz = prim_from_e<true, true, NOSERIES>(xz, xz, ez, r * e, y * zD, sc);
 }
 
 // a b + c in four FMAs (one rounding less per component than product, then sum)
@@ -290,7 +297,9 @@ enum {
     UCF_PH_IM = 2,       // |Im eta| < fast_im_max / 2 in every lane: in range from here on
     UCF_PH_LARGE = 4,    // Re eta > maxexp (1 + 2^-20) in every lane: no lane returns to the cosh/sinh form
     UCF_PH_YS = 8,       // |Im eta| < UCF_SC_SMALL in every lane: both sin/cos of the cosh/sinh form take sincos_small_
-    UCF_PH_YL = 16       // |Im eta| (1 - zD) < UCF_SC_SMALL in every lane: so does the one of the exponential form
+    UCF_PH_YL = 16,      // |Im eta| (1 - zD) < UCF_SC_SMALL in every lane: so does the one of the exponential form
+    UCF_PH_SH = 32       // Re eta zD >= UCF_ZB_SINH_SERIES (1 + 2^-20) in every lane: sinh(eta zD) and sinh(eta) are past their
+                         // series for good (set by the units' classifiers only, read by the proven cosh/sinh loops; never at zD = 0)
 };
 // The bits known before the first abscissa of a part none of whose abscissae exceeds a_max (wave-uniform: the upper end of
 // the part's last quadrature interval): Re p > 0 gives Re q >= Re p > 0 whatever a; Re eta <= sqrt(|q| / kappa) <=
@@ -595,12 +604,13 @@ UCF_DEV cplx fast_sample_z(const ucf_dev_params& P, const fast_common& S, int iz
 // until it first holds, the form test until every lane is past maxexp by a margin.  A wave with lanes on both forms takes
 // the general code.  (One plan per launch: a parameter batch never folds.)
 // KB: what the caller knows of beta (wave-uniform): -1 nothing (tested here), 0 beta = 0, 1 beta != 0
-template <bool SMALLY, int KB = -1>
+// PROVEN: every lane is on this form (a proven unit): no clamp.  SH: ... and UCF_PH_SH holds: no series test (prim_pair_min)
+template <bool SMALLY, int KB = -1, bool PROVEN = false, bool SH = false>
 UCF_DEV void zpair_arm_small(const ucf_dev_params& P, const lane_consts& L, const fast_common& S, double zD, cplx* g, cplx* den)
 {
     fprim p1, pz;
-    if (SMALLY) prim_pair_small(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
-    else prim_pair_min(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
+    if (SMALLY) prim_pair_small<!PROVEN, SH>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
+    else prim_pair_min<!PROVEN, SH>(S.eta.re, S.eta.im, zD, P.maxexp, S.sc, &p1, &pz);
     *g = pcosh(pz);
     const cplx che = pcosh(p1), she = psinh(p1);
     const cplx xi = cmul(S.eta, L.xifac);
@@ -690,13 +700,22 @@ UCF_DEV cplx fast_sample_zpair(const ucf_dev_params& P, const lane_consts& L, co
 // runs the loop with the UCF_PH_* bits.  Margins as the bits have them, none of which a rounding of the computed eta
 // bridges (it follows the true one to a few ulp): 1 % on fast_eta_max, a factor 2 on fast_im_max, 2^-20 on maxexp;
 // UCF_SC_SMALL carries its own 2 % (ucf_math.h).  A NaN proves nothing.
+// A unit proven on the cosh/sinh form also settles, from its lower end, whether sinh still needs its series (UCF_PH_SH: Re eta zD
+// past UCF_ZB_SINH_SERIES by 2^-20 in every lane -- Re eta only grows, so it holds for the rest of the part; zD = 0 never
+// passes).  A proven cosh/sinh J0 interval of a part that has the bit runs the loop of the _SH twin of its class, whose two
+// prim_from_e hold the difference form alone; the tanh-sinh runs keep the plain loops (the instruction cache has no room for
+// four more), and so does every unit before the bit.
 enum {
     UCF_IV_UNPROVEN = 0,
     UCF_IV_CS_TAB = 1,       // cosh/sinh form in every lane at every node, sin/cos from the table
     UCF_IV_CS_SHORT = 2,     // ... both sin/cos from sincos_small_
     UCF_IV_EX_TAB = 3,       // exponential form in every lane at every node, sin/cos from the table
-    UCF_IV_EX_SHORT = 4      // ... from sincos_small_
+    UCF_IV_EX_SHORT = 4,     // ... from sincos_small_
+    // the two cosh/sinh classes in a part that has UCF_PH_SH (the caller's business: no classifier returns them)
+    UCF_IV_CS_TAB_SH = 5,
+    UCF_IV_CS_SHORT_SH = 6
 };
+static_assert(UCF_IV_CS_SHORT_SH - UCF_IV_CS_SHORT == UCF_IV_CS_TAB_SH - UCF_IV_CS_TAB, "one offset takes a cosh/sinh class to its settled-sinh twin");
 // What the units (the J0 intervals, and the runs of tanh-sinh nodes that integrate_kernel classifies like them) cost to decide:
 //   - the ends of the J0 intervals come from the table abscissa_kernel writes behind the rows (lane = time layout: the
 //     radius is wave-uniform), one scalar load per interval, instead of two IEEE divisions
@@ -715,6 +734,8 @@ static_assert(UCF_ZB_SC_SMALL == UCF_SC_SMALL, "the plan's short sin/cos limit (
 // Returns a class (UCF_IV_*, with *ph_proven as zpair_interval_class) or -1: the bounds do not decide.  Decided means
 // what the exact classifier decides: the form proven, and the short sin/cos form either proven by the upper bound of
 // (Im eta)^2 or refuted in some lane by the lower one (a refuted unit takes the table, which is always valid).
+// UCF_PH_SH is set where the lower bound of kappa (Re eta)^2 at lob is past zb[UCF_ZB_SH] and left alone otherwise: the
+// plain loop is always valid, so a unit the bound leaves open is not sent to the exact classifier for it.
 UCF_DEV int zpair_unit_bounds(const double* __restrict__ zb, const lane_consts& L, double lob, double hib, int* ph_proven)
 {
     *ph_proven = 0;
@@ -725,9 +746,11 @@ UCF_DEV int zpair_unit_bounds(const double* __restrict__ zb, const lane_consts& 
     if (__builtin_amdgcn_ballot_w64(!in_range) != 0) return -1;
     const bool ys = __builtin_amdgcn_ballot_w64(!(i2 < zb[UCF_ZB_YS] * lo_lo)) == 0;
     if (__builtin_amdgcn_ballot_w64(!(up_hi < zb[UCF_ZB_CS])) == 0) {
-        if (ys) { *ph_proven = UCF_PH_IM | UCF_PH_YS | UCF_PH_YL; return UCF_IV_CS_SHORT; }
+        // (the sinh form: settled where the lower bound is past the limit; a unit it leaves open keeps the test, in its class)
+        const int sh = __builtin_amdgcn_ballot_w64(!(lo_lo > zb[UCF_ZB_SH])) == 0 ? UCF_PH_SH : 0;
+        if (ys) { *ph_proven = UCF_PH_IM | UCF_PH_YS | UCF_PH_YL | sh; return UCF_IV_CS_SHORT; }
         if (__builtin_amdgcn_ballot_w64(i2 >= zb[UCF_ZB_YS] * __builtin_fma(lob, lob, u)) == 0) return -1;
-        *ph_proven = UCF_PH_IM;
+        *ph_proven = UCF_PH_IM | sh;
         return UCF_IV_CS_TAB;
     }
     if (__builtin_amdgcn_ballot_w64(!(lo_lo > zb[UCF_ZB_EX])) == 0) {
@@ -763,7 +786,10 @@ UCF_DEV int zpair_interval_class(const ucf_dev_params& P, const lane_consts& L, 
     const bool yl = ys || __builtin_amdgcn_ballot_w64(!(im_lo * (1.0 - zD) < UCF_SC_SMALL)) == 0;
     if (ys) *ph_proven |= UCF_PH_YS;
     if (yl) *ph_proven |= UCF_PH_YL;
-    if (__builtin_amdgcn_ballot_w64(!(re_hi * (1.0 + 0x1p-20) < P.maxexp)) == 0) return ys ? UCF_IV_CS_SHORT : UCF_IV_CS_TAB;
+    if (__builtin_amdgcn_ballot_w64(!(re_hi * (1.0 + 0x1p-20) < P.maxexp)) == 0) {
+        if (__builtin_amdgcn_ballot_w64(!(re_lo * (1.0 - 0x1p-20) * zD >= UCF_ZB_SINH_SERIES)) == 0) *ph_proven |= UCF_PH_SH;
+        return ys ? UCF_IV_CS_SHORT : UCF_IV_CS_TAB;
+    }
     if (__builtin_amdgcn_ballot_w64(!(re_lo * (1.0 - 0x1p-20) > P.maxexp)) == 0) {
         *ph_proven |= UCF_PH_LARGE;
         return yl ? UCF_IV_EX_SHORT : UCF_IV_EX_TAB;
@@ -771,14 +797,17 @@ UCF_DEV int zpair_interval_class(const ucf_dev_params& P, const lane_consts& L, 
     return UCF_IV_UNPROVEN;
 }
 // The sample at a node of a proven interval: fast_sample_zpair's arm of that class and its tail, nothing else.
-// CLS: UCF_IV_*; BETA: the launch's beta != 0 (wave-uniform, one plan per launch), known to the loop
+// CLS: UCF_IV_*; BETA: the launch's beta != 0 (wave-uniform, one plan per launch), known to the loop.  The cosh/sinh arm
+// drops what the class has decided: the clamp at maxexp (every lane is below it), and in the _SH classes the choice of the
+// sinh form
 template <int CLS, bool BETA>
 UCF_DEV cplx fast_sample_zpair_proven(const ucf_dev_params& P, const lane_consts& L, const fast_common& S)
 {
     const double zD = P.zD[0];
     cplx den, g;
-    if (CLS == UCF_IV_CS_TAB || CLS == UCF_IV_CS_SHORT) {
-        zpair_arm_small<CLS == UCF_IV_CS_SHORT, BETA ? 1 : 0>(P, L, S, zD, &g, &den);
+    if (CLS != UCF_IV_EX_TAB && CLS != UCF_IV_EX_SHORT) {
+        constexpr bool SH = CLS == UCF_IV_CS_TAB_SH || CLS == UCF_IV_CS_SHORT_SH;
+        zpair_arm_small<CLS == UCF_IV_CS_SHORT || CLS == UCF_IV_CS_SHORT_SH, BETA ? 1 : 0, true, SH>(P, L, S, zD, &g, &den);
     } else {
         const double c = 1.0 - zD;
         const double x = S.eta.re * c, y = S.eta.im * c;

@@ -63,14 +63,19 @@ struct ucf_dev_params {
 //   UCF_ZB_EX     kappa maxexp^2 / (1 - 2^-19)    lower bound above it: exponential form
 //   UCF_ZB_YS     4 kappa UCF_SC_SMALL^2          (Im p)^2 < it times (Re p + a^2): |Im eta| < UCF_SC_SMALL
 //   UCF_ZB_YL     that / (1 - zD[0])^2            ... |Im eta| (1 - zD) < UCF_SC_SMALL (infinite at zD = 1: always)
+//   UCF_ZB_SH     kappa (UCF_ZB_SINH_SERIES / zD[0])^2 / (1 - 2^-19)
+//                                                 lower bound above it: Re eta zD >= UCF_ZB_SINH_SERIES, no sinh by its series
+//                                                 (infinite at zD = 0: never)
 #define UCF_ZB_SC_SMALL 0.012   /* UCF_SC_SMALL (ucf_math.h) */
-enum { UCF_ZB_RANGE = 0, UCF_ZB_IM, UCF_ZB_CS, UCF_ZB_EX, UCF_ZB_YS, UCF_ZB_YL, UCF_ZB_COUNT = 8 };
+#define UCF_ZB_SINH_SERIES 0.35 /* below it prim_from_e (ucf_fastpath.h) takes sinh from its series */
+enum { UCF_ZB_RANGE = 0, UCF_ZB_IM, UCF_ZB_CS, UCF_ZB_EX, UCF_ZB_YS, UCF_ZB_YL, UCF_ZB_SH, UCF_ZB_COUNT = 8 };
 // limit `which` of a call's parameter block (constexpr: host and device; every operation rounded on its own where
 // abscissa_kernel is compiled)
 static constexpr double zpair_bound_limit(const ucf_dev_params& dp, int which)
 {
     const double lim = 0.99 * dp.fast_eta_max, me2 = dp.kappa * (dp.maxexp * dp.maxexp), c = 1.0 - dp.zD[0];
     const double ys = 4.0 * dp.kappa * (UCF_ZB_SC_SMALL * UCF_ZB_SC_SMALL);
+    const double sh = UCF_ZB_SINH_SERIES / dp.zD[0];
     switch (which) {
     case UCF_ZB_RANGE: return lim > 0.0 ? dp.kappa * (lim * lim) : 0.0;
     case UCF_ZB_IM: return dp.kappa * (dp.fast_im_max * dp.fast_im_max);
@@ -78,6 +83,7 @@ static constexpr double zpair_bound_limit(const ucf_dev_params& dp, int which)
     case UCF_ZB_EX: return me2 / (1.0 - 0x1p-19);
     case UCF_ZB_YS: return ys;
     case UCF_ZB_YL: return ys / (c * c);
+    case UCF_ZB_SH: return dp.kappa * (sh * sh) / (1.0 - 0x1p-19);
     default: return 0.0;
     }
 }
