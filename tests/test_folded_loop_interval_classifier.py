@@ -16,11 +16,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def test_no_node_of_a_proven_interval_violates_what_was_proven():
-    import folded_loop_phase_shares as S
-    tD, radii, zD = S.bench_grid()
+def check_grid(S, tD, radii, zD, seen):
+    """every J0 interval of the grid at the depth zD; seen[class] counts them (S: the tool's module or a Model of it)"""
     kappa, M, nacc, ngl = S.P.kappa, S.M, S.nacc, S.ngl
-    seen = dict.fromkeys(S.CLASSES, 0)
     for s, p in S.waves(tD):
         for rD in radii:
             a = S.row(rD, s)[S.N:].reshape(nacc, ngl)
@@ -46,6 +44,13 @@ def test_no_node_of_a_proven_interval_violates_what_was_proven():
                         arg = np.abs(eta.imag) * (1.0 - zD)
                     if cls.endswith("short"):
                         assert np.all(arg < S.SMALL), where
+
+
+def test_no_node_of_a_proven_interval_violates_what_was_proven():
+    import folded_loop_phase_shares as S
+    tD, radii, zD = S.bench_grid()
+    seen = dict.fromkeys(S.CLASSES, 0)
+    check_grid(S, tD, radii, zD, seen)
     # the sweep exercises every class, and the classifier proves most of it (the premise of the interval loops)
     assert all(seen[c] > 0 for c in S.CLASSES), seen
     assert sum(seen[c] for c in S.CLASSES if c != "unproven") >= 0.8 * sum(seen.values()), seen

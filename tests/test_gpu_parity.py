@@ -203,6 +203,16 @@ def _truth(name):
 
 
 BASELINE_DECKS = ["c2_neuman74_fullpen", "c3_moench", "c4_malama_partpen", "c5_mishra_fd64"]
+
+
+def gate1_bounds(mode, finite_differences, er):
+    """(bound on the largest, bound on the median) error of the device against binary128 under gate (1), from the errors `er`
+    of the binary64 oracle at the same points"""
+    fmed = 50.0 if finite_differences else 20.0      # FD: Thomas recursion amplifies
+    # the max over ~100 points of a 1e5..1e7x amplified rounding error is heavy-tailed: the fast flavour
+    # (different roundings in exp/sincos/sqrt) gets 20x the reference's own worst point, the faithful one 10x
+    fmax = 10.0 if mode == "faithful" else 20.0
+    return max(1e-10, fmax * er.max()), max(2e-12, fmed * np.median(er))
 ENTRIES = [(n, "list") for n in NAMES] + [(n, "grid") for n in BASELINE_DECKS]
 
 
@@ -254,14 +264,11 @@ def test_end_to_end_vs_binary128_truth(engine, oracle, name, entry, mode):
         floor = 1e-3 / (1.0 if dk.dimless else D.Hc)
         for got, ref, truth, label in ((h, ho, tr[f"h_r{ir}"], "h"), (dh, dho, tr[f"dh_r{ir}"], "dh")):
             eg, er = rel_err(got, truth, floor), rel_err(ref, truth, floor)
-            fmed = 50.0 if (dk.model == 6 and dk.MNtype == 2) else 20.0      # FD: Thomas recursion amplifies
-            # the max over ~100 points of a 1e5..1e7x amplified rounding error is heavy-tailed: the fast flavour
-            # (different roundings in exp/sincos/sqrt) gets 20x the reference's own worst point, the faithful one 10x
-            fmax = 10.0 if mode == "faithful" else 20.0
-            _record("vs_binary128_truth", name + ("" if entry == "list" else "@grid"), mode, label + "_max", eg.max() / max(1e-10, fmax * er.max()), err=eg.max(), ref_err=er.max())
-            _record("vs_binary128_truth", name + ("" if entry == "list" else "@grid"), mode, label + "_median", np.median(eg) / max(2e-12, fmed * np.median(er)), err=np.median(eg))
-            assert eg.max() <= max(1e-10, fmax * er.max()), (name, mode, ir, label, float(eg.max()), float(er.max()))
-            assert np.median(eg) <= max(2e-12, fmed * np.median(er)), (name, mode, ir, label, float(np.median(eg)), float(np.median(er)))
+            bound_max, bound_med = gate1_bounds(mode, dk.model == 6 and dk.MNtype == 2, er)
+            _record("vs_binary128_truth", name + ("" if entry == "list" else "@grid"), mode, label + "_max", eg.max() / bound_max, err=eg.max(), ref_err=er.max())
+            _record("vs_binary128_truth", name + ("" if entry == "list" else "@grid"), mode, label + "_median", np.median(eg) / bound_med, err=np.median(eg))
+            assert eg.max() <= bound_max, (name, mode, ir, label, float(eg.max()), float(er.max()))
+            assert np.median(eg) <= bound_med, (name, mode, ir, label, float(np.median(eg)), float(np.median(er)))
 
 
 @pytest.mark.parametrize("mode", MODES)

@@ -114,6 +114,6 @@ for n in ("bench_default", "bench_faithful", "bench_c2pp", "bench_c3", "bench_c4
         json.dump(line, open(os.path.join(P, f"{tag}_{n}.json"), "w"))
         r = line["roofline"]
         print(n, round(line["value"]), "pt/s", "kernel_ms", round(r["kernel_ms"], 2), "x", r.get("kernel_launches_per_step"), "frac", r.get("frac"))
-for f in ("parity_r03.json", "stages_r03.json", "stages_families.json", "dehoog_big.json"):
+for f in ("parity_r03.json", "stages_r03.json", "stages_families.json", "dehoog_big.json", "stages_folded.json"):
     if os.path.exists(os.path.join(G, f)):
         shutil.copy(os.path.join(G, f), os.path.join(P, f))

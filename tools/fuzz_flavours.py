@@ -9,6 +9,12 @@ from golden_util import load_deck
 from unconfined_amd import engine
 from unconfined_amd.abi import params_from_deck
 
+def nan_patterns_agree(ndiff, size, kappa):
+    """NaN patterns count as equal when they are, or -- deep in the overflow regime (kappa < 0.05: Re(eta) up to 1500, every
+    value there is the product of the in-band rules acting on overflowed samples) -- when at most 3 % of the values differ"""
+    return ndiff == 0 or (kappa < 0.05 and ndiff <= 0.03 * size)
+
+
 def run(nsets=40, seed=7, verbose=True, judge_above=1e-6, max_judged=6, models=(1, 3, 4, 5, 6)):
     rng = np.random.default_rng(seed)
     # key -> base deck; the keys >= 10 are further variants of a model (its other evaluator / screen position)
@@ -60,9 +66,7 @@ def run(nsets=40, seed=7, verbose=True, judge_above=1e-6, max_judged=6, models=(
             den = max(abs(ht[0, k[1]]), 1e-4 * sc)
             judged.append((i, abs(hf[k] - ht[0, k[1]]) / den, abs(hg[k] - ht[0, k[1]]) / den, abs(ho[0, k[1]] - ht[0, k[1]]) / den))
         ndiff = int(np.sum(np.isnan(hf) != np.isnan(hg)))
-        # NaN patterns count as equal when they are, or -- deep in the overflow regime (kappa < 0.05: Re(eta) up to 1500, every
-        # value there is the product of the in-band rules acting on overflowed samples) -- when at most 3 % of the values differ
-        nan_ok = ndiff == 0 or (float(dk2.kappa) < 0.05 and ndiff <= 0.03 * hf.size)
+        nan_ok = nan_patterns_agree(ndiff, hf.size, float(dk2.kappa))
         if not nan_ok and ndiff <= 0.03 * hf.size:
             # ... or where the reference has lost the answer anyway: at (up to three of) the points in question the CPU oracle
             # is NaN itself or further than 1e-6 from the binary128 evaluation (whether an overflowing intermediate ends as
