@@ -1058,6 +1058,72 @@ int ucf_field_yield(ucf_field* field, ucf_plan* plan, int npar, const int* ids,
 int ucf_debug_field_yield(int nctl, int nens, int ncon, int npat, const double* R, const double* x, const double* limit_con,
                           const int* con, double smax, double* y, double* fe, double* hi, double* lo, int* bind, int* dead,
                           long long* nbad /*[1]*/);
+/* ---- well-field times: WHEN does the drawdown at a receptor first pass a permitted value, from when on does it stay below one
+ * after the pumps have stopped, and how sure is either under the posterior.  The member maps of an ensemble are on the device when
+ * its member loop ends; field_times_kernel turns every member's time series at every (location, depth) into a time per limit,
+ * and the member reduction of ucf_field_ensemble runs on those times.  Only the maps that are asked for cross the bus.
+ *   notation     nsite = nloc nz, site e = iloc nz + z; a = the s slots [nens][nt][nsite] of ucf_field_ensemble (the dimensional
+ *                drawdown; ds takes no part); T [nens][nlim][nsite]; nout = nlim nsite for everything the reduction writes.
+ *   abscissa     tau [nt], strictly increasing and finite: what the answer is expressed in and interpolated in.  NULL: the field's
+ *                t.  (ln t is the usual other choice: drawdown is close to linear in it.)  tau_never, finite and above tau[nt-1]:
+ *                the censoring value for "not within the horizon of the map".
+ *   limits       limit [nlim] dimensional drawdowns, finite, with kind [nlim], nlim in 1..UCF_ENSEMBLE_MAX_Q.
+ *   members      those of ucf_field_ensemble; with weight != NULL those of ucf_field_ensemble_weighted: u =
+ *                ucf_ensemble_quantise(weight) after the other argument checks, a member with u[m] = 0 is validated but not
+ *                launched and its slots are NaN bytes; u, *ess, *nlaunched are written before any GPU work, with or without a
+ *                device.  The plan, the validation of every member before the first launch and what runs per member are exactly
+ *                those of ucf_field_ensemble: slot m of a has the bits of its member map.
+ *   times        field_times_kernel, one thread per (member m, limit l, site e), e fastest; the thread walks k = 0 .. nt-1 once;
+ *                every operation rounded on its own (no FMA contraction); L = limit[l]; no atomics.
+ *                kind[l] == UCF_TIME_FIRST_ABOVE, the first up-crossing: for k ascending, v = a[m][k][e]:
+ *                    v not finite:   T = NaN, stop
+ *                    v > L (strict, as in pexc), stop with
+ *                        k == 0:     T = tau[0]
+ *                        otherwise   v0 = a[m][k-1][e];   f = (L - v0) / (v - v0);   T = tau[k-1] + f * (tau[k] - tau[k-1])
+ *                    no k stops:     T = tau_never
+ *                  Values behind the crossing are not read: a NaN there does not matter.  v0 <= L < v, so f is in [0, 1).
+ *                kind[l] == UCF_TIME_LAST_ABOVE, the abscissa from which the value stays at or below L (the recovery time): all
+ *                nt values are read and any that is not finite gives T = NaN.  Otherwise, with k* the last k with a[m][k][e] > L:
+ *                    there is none:  T = tau[0]
+ *                    k* == nt-1:     T = tau_never
+ *                    otherwise       v0 = a[m][k*][e];  v1 = a[m][k*+1][e];   f = (v0 - L) / (v0 - v1);
+ *                                    T = tau[k*] + f * (tau[k*+1] - tau[k*])                       (v1 <= L < v0: f is in (0, 1])
+ *                The Wynn sentinel is finite and takes part, as everywhere.  A slot of NaN bytes (a member that was not launched)
+ *                gives NaN.  The NaN written is the quiet NaN 0x7ff8000000000000.
+ *   reduction    no kernel of its own and none edited: the reduction of ucf_field_ensemble (of ucf_field_ensemble_weighted with
+ *                weights), through its launcher, once, on T as [nens][nout], with horizon [nhor] in the place of its limit: T-> mean,
+ *                sd, min, max, nfin [nout], quant [nq][nout], all = T itself; plater [nhor][nout] is its pexc, the share of the
+ *                finite members with T > horizon[h] -- the chance of crossing by H is 1 - plater, the chance of never crossing
+ *                within the map is plater at H = tau[nt-1]; nbad[0] is its count (the outputs where a member that counts has
+ *                T = NaN).  Row l of every array belongs to limit l.  A censored member takes part with T = tau_never: quantiles
+ *                below the censored share are exact, mean and sd are those of the censored values.
+ * T is a buffer of the field (grown on demand, kept, counted in ucf_field_alloc_count) beside those of ucf_field_ensemble, which
+ * the call shares: a repeated call of the same or a smaller size allocates nothing, and ucf_field_ensemble before and after it
+ * gives the same bits.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything ucf_field_ensemble (with
+ * weight: _weighted) checks on field, nz, z, npar, ids, nens, thetas, nq, q, quant and, as its nlim and limit, on nhor and horizon
+ * (nhor outside 0..UCF_ENSEMBLE_MAX_Q, or positive with a NULL horizon; a horizon that is not finite); a NULL T; plater with
+ * nhor = 0; nlim outside 1..UCF_ENSEMBLE_MAX_Q; a NULL limit or kind; a limit that is not finite; a kind outside the enum; a tau
+ * that is not finite or does not increase strictly; tau_never not finite or not above tau[nt-1]; nens nlim nsite beyond what one
+ * buffer may hold.  With a NULL plan UCF_ERR_NO_DEVICE comes before "NULL plan". */
+enum { UCF_TIME_FIRST_ABOVE = 0, UCF_TIME_LAST_ABOVE = 1 };
+int ucf_field_ensemble_times(ucf_field* field, ucf_plan* plan, int npar, const int* ids,
+                             int nens, const double* thetas /*[nens][npar]*/,
+                             const double* weight /*[nens]; NULL: every member counts equally*/,
+                             int nz, const double* z,
+                             const double* tau /*[nt]; NULL: the field's t*/, double tau_never,
+                             int nlim, const double* limit /*[nlim]*/, const int* kind /*[nlim]*/,
+                             int nq, const double* q /*[nq]*/, int nhor, const double* horizon /*[nhor], in units of tau*/,
+                             const ucf_ensemble_maps* T /*every array over nlim nloc nz outputs; all: [nens][nlim][nloc][nz]*/,
+                             double* plater /*[nhor][nlim nloc nz]; NULL ok*/,
+                             long long* nbad /*[1]; NULL ok*/, ucf_stats* stats /*NULL ok*/,
+                             unsigned long long* u /*[nens]; NULL ok*/, double* ess /*NULL ok*/, int* nlaunched /*NULL ok*/);
+/* field_times_kernel exactly as ucf_field_ensemble_times launches it (the same launcher), once, on caller data a [nens][nt][nsite]:
+ * a, tau, limit and kind are uploaded, T [nens][nlim][nsite] is copied back.  a may hold anything.  UCF_ERR_BAD_ARGUMENT: nens
+ * outside 1..UCF_ENSEMBLE_MAX, nt or nsite < 1, a NULL a, tau or T, what ucf_field_ensemble_times checks on nlim, limit, kind, tau
+ * and tau_never, nens nsite max(nt, nlim) beyond 2^31-1 values.  Then UCF_ERR_NO_DEVICE without a device. */
+int ucf_debug_field_times(int nens, int nt, long long nsite, const double* a, const double* tau, double tau_never,
+                          int nlim, const double* limit, const int* kind, double* T);
 /* The reduction kernel of ucf_fit_evaluate exactly as a fit launches it (the same launcher, and through it the same choice among the
  * instantiations: npar 0..UCF_FIT_MAX_PAR x source x with / without derivative data), on caller data.  One 256-thread workgroup
  * per parameter set; set s owns the plans s (1 + 2 npar) + (0 base | 1 + 2j: parameter j up | 2 + 2j: parameter j down);

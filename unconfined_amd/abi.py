@@ -16,6 +16,9 @@ UCF_WORTH_MAX_PICK = 16       # wells that one ucf_field_worth picks
 UCF_YIELD_MAX_CTL = 8         # controls of one ucf_field_yield
 UCF_YIELD_MAX_PAT = 4096      # rate patterns of one ucf_field_yield
 UCF_YIELD_PAT_TILE = 8        # patterns per workgroup of field_yield_kernel
+UCF_TIME_FIRST_ABOVE = 0      # kinds of ucf_field_ensemble_times: the first up-crossing of a limit
+UCF_TIME_LAST_ABOVE = 1       # ... and the abscissa from which the value stays at or below it
+TIME_KINDS = {"first_above": UCF_TIME_FIRST_ABOVE, "last_above": UCF_TIME_LAST_ABOVE}
 # parameter ids of a fit (enum UCF_PAR_* of include/ucf.h); a Moench alpha is PAR_MOENCH_ALPHA0 + i
 PAR_KR, PAR_KAPPA, PAR_SS, PAR_SY, PAR_AC, PAR_AK, PAR_USL, PAR_MOENCH_ALPHA0 = range(8)
 PAR_IDS = {"Kr": PAR_KR, "kappa": PAR_KAPPA, "Ss": PAR_SS, "Sy": PAR_SY, "ac": PAR_AC, "ak": PAR_AK, "usL": PAR_USL}

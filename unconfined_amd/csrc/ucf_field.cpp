@@ -45,14 +45,16 @@ struct ucf_field {
     // ucf_field_yield: the response slots R [nens][nctl + 1][ncon]; con [ncon] and ctl [nwell]; x [npat][nctl] and the limits
     // [ncon]; y, fe, hi, lo [4][nens][npat]; bind, dead [2][nens][npat].  Its statistics are staged in b_ens.
     ucf_buffer b_yR, b_yint, b_ysmall, b_yval, b_yidx;
+    // ucf_field_ensemble_times: T [nens][nlim][nloc][nz]; its series are b_sall, its tau, limits and kinds are staged in b_ens
+    ucf_buffer b_tall;
     ucf_plan* scratch = nullptr;           // the plan that ucf_field_forecast refreshes for every parameter set
     long long n_alloc = 0;
     // every device buffer above: the one list (ucf_field_destroy frees through it)
-    std::array<ucf_buffer*, 33> buffers()
+    std::array<ucf_buffer*, 34> buffers()
     {
         return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats, &b_sall, &b_dsall, &b_sens, &b_dsens,
                  &b_se, &b_dse, &b_cov, &b_nbad, &b_ens, &b_u, &b_wpost, &b_wcrit, &b_wnused, &b_wsmall, &b_wtsel, &b_widx, &b_wval,
-                 &b_yR, &b_yint, &b_ysmall, &b_yval, &b_yidx}};
+                 &b_yR, &b_yint, &b_ysmall, &b_yval, &b_yidx, &b_tall}};
     }
 };
 
@@ -910,22 +912,65 @@ static int ensemble_sets_of(const ucf_field* f, const ucf_plan* pl, int npar, co
     return UCF_OK;
 }
 
+// What ucf_field_ensemble_times asks of field_ensemble_core beyond an ensemble: the abscissa (tau NULL: the field's t), the
+// limits on the drawdown and their kinds
+struct times_request {
+    const double* tau;
+    double tau_never;
+    int nlim;
+    const double *limit;
+    const int* kind;
+};
+
+// what ucf_field_ensemble_times and ucf_debug_field_times check on the abscissa, the limits and the kinds
+static int times_check(int nt, const double* tau, double tau_never, int nlim, const double* limit, const int* kind)
+{
+    if (nlim < 1 || nlim > UCF_ENSEMBLE_MAX_Q) return fail(UCF_ERR_BAD_ARGUMENT, "nlim=%d outside 1..%d", nlim, UCF_ENSEMBLE_MAX_Q);
+    if (!limit || !kind) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !limit ? "limit" : "kind");
+    int rc = field_check_finite("limit", nlim, limit);
+    if (rc) return rc;
+    for (int l = 0; l < nlim; l++)
+        if (kind[l] != UCF_TIME_FIRST_ABOVE && kind[l] != UCF_TIME_LAST_ABOVE)
+            return fail(UCF_ERR_BAD_ARGUMENT, "kind[%d]=%d is neither UCF_TIME_FIRST_ABOVE (0) nor UCF_TIME_LAST_ABOVE (1)", l, kind[l]);
+    if ((rc = field_check_finite("tau", nt, tau))) return rc;
+    for (int k = 1; k < nt; k++)
+        if (!(tau[k] > tau[k - 1]))
+            return fail(UCF_ERR_BAD_ARGUMENT, "tau[%d]=%g does not lie after tau[%d]=%g: the abscissa must increase strictly", k, tau[k], k - 1, tau[k - 1]);
+    if (!std::isfinite(tau_never) || !(tau_never > tau[nt - 1]))
+        return fail(UCF_ERR_BAD_ARGUMENT, "tau_never=%g must be finite and lie after tau[%d]=%g", tau_never, nt - 1, tau[nt - 1]);
+    return UCF_OK;
+}
+
 // ucf_field_ensemble (weighted == false: weight, u_out, ess, nlaunched are not read) and ucf_field_ensemble_weighted: one
 // sequence.  The weighted call differs in three places: the weights are quantised among the checks; a member with u = 0 is
 // validated but not launched, and its slots are filled with NaN bytes; the reduction runs with the weights.
+// ucf_field_ensemble_times (tr not NULL) is the same sequence with field_times_kernel between the members and the reduction:
+// the reduction then runs once, on T [nens][nlim nsite] in b_tall; s takes the maps of T, ds is NULL, nlim / limit are the
+// horizons (named so in the messages) and pexc is plater.
 static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, int nz, const double* z,
                                int nq, const double* q, int nlim, const double* limit, const ucf_ensemble_maps* s, const ucf_ensemble_maps* ds,
                                double* pexc, long long* nbad, ucf_stats* stats, bool weighted, const double* weight,
-                               unsigned long long* u_out, double* ess, int* nlaunched)
+                               unsigned long long* u_out, double* ess, int* nlaunched, const times_request* tr = nullptr)
 {
     long long nout = 0;
     int rc = field_check_call(f, nz, !z ? "NULL z" : !ids ? "NULL ids" : !thetas ? "NULL thetas" : nullptr, z, nout);
     if (rc) return rc;
     if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
-    if ((rc = ensemble_check_levels(nens, nq, q, nlim, limit, (s && s->quant) || (ds && ds->quant), pexc != nullptr))) return rc;
+    if ((rc = ensemble_check_levels(nens, nq, q, nlim, limit, (s && s->quant) || (ds && ds->quant), !tr && pexc != nullptr, tr ? "nhor" : "nlim",
+                                    tr ? "horizon" : "limit"))) return rc;
     if ((rc = ensemble_check_thetas(npar, ids, nens, thetas))) return rc;
     if (nens * nout > 0x7fffffffLL * 256)
         return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d times x %d locations x %d depths: too many values for one buffer", nens, f->nt, f->nloc, nz);
+    // what the reduction works on: the nout outputs of a map, or the times of nlim limits at the nsite = nloc nz sites
+    const long long nsite = nout / f->nt, nred = tr ? tr->nlim * nsite : nout;
+    const double* tau = tr && tr->tau ? tr->tau : f->t.data();
+    if (tr) {
+        if (!s) return fail(UCF_ERR_BAD_ARGUMENT, "NULL T");
+        if (pexc && nlim == 0) return fail(UCF_ERR_BAD_ARGUMENT, "plater is asked for with nhor=0: no horizon to lie beyond");
+        if ((rc = times_check(f->nt, tau, tr->tau_never, tr->nlim, tr->limit, tr->kind))) return rc;
+        if (nens * nred > 0x7fffffffLL * 256)
+            return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d limits x %d locations x %d depths: too many values for one buffer", nens, tr->nlim, f->nloc, nz);
+    }
     ensemble_members E;
     if ((rc = ensemble_weights_of(nens, weighted ? weight : nullptr, weighted, u_out, ess, nlaunched, E)) ||
         (rc = ensemble_sets_of(f, pl, npar, ids, nens, thetas, E))) return rc;
@@ -937,8 +982,9 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
     ucf_plan* sp = f->scratch;
     device_switch dg(pl->device);
     // b_ens: q [MAX_Q], limit [MAX_Q], then per map what is asked for of mean, sd, min, max [nout], quant [nq][nout], nfin
-    // [nout] (ints, padded to whole doubles), then pexc [nlim][nout]
-    const size_t no = (size_t)nout, so = sizeof(double) * no, sa = so * nens;
+    // [nout] (ints, padded to whole doubles), then pexc [nlim][nout]; for the times nout = nlim nsite, and behind pexc tau [nt],
+    // the limits [nlim] and the kinds [nlim] (ints, padded)
+    const size_t no = (size_t)nred, so = sizeof(double) * no, sa = sizeof(double) * (size_t)nout * nens;
     const ucf_ensemble_maps none = {};
     const ucf_ensemble_maps* want[2] = {s ? s : &none, ds ? ds : &none};
     struct map_at { double *mean, *sd, *min, *max, *quant; int* nfin; } at[2];
@@ -950,10 +996,12 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
         off[i][3] = take(want[i]->max, no); off[i][4] = take(want[i]->quant, no * nq); off[i][5] = take(want[i]->nfin, (no + 1) / 2);
     }
     off_pexc = take(pexc, no * nlim);
+    const size_t off_tau = take(tr != nullptr, f->nt), off_tlim = take(tr != nullptr, tr ? tr->nlim : 0), off_kind = take(tr != nullptr, tr ? (tr->nlim + 1) / 2 : 0);
     if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every member", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every member", f->n_alloc)) ||
         (rc = grow_buffer(f->b_nbad, sizeof(long long) * 2, "counts", f->n_alloc)) ||
         (rc = grow_buffer(f->b_ens, sizeof(double) * used, "ensemble statistics", f->n_alloc)) ||
-        (weighted && (rc = grow_buffer(f->b_u, sizeof(unsigned long long) * nens, "ensemble weights", f->n_alloc)))) return rc;
+        (weighted && (rc = grow_buffer(f->b_u, sizeof(unsigned long long) * nens, "ensemble weights", f->n_alloc))) ||
+        (tr && (rc = grow_buffer(f->b_tall, so * nens, "times of every member", f->n_alloc)))) return rc;
     double* base = (double*)f->b_ens.p;
     auto dev = [&](size_t o) { return o == (size_t)-1 ? nullptr : base + o; };
     for (int i = 0; i < 2; i++) at[i] = map_at{dev(off[i][0]), dev(off[i][1]), dev(off[i][2]), dev(off[i][3]), dev(off[i][4]), (int*)dev(off[i][5])};
@@ -969,19 +1017,34 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
     if (hipMemsetAsync(f->b_nbad.p, 0, sizeof(long long) * 2, st) != hipSuccess ||
         hipMemcpyAsync(base, ql, sizeof(ql), hipMemcpyHostToDevice, st) != hipSuccess)
         return fail(UCF_ERR_HIP, "upload of the ensemble's arrays failed: %s", hipGetErrorString(hipGetLastError()));
+    const size_t sm = sizeof(double) * (size_t)nout;      // a member's slot
     const double* slots[2] = {(const double*)f->b_sall.p, (const double*)f->b_dsall.p};
     if (weighted) {
         // the weights, and NaN bytes into the slots of the members that were not launched, so that `all` is defined
         bool ok = hipMemcpyAsync(f->b_u.p, u.data(), sizeof(unsigned long long) * nens, hipMemcpyHostToDevice, st) == hipSuccess;
         for (int m = 0; m < nens && ok; m++)
             if (u[m] == 0)
-                ok = hipMemsetAsync((double*)f->b_sall.p + (size_t)m * no, 0xff, so, st) == hipSuccess &&
-                     hipMemsetAsync((double*)f->b_dsall.p + (size_t)m * no, 0xff, so, st) == hipSuccess;
+                ok = hipMemsetAsync((double*)f->b_sall.p + (size_t)m * nout, 0xff, sm, st) == hipSuccess &&
+                     hipMemsetAsync((double*)f->b_dsall.p + (size_t)m * nout, 0xff, sm, st) == hipSuccess;
         if (!ok) return fail(UCF_ERR_HIP, "upload of the ensemble's weights failed: %s", hipGetErrorString(hipGetLastError()));
     }
-    for (int i = 0; i < 2 && rc == UCF_OK; i++) {
+    if (tr) {
+        // the s slots become times: T [nens][nlim][nsite], the only map that is reduced
+        if (hipMemcpyAsync(dev(off_tau), tau, sizeof(double) * f->nt, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(dev(off_tlim), tr->limit, sizeof(double) * tr->nlim, hipMemcpyHostToDevice, st) != hipSuccess ||
+            hipMemcpyAsync(dev(off_kind), tr->kind, sizeof(int) * tr->nlim, hipMemcpyHostToDevice, st) != hipSuccess)
+            return fail(UCF_ERR_HIP, "upload of the abscissa, limits and kinds failed: %s", hipGetErrorString(hipGetLastError()));
+        ucf_times_args ta = {};
+        ta.nens = nens; ta.nt = f->nt; ta.nsite = nsite; ta.d_a = slots[0]; ta.d_tau = dev(off_tau); ta.tau_never = tr->tau_never;
+        ta.nlim = tr->nlim; ta.d_limit = dev(off_tlim); ta.d_kind = (const int*)dev(off_kind); ta.d_T = (double*)f->b_tall.p;
+        if ((rc = ucf_field_launch_times(&ta, st))) return fail(rc, "times kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        slots[0] = (const double*)f->b_tall.p;
+        slots[1] = nullptr;
+    }
+    const int nmap = tr ? 1 : 2;
+    for (int i = 0; i < nmap && rc == UCF_OK; i++) {
         ucf_ensemble_reduce_args ra = {};
-        ra.nens = nens; ra.nout = nout; ra.d_a = slots[i];
+        ra.nens = nens; ra.nout = nred; ra.d_a = slots[i];
         ra.d_u = weighted ? (const unsigned long long*)f->b_u.p : nullptr;
         ra.nq = nq; ra.d_q = base; ra.nlim = nlim; ra.d_limit = base + UCF_ENSEMBLE_MAX_Q;
         ra.d_mean = at[i].mean; ra.d_sd = at[i].sd; ra.d_min = at[i].min; ra.d_max = at[i].max; ra.d_nfin = at[i].nfin;
@@ -990,11 +1053,11 @@ static int field_ensemble_core(ucf_field* f, ucf_plan* pl, int npar, const int* 
     }
     if (rc) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     // only what is asked for crosses the bus
-    std::vector<device_copy> back = {{pexc, d_pexc, so * nlim}, {nbad, f->b_nbad.p, sizeof(long long) * 2}};
-    for (int i = 0; i < 2; i++) {
+    std::vector<device_copy> back = {{pexc, d_pexc, so * nlim}, {nbad, f->b_nbad.p, sizeof(long long) * nmap}};
+    for (int i = 0; i < nmap; i++) {
         const ucf_ensemble_maps* w = want[i];
         back.insert(back.end(), {{w->mean, at[i].mean, so}, {w->sd, at[i].sd, so}, {w->min, at[i].min, so}, {w->max, at[i].max, so},
-                                 {w->quant, at[i].quant, so * nq}, {w->all, slots[i], sa}, {w->nfin, at[i].nfin, sizeof(int) * no}});
+                                 {w->quant, at[i].quant, so * nq}, {w->all, slots[i], so * nens}, {w->nfin, at[i].nfin, sizeof(int) * no}});
     }
     return copy_back(back, st, pl->device);
 }
@@ -1014,6 +1077,44 @@ int ucf_field_ensemble_weighted(ucf_field* f, ucf_plan* pl, int npar, const int*
 {
     return field_ensemble_core(f, pl, npar, ids, nens, thetas, nz, z, nq, q, nlim, limit, s, ds, pexc, nbad, stats, true, weight, u, ess,
                                nlaunched);
+}
+
+int ucf_field_ensemble_times(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, const double* weight,
+                             int nz, const double* z, const double* tau, double tau_never, int nlim, const double* limit, const int* kind,
+                             int nq, const double* q, int nhor, const double* horizon, const ucf_ensemble_maps* T, double* plater,
+                             long long* nbad, ucf_stats* stats, unsigned long long* u, double* ess, int* nlaunched)
+{
+    const times_request tr = {tau, tau_never, nlim, limit, kind};
+    return field_ensemble_core(f, pl, npar, ids, nens, thetas, nz, z, nq, q, nhor, horizon, T, nullptr, plater, nbad, stats, weight != nullptr,
+                               weight, u, ess, nlaunched, &tr);
+}
+
+int ucf_debug_field_times(int nens, int nt, long long nsite, const double* a, const double* tau, double tau_never, int nlim,
+                          const double* limit, const int* kind, double* T)
+{
+    if (nens < 1 || nens > UCF_ENSEMBLE_MAX) return fail(UCF_ERR_BAD_ARGUMENT, "nens=%d outside 1..%d", nens, UCF_ENSEMBLE_MAX);
+    if (nt < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nt=%d: at least one time", nt);
+    if (nsite < 1) return fail(UCF_ERR_BAD_ARGUMENT, "nsite=%lld: at least one site", nsite);
+    if (!a || !tau || !T) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !a ? "a" : !tau ? "tau" : "T");
+    int rc = times_check(nt, tau, tau_never, nlim, limit, kind);
+    if (rc) return rc;
+    if (nens * nsite > 0x7fffffffLL / (nt > nlim ? nt : nlim))
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d times or %d limits x %lld sites: more than 2^31-1 values", nens, nt, nlim, nsite);
+    if ((rc = require_device())) return rc;
+    const size_t sa = sizeof(double) * nens * nt * (size_t)nsite, sT = sizeof(double) * nens * nlim * (size_t)nsite;
+    dev_buf b_a, b_tau, b_lim, b_kind, b_T;
+    if (b_a.alloc(sa) || b_tau.alloc(sizeof(double) * nt) || b_lim.alloc(sizeof(double) * nlim) || b_kind.alloc(sizeof(int) * nlim) || b_T.alloc(sT))
+        return fail(UCF_ERR_NOMEM, "device allocation failed");
+    HIP_TRY(hipMemcpy(b_a.p, a, sa, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_tau.p, tau, sizeof(double) * nt, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_lim.p, limit, sizeof(double) * nlim, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(b_kind.p, kind, sizeof(int) * nlim, hipMemcpyHostToDevice));
+    ucf_times_args ta = {};
+    ta.nens = nens; ta.nt = nt; ta.nsite = nsite; ta.d_a = (const double*)b_a.p; ta.d_tau = (const double*)b_tau.p; ta.tau_never = tau_never;
+    ta.nlim = nlim; ta.d_limit = (const double*)b_lim.p; ta.d_kind = (const int*)b_kind.p; ta.d_T = (double*)b_T.p;
+    if ((rc = ucf_field_launch_times(&ta, nullptr))) return fail(rc, "times kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return copy_back_sync({{T, ta.d_T, sT}});
 }
 
 // what ucf_field_yield and ucf_debug_field_yield check on the controls' count, the patterns and smax

@@ -1,7 +1,8 @@
 // ucf_field.h -- launchers of the well-field kernels: the superposition, called by ucf_field_drawdown, ucf_field_forecast and
 // ucf_field_ensemble (ucf_field.cpp), the response slots of ucf_field_yield, the combination of a forecast (all three
 // ucf_field.hip), the reduction of an ensemble (ucf_field_ensemble.hip), the data worth of candidate wells
-// (ucf_field_worth.hip) and the ratio test of ucf_field_yield (ucf_field_yield.hip).
+// (ucf_field_worth.hip), the ratio test of ucf_field_yield (ucf_field_yield.hip) and the time kernel of
+// ucf_field_ensemble_times (ucf_field_times.hip).
 #pragma once
 #include <cstddef>
 
@@ -45,6 +46,23 @@ struct ucf_yield_args {
 };
 // UCF_ERR_BAD_ARGUMENT for what the comments above exclude and for a NULL array
 int ucf_field_launch_yield(const ucf_yield_args* a, void* stream);
+
+// The time kernel of ucf_field_ensemble_times (ucf_field_times.hip), field_times_kernel: one thread per (member m, limit l, site
+// e) of d_T [nens][nlim][nsite], e fastest, a workgroup of 256 threads per (tile of sites, l, m); the arithmetic is stated with
+// ucf_field_ensemble_times in include/ucf.h.  Device memory throughout.
+struct ucf_times_args {
+    int nens, nt;                          // 1..UCF_ENSEMBLE_MAX, >= 1
+    long long nsite;                       // >= 1, below 2^32 - 256
+    const double* d_a;                     // [nens][nt][nsite] the series, site fastest
+    const double* d_tau;                   // [nt] strictly increasing and finite
+    double tau_never;                      // finite, above d_tau[nt - 1]
+    int nlim;                              // 1..UCF_ENSEMBLE_MAX_Q
+    const double* d_limit;                 // [nlim] finite
+    const int* d_kind;                     // [nlim] UCF_TIME_FIRST_ABOVE or UCF_TIME_LAST_ABOVE
+    double* d_T;                           // [nens][nlim][nsite]
+};
+// UCF_ERR_BAD_ARGUMENT for what the comments above exclude and for a NULL array (the caller has checked tau, the limits and the kinds)
+int ucf_field_launch_times(const ucf_times_args* a, void* stream);
 
 // The combination of a forecast, field_forecast_kernel<npar>: one thread per output e of the slots d_a [1 + 2 npar][nout]
 // (slot 0 the base set, slot 1 + 2j / 2 + 2j parameter j up / down), every operation rounded on its own:

@@ -43,6 +43,13 @@ one control and 64 splits between two such pairs are tried, up to three times to
     out = field.sustainable_yield(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], controls=[0, 1, 0, 1], patterns=patterns,
                                   limit=2.0, smax=3.0, levels=[1.0])
     out["quant"][0], out["pexc"], out["bind"]                                                 # the scale that 95 % admit, P(scale > 1), where it binds
+
+When the drawdown first passes a permitted value, from when on it stays below one after the pumps have stopped, and how sure that
+is -- one time per member, limit, location and depth, formed and reduced on the GPU (ucf_field_ensemble_times):
+
+    res = field.time_to_limit(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], limits=[0.5, 0.1], kinds=["first_above", "last_above"],
+                              horizons=[365.0], abscissa="lnt")
+    res.quant[1], 1.0 - res.later[0]                                                          # the median time, P(crossed within a year)
 """
 from __future__ import annotations
 
@@ -51,7 +58,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _libmod
-from .abi import UcfEnsembleMaps, UcfParams, UcfStats
+from .abi import TIME_KINDS, UcfEnsembleMaps, UcfParams, UcfStats
 from .fit import par_id
 
 KINDS = {"no_flow": 0, "constant_head": 1, 0: 0, 1: 1}
@@ -128,6 +135,24 @@ def images(wells, line, kind):
     return np.stack(out, axis=1)
 
 
+class TimeToLimit:
+    """what ``WellField.time_to_limit`` returns.  limits [nlim], kinds [nlim] (int32, UCF_TIME_*), abscissa ('t' or 'lnt'), never,
+    q [nq], horizons [nhor]; mean, sd, min, max, nfin [nlim, nloc, nz]; quant [nq, nlim, nloc, nz]; later [nhor, nlim, nloc, nz], the
+    share of members whose time lies beyond a horizon (the chance of crossing by then is 1 - later); all [nens, nlim, nloc, nz]
+    where asked for; nbad, the outputs where a member that counts has no time (a drawdown that is not finite); with weights u,
+    ess, nlaunched.  An array that was not asked for is None.  Everything is a time EXCEPT, where ``log_moments`` is true (abscissa
+    'lnt'), mean and sd: those are the mean and the standard deviation of ln(time).  A member that does not cross within the
+    field's times takes part with ``never``."""
+
+    def __init__(self, **kw):
+        self.quant = self.later = self.all = self.u = self.ess = self.nlaunched = self.stats = None
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return (f"TimeToLimit(limits={self.limits.tolist()}, kinds={self.kinds.tolist()}, abscissa={self.abscissa!r}, never={self.never!r}, "
+                f"shape={self.mean.shape}, nbad={self.nbad})")
+
+
 class WellField:
     """wells (x, y, q, t0), locations (x, y) and strictly increasing times, all dimensional"""
 
@@ -140,6 +165,7 @@ class WellField:
             raise ValueError("locations: one (x, y) per location")
         t = np.atleast_1d(_f64(times))
         self.nwell, self.nloc, self.nt = len(w), len(loc), len(t)
+        self._times = t.copy()
         _libmod.check(self._lib.ucf_field_create(self.nwell, _f64(w[:, 0]), _f64(w[:, 1]), _f64(w[:, 2]), _f64(w[:, 3]), self.nloc,
                                                  _f64(loc[:, 0]), _f64(loc[:, 1]), self.nt, t, C.byref(self._h)))
 
@@ -398,6 +424,79 @@ class WellField:
         if with_stats:
             out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
         return out
+
+    def time_to_limit(self, plan, free, thetas, z, limits, kinds="first_above", weights=None, q=(0.05, 0.5, 0.95), horizons=(),
+                      abscissa: str = "t", never=None, all_times: bool = False, with_stats: bool = False) -> "TimeToLimit":
+        """when the drawdown passes a limit, and how sure that is under the ensemble ``thetas`` [nens, npar]
+        (ucf_field_ensemble_times).  ``limits`` [nlim] are dimensional drawdowns; ``kinds`` (one for all, or one per limit) is
+        'first_above', the time of the first up-crossing, or 'last_above', the time from which the drawdown stays at or below
+        the limit (the recovery time).  Per member, limit, location and depth the time is interpolated linearly in the
+        ``abscissa`` -- 't', or 'lnt', the logarithm of the field's times -- between the two times of the field that bracket the
+        crossing; a member that does not cross within the field's times gets ``never`` (default 2 t[-1]).  The members are
+        reduced on the GPU as in ``ensemble``, with ``weights`` as there.  Returns a ``TimeToLimit`` whose arrays are
+        [nlim, nloc, nz], a leading axis for quantile levels, horizons or members before it: mean, sd, min, max, nfin, quant at
+        the levels ``q``, later [nhor, ...], the share of members whose time lies beyond a horizon (given as times) and, with
+        ``all_times``, all [nens, ...].  With 'lnt' min, max, quant, all (and never, horizons) are times, exponentiated back --
+        monotone, hence exact in rank; a censored value comes back as ``never`` itself --, while mean and sd stay in ln t:
+        ``log_moments`` says so.  ``plan`` is not modified."""
+        ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
+        thetas = np.atleast_2d(_f64(thetas))
+        if thetas.ndim != 2 or thetas.shape[1] != len(ids):
+            raise ValueError("thetas: [nens, npar], one value per free parameter")
+        nens = len(thetas)
+        z = np.atleast_1d(_f64(z))
+        lim = np.atleast_1d(_f64(limits))
+        if lim.ndim != 1 or len(lim) < 1:
+            raise ValueError("limits: at least one drawdown limit")
+        if isinstance(kinds, (str, int)):
+            kinds = [kinds] * len(lim)
+        try:
+            kind = np.ascontiguousarray([TIME_KINDS.get(k, k) for k in kinds], dtype=np.int32)
+        except (TypeError, ValueError):
+            raise ValueError("kinds: 'first_above' or 'last_above'") from None
+        if kind.shape != lim.shape:
+            raise ValueError("kinds: one for all limits, or one per limit")
+        if abscissa not in ("t", "lnt"):
+            raise ValueError("abscissa: 't' or 'lnt'")
+        log = abscissa == "lnt"
+        w = None if weights is None else np.atleast_1d(_f64(weights))
+        if w is not None and len(w) != nens:
+            raise ValueError("weights: one value per member")
+        qs = np.atleast_1d(_f64(q if q is not None else []))
+        hor = np.atleast_1d(_f64(horizons if horizons is not None else []))
+        never = 2.0 * self._times[-1] if never is None else float(never)
+        tau = np.log(self._times) if log else None
+        with np.errstate(invalid="ignore", divide="ignore"):
+            tau_never, hor_tau = (float(np.log(never)), np.log(hor)) if log else (never, hor)
+        shape = (len(lim), self.nloc, len(z))
+        out = {key: np.zeros(shape) for key in ("mean", "sd", "min", "max")}
+        out["nfin"] = np.zeros(shape, np.int32)
+        if len(qs):
+            out["quant"] = np.zeros((len(qs),) + shape)
+        if all_times:
+            out["all"] = np.zeros((nens,) + shape)
+        if len(hor):
+            out["later"] = np.zeros((len(hor),) + shape)
+        maps = UcfEnsembleMaps(*(_addr(out.get(key)) for key in ("mean", "sd", "min", "max", "quant", "all", "nfin")))
+        nbad, st = C.c_longlong(), UcfStats()
+        u, ess, nl = np.zeros(nens, np.uint64), C.c_double(), C.c_int()
+        _libmod.check(self._lib.ucf_field_ensemble_times(
+            self._h, plan._h, len(ids), _addr(ids), nens, _addr(thetas), _addr(w), len(z), _addr(z), _addr(tau), tau_never, len(lim),
+            _addr(lim), _addr(kind), len(qs), _addr(qs) if len(qs) else None, len(hor), _addr(hor_tau) if len(hor) else None,
+            C.byref(maps), _addr(out.get("later")), C.addressof(nbad), C.byref(st) if with_stats else None, _addr(u), C.addressof(ess),
+            C.addressof(nl)))
+        if log:
+            for key in ("min", "max", "quant", "all"):
+                if key in out:
+                    censored = out[key] == tau_never         # exp(ln(never)) need not be never: the censoring value comes back as given
+                    np.exp(out[key], out=out[key])
+                    out[key][censored] = never
+        res = TimeToLimit(limits=lim, kinds=kind, abscissa=abscissa, never=never, q=qs, horizons=hor, log_moments=log, nbad=int(nbad.value), **out)
+        if w is not None:
+            res.u, res.ess, res.nlaunched = u, float(ess.value), int(nl.value)
+        if with_stats:
+            res.stats = {k: getattr(st, k) for k, _ in UcfStats._fields_}
+        return res
 
     def alloc_count(self) -> int:
         """device allocations made so far by the field"""

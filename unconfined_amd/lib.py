@@ -48,6 +48,7 @@ EXPORTS = [
     "ucf_debug_ensemble_weighted",
     "ucf_field_worth", "ucf_worth_condition", "ucf_debug_field_worth",
     "ucf_field_yield", "ucf_debug_field_yield",
+    "ucf_field_ensemble_times", "ucf_debug_field_times",
     "ucf_fit_loss_terms", "ucf_fit_robust_scale", "ucf_fit_set_loss", "ucf_fit_get_loss", "ucf_fit_loss_report", "ucf_debug_fit_reduce_loss",
     "ucf_fit_set_resample", "ucf_fit_evaluate_resampled", "ucf_fit_objective_resampled", "ucf_fit_lm_resampled",
     "ucf_fit_resample_blocks", "ucf_fit_resample_jackknife", "ucf_fit_resample_cov", "ucf_debug_fit_reduce_resampled",
@@ -202,6 +203,12 @@ def load() -> C.CDLL:
                                     [C.POINTER(UcfStats)] + [vp] * 3)
     # nctl, nens, ncon, npat, R, x, limit_con, con, smax, y, fe, hi, lo, bind, dead, nbad
     lib.ucf_debug_field_yield.argtypes = [C.c_int] * 4 + [vp] * 4 + [C.c_double] + [vp] * 7
+    # every array may be NULL: plain addresses.  field, plan, npar, ids, nens, thetas, weight, nz, z | tau, tau_never | nlim, limit,
+    # kind | nq, q, nhor, horizon | T, plater, nbad | stats | u, ess, nlaunched
+    lib.ucf_field_ensemble_times.argtypes = ([vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp] + [vp, C.c_double] + [C.c_int, vp, vp] +
+                                             [C.c_int, vp, C.c_int, vp] + [C.POINTER(UcfEnsembleMaps), vp, vp] + [C.POINTER(UcfStats)] + [vp] * 3)
+    # nens, nt, nsite, a, tau, tau_never, nlim, limit, kind, T
+    lib.ucf_debug_field_times.argtypes = [C.c_int, C.c_int, C.c_longlong, vp, vp, C.c_double, C.c_int, vp, vp, vp]
     # every array may be NULL for a source or a call that does not read it: plain addresses
     lib.ucf_debug_fit_reduce.argtypes = ([C.c_int] * 4 + [C.c_double, C.c_longlong] + [vp] * 8 + [C.c_longlong, C.c_int] + [vp] * 7 + [vp] * 6)
     # x, rho, b, scale and every output may be NULL: plain addresses
