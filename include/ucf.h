@@ -1124,6 +1124,81 @@ int ucf_field_ensemble_times(ucf_field* field, ucf_plan* plan, int npar, const i
  * and tau_never, nens nsite max(nt, nlim) beyond 2^31-1 values.  Then UCF_ERR_NO_DEVICE without a device. */
 int ucf_debug_field_times(int nens, int nt, long long nsite, const double* a, const double* tau, double tau_never,
                           int nlim, const double* limit, const int* kind, double* T);
+/* ---- well-field Sobol indices: WHICH parameter causes the spread of a forecast where the posterior is too wide to linearise.
+ * The sensitivities of ucf_field_forecast are derivatives at one point; over the width of a real posterior the drawdown is not
+ * linear in ln Sy, ln kappa or ln Ss (see the ensembles above), and a parameter may matter only through an interaction, which a
+ * one-at-a-time derivative never sees.  Variance-based global sensitivity analysis answers per output with the first-order index
+ * S_j, the share of the variance that parameter j explains alone, the total index ST_j, its share including every interaction,
+ * and a standard error of each.  A Saltelli design is an ensemble of (npar + 2) nbase members; its member maps stay on the device
+ * and are reduced there over the member axis.  Only the maps that are asked for cross the bus.
+ *   design       ucf_sobol_design, host only, pure copies, no arithmetic.  With N = nbase and draws [2 N][npar]:
+ *                    block 0, rows 0 .. N-1 of thetas:       A = draws[0 .. N)
+ *                    block 1, rows N .. 2N-1:                B = draws[N .. 2N)
+ *                    block 2 + j, j = 0 .. npar-1:           A with column j taken from B
+ *                thetas [(npar + 2) N][npar], row (block) N + r.  Any source of the 2 N draws is legal: ucf_field_ensemble_draw
+ *                with one seed, a Latin hypercube, anything else.  The variance decomposition PRESUPPOSES INDEPENDENT
+ *                PARAMETERS, so a design drawn with a diagonal cov.  With correlated draws the numbers are still computed and
+ *                still repeatable, but S and ST lose that meaning.  UCF_ERR_BAD_ARGUMENT: npar outside 1..UCF_FIT_MAX_PAR,
+ *                nbase outside 2..UCF_SOBOL_MAX_BASE, a NULL array, a draw that is not positive and finite (row and parameter
+ *                are named).
+ *   members      ucf_field_sobol does with the (npar + 2) N members exactly what ucf_field_ensemble does with its nens: the
+ *                same plan rules, the same scratch plan, every member validated and its launch arrays checked before the first
+ *                launch, the same launch sequence per member, the same slots.  Slot m has the bits of ucf_field_drawdown on a
+ *                fresh field and a fresh plan of member m.  No member is skipped or deduplicated.
+ *   reduction    field_sobol_kernel<npar>, one thread per output e, once on the s slots (a = the s slots) and once on the ds
+ *                slots, every operation rounded on its own (no FMA contraction).  fa = a[r][e], fb = a[N + r][e],
+ *                fj = a[(2 + j) N + r][e].  Base row r is COMPLETE at e where all npar + 2 of these values are finite; the Wynn
+ *                sentinel is finite and takes part, as everywhere.  C = the complete rows in ascending r, n = |C|; rows that
+ *                are not complete take part in nothing.
+ *                    nrow[e] = n
+ *                    sA = +0.0; sB = +0.0;   for r in C:  sA = sA + fa;  sB = sB + fb
+ *                    mean[e] = (sA + sB) / (double)(2 n)                                (n = 0: NaN, and everything below NaN)
+ *                    qA = +0.0; qB = +0.0;   for r in C:  d = fa - mean; qA = qA + d*d;  d = fb - mean; qB = qB + d*d
+ *                    var[e] = (qA + qB) / (double)(2 n - 1)
+ *                    per j:  v1 = q1 = vt = qt = +0.0;  for r in C:
+ *                                p  = (fb - mean) * (fj - fa);   v1 = v1 + p;    q1 = q1 + p*p
+ *                                dt = fa - fj;  pt = dt*dt;      vt = vt + pt;   qt = qt + pt*pt
+ *                            m1 = v1 / (double)n;   mt = vt / (double)n
+ *                            S[j][e]  = m1 / var              ST[j][e] = (0.5 * mt) / var               (NaN unless var > 0)
+ *                            w1 = q1/(double)n - m1*m1;   wt = qt/(double)n - mt*mt            (a negative w counts as +0.0)
+ *                            seS[j][e]  = sqrt(w1/(double)(n-1)) / var
+ *                            seST[j][e] = (0.5 * sqrt(wt/(double)(n-1))) / var               (n < 2 or not var > 0: NaN)
+ *                The estimators are Saltelli's of 2010 for the first-order index, with f(B) centred, and Jansen's for the total
+ *                index, both normalised by the pooled sample variance of A u B; seS and seST are the standard errors of the row
+ *                means m1 and mt, taking var as given.  Every NaN written is the quiet NaN 0x7ff8000000000000.
+ *                nbad[0] (s) and nbad[1] (ds) count the outputs with n < nbase (a ballot per wave, one integer atomic per wave,
+ *                no floating-point atomics: a call repeated gives the same bits).
+ *                What the statement implies: a parameter that the map does not depend on has fj bitwise equal to fa in every
+ *                row; its ST and seST are then exactly +0.0, and so are its S and seS, because every p is +-0 and the sums
+ *                start from +0.0 (where var > 0, and for the errors n >= 2).  A constant column has var = 0: all four are NaN.
+ *   outputs      per map one ucf_sobol_maps; every pointer may be NULL, and a NULL struct asks for nothing of that map.  `all`
+ *                [(npar + 2) N][nout] are the member maps as they stand.  stats: summed over all members and groups.
+ * The slots are those of ucf_field_ensemble; the statistics' staging is one more buffer of the field, grown on demand, kept and
+ * counted in ucf_field_alloc_count: a repeated call of the same or a smaller size allocates nothing, and ucf_field_ensemble before
+ * and after it gives the same bits.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything ucf_field_drawdown
+ * checks (its s, ds aside); NULL ids or thetas; npar outside 1..UCF_FIT_MAX_PAR; nbase outside 2..UCF_SOBOL_MAX_BASE; a theta that
+ * is not positive and finite (the member is named); thetas that do not have the design's structure bit for bit --
+ * thetas[(2 + j) N + r][k] is B[r][k] where k == j and A[r][k] otherwise -- (block, row and parameter are named); (npar + 2) N nout
+ * beyond what one buffer may hold.  With a NULL plan UCF_ERR_NO_DEVICE comes before "NULL plan"; with a plan the checks of
+ * ucf_fit_perturb and of every member run before any launch. */
+#define UCF_SOBOL_MAX_BASE 1024     /* base rows N of one design; members = (npar + 2) N */
+typedef struct ucf_sobol_maps {     /* per map (one for s, one for ds); every pointer may be NULL */
+    double *S, *ST, *seS, *seST;    /* [npar][nout] */
+    double *mean, *var;             /* [nout] */
+    double *all;                    /* [(npar + 2) nbase][nout]: the member maps */
+    int    *nrow;                   /* [nout]: complete base rows there */
+} ucf_sobol_maps;
+int ucf_sobol_design(int npar, int nbase, const double* draws /*[2 nbase][npar]*/, double* thetas /*[(npar+2) nbase][npar]*/);
+int ucf_field_sobol(ucf_field* field, ucf_plan* plan, int npar, const int* ids, int nbase, const double* thetas,
+                    int nz, const double* z, const ucf_sobol_maps* s, const ucf_sobol_maps* ds /*either may be NULL*/,
+                    long long* nbad /*[2]: s, ds; NULL ok*/, ucf_stats* stats /*NULL ok*/);
+/* field_sobol_kernel exactly as ucf_field_sobol launches it (the same launcher, and through it the same instantiation), once, on
+ * caller data a [(npar + 2) nbase][nout]: a is uploaded, the maps that `out` asks for (out->all is ignored; out may be NULL) and
+ * nbad[0] are copied back.  a may hold anything.  UCF_ERR_BAD_ARGUMENT: npar or nbase out of range, nout < 1, a NULL a,
+ * (npar + 2) nbase nout beyond what one buffer may hold.  Then UCF_ERR_NO_DEVICE without a device. */
+int ucf_debug_sobol(int npar, int nbase, long long nout, const double* a /*[(npar+2) nbase][nout]*/,
+                    const ucf_sobol_maps* out /*all ignored*/, long long* nbad /*[1]*/);
 /* The reduction kernel of ucf_fit_evaluate exactly as a fit launches it (the same launcher, and through it the same choice among the
  * instantiations: npar 0..UCF_FIT_MAX_PAR x source x with / without derivative data), on caller data.  One 256-thread workgroup
  * per parameter set; set s owns the plans s (1 + 2 npar) + (0 base | 1 + 2j: parameter j up | 2 + 2j: parameter j down);

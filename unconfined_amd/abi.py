@@ -18,6 +18,7 @@ UCF_YIELD_MAX_PAT = 4096      # rate patterns of one ucf_field_yield
 UCF_YIELD_PAT_TILE = 8        # patterns per workgroup of field_yield_kernel
 UCF_TIME_FIRST_ABOVE = 0      # kinds of ucf_field_ensemble_times: the first up-crossing of a limit
 UCF_TIME_LAST_ABOVE = 1       # ... and the abscissa from which the value stays at or below it
+UCF_SOBOL_MAX_BASE = 1024     # base rows N of one Saltelli design; ucf_field_sobol runs (npar + 2) N members
 TIME_KINDS = {"first_above": UCF_TIME_FIRST_ABOVE, "last_above": UCF_TIME_LAST_ABOVE}
 # parameter ids of a fit (enum UCF_PAR_* of include/ucf.h); a Moench alpha is PAR_MOENCH_ALPHA0 + i
 PAR_KR, PAR_KAPPA, PAR_SS, PAR_SY, PAR_AC, PAR_AK, PAR_USL, PAR_MOENCH_ALPHA0 = range(8)
@@ -82,6 +83,12 @@ class UcfEnsembleMaps(C.Structure):
     """ucf_ensemble_maps: the statistics of one map of an ensemble; every address may be NULL"""
     _fields_ = [("mean", C.c_void_p), ("sd", C.c_void_p), ("min", C.c_void_p), ("max", C.c_void_p), ("quant", C.c_void_p),
                 ("all", C.c_void_p), ("nfin", C.c_void_p)]
+
+
+class UcfSobolMaps(C.Structure):
+    """ucf_sobol_maps: the Sobol statistics of one map of a Saltelli design; every address may be NULL"""
+    _fields_ = [("S", C.c_void_p), ("ST", C.c_void_p), ("seS", C.c_void_p), ("seST", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
+                ("all", C.c_void_p), ("nrow", C.c_void_p)]
 
 
 def params_from_deck(dk) -> UcfParams:

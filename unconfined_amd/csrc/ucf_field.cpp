@@ -47,14 +47,16 @@ struct ucf_field {
     ucf_buffer b_yR, b_yint, b_ysmall, b_yval, b_yidx;
     // ucf_field_ensemble_times: T [nens][nlim][nloc][nz]; its series are b_sall, its tau, limits and kinds are staged in b_ens
     ucf_buffer b_tall;
+    // ucf_field_sobol: its slots [(npar + 2) nbase][nout] are b_sall / b_dsall; the staging of every statistic of both maps
+    ucf_buffer b_sob;
     ucf_plan* scratch = nullptr;           // the plan that ucf_field_forecast refreshes for every parameter set
     long long n_alloc = 0;
     // every device buffer above: the one list (ucf_field_destroy frees through it)
-    std::array<ucf_buffer*, 34> buffers()
+    std::array<ucf_buffer*, 35> buffers()
     {
         return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats, &b_sall, &b_dsall, &b_sens, &b_dsens,
                  &b_se, &b_dse, &b_cov, &b_nbad, &b_ens, &b_u, &b_wpost, &b_wcrit, &b_wnused, &b_wsmall, &b_wtsel, &b_widx, &b_wval,
-                 &b_yR, &b_yint, &b_ysmall, &b_yval, &b_yidx, &b_tall}};
+                 &b_yR, &b_yint, &b_ysmall, &b_yval, &b_yidx, &b_tall, &b_sob}};
     }
 };
 
@@ -1115,6 +1117,149 @@ int ucf_debug_field_times(int nens, int nt, long long nsite, const double* a, co
     if ((rc = ucf_field_launch_times(&ta, nullptr))) return fail(rc, "times kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
     HIP_TRY(hipStreamSynchronize(nullptr));
     return copy_back_sync({{T, ta.d_T, sT}});
+}
+
+// what ucf_sobol_design, ucf_field_sobol and ucf_debug_sobol check on the size of a design
+static int sobol_check_size(int npar, int nbase)
+{
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if (nbase < 2 || nbase > UCF_SOBOL_MAX_BASE) return fail(UCF_ERR_BAD_ARGUMENT, "nbase=%d outside 2..%d", nbase, UCF_SOBOL_MAX_BASE);
+    return UCF_OK;
+}
+
+// thetas [(npar + 2) nbase][npar] has the structure of ucf_sobol_design, bit for bit
+static int sobol_check_structure(int npar, int nbase, const double* thetas)
+{
+    const size_t N = (size_t)nbase;
+    for (int j = 0; j < npar; j++)
+        for (int r = 0; r < nbase; r++)
+            for (int k = 0; k < npar; k++) {
+                const double got = thetas[((2 + j) * N + r) * npar + k], want = thetas[((k == j ? N : 0) + r) * npar + k];
+                if (std::memcmp(&got, &want, sizeof(double)) != 0)
+                    return fail(UCF_ERR_BAD_ARGUMENT, "thetas is not a Saltelli design: block %d, row %d, parameter %d is %.17g, but %s[%d][%d] is %.17g",
+                                2 + j, r, k, got, k == j ? "B" : "A", r, k, want);
+            }
+    return UCF_OK;
+}
+
+// the maps of one ucf_sobol_maps in the order of their staging: four [npar][nout], two [nout], then nrow
+static std::array<double*, 6> sobol_doubles(const ucf_sobol_maps& w) { return {{w.S, w.ST, w.seS, w.seST, w.mean, w.var}}; }
+
+int ucf_sobol_design(int npar, int nbase, const double* draws, double* thetas)
+{
+    int rc = sobol_check_size(npar, nbase);
+    if (rc) return rc;
+    if (!draws || !thetas) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !draws ? "draws" : "thetas");
+    for (int r = 0; r < 2 * nbase; r++)
+        for (int k = 0; k < npar; k++) {
+            const double v = draws[(size_t)r * npar + k];
+            if (!(v > 0.0) || !std::isfinite(v))
+                return fail(UCF_ERR_BAD_ARGUMENT, "draws[%d][%d]=%g: row %d, parameter %d must be positive and finite", r, k, v, r, k);
+        }
+    const size_t N = (size_t)nbase;
+    std::copy(draws, draws + 2 * N * npar, thetas);
+    for (int j = 0; j < npar; j++)
+        for (size_t r = 0; r < N; r++)
+            for (int k = 0; k < npar; k++) thetas[((2 + j) * N + r) * npar + k] = draws[((k == j ? N : 0) + r) * npar + k];
+    return UCF_OK;
+}
+
+// The members run as those of ucf_field_ensemble run (field_map_sets into the slots of field_slot_superpose); what differs is
+// their number, the check of the design and the reduction.
+int ucf_field_sobol(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nbase, const double* thetas, int nz, const double* z,
+                    const ucf_sobol_maps* s, const ucf_sobol_maps* ds, long long* nbad, ucf_stats* stats)
+{
+    long long nout = 0;
+    int rc = field_check_call(f, nz, !z ? "NULL z" : !ids ? "NULL ids" : !thetas ? "NULL thetas" : nullptr, z, nout);
+    if (rc) return rc;
+    if ((rc = sobol_check_size(npar, nbase))) return rc;
+    const int nmem = (npar + 2) * nbase;
+    if ((rc = ensemble_check_thetas(npar, ids, nmem, thetas)) || (rc = sobol_check_structure(npar, nbase, thetas))) return rc;
+    if (nmem * nout > 0x7fffffffLL * 256)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d times x %d locations x %d depths: too many values for one buffer", nmem, f->nt, f->nloc, nz);
+    ensemble_members E;
+    if ((rc = ensemble_weights_of(nmem, nullptr, false, nullptr, nullptr, nullptr, E)) ||
+        (rc = ensemble_sets_of(f, pl, npar, ids, nmem, thetas, E))) return rc;
+    std::vector<ucf_params>& sets = E.sets;
+    std::vector<field_launch> L;
+    auto failed = [&](int rc_m, int m) { return ensemble_member_failed(rc_m, m, npar, ids, thetas + (size_t)m * npar); };
+    if ((rc = field_begin_launches(f, pl, stats, &sets[0]))) return rc;
+    ucf_plan* sp = f->scratch;
+    device_switch dg(pl->device);
+    // b_sob: per map what is asked for of S, ST, seS, seST [npar][nout], mean, var [nout], nrow [nout] (ints, padded to whole doubles)
+    const size_t no = (size_t)nout, so = sizeof(double) * no, sa = so * nmem;
+    const ucf_sobol_maps none = {};
+    const ucf_sobol_maps* want[2] = {s ? s : &none, ds ? ds : &none};
+    size_t used = 0, off[2][7];                          // in doubles
+    for (int i = 0; i < 2; i++) {
+        const std::array<double*, 6> w = sobol_doubles(*want[i]);
+        for (int v = 0; v < 7; v++) {
+            const bool asked = v < 6 ? w[v] != nullptr : want[i]->nrow != nullptr;
+            off[i][v] = asked ? used : (size_t)-1;
+            if (asked) used += v < 4 ? no * npar : v < 6 ? no : (no + 1) / 2;
+        }
+    }
+    if ((rc = grow_buffer(f->b_sall, sa, "drawdown of every member", f->n_alloc)) || (rc = grow_buffer(f->b_dsall, sa, "derivative of every member", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_nbad, sizeof(long long) * 2, "counts", f->n_alloc)) ||
+        (used && (rc = grow_buffer(f->b_sob, sizeof(double) * used, "Sobol statistics", f->n_alloc)))) return rc;
+    double* base = (double*)f->b_sob.p;
+    auto dev = [&](size_t o) { return o == (size_t)-1 ? nullptr : base + o; };
+    rc = field_map_sets(f, nmem, sets.data(), [&](int m, const std::vector<field_launch>*& Lm) { Lm = &L; return field_launches_of(f, sets[m], L); },
+                        nz, z, field_slot_superpose(f, nz, nout), stats, failed);
+    if (rc) return rc;
+    hipStream_t st = plan_stream(sp);
+    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
+    drain drained{st};
+    if (hipMemsetAsync(f->b_nbad.p, 0, sizeof(long long) * 2, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "clearing the counts failed: %s", hipGetErrorString(hipGetLastError()));
+    const double* slots[2] = {(const double*)f->b_sall.p, (const double*)f->b_dsall.p};
+    for (int i = 0; i < 2 && rc == UCF_OK; i++) {
+        ucf_sobol_args ka = {};
+        ka.npar = npar; ka.nbase = nbase; ka.nout = nout; ka.d_a = slots[i];
+        ka.d_S = dev(off[i][0]); ka.d_ST = dev(off[i][1]); ka.d_seS = dev(off[i][2]); ka.d_seST = dev(off[i][3]);
+        ka.d_mean = dev(off[i][4]); ka.d_var = dev(off[i][5]); ka.d_nrow = (int*)dev(off[i][6]); ka.d_nbad = (long long*)f->b_nbad.p + i;
+        rc = ucf_field_launch_sobol(&ka, st);
+    }
+    if (rc) return fail(rc, "Sobol kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    // only what is asked for crosses the bus
+    std::vector<device_copy> back = {{nbad, f->b_nbad.p, sizeof(long long) * 2}};
+    for (int i = 0; i < 2; i++) {
+        const std::array<double*, 6> w = sobol_doubles(*want[i]);
+        for (int v = 0; v < 6; v++) back.push_back({w[v], dev(off[i][v]), v < 4 ? so * npar : so});
+        back.push_back({want[i]->nrow, dev(off[i][6]), sizeof(int) * no});
+        back.push_back({want[i]->all, slots[i], sa});
+    }
+    return copy_back(back, st, pl->device);
+}
+
+int ucf_debug_sobol(int npar, int nbase, long long nout, const double* a, const ucf_sobol_maps* out, long long* nbad)
+{
+    int rc = sobol_check_size(npar, nbase);
+    if (rc) return rc;
+    const long long nmem = (long long)(npar + 2) * nbase;
+    if (nout < 1 || nout > 0x7fffffffLL * 256 / nmem)
+        return fail(UCF_ERR_BAD_ARGUMENT, "nout=%lld: at least one output, at most 2^39 values in %lld members", nout, nmem);
+    if (!a) return fail(UCF_ERR_BAD_ARGUMENT, "NULL a");
+    if ((rc = require_device())) return rc;
+    const ucf_sobol_maps none = {};
+    const std::array<double*, 6> w = sobol_doubles(out ? *out : none);
+    int* nrow = out ? out->nrow : nullptr;
+    const size_t no = (size_t)nout, so = sizeof(double) * no, sa = so * (size_t)nmem;
+    dev_buf b_a, b_w[6], b_nrow, b_nbad;
+    bool short_of = b_a.alloc(sa) || b_nbad.alloc(sizeof(long long)) || (nrow && b_nrow.alloc(sizeof(int) * no));
+    for (int v = 0; v < 6 && !short_of; v++) short_of = w[v] && b_w[v].alloc(v < 4 ? so * npar : so);
+    if (short_of) return fail(UCF_ERR_NOMEM, "device allocation failed");
+    HIP_TRY(hipMemcpy(b_a.p, a, sa, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b_nbad.p, 0, sizeof(long long)));
+    ucf_sobol_args ka = {};
+    ka.npar = npar; ka.nbase = nbase; ka.nout = nout; ka.d_a = (const double*)b_a.p;
+    ka.d_S = (double*)b_w[0].p; ka.d_ST = (double*)b_w[1].p; ka.d_seS = (double*)b_w[2].p; ka.d_seST = (double*)b_w[3].p;
+    ka.d_mean = (double*)b_w[4].p; ka.d_var = (double*)b_w[5].p; ka.d_nrow = (int*)b_nrow.p; ka.d_nbad = (long long*)b_nbad.p;
+    if ((rc = ucf_field_launch_sobol(&ka, nullptr))) return fail(rc, "Sobol kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    std::vector<device_copy> back = {{nbad, b_nbad.p, sizeof(long long)}, {nrow, b_nrow.p, sizeof(int) * no}};
+    for (int v = 0; v < 6; v++) back.push_back({w[v], b_w[v].p, v < 4 ? so * npar : so});
+    return copy_back_sync(back);
 }
 
 // what ucf_field_yield and ucf_debug_field_yield check on the controls' count, the patterns and smax

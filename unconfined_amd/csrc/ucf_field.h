@@ -1,8 +1,8 @@
 // ucf_field.h -- launchers of the well-field kernels: the superposition, called by ucf_field_drawdown, ucf_field_forecast and
 // ucf_field_ensemble (ucf_field.cpp), the response slots of ucf_field_yield, the combination of a forecast (all three
 // ucf_field.hip), the reduction of an ensemble (ucf_field_ensemble.hip), the data worth of candidate wells
-// (ucf_field_worth.hip), the ratio test of ucf_field_yield (ucf_field_yield.hip) and the time kernel of
-// ucf_field_ensemble_times (ucf_field_times.hip).
+// (ucf_field_worth.hip), the ratio test of ucf_field_yield (ucf_field_yield.hip), the time kernel of
+// ucf_field_ensemble_times (ucf_field_times.hip) and the reduction of a Saltelli design (ucf_field_sobol.hip).
 #pragma once
 #include <cstddef>
 
@@ -63,6 +63,22 @@ struct ucf_times_args {
 };
 // UCF_ERR_BAD_ARGUMENT for what the comments above exclude and for a NULL array (the caller has checked tau, the limits and the kinds)
 int ucf_field_launch_times(const ucf_times_args* a, void* stream);
+
+// The reduction of a Saltelli design over its member axis (ucf_field_sobol.hip), field_sobol_kernel<npar>: one thread per output
+// e of the member maps d_a [(npar + 2) nbase][nout] -- block 0 the rows of A, block 1 those of B, block 2 + j those of A with
+// column j from B --, a workgroup of 256 threads; the arithmetic is stated with ucf_field_sobol in include/ucf.h.  Device memory
+// throughout.
+struct ucf_sobol_args {
+    int npar, nbase;                       // 1..UCF_FIT_MAX_PAR, 2..UCF_SOBOL_MAX_BASE
+    long long nout;                        // >= 1
+    const double* d_a;                     // [(npar + 2) nbase][nout]
+    double *d_S, *d_ST, *d_seS, *d_seST;   // [npar][nout]; these, d_mean, d_var and d_nrow may each be NULL (not written)
+    double *d_mean, *d_var;                // [nout]
+    int* d_nrow;                           // [nout] the complete base rows
+    long long* d_nbad;                     // += the outputs with fewer than nbase complete rows; the caller zeroes it
+};
+// UCF_ERR_BAD_ARGUMENT for what the comments above exclude and for a grid beyond 2^31 - 1 workgroups
+int ucf_field_launch_sobol(const ucf_sobol_args* a, void* stream);
 
 // The combination of a forecast, field_forecast_kernel<npar>: one thread per output e of the slots d_a [1 + 2 npar][nout]
 // (slot 0 the base set, slot 1 + 2j / 2 + 2j parameter j up / down), every operation rounded on its own:

@@ -50,6 +50,13 @@ is -- one time per member, limit, location and depth, formed and reduced on the 
     res = field.time_to_limit(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], limits=[0.5, 0.1], kinds=["first_above", "last_above"],
                               horizons=[365.0], abscissa="lnt")
     res.quant[1], 1.0 - res.later[0]                                                          # the median time, P(crossed within a year)
+
+Which parameter causes the spread of the forecast where the posterior is too wide to linearise -- first-order and total Sobol
+indices per output with their standard errors, from a Saltelli design of (npar + 2) n members that stay on the GPU (ucf_field_sobol):
+
+    design = sobol_design(res["theta"][0], res["cov"][0], 64, seed=1)                         # [(npar + 2) 64, npar]
+    sob = field.sobol(plan, ["Kr", "Ss"], design, z=[145.7, 100.0])
+    sob.S, sob.ST - sob.S, sob.se_S                                                           # alone, through interactions, how sure
 """
 from __future__ import annotations
 
@@ -58,7 +65,7 @@ import ctypes as C
 import numpy as np
 
 from . import lib as _libmod
-from .abi import TIME_KINDS, UcfEnsembleMaps, UcfParams, UcfStats
+from .abi import TIME_KINDS, UcfEnsembleMaps, UcfParams, UcfSobolMaps, UcfStats
 from .fit import par_id
 
 KINDS = {"no_flow": 0, "constant_head": 1, 0: 0, 1: 1}
@@ -94,6 +101,23 @@ def ensemble_draw(theta, cov, n: int, seed: int = 0):
         raise ValueError("cov: [npar, npar]")
     out = np.zeros((max(int(n), 0), len(theta)))
     _libmod.check(_libmod.load().ucf_field_ensemble_draw(len(theta), _addr(theta), _addr(cov), int(n), int(seed) & (2 ** 64 - 1), _addr(out)))
+    return out
+
+
+def sobol_design(theta, cov, n: int, seed: int = 0):
+    """the Saltelli design [(npar + 2) n, npar] of ``n`` base rows for ``WellField.sobol``: 2 n parameter sets are drawn as
+    ``ensemble_draw(theta, diag(diag(cov)), 2 n, seed)`` does, the first n are A, the next n are B, and block 2 + j is A with
+    column j taken from B (ucf_sobol_design; no GPU).  ONLY THE DIAGONAL of ``cov`` is used: the variance decomposition behind S
+    and ST presupposes independent parameters, and with correlated draws the indices, though still computed, would not mean
+    the shares of the variance that they are read as."""
+    theta = np.atleast_1d(_f64(theta))
+    cov = np.atleast_2d(_f64(cov))
+    if cov.shape != (len(theta), len(theta)):
+        raise ValueError("cov: [npar, npar]")
+    n = int(n)
+    draws = ensemble_draw(theta, np.diag(np.diag(cov)), 2 * n, seed)
+    out = np.zeros(((len(theta) + 2) * max(n, 0), len(theta)))
+    _libmod.check(_libmod.load().ucf_sobol_design(len(theta), n, _addr(draws), _addr(out)))
     return out
 
 
@@ -151,6 +175,22 @@ class TimeToLimit:
     def __repr__(self):
         return (f"TimeToLimit(limits={self.limits.tolist()}, kinds={self.kinds.tolist()}, abscissa={self.abscissa!r}, never={self.never!r}, "
                 f"shape={self.mean.shape}, nbad={self.nbad})")
+
+
+class SobolMaps:
+    """what ``WellField.sobol`` returns.  S, ST, se_S, se_ST [npar, nt, nloc, nz]: the first-order and the total Sobol index of
+    every free parameter for the drawdown and their standard errors; mean, var [nt, nloc, nz], the pooled mean and variance of
+    the two base samples; nrow (int32) the base rows that are complete at an output -- the others take part in nothing; with the
+    derivative dS, dST, dse_S, dse_ST, dmean, dvar, dnrow of t ds/dt; with the members all (and dall) [(npar + 2) n, nt, nloc, nz];
+    nbad [2], the outputs of s and of ds where a base row is not complete; nbase; stats where asked for.  An array that was not
+    asked for is None.  An index is NaN where the variance is not positive."""
+
+    def __init__(self, **kw):
+        self.dS = self.dST = self.dse_S = self.dse_ST = self.dmean = self.dvar = self.dnrow = self.all = self.dall = self.stats = None
+        self.__dict__.update(kw)
+
+    def __repr__(self):
+        return f"SobolMaps(npar={self.S.shape[0]}, nbase={self.nbase}, shape={self.mean.shape}, nbad={self.nbad.tolist()})"
 
 
 class WellField:
@@ -494,6 +534,40 @@ class WellField:
         res = TimeToLimit(limits=lim, kinds=kind, abscissa=abscissa, never=never, q=qs, horizons=hor, log_moments=log, nbad=int(nbad.value), **out)
         if w is not None:
             res.u, res.ess, res.nlaunched = u, float(ess.value), int(nl.value)
+        if with_stats:
+            res.stats = {k: getattr(st, k) for k, _ in UcfStats._fields_}
+        return res
+
+    def sobol(self, plan, free, thetas, z, derivative: bool = True, members: bool = False, with_stats: bool = False) -> "SobolMaps":
+        """which parameter causes the spread of the drawdown (ucf_field_sobol): ``thetas`` [(npar + 2) n, npar] is a Saltelli
+        design of the free parameters as ``sobol_design`` makes it (the library checks its structure); all its members are
+        evaluated as ``ensemble`` evaluates them, stay on the GPU and are reduced there, per output, to the first-order index S
+        (the share of the variance that a parameter explains alone), the total index ST (its share with every interaction) and
+        their standard errors.  Returns a ``SobolMaps``.  ``plan`` is not modified."""
+        ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
+        thetas = np.atleast_2d(_f64(thetas))
+        npar = len(ids)
+        if thetas.ndim != 2 or thetas.shape[1] != npar:
+            raise ValueError("thetas: [(npar + 2) n, npar], one value per free parameter")
+        if len(thetas) % (npar + 2):
+            raise ValueError("thetas: (npar + 2) n rows, the blocks of a Saltelli design")
+        nbase, nmem = len(thetas) // (npar + 2), len(thetas)
+        z = np.atleast_1d(_f64(z))
+        shape = (self.nt, self.nloc, len(z))
+        out, keep = {}, []
+        for pre in ("", "d") if derivative else ("",):
+            for key in ("S", "ST", "se_S", "se_ST"):
+                out[pre + key] = np.zeros((npar,) + shape)
+            out[pre + "mean"], out[pre + "var"] = np.zeros(shape), np.zeros(shape)
+            out[pre + "nrow"] = np.zeros(shape, np.int32)
+            if members:
+                out[pre + "all"] = np.zeros((nmem,) + shape)
+            keep.append(UcfSobolMaps(*(_addr(out.get(pre + key)) for key in ("S", "ST", "se_S", "se_ST", "mean", "var", "all", "nrow"))))
+        out["nbad"] = np.zeros(2, np.int64)
+        st = UcfStats()
+        _libmod.check(self._lib.ucf_field_sobol(self._h, plan._h, npar, _addr(ids), nbase, _addr(thetas), len(z), _addr(z), C.byref(keep[0]),
+                                                C.byref(keep[1]) if derivative else None, _addr(out["nbad"]), C.byref(st) if with_stats else None))
+        res = SobolMaps(nbase=nbase, **out)
         if with_stats:
             res.stats = {k: getattr(st, k) for k, _ in UcfStats._fields_}
         return res

@@ -12,7 +12,7 @@ import subprocess
 
 import numpy as np
 
-from .abi import UcfDerived, UcfEnsembleMaps, UcfFitOptions, UcfParams, UcfStats
+from .abi import UcfDerived, UcfEnsembleMaps, UcfFitOptions, UcfParams, UcfSobolMaps, UcfStats
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # UCF_LIB_PATH: an experimental build of the SAME library (tools/ubench/build_variant.sh) for A/B timing; the product
@@ -49,6 +49,7 @@ EXPORTS = [
     "ucf_field_worth", "ucf_worth_condition", "ucf_debug_field_worth",
     "ucf_field_yield", "ucf_debug_field_yield",
     "ucf_field_ensemble_times", "ucf_debug_field_times",
+    "ucf_sobol_design", "ucf_field_sobol", "ucf_debug_sobol",
     "ucf_fit_loss_terms", "ucf_fit_robust_scale", "ucf_fit_set_loss", "ucf_fit_get_loss", "ucf_fit_loss_report", "ucf_debug_fit_reduce_loss",
     "ucf_fit_set_resample", "ucf_fit_evaluate_resampled", "ucf_fit_objective_resampled", "ucf_fit_lm_resampled",
     "ucf_fit_resample_blocks", "ucf_fit_resample_jackknife", "ucf_fit_resample_cov", "ucf_debug_fit_reduce_resampled",
@@ -209,6 +210,13 @@ def load() -> C.CDLL:
                                              [C.c_int, vp, C.c_int, vp] + [C.POINTER(UcfEnsembleMaps), vp, vp] + [C.POINTER(UcfStats)] + [vp] * 3)
     # nens, nt, nsite, a, tau, tau_never, nlim, limit, kind, T
     lib.ucf_debug_field_times.argtypes = [C.c_int, C.c_int, C.c_longlong, vp, vp, C.c_double, C.c_int, vp, vp, vp]
+    # every array may be NULL: plain addresses.  npar, nbase, draws, thetas
+    lib.ucf_sobol_design.argtypes = [C.c_int, C.c_int, vp, vp]
+    # field, plan, npar, ids, nbase, thetas, nz, z | s, ds | nbad | stats
+    lib.ucf_field_sobol.argtypes = ([vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp] + [C.POINTER(UcfSobolMaps), C.POINTER(UcfSobolMaps)] +
+                                    [vp, C.POINTER(UcfStats)])
+    # npar, nbase, nout, a, out, nbad
+    lib.ucf_debug_sobol.argtypes = [C.c_int, C.c_int, C.c_longlong, vp, C.POINTER(UcfSobolMaps), vp]
     # every array may be NULL for a source or a call that does not read it: plain addresses
     lib.ucf_debug_fit_reduce.argtypes = ([C.c_int] * 4 + [C.c_double, C.c_longlong] + [vp] * 8 + [C.c_longlong, C.c_int] + [vp] * 7 + [vp] * 6)
     # x, rho, b, scale and every output may be NULL: plain addresses
