@@ -1058,6 +1058,146 @@ int ucf_field_yield(ucf_field* field, ucf_plan* plan, int npar, const int* ids,
 int ucf_debug_field_yield(int nctl, int nens, int ncon, int npat, const double* R, const double* x, const double* limit_con,
                           const int* con, double smax, double* y, double* fe, double* hi, double* lo, int* bind, int* dead,
                           long long* nbad /*[1]*/);
+/* ---- well-field allocation: HOW should the abstraction be distributed over the wells so that the total is largest and every
+ * receptor stays within its limit, which receptors limit that optimum, what would relaxing a limit buy, and how sure is that
+ * under the posterior (the response-matrix method, Gorelick 1983).  Drawdown is linear in the rates, so per member the question is a
+ * linear programme in at most UCF_YIELD_MAX_CTL unknowns; its data are the response slots R that the member loop of
+ * ucf_field_yield leaves on the device.  Controls, ctl, the fixed-well slot, con, limit and R are exactly those of ucf_field_yield.
+ *   programme    per member m and objective o, in the multipliers x_c (c = 0 .. nctl-1) on the qw of the wells of control c -- what
+ *                a pattern of ucf_field_yield is at scale 1:
+ *                    maximise    g = sum_c w[o][c] x_c
+ *                    subject to  R[m][nctl][i] + sum_c x_c R[m][c][i] <= limit[con[i]]      i = 0 .. ncon-1
+ *                                0 <= x_c <= xmax[c]
+ *                w [nobj][nctl] finite (negative and zero are legal), nobj in 1..UCF_ALLOC_MAX_OBJ; xmax [nctl] positive and finite:
+ *                the pump capacities, which keep every programme bounded.
+ *   constraints  every constraint is a row a . x <= beta with an id, used for every tie-break and in every output:
+ *                    id c          (c = 0 .. nctl-1)   lower bound   a = -e_c (-1.0 at c, +0.0 elsewhere),  beta = +0.0
+ *                    id nctl + c                       upper bound   a = +e_c (1.0 at c, +0.0 elsewhere),   beta = xmax[c]
+ *                    id 2 nctl + i (i = 0 .. ncon-1)   output row    a_c = R[m][c][i],   beta = room_i = limit[con[i]] - R[m][nctl][i]
+ *   solve(A, b)  the nctl x nctl systems: Gaussian elimination with partial pivoting on copies of A and b, n = nctl:
+ *                    for col = 0 .. n-1:
+ *                        piv = the row r in col .. n-1 with the largest |A[r][col]|, the lowest r among equals (a later row wins only
+ *                              with a magnitude that is greater under >)
+ *                        a pivot magnitude that is zero, NaN or infinite ends the programme: status NUMERIC
+ *                        rows piv and col of A and b are exchanged
+ *                        for r = col+1 .. n-1:   f = A[r][col] / A[col][col]
+ *                                                A[r][c] = A[r][c] - f * A[col][c],  c = col+1 .. n-1;     b[r] = b[r] - f * b[col]
+ *                    for r = n-1 .. 0:   s = b[r];   s = s - A[r][c] * y[c],  c = r+1 .. n-1 ascending;   y[r] = s / A[r][r]
+ *                every product, difference and quotient rounded on its own.
+ *   algorithm    a primal active-set simplex from the vertex x = +0.0, working set W[s] = s (the lower bounds), s = 0 .. nctl-1:
+ *                    valid:   every one of the (nctl + 1) ncon slot values of the member is finite; else status INVALID
+ *                    start:   if any room_i < 0 the fixed wells alone exceed a limit: status INFEASIBLE_AT_ZERO, nothing is solved
+ *                             (injection, a negative x, as a repair is out of scope)
+ *                    iters = 0;  repeat at most maxit times (maxit in 1..UCF_ALLOC_MAX_ITER):
+ *                      1. B = the rows of W, row s = a of W[s].  lambda = solve(B', w[o]).  No lambda_s < 0: status OPTIMAL, stop.
+ *                      2. k = the slot s with the lowest id W[s] among those with lambda_s < 0 (Bland's rule).
+ *                      3. d = solve(B, -e_k), the right-hand side -1.0 at k and +0.0 elsewhere.
+ *                      4. over every constraint j that is not in W:
+ *                             output row:   D = +0.0, S = +0.0, ax = +0.0;  for c ascending:  p = a_c * d_c;  D = D + p;
+ *                                           S = S + |p|;  ax = ax + a_c * x_c;            slack = room_i - ax
+ *                             lower bound:  D = -d_c, slack = x_c;       upper bound:  D = d_c, slack = xmax[c] - x_c;
+ *                                           S = dmax = the largest |d_c| (any order: it is a maximum)
+ *                             D > UCF_ALLOC_DTOL * S:  if slack < 0 (rounding):  slack = +0.0;     cand = slack / D
+ *                         (step, enter) = the lexicographic minimum of (cand, id j) over the constraints that pass the test on D,
+ *                         defined without order as hi and bind of the ratio test are: the least cand, the lowest id among those
+ *                         that attain it under ==.  A cand, a D or an S that is NaN passes no comparison.  No candidate: status
+ *                         NUMERIC, stop.  Why D > 0 alone does not do: the twin of a working row (the same drawdown at two depths
+ *                         of a fully penetrating well) and a row through the vertex along the edge have D = 0 exactly, computed as
+ *                         rounding noise of either sign; a positive one has slack 0, wins the test and makes B singular.  The
+ *                         rounding of D is at most nctl 2^-53 S (nctl products and sums of terms bounded by S), the error that d
+ *                         inherits from its solve is of the order of cond(B) 2^-53 S; UCF_ALLOC_DTOL = 2^-40 lies 2^10 above the
+ *                         first and still far below any D that moves the vertex by a representable amount.  With S = 0 the test is
+ *                         D > 0.
+ *                      5. W[k] = enter;  x = solve(B, beta) on the rows and right-hand sides of the new W (never x + step d);
+ *                         iters = iters + 1.
+ *                    the maxit pivots are spent and step 1 has not said OPTIMAL: status ITERATION_CAP (a programme that needs
+ *                    exactly maxit pivots ends so: optimality is tested before a pivot, not after the last)
+ *   polish       at OPTIMAL, before anything is written: x and g in double-double (a value is hi + lo), so that what is returned
+ *                is the vertex of the final working set and its value rounded once and not the sum of the roundings of one
+ *                elimination.  two_sum(a, b) = (s, err):  s = a + b;  bb = s - a;  err = (a - (s - bb)) + (b - bb)   (exact).
+ *                add((h, l), (p, e)):  (s, t) = two_sum(h, p);  low = l + (t + e);  h = s + low;  l = low - (h - s).
+ *                addprod((h, l), sign, a, (xh, xl)):  p = a * xh;  e = fma(a, xh, -p) (the exact error of p; the one fused
+ *                operation of the contract);  add((h, l), (sign * p, sign * (e + a * xl))).
+ *                    xl = +0.0;  twice:
+ *                        per slot s:  (h, l) = (beta, +0.0) of a bound, two_sum(limit[con[i]], -R[m][nctl][i]) of an output row;
+ *                                     addprod((h, l), -1.0, B[s][c], (x_c, xl_c)), c ascending;     r_s = h
+ *                        e = solve(B, r);     (x_c, xl_c) = add((x_c, xl_c), (e_c, +0.0))
+ *                    (g, gl) = (+0.0, +0.0);  addprod((g, gl), 1.0, w[o][c], (x_c, xl_c)), c ascending
+ *                x (the high parts) and g are what is returned, and x is what the reliability stage scales.
+ *   outputs      per (m, o), [nens][nobj] leading: x [nctl] and g, both as polished; status (UCF_ALLOC_*) and
+ *                iters, the pivots made; work [nctl], the ids of W at the optimum, ascending -- the receptors (and capacities) that
+ *                limit the well field --, and lam [nctl], the lambda of step 1 of the same constraints: the shadow prices, the gain
+ *                in g per unit of relaxed limit.  With a status other than OPTIMAL x, g and lam are NaN and work is -1; for an
+ *                invalid member iters is 0.  *nbad = the launched members that are invalid, each counted once (one integer atomic
+ *                per member).  A member of weight 0 is not launched (its R is NaN bytes): its outputs are those of an invalid member
+ *                and it is not counted.  No floating-point atomics: a call repeated gives the same bits.
+ *   kernel       field_allocate_kernel<nctl>, one workgroup of 256 threads per (m, o).  Steps 1 to 3 and 5 are done by one thread
+ *                on LDS; step 4 is shared by the 256 threads, combined by a wave butterfly on (cand, id) and through LDS.  A
+ *                member's R is reread once per iteration.  ucf_allocate_solve is the same arithmetic on the host, bit for bit.
+ *   reliability  optional, in the same call, while R is on the device; skipped when quant, value, best and best_x are all NULL;
+ *                needs nq >= 1 and nens nobj <= UCF_YIELD_MAX_PAT.  The optima become rate patterns: pattern p = m nobj + o is
+ *                x of (m, o), all +0.0 where the status is not OPTIMAL.  They run through field_yield_kernel as in
+ *                ucf_field_yield with smax = 1 (candidates are only ever scaled DOWN and stay within xmax); the member reduction
+ *                of ucf_field_ensemble (weighted with weights) on y [nens][npat] gives quant [nq][npat]: quant[q][p] is the scale
+ *                of candidate p that a share 1 - q of the members admits.  On the host (ucf_allocate_select):
+ *                    value[q][p] = quant[q][p] * g[p]                                   (one product; NaN propagates)
+ *                    best[q][o]  = the p = m nobj + o with the largest value[q][p] under >, m ascending: the lowest p wins ties,
+ *                                  a NaN value is never chosen, -1 where none is
+ *                    best_x[q][o][c] = quant[q][best] * x[best][c]                      (NaN where best is -1)
+ *                What this is: a FEASIBLE allocation at reliability 1 - q, chosen among the nens scenario optima and scaled down
+ *                -- a lower bound on the chance-constrained optimum, not that optimum.  gquant [nq][nobj], the quantiles of the
+ *                per-member g (the same reduction on g, members without an optimum left out), is the wait-and-see figure above it:
+ *                what a manager who knew the member could pump.
+ * x, g, lam, status, iters and work are buffers of the field like those of ucf_field_yield, and so are the y, hi, lo, bind, dead
+ * of the reliability stage: a repeated call of the same or a smaller size allocates nothing.
+ * Validation comes first and needs no GPU (UCF_ERR_BAD_ARGUMENT, offender in ucf_last_error): everything ucf_field_yield checks on
+ * field, nz, z, npar, ids, nens, thetas, nq, q, weight, nctl, ctl and limit (nq may be 0 unless the reliability stage or gquant is
+ * asked for); nobj outside 1..UCF_ALLOC_MAX_OBJ; a NULL w or xmax; a w that is not finite; an xmax that is not positive and finite;
+ * maxit outside 1..UCF_ALLOC_MAX_ITER; the reliability stage with nens nobj > UCF_YIELD_MAX_PAT. */
+#define UCF_ALLOC_MAX_OBJ 8        /* objectives of one ucf_field_allocate */
+#define UCF_ALLOC_MAX_ITER 256     /* the largest maxit */
+#define UCF_ALLOC_DTOL 0x1p-40     /* step 4: a D that is not above this times its scale S is zero up to rounding */
+#define UCF_ALLOC_INVALID (-1)
+#define UCF_ALLOC_OPTIMAL 0
+#define UCF_ALLOC_ITERATION_CAP 1
+#define UCF_ALLOC_INFEASIBLE_AT_ZERO 2
+#define UCF_ALLOC_NUMERIC 3
+int ucf_field_allocate(ucf_field* field, ucf_plan* plan, int npar, const int* ids,
+                       int nens, const double* thetas /*[nens][npar]*/, const double* weight /*[nens]; NULL ok: unweighted*/,
+                       int nz, const double* z,
+                       int nctl, const int* ctl /*[nwell]*/,
+                       int nobj, const double* w /*[nobj][nctl]*/, const double* xmax /*[nctl]*/, int maxit,
+                       const double* limit /*[nt][nloc][nz]*/,
+                       double* x /*[nens][nobj][nctl]*/, double* g /*[nens][nobj]*/, int* status, int* iters /*[nens][nobj]*/,
+                       int* work /*[nens][nobj][nctl]*/, double* lam /*[nens][nobj][nctl]*/,
+                       int nq, const double* q /*[nq]*/,
+                       double* quant /*[nq][nens nobj]*/, double* value /*[nq][nens nobj]*/, int* best /*[nq][nobj]*/,
+                       double* best_x /*[nq][nobj][nctl]*/, double* gquant /*[nq][nobj]*/,
+                       double* resp /*[nens][nctl+1][ncon]*/, int* con /*[nout], first *ncon filled*/, int* ncon,
+                       long long* nbad /*[1]*/, ucf_stats* stats,
+                       unsigned long long* u /*[nens]*/, double* ess, int* nlaunched);
+/* The arithmetic of field_allocate_kernel for ONE member on host arrays, no GPU: R_m [nctl + 1][ncon] (may hold anything),
+ * limit_con [ncon] (the limit of constrained output i), w [nobj][nctl], xmax [nctl]; x, lam [nobj][nctl], g [nobj], status, iters
+ * [nobj], work [nobj][nctl]: each NULL ok.  The kernel is held to it bit for bit.  UCF_ERR_BAD_ARGUMENT as ucf_debug_field_allocate
+ * on the arguments the two share. */
+int ucf_allocate_solve(int nctl, int ncon, const double* R_m, const double* limit_con, int nobj, const double* w, const double* xmax,
+                       int maxit, double* x, double* g, int* status, int* iters, int* work, double* lam);
+/* The host step of the reliability stage, no GPU: value, best and best_x as stated above from quant [nq][nens nobj], g
+ * [nens][nobj] and x [nens][nobj][nctl] (any values).  value, best, best_x: each NULL ok.  UCF_ERR_BAD_ARGUMENT: nq outside
+ * 1..UCF_ENSEMBLE_MAX_Q, nens outside 1..UCF_ENSEMBLE_MAX, nobj outside 1..UCF_ALLOC_MAX_OBJ, nctl outside 1..UCF_YIELD_MAX_CTL, a
+ * NULL quant, g or x. */
+int ucf_allocate_select(int nq, int nens, int nobj, int nctl, const double* quant, const double* g, const double* x, double* value,
+                        int* best, double* best_x);
+/* field_allocate_kernel exactly as ucf_field_allocate launches it (the same launcher), once, on caller data R
+ * [nens][nctl + 1][ncon], limit_con [ncon], con [ncon], w [nobj][nctl], xmax [nctl]: the twin of ucf_debug_field_yield.  x, g,
+ * status, iters, work, lam as in ucf_field_allocate and nbad [1] (every invalid member): each NULL ok.  R may hold anything.
+ * UCF_ERR_BAD_ARGUMENT: nctl outside 1..UCF_YIELD_MAX_CTL, nens outside 1..UCF_ENSEMBLE_MAX, ncon < 1, nobj outside
+ * 1..UCF_ALLOC_MAX_OBJ, maxit outside 1..UCF_ALLOC_MAX_ITER, nens (nctl + 1) ncon beyond 2^31-1 values, a NULL R, limit_con, con, w
+ * or xmax, a w or a limit_con that is not finite, an xmax that is not positive and finite, a con that is negative or does not
+ * ascend strictly.  Then UCF_ERR_NO_DEVICE without a device. */
+int ucf_debug_field_allocate(int nctl, int nens, int ncon, int nobj, const double* R, const double* limit_con, const int* con,
+                             const double* w, const double* xmax, int maxit, double* x, double* g, int* status, int* iters, int* work,
+                             double* lam, long long* nbad /*[1]*/);
 /* ---- well-field times: WHEN does the drawdown at a receptor first pass a permitted value, from when on does it stay below one
  * after the pumps have stopped, and how sure is either under the posterior.  The member maps of an ensemble are on the device when
  * its member loop ends; field_times_kernel turns every member's time series at every (location, depth) into a time per limit,

@@ -16,6 +16,11 @@ UCF_WORTH_MAX_PICK = 16       # wells that one ucf_field_worth picks
 UCF_YIELD_MAX_CTL = 8         # controls of one ucf_field_yield
 UCF_YIELD_MAX_PAT = 4096      # rate patterns of one ucf_field_yield
 UCF_YIELD_PAT_TILE = 8        # patterns per workgroup of field_yield_kernel
+UCF_ALLOC_MAX_OBJ = 8         # objectives of one ucf_field_allocate
+UCF_ALLOC_MAX_ITER = 256      # the largest maxit of ucf_field_allocate
+UCF_ALLOC_DTOL = 2.0 ** -40   # its ratio test: a D that is not above this times its scale is zero up to rounding
+# the status of one linear programme of ucf_field_allocate
+UCF_ALLOC_INVALID, UCF_ALLOC_OPTIMAL, UCF_ALLOC_ITERATION_CAP, UCF_ALLOC_INFEASIBLE_AT_ZERO, UCF_ALLOC_NUMERIC = -1, 0, 1, 2, 3
 UCF_TIME_FIRST_ABOVE = 0      # kinds of ucf_field_ensemble_times: the first up-crossing of a limit
 UCF_TIME_LAST_ABOVE = 1       # ... and the abscissa from which the value stays at or below it
 UCF_SOBOL_MAX_BASE = 1024     # base rows N of one Saltelli design; ucf_field_sobol runs (npar + 2) N members

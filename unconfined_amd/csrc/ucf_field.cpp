@@ -45,6 +45,10 @@ struct ucf_field {
     // ucf_field_yield: the response slots R [nens][nctl + 1][ncon]; con [ncon] and ctl [nwell]; x [npat][nctl] and the limits
     // [ncon]; y, fe, hi, lo [4][nens][npat]; bind, dead [2][nens][npat].  Its statistics are staged in b_ens.
     ucf_buffer b_yR, b_yint, b_ysmall, b_yval, b_yidx;
+    // ucf_field_allocate: x, lam [2][nens][nobj][nctl] and g [nens][nobj]; status, iters [2][nens][nobj] and work
+    // [nens][nobj][nctl].  Its slots, limits and controls are those of ucf_field_yield (w, xmax and the patterns of the reliability
+    // stage in b_ysmall), the reliability stage runs in b_yval / b_yidx and its statistics are staged in b_ens.
+    ucf_buffer b_aval, b_aidx;
     // ucf_field_ensemble_times: T [nens][nlim][nloc][nz]; its series are b_sall, its tau, limits and kinds are staged in b_ens
     ucf_buffer b_tall;
     // ucf_field_sobol: its slots [(npar + 2) nbase][nout] are b_sall / b_dsall; the staging of every statistic of both maps
@@ -52,11 +56,11 @@ struct ucf_field {
     ucf_plan* scratch = nullptr;           // the plan that ucf_field_forecast refreshes for every parameter set
     long long n_alloc = 0;
     // every device buffer above: the one list (ucf_field_destroy frees through it)
-    std::array<ucf_buffer*, 35> buffers()
+    std::array<ucf_buffer*, 37> buffers()
     {
         return {{&b_tD, &b_sv, &b_rD, &b_tfac, &b_col, &b_wells, &b_h, &b_dh, &b_s, &b_ds, &b_stats, &b_sall, &b_dsall, &b_sens, &b_dsens,
                  &b_se, &b_dse, &b_cov, &b_nbad, &b_ens, &b_u, &b_wpost, &b_wcrit, &b_wnused, &b_wsmall, &b_wtsel, &b_widx, &b_wval,
-                 &b_yR, &b_yint, &b_ysmall, &b_yval, &b_yidx, &b_tall, &b_sob}};
+                 &b_yR, &b_yint, &b_ysmall, &b_yval, &b_yidx, &b_tall, &b_sob, &b_aval, &b_aidx}};
     }
 };
 
@@ -1262,6 +1266,143 @@ int ucf_debug_sobol(int npar, int nbase, long long nout, const double* a, const 
     return copy_back_sync(back);
 }
 
+// ---- the response slots R [nens][nctl + 1][ncon] of an ensemble: what ucf_field_yield and ucf_field_allocate share, in one
+// place.  response_prepare is every check in the order of ucf_field_yield (check_own: the caller's own arguments, where
+// ucf_field_yield checks its patterns), con and *ncon, the weights, the members and field_begin_launches; response_grow the
+// buffers; response_members the uploads and the member loop with field_response_kernel; response_unlaunched the weights on the
+// device and NaN bytes into the slots of the members that were not launched.  The caller holds the device switch, the stream
+// and its drain between them.
+struct response_call {
+    ucf_field* f;
+    ucf_plan* pl;
+    int npar;
+    const int* ids;
+    int nens;
+    const double *thetas, *weight;
+    int nz;
+    const double* z;
+    int nctl;
+    const int* ctl;
+    const double* limit;
+    int nq;
+    const double* q;
+    int nlev;
+    const double* level;
+    bool want_quant, want_pexc;
+    int *con, *ncon;
+    ucf_stats* stats;
+    unsigned long long* u_out;
+    double* ess;
+    int* nlaunched;
+};
+struct response_slots {
+    std::vector<int> hcon;                 // the staging of con and the limits: it outlives its copies
+    std::vector<double> hlim;
+    int nc = 0;
+    size_t nslot = 0;                      // (nctl + 1) ncon
+    bool weighted = false;
+    ensemble_members E;
+    double *d_R = nullptr, *d_small = nullptr, *d_lim = nullptr;       // b_yR; b_ysmall: the caller's own doubles, then the limits [ncon]
+    int *d_con = nullptr, *d_ctl = nullptr;                            // b_yint
+};
+
+static int response_prepare(const response_call& a, const std::function<int()>& check_own, response_slots& S)
+{
+    ucf_field* f = a.f;
+    const int nctl = a.nctl, nens = a.nens, npar = a.npar, nz = a.nz;
+    long long nout = 0;
+    int rc = field_check_call(f, nz, !a.z ? "NULL z" : !a.ids ? "NULL ids" : !a.thetas ? "NULL thetas" : nullptr, a.z, nout);
+    if (rc) return rc;
+    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
+    if ((rc = ensemble_check_levels(nens, a.nq, a.q, a.nlev, a.level, a.want_quant, a.want_pexc, "nlev", "level")) ||
+        (rc = ensemble_check_thetas(npar, a.ids, nens, a.thetas))) return rc;
+    if (!a.ctl || !a.limit) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !a.ctl ? "ctl" : "limit");
+    if ((rc = check_own())) return rc;
+    int owned[UCF_YIELD_MAX_CTL] = {};
+    for (int j = 0; j < f->nwell; j++) {
+        if (a.ctl[j] < -1 || a.ctl[j] >= nctl) return fail(UCF_ERR_BAD_ARGUMENT, "ctl[%d]=%d outside -1..%d", j, a.ctl[j], nctl - 1);
+        if (a.ctl[j] >= 0) owned[a.ctl[j]]++;
+    }
+    for (int c = 0; c < nctl; c++)
+        if (!owned[c]) return fail(UCF_ERR_BAD_ARGUMENT, "control %d owns no well", c);
+    if (nout > 0x7fffffffLL)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d times x %d locations x %d depths: more than 2^31-1 outputs (con and bind are ints)", f->nt, f->nloc, nz);
+    // con: the outputs with a finite limit, ascending, and their limits
+    for (long long e = 0; e < nout; e++) {
+        const double v = a.limit[e];
+        if (std::isnan(v) || (std::isinf(v) && v < 0.0))
+            return fail(UCF_ERR_BAD_ARGUMENT, "limit[%lld]=%g: a limit is finite, or +inf where the output is not constrained", e, v);
+        if (std::isfinite(v)) { S.hcon.push_back((int)e); S.hlim.push_back(v); }
+    }
+    if (S.hcon.empty()) return fail(UCF_ERR_BAD_ARGUMENT, "no finite limit among the %lld outputs: nothing is constrained", nout);
+    const int nc = S.nc = (int)S.hcon.size();
+    S.nslot = (size_t)(nctl + 1) * nc;
+    if ((long long)nens * (nctl + 1) * nc > 0x7fffffffLL * 256)
+        return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d slots x %d constrained outputs: too many values for one buffer", nens, nctl + 1, nc);
+    if (a.con) std::copy(S.hcon.begin(), S.hcon.end(), a.con);
+    if (a.ncon) *a.ncon = nc;
+    S.weighted = a.weight != nullptr;
+    if ((rc = ensemble_weights_of(nens, a.weight, S.weighted, a.u_out, a.ess, a.nlaunched, S.E)) ||
+        (rc = ensemble_sets_of(f, a.pl, npar, a.ids, nens, a.thetas, S.E)))
+        return rc;
+    return field_begin_launches(f, a.pl, a.stats, &S.E.sets[S.E.first]);
+}
+
+// b_yR, b_yint and b_ysmall with own_small doubles of the caller's in front of the limits
+static int response_grow(const response_call& a, size_t own_small, response_slots& S)
+{
+    ucf_field* f = a.f;
+    int rc;
+    if ((rc = grow_buffer(f->b_yR, sizeof(double) * a.nens * S.nslot, "response slots", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_yint, sizeof(int) * ((size_t)S.nc + f->nwell), "constrained outputs and controls", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_ysmall, sizeof(double) * (own_small + S.nc), "patterns and limits", f->n_alloc))) return rc;
+    S.d_R = (double*)f->b_yR.p;
+    S.d_small = (double*)f->b_ysmall.p;
+    S.d_lim = S.d_small + own_small;
+    S.d_con = (int*)f->b_yint.p;
+    S.d_ctl = S.d_con + S.nc;
+    return UCF_OK;
+}
+
+static int response_members(const response_call& a, const response_slots& S, hipStream_t st)
+{
+    ucf_field* f = a.f;
+    const int nc = S.nc, nctl = a.nctl, nz = a.nz, npar = a.npar;
+    const size_t nslot = S.nslot;
+    double* d_R = S.d_R;
+    int *d_con = S.d_con, *d_ctl = S.d_ctl;
+    if (hipMemcpyAsync(d_con, S.hcon.data(), sizeof(int) * nc, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_ctl, a.ctl, sizeof(int) * f->nwell, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(S.d_lim, S.hlim.data(), sizeof(double) * nc, hipMemcpyHostToDevice, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the controls, patterns and limits failed: %s", hipGetErrorString(hipGetLastError()));
+    const int* ids = a.ids;
+    const double* thetas = a.thetas;
+    auto failed = [&](int rc_m, int m) { return ensemble_member_failed(rc_m, m, npar, ids, thetas + (size_t)m * npar); };
+    // per member the groups as in ucf_field_ensemble, finished by field_response_kernel into the member's slots (the buffers
+    // of the groups may grow from member to member: their addresses are read at the launch)
+    auto response_of = [=](int m) {
+        return field_finish{"response", [=](const ucf_plan* p, hipStream_t s) {
+                                return ucf_field_launch_response(nc, nctl, f->nloc, nz, f->nwell, (const ucf_field_well*)f->b_wells.p,
+                                                                 (const int*)f->b_col.p, d_ctl, d_con, (const double*)f->b_h.p, p->D.Hc,
+                                                                 d_R + (size_t)m * nslot, s);
+                            }};
+    };
+    std::vector<field_launch> L;
+    return field_map_sets(f, a.nens, S.E.sets.data(), [&](int m, const std::vector<field_launch>*& Lm) { Lm = &L; return field_launches_of(f, S.E.sets[m], L); },
+                          nz, a.z, response_of, a.stats, failed, S.weighted ? S.E.u.data() : nullptr);
+}
+
+// b_u (grown by the caller) and NaN bytes into the slots of the members that were not launched
+static int response_unlaunched(const response_call& a, const response_slots& S, hipStream_t st)
+{
+    if (!S.weighted) return UCF_OK;
+    bool ok = hipMemcpyAsync(a.f->b_u.p, S.E.u.data(), sizeof(unsigned long long) * a.nens, hipMemcpyHostToDevice, st) == hipSuccess;
+    for (int m = 0; m < a.nens && ok; m++)
+        if (S.E.u[m] == 0) ok = hipMemsetAsync(S.d_R + (size_t)m * S.nslot, 0xff, sizeof(double) * S.nslot, st) == hipSuccess;
+    if (!ok) return fail(UCF_ERR_HIP, "upload of the ensemble's weights failed: %s", hipGetErrorString(hipGetLastError()));
+    return UCF_OK;
+}
+
 // what ucf_field_yield and ucf_debug_field_yield check on the controls' count, the patterns and smax
 static int yield_check_patterns(int nctl, int npat, const double* x, double smax)
 {
@@ -1280,49 +1421,18 @@ int ucf_field_yield(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int ne
                     double* lo, int* bind, int* dead, double* resp, int* con, int* ncon, long long* nbad, ucf_stats* stats,
                     unsigned long long* u_out, double* ess, int* nlaunched)
 {
-    long long nout = 0;
-    int rc = field_check_call(f, nz, !z ? "NULL z" : !ids ? "NULL ids" : !thetas ? "NULL thetas" : nullptr, z, nout);
+    response_call a = {f, pl, npar, ids, nens, thetas, weight, nz, z, nctl, ctl, limit, nq, q, nlev, level, ystat && ystat->quant, pexc != nullptr,
+                       con, ncon, stats, u_out, ess, nlaunched};
+    response_slots S;
+    int rc = response_prepare(a, [&] { return yield_check_patterns(nctl, npat, x, smax); }, S);
     if (rc) return rc;
-    if (npar < 1 || npar > UCF_FIT_MAX_PAR) return fail(UCF_ERR_BAD_ARGUMENT, "npar=%d outside 1..%d", npar, UCF_FIT_MAX_PAR);
-    if ((rc = ensemble_check_levels(nens, nq, q, nlev, level, ystat && ystat->quant, pexc != nullptr, "nlev", "level")) ||
-        (rc = ensemble_check_thetas(npar, ids, nens, thetas))) return rc;
-    if (!ctl || !limit) return fail(UCF_ERR_BAD_ARGUMENT, "NULL %s", !ctl ? "ctl" : "limit");
-    if ((rc = yield_check_patterns(nctl, npat, x, smax))) return rc;
-    int owned[UCF_YIELD_MAX_CTL] = {};
-    for (int j = 0; j < f->nwell; j++) {
-        if (ctl[j] < -1 || ctl[j] >= nctl) return fail(UCF_ERR_BAD_ARGUMENT, "ctl[%d]=%d outside -1..%d", j, ctl[j], nctl - 1);
-        if (ctl[j] >= 0) owned[ctl[j]]++;
-    }
-    for (int c = 0; c < nctl; c++)
-        if (!owned[c]) return fail(UCF_ERR_BAD_ARGUMENT, "control %d owns no well", c);
-    if (nout > 0x7fffffffLL)
-        return fail(UCF_ERR_BAD_ARGUMENT, "%d times x %d locations x %d depths: more than 2^31-1 outputs (con and bind are ints)", f->nt, f->nloc, nz);
-    // con: the outputs with a finite limit, ascending, and their limits
-    std::vector<int> hcon;
-    std::vector<double> hlim;
-    for (long long e = 0; e < nout; e++) {
-        const double v = limit[e];
-        if (std::isnan(v) || (std::isinf(v) && v < 0.0))
-            return fail(UCF_ERR_BAD_ARGUMENT, "limit[%lld]=%g: a limit is finite, or +inf where the output is not constrained", e, v);
-        if (std::isfinite(v)) { hcon.push_back((int)e); hlim.push_back(v); }
-    }
-    if (hcon.empty()) return fail(UCF_ERR_BAD_ARGUMENT, "no finite limit among the %lld outputs: nothing is constrained", nout);
-    const int nc = (int)hcon.size();
-    if ((long long)nens * (nctl + 1) * nc > 0x7fffffffLL * 256)
-        return fail(UCF_ERR_BAD_ARGUMENT, "%d members x %d slots x %d constrained outputs: too many values for one buffer", nens, nctl + 1, nc);
-    if (con) std::copy(hcon.begin(), hcon.end(), con);
-    if (ncon) *ncon = nc;
-    const bool weighted = weight != nullptr;
-    ensemble_members E;
-    if ((rc = ensemble_weights_of(nens, weight, weighted, u_out, ess, nlaunched, E)) || (rc = ensemble_sets_of(f, pl, npar, ids, nens, thetas, E)))
-        return rc;
-    auto failed = [&](int rc_m, int m) { return ensemble_member_failed(rc_m, m, npar, ids, thetas + (size_t)m * npar); };
-    if ((rc = field_begin_launches(f, pl, stats, &E.sets[E.first]))) return rc;
+    const int nc = S.nc;
+    const bool weighted = S.weighted;
     ucf_plan* sp = f->scratch;
     device_switch dg(pl->device);
     // b_ens: q [MAX_Q], level [MAX_Q], the limit 0.5 of pfeas, then what is asked for of mean, sd, min, max [npat], quant
     // [nq][npat], nfin [npat] (ints, padded to whole doubles), pexc [nlev][npat], pfeas [npat]
-    const size_t np = (size_t)npat, nmp = (size_t)nens * np, nslot = (size_t)(nctl + 1) * nc, so = sizeof(double) * np;
+    const size_t np = (size_t)npat, nmp = (size_t)nens * np, nslot = S.nslot, so = sizeof(double) * np;
     const ucf_ensemble_maps none = {};
     const ucf_ensemble_maps* want = ystat ? ystat : &none;
     constexpr size_t OFF_HALF = 2 * UCF_ENSEMBLE_MAX_Q;
@@ -1331,9 +1441,7 @@ int ucf_field_yield(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int ne
     const size_t o_mean = take(want->mean, np), o_sd = take(want->sd, np), o_min = take(want->min, np), o_max = take(want->max, np),
                  o_quant = take(want->quant, np * nq), o_nfin = take(want->nfin, (np + 1) / 2), o_pexc = take(pexc, np * nlev),
                  o_pfeas = take(pfeas, np);
-    if ((rc = grow_buffer(f->b_yR, sizeof(double) * nens * nslot, "response slots", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_yint, sizeof(int) * ((size_t)nc + f->nwell), "constrained outputs and controls", f->n_alloc)) ||
-        (rc = grow_buffer(f->b_ysmall, sizeof(double) * (np * nctl + nc), "patterns and limits", f->n_alloc)) ||
+    if ((rc = response_grow(a, np * nctl, S)) ||
         (rc = grow_buffer(f->b_yval, sizeof(double) * 4 * nmp, "admissible scales", f->n_alloc)) ||
         (rc = grow_buffer(f->b_yidx, sizeof(int) * 2 * nmp, "binding outputs", f->n_alloc)) ||
         (rc = grow_buffer(f->b_nbad, sizeof(long long) * 3, "counts", f->n_alloc)) ||
@@ -1341,30 +1449,15 @@ int ucf_field_yield(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int ne
         (weighted && (rc = grow_buffer(f->b_u, sizeof(unsigned long long) * nens, "ensemble weights", f->n_alloc)))) return rc;
     double* base = (double*)f->b_ens.p;
     auto dev = [&](size_t o) { return o == (size_t)-1 ? nullptr : base + o; };
-    double *d_R = (double*)f->b_yR.p, *d_x = (double*)f->b_ysmall.p, *d_lim = d_x + np * nctl;
+    double *d_R = S.d_R, *d_x = S.d_small, *d_lim = S.d_lim;
     double *d_y = (double*)f->b_yval.p, *d_fe = d_y + nmp, *d_hi = d_fe + nmp, *d_lo = d_hi + nmp;
-    int *d_con = (int*)f->b_yint.p, *d_ctl = d_con + nc, *d_bind = (int*)f->b_yidx.p, *d_dead = d_bind + nmp;
+    int *d_con = S.d_con, *d_bind = (int*)f->b_yidx.p, *d_dead = d_bind + nmp;
     hipStream_t st = plan_stream(sp);
     if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
     drain drained{st};                     // the staging outlives its copies
-    if (hipMemcpyAsync(d_con, hcon.data(), sizeof(int) * nc, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_ctl, ctl, sizeof(int) * f->nwell, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_x, x, sizeof(double) * np * nctl, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_lim, hlim.data(), sizeof(double) * nc, hipMemcpyHostToDevice, st) != hipSuccess)
+    if (hipMemcpyAsync(d_x, x, sizeof(double) * np * nctl, hipMemcpyHostToDevice, st) != hipSuccess)
         return fail(UCF_ERR_HIP, "upload of the controls, patterns and limits failed: %s", hipGetErrorString(hipGetLastError()));
-    // per member the groups as in ucf_field_ensemble, finished by field_response_kernel into the member's slots (the buffers
-    // of the groups may grow from member to member: their addresses are read at the launch)
-    auto response_of = [=](int m) {
-        return field_finish{"response", [=](const ucf_plan* p, hipStream_t s) {
-                                return ucf_field_launch_response(nc, nctl, f->nloc, nz, f->nwell, (const ucf_field_well*)f->b_wells.p,
-                                                                 (const int*)f->b_col.p, d_ctl, d_con, (const double*)f->b_h.p, p->D.Hc,
-                                                                 d_R + (size_t)m * nslot, s);
-                            }};
-    };
-    std::vector<field_launch> L;
-    rc = field_map_sets(f, nens, E.sets.data(), [&](int m, const std::vector<field_launch>*& Lm) { Lm = &L; return field_launches_of(f, E.sets[m], L); },
-                        nz, z, response_of, stats, failed, weighted ? E.u.data() : nullptr);
-    if (rc) return rc;
+    if ((rc = response_members(a, S, st))) return rc;
     double ql[2 * UCF_ENSEMBLE_MAX_Q];
     ensemble_pack_levels(nq, q, nlev, level, ql);
     const double half = 0.5;
@@ -1372,13 +1465,7 @@ int ucf_field_yield(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int ne
         hipMemcpyAsync(base, ql, sizeof(ql), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(base + OFF_HALF, &half, sizeof(half), hipMemcpyHostToDevice, st) != hipSuccess)
         return fail(UCF_ERR_HIP, "upload of the ensemble's arrays failed: %s", hipGetErrorString(hipGetLastError()));
-    if (weighted) {
-        // the weights, and NaN bytes into the slots of the members that were not launched
-        bool ok = hipMemcpyAsync(f->b_u.p, E.u.data(), sizeof(unsigned long long) * nens, hipMemcpyHostToDevice, st) == hipSuccess;
-        for (int m = 0; m < nens && ok; m++)
-            if (E.u[m] == 0) ok = hipMemsetAsync(d_R + (size_t)m * nslot, 0xff, sizeof(double) * nslot, st) == hipSuccess;
-        if (!ok) return fail(UCF_ERR_HIP, "upload of the ensemble's weights failed: %s", hipGetErrorString(hipGetLastError()));
-    }
+    if ((rc = response_unlaunched(a, S, st))) return rc;
     long long* d_nbad = (long long*)f->b_nbad.p;
     ucf_yield_args ya = {};
     ya.nctl = nctl; ya.nens = nens; ya.ncon = nc; ya.npat = npat; ya.d_R = d_R; ya.d_x = d_x; ya.d_lim = d_lim; ya.d_con = d_con; ya.smax = smax;
@@ -1407,7 +1494,7 @@ int ucf_field_yield(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int ne
                     {dead, d_dead, sizeof(int) * nmp}, {resp, d_R, sizeof(double) * nens * nslot}, {&invalid, d_nbad + 2, sizeof(long long)}},
                    st, pl->device);
     if (rc) return rc;
-    if (nbad) *nbad = invalid - (nens - E.nrun);          // a member that was not launched is not counted
+    if (nbad) *nbad = invalid - (nens - S.E.nrun);        // a member that was not launched is not counted
     return UCF_OK;
 }
 
@@ -1445,6 +1532,129 @@ int ucf_debug_field_yield(int nctl, int nens, int ncon, int npat, const double* 
     HIP_TRY(hipStreamSynchronize(nullptr));
     return copy_back_sync({{y, ya.d_y, sm}, {fe, ya.d_fe, sm}, {hi, ya.d_hi, sm}, {lo, ya.d_lo, sm}, {bind, ya.d_bind, sizeof(int) * nmp},
                            {dead, ya.d_dead, sizeof(int) * nmp}, {nbad, b_nbad.p, sizeof(long long)}});
+}
+
+int ucf_field_allocate(ucf_field* f, ucf_plan* pl, int npar, const int* ids, int nens, const double* thetas, const double* weight, int nz,
+                       const double* z, int nctl, const int* ctl, int nobj, const double* w, const double* xmax, int maxit, const double* limit,
+                       double* x, double* g, int* status, int* iters, int* work, double* lam, int nq, const double* q, double* quant,
+                       double* value, int* best, double* best_x, double* gquant, double* resp, int* con, int* ncon, long long* nbad,
+                       ucf_stats* stats, unsigned long long* u_out, double* ess, int* nlaunched)
+{
+    const bool reliability = quant || value || best || best_x;
+    response_call a = {f, pl, npar, ids, nens, thetas, weight, nz, z, nctl, ctl, limit, nq, q, 0, nullptr, reliability || gquant != nullptr, false,
+                       con, ncon, stats, u_out, ess, nlaunched};
+    response_slots S;
+    int rc = response_prepare(a, [&] {
+        int rc_own = allocate_check_programme(nctl, nobj, w, xmax, maxit);
+        if (rc_own == UCF_OK && reliability && (long long)nens * nobj > UCF_YIELD_MAX_PAT)
+            rc_own = fail(UCF_ERR_BAD_ARGUMENT, "the reliability stage: %d members x %d objectives are more than %d rate patterns", nens, nobj, UCF_YIELD_MAX_PAT);
+        return rc_own;
+    }, S);
+    if (rc) return rc;
+    const int nc = S.nc;
+    ucf_plan* sp = f->scratch;
+    device_switch dg(pl->device);
+    // b_ysmall: w [nobj][nctl], xmax [nctl], the patterns [nens nobj][nctl] of the reliability stage, then the limits
+    // b_ens: q [MAX_Q] and MAX_Q unused limits, then quant [nq][npat] and gquant [nq][nobj] where they are formed
+    const size_t nmo = (size_t)nens * nobj, nw = (size_t)nobj * nctl, nx = nmo * nctl, npat = nmo;
+    const size_t o_quant = 2 * UCF_ENSEMBLE_MAX_Q, o_gquant = o_quant + (reliability ? npat * nq : 0), used = o_gquant + (gquant ? (size_t)nobj * nq : 0);
+    if ((rc = response_grow(a, nw + nctl + (reliability ? nx : 0), S)) ||
+        (rc = grow_buffer(f->b_aval, sizeof(double) * (2 * nx + nmo), "allocations", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_aidx, sizeof(int) * (2 * nmo + nx), "working sets", f->n_alloc)) ||
+        (reliability && ((rc = grow_buffer(f->b_yval, sizeof(double) * 4 * nens * npat, "admissible scales", f->n_alloc)) ||
+                         (rc = grow_buffer(f->b_yidx, sizeof(int) * 2 * nens * npat, "binding outputs", f->n_alloc)))) ||
+        (rc = grow_buffer(f->b_nbad, sizeof(long long) * 4, "counts", f->n_alloc)) ||
+        (rc = grow_buffer(f->b_ens, sizeof(double) * used, "ensemble statistics", f->n_alloc)) ||
+        (S.weighted && (rc = grow_buffer(f->b_u, sizeof(unsigned long long) * nens, "ensemble weights", f->n_alloc)))) return rc;
+    double* base = (double*)f->b_ens.p;
+    double *d_w = S.d_small, *d_xmax = d_w + nw, *d_xpat = reliability ? d_xmax + nctl : nullptr;
+    double *d_x = (double*)f->b_aval.p, *d_lam = d_x + nx, *d_g = d_lam + nx;
+    int *d_status = (int*)f->b_aidx.p, *d_iters = d_status + nmo, *d_work = d_iters + nmo;
+    hipStream_t st = plan_stream(sp);
+    if (!st) return fail(UCF_ERR_HIP, "cannot create a HIP stream on device %d", pl->device);
+    drain drained{st};                     // the staging outlives its copies
+    double ql[2 * UCF_ENSEMBLE_MAX_Q];
+    ensemble_pack_levels(nq, q, 0, nullptr, ql);
+    if (hipMemcpyAsync(d_w, w, sizeof(double) * nw, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_xmax, xmax, sizeof(double) * nctl, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(base, ql, sizeof(ql), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(f->b_nbad.p, 0, sizeof(long long) * 4, st) != hipSuccess)
+        return fail(UCF_ERR_HIP, "upload of the objectives and capacities failed: %s", hipGetErrorString(hipGetLastError()));
+    if ((rc = response_members(a, S, st)) || (rc = response_unlaunched(a, S, st))) return rc;
+    long long* d_nbad = (long long*)f->b_nbad.p;
+    ucf_allocate_args aa = {};
+    aa.nctl = nctl; aa.nens = nens; aa.ncon = nc; aa.nobj = nobj; aa.maxit = maxit; aa.d_R = S.d_R; aa.d_lim = S.d_lim; aa.d_w = d_w; aa.d_xmax = d_xmax;
+    aa.d_x = d_x; aa.d_g = d_g; aa.d_lam = d_lam; aa.d_status = d_status; aa.d_iters = d_iters; aa.d_work = d_work; aa.d_xpat = d_xpat;
+    aa.d_nbad = d_nbad + 3;
+    if ((rc = ucf_field_launch_allocate(&aa, st))) return fail(rc, "allocate kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    const unsigned long long* d_u = S.weighted ? (const unsigned long long*)f->b_u.p : nullptr;
+    if (reliability) {
+        // the optima as rate patterns through the ratio test of ucf_field_yield with smax = 1, then its member reduction
+        const size_t nmp = (size_t)nens * npat;
+        ucf_yield_args ya = {};
+        ya.nctl = nctl; ya.nens = nens; ya.ncon = nc; ya.npat = (int)npat; ya.d_R = S.d_R; ya.d_x = d_xpat; ya.d_lim = S.d_lim; ya.d_con = S.d_con;
+        ya.smax = 1.0;
+        ya.d_y = (double*)f->b_yval.p; ya.d_fe = ya.d_y + nmp; ya.d_hi = ya.d_fe + nmp; ya.d_lo = ya.d_hi + nmp;
+        ya.d_bind = (int*)f->b_yidx.p; ya.d_dead = ya.d_bind + nmp; ya.d_nbad = d_nbad + 2;
+        if ((rc = ucf_field_launch_yield(&ya, st))) return fail(rc, "yield kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+        ucf_ensemble_reduce_args ra = {};
+        ra.nens = nens; ra.nout = (long long)npat; ra.d_a = ya.d_y; ra.d_u = d_u; ra.nq = nq; ra.d_q = base; ra.d_quant = base + o_quant; ra.d_nbad = d_nbad;
+        if ((rc = ucf_field_launch_ensemble_reduce(&ra, st))) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    if (gquant) {
+        ucf_ensemble_reduce_args rg = {};
+        rg.nens = nens; rg.nout = nobj; rg.d_a = d_g; rg.d_u = d_u; rg.nq = nq; rg.d_q = base; rg.d_quant = base + o_gquant; rg.d_nbad = d_nbad + 1;
+        if ((rc = ucf_field_launch_ensemble_reduce(&rg, st))) return fail(rc, "ensemble kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    // the host step of the reliability stage reads quant, g and x whether the caller asked for them or not
+    std::vector<double> hquant(reliability ? npat * nq : 0), hg(reliability ? nmo : 0), hx(reliability ? nx : 0);
+    long long invalid = 0;
+    rc = copy_back({{x, d_x, sizeof(double) * nx}, {g, d_g, sizeof(double) * nmo}, {lam, d_lam, sizeof(double) * nx}, {status, d_status, sizeof(int) * nmo},
+                    {iters, d_iters, sizeof(int) * nmo}, {work, d_work, sizeof(int) * nx}, {hquant.data(), base + o_quant, sizeof(double) * hquant.size()},
+                    {hg.data(), d_g, sizeof(double) * hg.size()}, {hx.data(), d_x, sizeof(double) * hx.size()},
+                    {gquant, base + o_gquant, sizeof(double) * nobj * nq}, {resp, S.d_R, sizeof(double) * nens * S.nslot},
+                    {&invalid, d_nbad + 3, sizeof(long long)}},
+                   st, pl->device);
+    if (rc) return rc;
+    if (reliability) {
+        if (quant) std::copy(hquant.begin(), hquant.end(), quant);
+        if ((rc = ucf_allocate_select(nq, nens, nobj, nctl, hquant.data(), hg.data(), hx.data(), value, best, best_x))) return rc;
+    }
+    if (nbad) *nbad = invalid - (nens - S.E.nrun);        // a member that was not launched is not counted
+    return UCF_OK;
+}
+
+int ucf_debug_field_allocate(int nctl, int nens, int ncon, int nobj, const double* R, const double* limit_con, const int* con, const double* w,
+                             const double* xmax, int maxit, double* x, double* g, int* status, int* iters, int* work, double* lam, long long* nbad)
+{
+    int rc = allocate_check_programme(nctl, nobj, w, xmax, maxit);
+    if (rc || (rc = allocate_check_slots(nctl, nens, ncon, R, limit_con))) return rc;
+    if (!con) return fail(UCF_ERR_BAD_ARGUMENT, "NULL con");
+    for (int i = 0; i < ncon; i++)
+        if (con[i] < 0 || (i > 0 && con[i] <= con[i - 1]))
+            return fail(UCF_ERR_BAD_ARGUMENT, "con[%d]=%d: the constrained outputs are not negative and ascend strictly", i, con[i]);
+    if ((rc = require_device())) return rc;
+    const size_t nmo = (size_t)nens * nobj, nx = nmo * nctl, nw = (size_t)nobj * nctl, sR = sizeof(double) * nens * (nctl + 1) * (size_t)ncon;
+    dev_buf b_R, b_small, b_val, b_idx, b_nbad;
+    if (b_R.alloc(sR) || b_small.alloc(sizeof(double) * (nw + nctl + ncon)) || b_val.alloc(sizeof(double) * (2 * nx + nmo)) ||
+        b_idx.alloc(sizeof(int) * (2 * nmo + nx)) || b_nbad.alloc(sizeof(long long)))
+        return fail(UCF_ERR_NOMEM, "device allocation failed");
+    double *d_w = (double*)b_small.p, *d_xmax = d_w + nw, *d_lim = d_xmax + nctl;
+    HIP_TRY(hipMemcpy(b_R.p, R, sR, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_w, w, sizeof(double) * nw, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_xmax, xmax, sizeof(double) * nctl, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_lim, limit_con, sizeof(double) * ncon, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b_nbad.p, 0, sizeof(long long)));
+    ucf_allocate_args aa = {};
+    aa.nctl = nctl; aa.nens = nens; aa.ncon = ncon; aa.nobj = nobj; aa.maxit = maxit;
+    aa.d_R = (const double*)b_R.p; aa.d_lim = d_lim; aa.d_w = d_w; aa.d_xmax = d_xmax;
+    aa.d_x = (double*)b_val.p; aa.d_lam = aa.d_x + nx; aa.d_g = aa.d_lam + nx;
+    aa.d_status = (int*)b_idx.p; aa.d_iters = aa.d_status + nmo; aa.d_work = aa.d_iters + nmo; aa.d_nbad = (long long*)b_nbad.p;
+    if ((rc = ucf_field_launch_allocate(&aa, nullptr))) return fail(rc, "allocate kernel launch failed: %s", hipGetErrorString(hipGetLastError()));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return copy_back_sync({{x, aa.d_x, sizeof(double) * nx}, {g, aa.d_g, sizeof(double) * nmo}, {lam, aa.d_lam, sizeof(double) * nx},
+                           {status, aa.d_status, sizeof(int) * nmo}, {iters, aa.d_iters, sizeof(int) * nmo}, {work, aa.d_work, sizeof(int) * nx},
+                           {nbad, b_nbad.p, sizeof(long long)}});
 }
 
 int ucf_ensemble_quantise(int nens, const double* weight, unsigned long long* u, double* ess)

@@ -1,7 +1,8 @@
 // ucf_field.h -- launchers of the well-field kernels: the superposition, called by ucf_field_drawdown, ucf_field_forecast and
 // ucf_field_ensemble (ucf_field.cpp), the response slots of ucf_field_yield, the combination of a forecast (all three
 // ucf_field.hip), the reduction of an ensemble (ucf_field_ensemble.hip), the data worth of candidate wells
-// (ucf_field_worth.hip), the ratio test of ucf_field_yield (ucf_field_yield.hip), the time kernel of
+// (ucf_field_worth.hip), the ratio test of ucf_field_yield (ucf_field_yield.hip), the linear programme of ucf_field_allocate
+// (ucf_field_allocate.hip; its serial steps, shared with the host twin, are ucf_field_allocate.h), the time kernel of
 // ucf_field_ensemble_times (ucf_field_times.hip) and the reduction of a Saltelli design (ucf_field_sobol.hip).
 #pragma once
 #include <cstddef>
@@ -46,6 +47,22 @@ struct ucf_yield_args {
 };
 // UCF_ERR_BAD_ARGUMENT for what the comments above exclude and for a NULL array
 int ucf_field_launch_yield(const ucf_yield_args* a, void* stream);
+
+// The linear programme of ucf_field_allocate (ucf_field_allocate.hip), field_allocate_kernel<nctl>: a workgroup of 256 threads
+// per (member, objective); the arithmetic is stated with ucf_field_allocate in include/ucf.h.  Device memory throughout.
+struct ucf_allocate_args {
+    int nctl, nens, ncon, nobj, maxit;     // 1..UCF_YIELD_MAX_CTL, 1..UCF_ENSEMBLE_MAX, >= 1, 1..UCF_ALLOC_MAX_OBJ, 1..UCF_ALLOC_MAX_ITER
+    const double* d_R;                     // [nens][nctl + 1][ncon]
+    const double* d_lim;                   // [ncon] the limit of constrained output i
+    const double* d_w;                     // [nobj][nctl]
+    const double* d_xmax;                  // [nctl]
+    double *d_x, *d_g, *d_lam;             // [nens][nobj][nctl], [nens][nobj], [nens][nobj][nctl]
+    int *d_status, *d_iters, *d_work;      // [nens][nobj], [nens][nobj], [nens][nobj][nctl]
+    double* d_xpat;                        // NULL ok: [nens nobj][nctl], x where the status is 0 and +0.0 elsewhere
+    long long* d_nbad;                     // += the members with a slot value that is not finite; the caller zeroes it
+};
+// UCF_ERR_BAD_ARGUMENT for what the comments above exclude and for a NULL array
+int ucf_field_launch_allocate(const ucf_allocate_args* a, void* stream);
 
 // The time kernel of ucf_field_ensemble_times (ucf_field_times.hip), field_times_kernel: one thread per (member m, limit l, site
 // e) of d_T [nens][nlim][nsite], e fastest, a workgroup of 256 threads per (tile of sites, l, m); the arithmetic is stated with

@@ -1,5 +1,5 @@
 // ucf_host.h -- what the host sources of the library share (ucf_api.cpp, ucf_plan.cpp, ucf_drawdown.cpp, ucf_multi.cpp,
-// ucf_debug.cpp, ucf_fit.cpp, ucf_field.cpp).  Internal: everything is in namespace ucf_host with hidden visibility, so
+// ucf_debug.cpp, ucf_fit.cpp, ucf_field.cpp, ucf_allocate.cpp).  Internal: everything is in namespace ucf_host with hidden visibility, so
 // the names link between the objects and are not exported from libucf.so.  Declarations and a few small inline helpers; the
 // comment that explains a declared function stands at its definition, in the file named here.
 #pragma once
@@ -178,5 +178,11 @@ inline void ensemble_pack_levels(int nq, const double* q, int nlim, const double
     for (int i = 0; i < nq; i++) ql[i] = q[i];
     for (int i = 0; i < nlim; i++) ql[UCF_ENSEMBLE_MAX_Q + i] = limit[i];
 }
+
+// ---- ucf_allocate.cpp
+// what ucf_field_allocate, ucf_debug_field_allocate and ucf_allocate_solve check on nctl, the objectives, xmax and maxit
+int allocate_check_programme(int nctl, int nobj, const double* w, const double* xmax, int maxit);
+// what the two entries on caller slots check on nens, ncon, R and limit_con
+int allocate_check_slots(int nctl, int nens, int ncon, const double* R, const double* limit_con);
 
 }  // namespace ucf_host

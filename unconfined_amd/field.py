@@ -44,6 +44,13 @@ one control and 64 splits between two such pairs are tried, up to three times to
                                   limit=2.0, smax=3.0, levels=[1.0])
     out["quant"][0], out["pexc"], out["bind"]                                                 # the scale that 95 % admit, P(scale > 1), where it binds
 
+How the pumping should be split between the controls so that the total is largest and every limit holds, what limits it and how
+sure that is -- one linear programme per member, solved on the GPU on the same response slots (ucf_field_allocate):
+
+    res = field.optimal_rates(plan, ["Kr", "Ss"], thetas, z=[145.7, 100.0], controls=[0, 1, 0, 1], objectives=[[1.0, 1.0]],
+                              xmax=[3.0, 3.0], limit=2.0)
+    res.x[:, 0], res.binding(0, 0), res.lam[0, 0], res.best_x[0, 0]                           # per member; what binds; shadow prices; the rates 95 % admit
+
 When the drawdown first passes a permitted value, from when on it stays below one after the pumps have stopped, and how sure that
 is -- one time per member, limit, location and depth, formed and reduced on the GPU (ucf_field_ensemble_times):
 
@@ -175,6 +182,35 @@ class TimeToLimit:
     def __repr__(self):
         return (f"TimeToLimit(limits={self.limits.tolist()}, kinds={self.kinds.tolist()}, abscissa={self.abscissa!r}, never={self.never!r}, "
                 f"shape={self.mean.shape}, nbad={self.nbad})")
+
+
+class Allocation:
+    """what ``WellField.optimal_rates`` returns.  Per member and objective, [nens, nobj] leading: x [.., nctl], the multipliers on
+    the wells' q that maximise the objective, and g, its value; status (int32: 0 optimal, 1 iteration cap, 2 the fixed wells alone
+    exceed a limit, 3 numeric, -1 the member is not finite -- x, g and lam are NaN unless it is 0) and iters; work [.., nctl]
+    (int32), the constraints that bind at the optimum, ascending -- id c: x_c = 0, id nctl + c: x_c = xmax[c], id 2 nctl + i: the
+    constrained output con[i] --, and lam [.., nctl], their shadow prices: the gain in g per unit of relaxed limit.  ``binding``
+    translates work into ('lower', c), ('upper', c) or ('output', flat index into the map).  resp [nens, nctl + 1, ncon] and con
+    [ncon] as in ``sustainable_yield``; nbad; q [nq]; gquant [nq, nobj], the quantiles of g over the members (the wait-and-see
+    figure).  With ``reliability``: quant [nq, nens nobj], the scale of candidate p = m nobj + o that a share 1 - q of the
+    members admits, value = quant g, best [nq, nobj] (int32; -1: none) the candidate of every objective with the largest value and
+    best_x [nq, nobj, nctl] its scaled rates: a FEASIBLE allocation at reliability 1 - q chosen among the members' optima, a lower
+    bound on the chance-constrained optimum.  With weights u, ess, nlaunched.  An array that was not asked for is None."""
+
+    def __init__(self, **kw):
+        self.quant = self.value = self.best = self.best_x = self.gquant = self.u = self.ess = self.nlaunched = self.stats = None
+        self.__dict__.update(kw)
+
+    def binding(self, m: int, o: int) -> list:
+        nctl = self.x.shape[2]
+        out = []
+        for j in self.work[m, o]:
+            j = int(j)
+            out.append(None if j < 0 else ("lower", j) if j < nctl else ("upper", j - nctl) if j < 2 * nctl else ("output", int(self.con[j - 2 * nctl])))
+        return out
+
+    def __repr__(self):
+        return f"Allocation(nens={self.x.shape[0]}, nobj={self.x.shape[1]}, nctl={self.x.shape[2]}, optimal={int((self.status == 0).sum())}, nbad={self.nbad})"
 
 
 class SobolMaps:
@@ -464,6 +500,69 @@ class WellField:
         if with_stats:
             out["stats"] = {k: getattr(st, k) for k, _ in UcfStats._fields_}
         return out
+
+    def optimal_rates(self, plan, free, thetas, z, controls, objectives, xmax, limit, weights=None, q=(0.05, 0.5, 0.95), maxit: int = 64,
+                      reliability: bool = True, with_stats: bool = False) -> "Allocation":
+        """how the abstraction should be distributed over the wells so that an objective is largest and every constrained output
+        stays within its limit, under the ensemble ``thetas`` [nens, npar] (ucf_field_allocate): per member and objective one
+        linear programme in the multipliers x_c on the q of the wells of control c, solved on the GPU on the response slots of
+        ``sustainable_yield``.  ``controls`` [nwell] and ``limit`` as there; ``objectives`` [nobj, nctl] (or [nctl]) are the weights
+        of g = sum_c w_c x_c (all ones: the total abstraction in units of today's rates); ``xmax`` [nctl] (or a scalar) the pump
+        capacities, 0 <= x_c <= xmax_c; ``maxit`` the pivots allowed per programme.  With ``reliability`` the members' optima are
+        scaled down to what a share 1 - q of the ensemble admits and the best of them is returned per level and objective.
+        Returns an ``Allocation``.  ``plan`` is not modified."""
+        ids = np.ascontiguousarray([par_id(n) for n in free], dtype=np.int32)
+        thetas = np.atleast_2d(_f64(thetas))
+        if thetas.ndim != 2 or thetas.shape[1] != len(ids):
+            raise ValueError("thetas: [nens, npar], one value per free parameter")
+        nens = len(thetas)
+        z = np.atleast_1d(_f64(z))
+        ctl = np.ascontiguousarray(np.atleast_1d(controls), dtype=np.int32)
+        if ctl.shape != (self.nwell,):
+            raise ValueError("controls: one control (or -1) per well")
+        w = np.atleast_2d(_f64(objectives))
+        if w.ndim != 2 or w.shape[1] < 1:
+            raise ValueError("objectives: [nobj, nctl]")
+        nobj, nctl = w.shape
+        if ctl.max() >= nctl:
+            raise ValueError("objectives: one column per control")
+        try:
+            cap = np.ascontiguousarray(np.broadcast_to(_f64(xmax), (nctl,)))
+        except ValueError:
+            raise ValueError("xmax: [nctl] or a scalar") from None
+        shape = (self.nt, self.nloc, len(z))
+        try:
+            lim = np.ascontiguousarray(np.broadcast_to(_f64(limit), shape))
+        except ValueError:
+            raise ValueError("limit: [nt, nloc, nz] or a scalar") from None
+        qs = np.atleast_1d(_f64(q if q is not None else []))
+        wt = None if weights is None else np.atleast_1d(_f64(weights))
+        if wt is not None and len(wt) != nens:
+            raise ValueError("weights: one value per member")
+        nslot = max(int(np.isfinite(lim).sum()), 1)
+        out = {"x": np.zeros((nens, nobj, nctl)), "g": np.zeros((nens, nobj)), "status": np.zeros((nens, nobj), np.int32),
+               "iters": np.zeros((nens, nobj), np.int32), "work": np.zeros((nens, nobj, nctl), np.int32), "lam": np.zeros((nens, nobj, nctl))}
+        if len(qs):
+            out["gquant"] = np.zeros((len(qs), nobj))
+        if reliability:
+            npat = nens * nobj
+            out["quant"], out["value"] = np.zeros((len(qs), npat)), np.zeros((len(qs), npat))
+            out["best"], out["best_x"] = np.zeros((len(qs), nobj), np.int32), np.zeros((len(qs), nobj, nctl))
+        out["resp"] = np.zeros((nens, nctl + 1, nslot))
+        con, ncon, nbad = np.zeros(lim.size, np.int32), C.c_int(), C.c_longlong()
+        st = UcfStats()
+        u, ess, nl = np.zeros(nens, np.uint64), C.c_double(), C.c_int()
+        _libmod.check(self._lib.ucf_field_allocate(
+            self._h, plan._h, len(ids), _addr(ids), nens, _addr(thetas), _addr(wt), len(z), _addr(z), nctl, _addr(ctl), nobj, _addr(w), _addr(cap),
+            int(maxit), _addr(lim), *(_addr(out[k]) for k in ("x", "g", "status", "iters", "work", "lam")), len(qs), _addr(qs) if len(qs) else None,
+            *(_addr(out.get(k)) for k in ("quant", "value", "best", "best_x", "gquant")), _addr(out["resp"]), _addr(con), C.addressof(ncon),
+            C.addressof(nbad), C.byref(st) if with_stats else None, _addr(u), C.addressof(ess), C.addressof(nl)))
+        res = Allocation(objectives=w, xmax=cap, q=qs, con=con[:ncon.value].copy(), nbad=int(nbad.value), **out)
+        if wt is not None:
+            res.u, res.ess, res.nlaunched = u, float(ess.value), int(nl.value)
+        if with_stats:
+            res.stats = {k: getattr(st, k) for k, _ in UcfStats._fields_}
+        return res
 
     def time_to_limit(self, plan, free, thetas, z, limits, kinds="first_above", weights=None, q=(0.05, 0.5, 0.95), horizons=(),
                       abscissa: str = "t", never=None, all_times: bool = False, with_stats: bool = False) -> "TimeToLimit":

@@ -48,6 +48,7 @@ EXPORTS = [
     "ucf_debug_ensemble_weighted",
     "ucf_field_worth", "ucf_worth_condition", "ucf_debug_field_worth",
     "ucf_field_yield", "ucf_debug_field_yield",
+    "ucf_field_allocate", "ucf_debug_field_allocate", "ucf_allocate_solve", "ucf_allocate_select",
     "ucf_field_ensemble_times", "ucf_debug_field_times",
     "ucf_sobol_design", "ucf_field_sobol", "ucf_debug_sobol",
     "ucf_fit_loss_terms", "ucf_fit_robust_scale", "ucf_fit_set_loss", "ucf_fit_get_loss", "ucf_fit_loss_report", "ucf_debug_fit_reduce_loss",
@@ -204,6 +205,17 @@ def load() -> C.CDLL:
                                     [C.POINTER(UcfStats)] + [vp] * 3)
     # nctl, nens, ncon, npat, R, x, limit_con, con, smax, y, fe, hi, lo, bind, dead, nbad
     lib.ucf_debug_field_yield.argtypes = [C.c_int] * 4 + [vp] * 4 + [C.c_double] + [vp] * 7
+    # every array may be NULL: plain addresses.  field, plan, npar, ids, nens, thetas, weight, nz, z | nctl, ctl | nobj, w, xmax,
+    # maxit | limit | x, g, status, iters, work, lam | nq, q | quant, value, best, best_x, gquant | resp, con, ncon, nbad | stats | u,
+    # ess, nlaunched
+    lib.ucf_field_allocate.argtypes = ([vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp] + [C.c_int, vp] + [C.c_int, vp, vp, C.c_int] + [vp] +
+                                       [vp] * 6 + [C.c_int, vp] + [vp] * 5 + [vp] * 4 + [C.POINTER(UcfStats)] + [vp] * 3)
+    # nctl, nens, ncon, nobj, R, limit_con, con, w, xmax, maxit, x, g, status, iters, work, lam, nbad
+    lib.ucf_debug_field_allocate.argtypes = [C.c_int] * 4 + [vp] * 5 + [C.c_int] + [vp] * 7
+    # nctl, ncon, R_m, limit_con, nobj, w, xmax, maxit, x, g, status, iters, work, lam
+    lib.ucf_allocate_solve.argtypes = [C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int] + [vp] * 6
+    # nq, nens, nobj, nctl, quant, g, x, value, best, best_x
+    lib.ucf_allocate_select.argtypes = [C.c_int] * 4 + [vp] * 6
     # every array may be NULL: plain addresses.  field, plan, npar, ids, nens, thetas, weight, nz, z | tau, tau_never | nlim, limit,
     # kind | nq, q, nhor, horizon | T, plater, nbad | stats | u, ess, nlaunched
     lib.ucf_field_ensemble_times.argtypes = ([vp, vp, C.c_int, vp, C.c_int, vp, vp, C.c_int, vp] + [vp, C.c_double] + [C.c_int, vp, vp] +
